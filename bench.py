@@ -13,9 +13,17 @@ batch 1,048,576 per GPU (1.95 GB of algorithmic traffic per step, far past the 2
 Cache).  BASELINE.json configs[1] (65,536 instances) is reported beside it as a side field.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config ground4_1m|ground4|sq8|mixed16|none4|solve5]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
-Rank 0 prints one JSON line.  Fields beyond the driver contract:
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K steps, writes the last timed
+step's outputs with --dump-outputs, and prints the line: metric, value, unit, ms_per_step (milliseconds
+per timed step) and the description of the run.  --dump-outputs DIR writes what the last timed step
+computed as DIR/<name>.npy in float64 (g, jac and norms; x, y, objective, status and iterations for
+solve5), a fixed seeded sample of the instances where the arrays are large (under 64 MB in all);
+the inputs are seeded, so two builds can be compared output for output.
+
+--full adds every other leg (each can still be switched off by its --no-* option).  Its fields:
   roofline      dominant kernel (cpl_eval_*): algorithmic bytes per launch / mean launch
                 duration from HIP events on the launch stream; traffic = HBM bytes per launch from
                 rocprofv3 PMC passes (FETCH_SIZE x2 per the gfx950 correction + WRITE_SIZE)
@@ -83,6 +91,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="ground4_1m", help="ground4_1m | ground4 | sq8 | mixed16 | none4 | solve5")
     ap.add_argument("--batch", type=int, default=0, help="override per-GPU batch")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: PMC traffic, CPU baseline, kernel-time "
+                         "roofline, checker, side configs (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy (float64)")
     ap.add_argument("--no-pmc", action="store_true")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-side", action="store_true", help="skip the configs[1] side measurement")
@@ -104,7 +117,49 @@ def parse():
     # CPU rehearsal of the multi-rank launch (tests only: gloo, the shard's evaluation supplied by a
     # file the test names; never on a GPU run)
     ap.add_argument("--rehearse-cpu", default="", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # a plain run: the headline figure only
+        args.no_pmc = args.no_cpu = args.no_side = args.no_check = True
+    return args
+
+
+# ------------------------------------------------------------------------------------------
+# --dump-outputs: what the last timed step computed, for output-for-output comparison of two builds
+# ------------------------------------------------------------------------------------------
+DUMP_SAMPLE = 32768  # instances written at most (1M x 4 Ground: g + jac of 32 768 instances, 53 MB in float64)
+DUMP_BYTES = 56 * 1000 * 1000  # of per-instance records at most (wider records: fewer instances)
+DUMP_SEED = 0xD0C5
+
+
+def dump_sample_index(batch, row_bytes):
+    """Sorted instance indices a dump holds (`row_bytes` = one instance's float64 records): every
+    instance of a small batch, else min(DUMP_SAMPLE, DUMP_BYTES // row_bytes) of them drawn once with
+    a fixed seed (the same for every run of the same batch and record width)."""
+    import numpy as np
+
+    count = max(1, min(DUMP_SAMPLE, DUMP_BYTES // row_bytes))
+    if batch <= count:
+        return np.arange(batch, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(batch, count, replace=False)).astype(np.int64)
+
+
+def dump_outputs(dirname, per_instance, whole=None):
+    """DIR/<name>.npy in float64: `per_instance` tensors [B, ...] at the sampled instances, `whole`
+    tensors as they are."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    batch = next(iter(per_instance.values())).shape[0]
+    row_bytes = 8 * sum(t[0].numel() for t in per_instance.values())
+    idx = torch.as_tensor(dump_sample_index(batch, row_bytes))
+    for name, t in per_instance.items():
+        a = t.index_select(0, idx.to(t.device)).to(torch.float64).cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+    for name, t in (whole or {}).items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(t.to(torch.float64).cpu().numpy()))
 
 
 # ------------------------------------------------------------------------------------------
@@ -885,7 +940,7 @@ def solve_bench(args):
     if world > 1:
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
     B = args.batch or SOLVE_CONFIG.batch
-    steps = max(1, min(args.steps, 5))
+    steps = args.steps
     warm = 1 if args.warmup > 0 else 0
     dt, r, cpu = run_solve5(dev, B, args.hessian, steps, warm, args.max_ls, args.max_soc,
                             0 if args.no_cpu else args.cpu_sample, rank, world,
@@ -896,6 +951,9 @@ def solve_bench(args):
         dt = float(tdt.item())
     ok = int((r.status <= 1).sum().item())
     its = r.iterations.double()
+    if rank == 0 and args.dump_outputs:  # the last timed solve's result
+        dump_outputs(args.dump_outputs, {"x": r.x, "y": r.y, "objective": r.objective, "status": r.status,
+                                         "iterations": r.iterations})
     if rank == 0:
         print(json.dumps({
             "metric": "concurrent CentroidalPlanner solves per second (full interior-point solve loop, GPU callbacks)",
@@ -1059,27 +1117,34 @@ def main():
         # rank's rows must be the norms it computed locally
         gather_info = runner.last_bucket_report(rank, K)
 
-    # live kernel timing: HIP events on the launch stream around back-to-back eval launches only
-    ms = ctypes.c_double()
-    reps = max(K, 20)
-
-    def p(t):
-        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-    # the step's launches (eval with fused norms + finish); events bracket each eval kernel alone
-    _abi.check(_abi.lib.cpl_time_eval_batch(ctypes.byref(prob.desc()), batch, p(xt), p(mt), p(tt), p(out["g"]), p(out["jac"]),
-                                            None, None, p(norms[0][0]), ctypes.c_void_p(stream.cuda_stream), reps,
-                                            ctypes.byref(ms)))
-    kernel_ms = ms.value
+    if rank == 0 and args.dump_outputs:  # the last timed step's outputs (before any other leg runs)
+        last = runner.sizes(K)
+        dump_outputs(args.dump_outputs, {"g": out["g"], "jac": out["jac"]},
+                     {"norms": norms[(len(last) - 1) % 2][last[-1] - 1]})
 
     bytes_inst, m = algorithmic_bytes(cfg.n_contacts, cfg.env)
     alg_bytes = bytes_inst * batch
     rows_total = total_batch * m * K
     value = rows_total / dt
-    achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
+
+    ms = ctypes.c_double()
+
+    def p(t):
+        return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+    kernel_ms = achieved = None
+    if args.full:
+        # live kernel timing: HIP events on the launch stream around back-to-back eval launches only
+        # (the step's launches: eval with fused norms + finish; events bracket each eval kernel alone)
+        reps = max(K, 20)
+        _abi.check(_abi.lib.cpl_time_eval_batch(ctypes.byref(prob.desc()), batch, p(xt), p(mt), p(tt), p(out["g"]),
+                                                p(out["jac"]), None, None, p(norms[0][0]),
+                                                ctypes.c_void_p(stream.cuda_stream), reps, ctypes.byref(ms)))
+        kernel_ms = ms.value
+        achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
 
     valu = None
-    if isinstance(valu_counters, dict):
+    if isinstance(valu_counters, dict) and kernel_ms is not None:
         valu = valu_roofline(valu_counters, kernel_ms)
     elif valu_counters:
         valu = {"error": valu_counters}
@@ -1092,7 +1157,7 @@ def main():
             check = {"ok": False, "error": f"checker leg failed: {e}"}
 
     folded = None
-    if rank == 0 and world == 1 and not args.no_side:
+    if rank == 0 and world == 1 and args.full and not args.no_side:
         # the values-only Jacobian layout (CPL_EVAL_JAC_FOLDED) of the same batch: the structural
         # constants are not written (same g, the remaining Jacobian values bit-identical)
         fo = prob.eval_batch(xt, mt, tt, outputs=("g", "jac", "norms"), jac_folded=True)
@@ -1193,7 +1258,7 @@ def main():
             },
             "instances_per_s": total_batch * K / dt,
             "residual_gather": gather_info,
-            "roofline": {
+            "roofline": None if not args.full else {
                 "bound": "hbm",
                 "achieved": achieved,
                 "peak": HBM_PEAK_GBPS,

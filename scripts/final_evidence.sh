@@ -28,7 +28,7 @@ step() {  # step <seconds> <command...>
 if [ "$part" != 2 ]; then
 step 900 bash -c "python -u -m pytest -q --timeout 240 --timeout-method thread tests -m gpu > $out/gpu_tests.log 2>&1"
 step 300 bash -c "python -u -c 'import __graft_entry__ as g; g.smoke(); print(\"smoke ok\")' > $out/smoke.log 2>&1"
-step 300 bash -c "python -u bench.py > $out/bench_default.json 2> $out/bench_default.err"
+step 300 bash -c "python -u bench.py --full > $out/bench_default.json 2> $out/bench_default.err"
 step 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof" -o run -- \
   python3 bench.py --steps 20 --no-pmc --no-cpu --no-check --no-side
 trace=$(find "$out/prof" -name "*kernel_trace.csv" | head -1)
@@ -37,10 +37,10 @@ stats=$(find "$out/prof" -name "*kernel_stats.csv" | head -1)
 [ -n "$stats" ] && cp "$stats" "$out/kernel_stats_bench_default.csv"
 fi
 [ "$part" = 1 ] && { echo done; exit 0; }
-step 300 bash -c "python -u bench.py --config sq8 > $out/bench_sq8.json 2> $out/bench_sq8.err"
-step 300 bash -c "python -u bench.py --config mixed16 > $out/bench_mixed16.json 2> $out/bench_mixed16.err"
-step 300 bash -c "python -u bench.py --config solve5 --hessian limited-memory > $out/bench_solve5_lbfgs.json 2> $out/bench_solve5_lbfgs.err"
-step 300 bash -c "python -u bench.py --config solve5 > $out/bench_solve5_exact.json 2> $out/bench_solve5_exact.err"
+step 300 bash -c "python -u bench.py --full --config sq8 > $out/bench_sq8.json 2> $out/bench_sq8.err"
+step 300 bash -c "python -u bench.py --full --config mixed16 > $out/bench_mixed16.json 2> $out/bench_mixed16.err"
+step 300 bash -c "python -u bench.py --full --config solve5 --hessian limited-memory > $out/bench_solve5_lbfgs.json 2> $out/bench_solve5_lbfgs.err"
+step 300 bash -c "python -u bench.py --full --config solve5 > $out/bench_solve5_exact.json 2> $out/bench_solve5_exact.err"
 step 300 bash -c "python -u scripts/solve_latency.py --reps 10 > $out/solve_latency.json 2> $out/solve_latency.err"
 step 300 bash -c "python -u scripts/testbasic_outcomes.py gpu > $out/testbasic_gpu.jsonl 2> $out/testbasic_gpu.err"
 step 300 bash -c "python -u scripts/testbasic_outcomes.py gpu ipopt > $out/testbasic_gpu_ipopt.jsonl 2> $out/testbasic_gpu_ipopt.err"

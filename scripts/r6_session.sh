@@ -6,7 +6,7 @@ out=${1:?out dir}
 mkdir -p "$out"
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > "$out/tests.log" 2>&1 || exit $?
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1 || exit $?
-timeout -k 10 400 python bench.py > "$out/bench.json" 2> "$out/bench.err" || exit $?
+timeout -k 10 400 python bench.py --full > "$out/bench.json" 2> "$out/bench.err" || exit $?
 if [ "$2" = sq8probe ]; then
   # sq8: full, no compute (1), no stores (2), no phase barriers (8192)
   timeout -k 10 300 python3 -u scripts/ab_kernels.py --config sq8 --rounds 5 --reps 20 \

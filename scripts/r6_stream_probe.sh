@@ -7,6 +7,6 @@ out=${1:?out dir}
 mkdir -p "$out"
 timeout -k 10 300 python3 -u scripts/mixed_stream_probe.py > "$out/streams_1m.jsonl" || exit $?
 timeout -k 10 200 python3 -u scripts/mixed_stream_probe.py --batch 131072 --reps 40 > "$out/streams_131k.jsonl" || exit $?
-timeout -k 10 300 python3 -u bench.py --config mixed16 > "$out/bench_mixed16_a.json" 2> "$out/bench_a.err" || exit $?
-timeout -k 10 300 python3 -u bench.py --config mixed16 --no-pmc > "$out/bench_mixed16_b.json" 2> "$out/bench_b.err" || exit $?
+timeout -k 10 300 python3 -u bench.py --full --config mixed16 > "$out/bench_mixed16_a.json" 2> "$out/bench_a.err" || exit $?
+timeout -k 10 300 python3 -u bench.py --full --config mixed16 --no-pmc > "$out/bench_mixed16_b.json" 2> "$out/bench_b.err" || exit $?
 echo done

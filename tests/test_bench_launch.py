@@ -66,6 +66,68 @@ def test_gpus_disagreeing_with_world_size_is_refused():
     assert not _json_lines(r.stdout)
 
 
+def _bench_module():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("_bench_under_test", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_plain_run_switches_every_other_leg_off(monkeypatch):
+    """Without --full the PMC, CPU, side and checker legs are off; with it each --no-* option decides."""
+    bench = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and a.no_pmc and a.no_cpu and a.no_side and a.no_check and a.steps == 3 and a.warmup == 1
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu"])
+    a = bench.parse()
+    assert a.full and a.no_cpu and not (a.no_pmc or a.no_side or a.no_check)
+
+
+def test_dump_sample_is_fixed_and_within_the_size_limit():
+    bench = _bench_module()
+    import numpy as np
+
+    # g + jac in float64 per instance: 4 and 16 contacts with an environment
+    for n_contacts in (4, 16):
+        row_bytes = 8 * (6 + 6 * n_contacts + 6 + 15 * n_contacts + 27 * n_contacts)
+        assert np.array_equal(bench.dump_sample_index(1000, row_bytes), np.arange(1000))
+        a, b = bench.dump_sample_index(1_048_576, row_bytes), bench.dump_sample_index(1_048_576, row_bytes)
+        assert np.array_equal(a, b) and np.all(np.diff(a) > 0) and 0 <= a[0] and a[-1] < 1_048_576
+        assert 1000 < a.size <= bench.DUMP_SAMPLE and a.size * row_bytes <= 60 * 1000 * 1000
+    assert bench.dump_sample_index(1_048_576, 8 * 204).size == bench.DUMP_SAMPLE
+
+
+@pytest.mark.gpu
+def test_dump_outputs_holds_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR` on a plain run: g, jac and norms of the timed path as float64 .npy files,
+    equal to a direct evaluation of the same seeded inputs, and the line reports the steps it timed."""
+    import numpy as np
+    import torch
+
+    from centroidalplanner_amd.workload import CONFIGS, generate, make_problem
+
+    cfg, B = CONFIGS["ground4"], 3001
+    r = _run(["--gpus", "1", "--config", "ground4", "--batch", str(B), "--steps", "7", "--warmup", "2", "--bucket", "3",
+              "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    (ln,) = _json_lines(r.stdout)
+    assert ln["steps"] == 7 and ln["warmup"] == 2 and ln["ms_per_step"] > 0.0
+    assert ln["value"] == pytest.approx(B * 30 / (ln["ms_per_step"] * 1e-3), rel=1e-9)
+    assert ln["roofline"] is None and ln["cpu_baseline"] is None and ln["check"] is None
+    assert sorted(os.listdir(tmp_path)) == ["g.npy", "jac.npy", "norms.npy"]
+    prob = make_problem(cfg.n_contacts, cfg.env)
+    x, mass, _ = generate(cfg.n_contacts, cfg.env, B, 0xC910 + cfg.config_id)
+    dev = torch.device("cuda:0")
+    ref = prob.eval_batch(torch.tensor(x, device=dev), torch.tensor(mass, device=dev), outputs=("g", "jac", "norms"))
+    for name in ("g", "jac", "norms"):
+        got = np.load(tmp_path / (name + ".npy"))
+        assert got.dtype == np.float64
+        assert np.array_equal(got, ref[name].cpu().numpy()), name
+
+
 def test_a_failing_rank_fails_the_launch():
     r = _run(["--gpus", "2", "--config", "ground4", "--batch", "64"] + BASE,
              env_extra={"CPL_REHEARSAL_FAIL_RANK": "1"})
