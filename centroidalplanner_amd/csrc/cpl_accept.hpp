@@ -115,31 +115,33 @@ __device__ __forceinline__ bool ls_acceptable_wave(double th, double ph, double 
 
 // The line search's per-instance setup after the Newton step (ls_setup_wave below)
 struct LsSetupArgs {
-  int32_t m;
-  const uint8_t* act;
-  const double *w, *dw, *dy, *c, *f, *g, *theta_k, *theta_min;
-  uint8_t* in_soft;
-  int32_t* soft_cnt;
-  uint8_t *tiny_last, *tiny_flag, *tiny_now, *soft_now;
-  double* a_min;
-  uint8_t* searching;
-  double *st_f, *st_g, *st_w, *st_alpha;
-  uint8_t* st_aug;
-  double* alpha;
-  uint8_t* any;
+  int32_t m = 0;
+  const uint8_t* act = nullptr;
+  const double *w = nullptr, *dw = nullptr, *dy = nullptr, *c = nullptr, *f = nullptr, *g = nullptr;
+  const double *theta_k = nullptr, *theta_min = nullptr;
+  uint8_t* in_soft = nullptr;
+  int32_t* soft_cnt = nullptr;
+  uint8_t *tiny_last = nullptr, *tiny_flag = nullptr, *tiny_now = nullptr, *soft_now = nullptr;
+  double* a_min = nullptr;
+  uint8_t* searching = nullptr;
+  double *st_f = nullptr, *st_g = nullptr, *st_w = nullptr, *st_alpha = nullptr;
+  uint8_t* st_aug = nullptr;
+  double* alpha = nullptr;
+  uint8_t* any = nullptr;
 };
 
 // The post-step quantities (cpl_ipm.hip's post-step kernel; the fused line-search kernel runs it as
 // its prologue: ipm_post_step_one below)
 struct PostStepArgs {
-  int32_t nw;
-  const double *w, *dw, *zL, *zU, *gphi, *mu, *tau;
-  const uint8_t *hasL, *hasU;
-  const double *wl0, *wu0, *theta, *theta_min;
-  const uint8_t* active;
-  const double* delta_w;
-  double *dwl, *dzL, *dzU, *a_max, *a_z, *gd_out;
-  uint8_t* switch_ok;
+  int32_t nw = 0;
+  const double *w = nullptr, *dw = nullptr, *zL = nullptr, *zU = nullptr, *gphi = nullptr, *mu = nullptr;
+  const double* tau = nullptr;
+  const uint8_t *hasL = nullptr, *hasU = nullptr;
+  const double *wl0 = nullptr, *wu0 = nullptr, *theta = nullptr, *theta_min = nullptr;
+  const uint8_t* active = nullptr;
+  const double* delta_w = nullptr;
+  double *dwl = nullptr, *dzL = nullptr, *dzU = nullptr, *a_max = nullptr, *a_z = nullptr, *gd_out = nullptr;
+  uint8_t* switch_ok = nullptr;
 };
 
 // The rest of the regular backtracking line search of every instance still searching after its
@@ -147,79 +149,79 @@ struct PostStepArgs {
 // ... until one is acceptable, alpha falls to alpha_min, or max_trials more trials were made
 // (batch_ipm.py regular_step, trials ls = 1 .. max_ls - 1).  Device pointers, rows of the batch.
 struct LsBacktrackArgs {
-  int64_t batch;
-  int32_t n, m, nf, nw, nfilt, max_trials;
-  const uint8_t* act;         // the instance iterates this iteration (active, not in restoration)
-  const uint8_t* tiny;        // tiny step this iteration (no line search)
-  const uint8_t* soft_now;    // in the soft restoration phase this iteration
-  const int32_t* soft_cnt;
-  uint8_t* searching;         // in/out
-  double* alpha;              // in/out: the next trial's step
-  const double* a_min;
-  const double* w;            // [batch, nw] the iterate
-  const double* dw;           // [batch, nw] the Newton step
-  const double* Xbase;        // [batch, n] fixed variables
-  const int32_t* freepos;     // [n] position in w of each variable, -1 fixed
-  const int32_t* row_slack;   // [m] slack of each inequality row, -1 equality
-  const double* gl;
-  const uint8_t* hasL;
-  const uint8_t* hasU;
-  const double* wl0;
-  const double* wu0;
-  const double* mu;
-  const double* theta_k;
-  const double* phi_k;
-  const double* gd;
-  const uint8_t* switch_ok;
-  const double* theta_max;
-  const double* filt_t;       // [batch, nfilt] the filter (after this iteration's barrier update)
-  const double* filt_p;
-  const double* mass;         // [batch] or NULL
-  const uint8_t* env_tag;     // [batch] (mixed batches) or NULL
-  double* st_f;               // the accepted trial: f, g, w, alpha, filter-augmenting
-  double* st_g;
-  double* st_w;
-  double* st_alpha;
-  uint8_t* st_aug;
+  int64_t batch = 0;
+  int32_t n = 0, m = 0, nf = 0, nw = 0, nfilt = 0, max_trials = 0;
+  const uint8_t* act = nullptr;         // the instance iterates this iteration (active, not in restoration)
+  const uint8_t* tiny = nullptr;        // tiny step this iteration (no line search)
+  const uint8_t* soft_now = nullptr;    // in the soft restoration phase this iteration
+  const int32_t* soft_cnt = nullptr;
+  uint8_t* searching = nullptr;         // in/out
+  double* alpha = nullptr;              // in/out: the next trial's step
+  const double* a_min = nullptr;
+  const double* w = nullptr;            // [batch, nw] the iterate
+  const double* dw = nullptr;           // [batch, nw] the Newton step
+  const double* Xbase = nullptr;        // [batch, n] fixed variables
+  const int32_t* freepos = nullptr;     // [n] position in w of each variable, -1 fixed
+  const int32_t* row_slack = nullptr;   // [m] slack of each inequality row, -1 equality
+  const double* gl = nullptr;
+  const uint8_t* hasL = nullptr;
+  const uint8_t* hasU = nullptr;
+  const double* wl0 = nullptr;
+  const double* wu0 = nullptr;
+  const double* mu = nullptr;
+  const double* theta_k = nullptr;
+  const double* phi_k = nullptr;
+  const double* gd = nullptr;
+  const uint8_t* switch_ok = nullptr;
+  const double* theta_max = nullptr;
+  const double* filt_t = nullptr;       // [batch, nfilt] the filter (after this iteration's barrier update)
+  const double* filt_p = nullptr;
+  const double* mass = nullptr;         // [batch] or NULL
+  const uint8_t* env_tag = nullptr;     // [batch] (mixed batches) or NULL
+  double* st_f = nullptr;               // the accepted trial: f, g, w, alpha, filter-augmenting
+  double* st_g = nullptr;
+  double* st_w = nullptr;
+  double* st_alpha = nullptr;
+  uint8_t* st_aug = nullptr;
   uint8_t* any;               // any[0] |= still searching (trials exhausted), any[1] |= soft candidate
   // restoration-phase search (resto != 0; batch_ipm.py resto_step): the trial also moves p, n along
   // dp, dn; theta = sum |c(w_t) - p_t + n_t|, phi = rho sum(p_t + n_t) + eta/2 |D_R (x_t - x_R)|^2 -
   // mu_R (sum log slacks + sum log p_t n_t); the flag is any[2]; no soft restoration
-  int32_t resto;
-  double rho;
-  const double* pR;
-  const double* nR;
-  const double* dp;
-  const double* dn;
-  const double* wR;
-  double* st_p;
-  double* st_n;
+  int32_t resto = 0;
+  double rho = 0.0;
+  const double* pR = nullptr;
+  const double* nR = nullptr;
+  const double* dp = nullptr;
+  const double* dn = nullptr;
+  const double* wR = nullptr;
+  double* st_p = nullptr;
+  double* st_n = nullptr;
   // first != 0 (regular search; systems the one-wave KKT kernel factorises): the kernel also makes
   // the first trial at alpha (alpha_max) and its up to max_soc second-order corrections (batch_ipm.py
   // regular_step, IPOPT's TrySecondOrderCorrection), re-solving with the factors the iteration's
   // factorisation kept (kkt_ws), before it backtracks — one launch for the whole search
-  int32_t first;
-  int32_t max_soc;
-  const double* c;            // [batch, m] c(w) at the iterate
-  const double* M;            // [batch, nw, nw] the Newton system's M
-  const double* r1;           // [batch, nw] its first right-hand side
-  const double* kkt_ws;       // cpl_kkt_solve's factor workspace (mode 0 of this iteration)
-  const double* tau;          // [batch] fraction-to-the-boundary parameter
+  int32_t first = 0;
+  int32_t max_soc = 0;
+  const double* c = nullptr;            // [batch, m] c(w) at the iterate
+  const double* M = nullptr;            // [batch, nw, nw] the Newton system's M
+  const double* r1 = nullptr;           // [batch, nw] its first right-hand side
+  const double* kkt_ws = nullptr;       // cpl_kkt_solve's factor workspace (mode 0 of this iteration)
+  const double* tau = nullptr;          // [batch] fraction-to-the-boundary parameter
   // soft_ws != NULL (the small-batch iteration, P_FUSED): the kernel's tail also starts IPOPT's soft
   // restoration step (the solver's k_soft_begin, which would be the next launch): soft_try = no
   // accepted trial (or in the soft phase within its budget), a_soft = min(alpha_max, alpha_z), the
   // point soft_ws = w + a_soft dw on those instances (= w elsewhere) and its X = unpack(soft_ws)
-  const double* a_max;
-  const double* a_z;
-  double* soft_ws;
-  double* soft_X;
-  uint8_t* soft_try;
-  double* a_soft;
+  const double* a_max = nullptr;
+  const double* a_z = nullptr;
+  double* soft_ws = nullptr;
+  double* soft_X = nullptr;
+  uint8_t* soft_try = nullptr;
+  double* a_soft = nullptr;
   // (FIRST) the post-step quantities and the search's setup of every instance, computed in the
   // kernel's prologue (with_post) instead of a launch of their own
   PostStepArgs post;
   LsSetupArgs setup;
-  int32_t with_post;
+  int32_t with_post = 0;
   // IPOPT's NLP scaling (cpl_solve_options.nlp_scaling): the trial's f times df[b], its g times
   // dc[b, r] (the scaled problem's values, as the solver's k_apply_scaling); nullptr: unscaled
   const double* df = nullptr;

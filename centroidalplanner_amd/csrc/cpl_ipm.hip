@@ -570,18 +570,14 @@ double ipm_mu_min(double tol) { return fmin(tol, 1e-4) / 11.0; }
 
 
 // cpl_ipm_post_step with the solve loop's line-search setup fused in (ls != NULL: LsSetupArgs)
-int32_t ipm_post_step_ex(int64_t batch, int32_t nw, const double* d_w, const double* d_dw, const double* d_zL,
-                         const double* d_zU, const double* d_gphi, const double* d_mu, const double* d_tau,
-                         const uint8_t* d_hasL, const uint8_t* d_hasU, const double* d_wl0, const double* d_wu0,
-                         const double* d_theta, const double* d_theta_min, const uint8_t* d_active,
-                         const double* d_delta_w, double* d_dwl, double* d_dzL, double* d_dzU, double* d_a_max,
-                         double* d_a_z, double* d_gd, uint8_t* d_switch_ok, const LsSetupArgs* ls, void* stream) {
-  LsSetupArgs L{};
-  if (ls) L = *ls;
-  const PostStepArgs P{(int32_t)nw, d_w, d_dw, d_zL, d_zU, d_gphi, d_mu, d_tau, d_hasL, d_hasU, d_wl0, d_wu0,
-                       d_theta, d_theta_min, d_active, d_delta_w, d_dwl, d_dzL, d_dzU, d_a_max, d_a_z, d_gd,
-                       d_switch_ok};
+int32_t ipm_post_step_ex(int64_t batch, const PostStepArgs& P, const LsSetupArgs* ls, void* stream) {
+  const LsSetupArgs L = ls ? *ls : LsSetupArgs{};
   IPM_LAUNCH(cpl_ipm_post_step_kernel, "cpl_ipm_post_step", batch, P, L);
+}
+
+// cpl_ipm_accept on the engine's argument block
+int32_t ipm_accept_ex(int64_t batch, const IpmAcceptArgs& a, void* stream) {
+  IPM_LAUNCH(cpl_ipm_accept_kernel, "cpl_ipm_accept", a, batch);
 }
 
 // cpl_ipm_optimality with the engine's extras: mu_rounds barrier decreases at most, the floor
@@ -744,9 +740,10 @@ int32_t cpl_ipm_post_step(int64_t batch, int32_t nw, const double* d_w, const do
       !d_theta || !d_theta_min || !d_active || !d_delta_w || !d_dwl || !d_dzL || !d_dzU || !d_a_max || !d_a_z ||
       !d_gd || !d_switch_ok)
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_post_step: missing buffer");
-  return ipm_post_step_ex(batch, nw, d_w, d_dw, d_zL, d_zU, d_gphi, d_mu, d_tau, d_hasL, d_hasU, d_wl0, d_wu0, d_theta,
-                          d_theta_min, d_active, d_delta_w, d_dwl, d_dzL, d_dzU, d_a_max, d_a_z, d_gd, d_switch_ok,
-                          nullptr, stream);
+  const PostStepArgs P{(int32_t)nw, d_w, d_dw, d_zL, d_zU, d_gphi, d_mu, d_tau, d_hasL, d_hasU, d_wl0, d_wu0,
+                       d_theta, d_theta_min, d_active, d_delta_w, d_dwl, d_dzL, d_dzU, d_a_max, d_a_z, d_gd,
+                       d_switch_ok};
+  return ipm_post_step_ex(batch, P, nullptr, stream);
 }
 
 int32_t cpl_ipm_accept(int64_t batch, int32_t nw, int32_t m, int32_t nfilt, const uint8_t* d_active,
@@ -768,7 +765,7 @@ int32_t cpl_ipm_accept(int64_t batch, int32_t nw, int32_t m, int32_t nfilt, cons
                         d_phi, d_filt_t_in, d_filt_p_in, d_fcount_in, d_w_new, d_dy, d_dzL, d_dzU, d_mu, d_hasL,
                         d_hasU, d_wl0, d_wu0, d_w, d_y, d_zL, d_zU, d_mu_state, d_iters, d_filt_t, d_filt_p,
                         d_fcount};
-  IPM_LAUNCH(cpl_ipm_accept_kernel, "cpl_ipm_accept", a, batch);
+  return ipm_accept_ex(batch, a, stream);
 }
 
 int32_t cpl_ipm_masked_rows(int64_t batch, int64_t row_len, const uint8_t* d_mask, const double* d_src, double* d_dst,

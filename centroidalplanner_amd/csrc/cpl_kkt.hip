@@ -1123,21 +1123,28 @@ static bool kkt_use_w4(int64_t batch) {
   }();
   return forced == 1 || (forced == 0 && batch <= KKT_W4_MAX);
 }
-static KktWaveKernel kkt_wave_kernel_for(int nw, int m) {
+// the one-wave kernel's two instantiations for a system size (nullptr: that size takes the workgroup kernel)
+struct KktWaveKernels {
+  KktWaveKernel w1 = nullptr, w4 = nullptr;  // one wave per system; four (the factorisation of small batches)
+};
+template <int NW, int M>
+static KktWaveKernels kkt_wave_kernels() {
+  return KktWaveKernels{cpl_kkt_wave_kernel<NW, M>, cpl_kkt_wave_kernel<NW, M, true>};
+}
+static KktWaveKernels kkt_wave_kernel_for(int nw, int m) {
   static const int forced = [] {
     const char* e = std::getenv("CPL_KKT_KERNEL");
     if (!e) return 0;
     return std::string(e) == "block" ? 1 : (std::string(e) == "wave" ? 2 : 0);
   }();
-  KktWaveKernel wk = nullptr;
-  if (nw == 47 && m == 30) wk = cpl_kkt_wave_kernel<47, 30>;
-  if (!wk || forced == 1) return nullptr;
-  return wk;
+  if (forced == 1) return {};
+  if (nw == 47 && m == 30) return kkt_wave_kernels<47, 30>();
+  return {};
 }
 
 // the system size runs the one-wave kernel (whose factors the fused line-search kernel re-solves with)
 namespace cpl {
-bool kkt_wave_size(int nw, int m) { return kkt_wave_kernel_for(nw, m) != nullptr; }
+bool kkt_wave_size(int nw, int m) { return kkt_wave_kernel_for(nw, m).w1 != nullptr; }
 
 // IPOPT's Jacobian regularisation (cpl_kkt_aug_kernel): its workspace doubles per system, or -1 when
 // the augmented system (nw + m unknowns) exceeds the workgroup kernel (128 unknowns, one LDS image)
@@ -1204,11 +1211,10 @@ int32_t cpl_kkt_solve(int32_t mode, int64_t batch, int32_t nw, int32_t m, const 
   if (mode == 0 && (!d_mu || !d_delta_w || !d_delta_c || !d_info))
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_kkt_solve: factorisation needs mu, delta_w, delta_c, info");
   if (batch > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_kkt_solve: batch too large");
-  if (KktWaveKernel wk = kkt_wave_kernel_for(nw, m)) {
+  if (const KktWaveKernels wk = kkt_wave_kernel_for(nw, m); wk.w1) {
     const size_t lds = sizeof(double) * (size_t)kktw_lds_doubles(nw, m);
     const bool w4 = mode == 0 && kkt_use_w4(batch);
-    const KktWaveKernel k = w4 ? static_cast<KktWaveKernel>(cpl_kkt_wave_kernel<47, 30, true>) : wk;
-    hipLaunchKernelGGL(k, dim3((unsigned)batch), dim3(w4 ? 256 : 64), lds,
+    hipLaunchKernelGGL(w4 ? wk.w4 : wk.w1, dim3((unsigned)batch), dim3(w4 ? 256 : 64), lds,
                        (hipStream_t)stream, (int)mode, batch, d_M, d_A, d_r1, d_r2, d_mu, d_delta_w_last, d_active, d_dw,
                        d_dy, d_delta_w, d_delta_c, d_info, d_ws);
   } else {

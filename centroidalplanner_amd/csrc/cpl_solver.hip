@@ -57,12 +57,9 @@ int32_t kkt_aug_solve(int mode, int64_t batch, int nw, int m, const double* d_M,
                       hipStream_t st);
 bool ls_post_prologue(int64_t batch);
 // cpl_ipm.hip: the post-step kernel with the line-search setup (LsSetupArgs) as its tail
-int32_t ipm_post_step_ex(int64_t batch, int32_t nw, const double* d_w, const double* d_dw, const double* d_zL,
-                         const double* d_zU, const double* d_gphi, const double* d_mu, const double* d_tau,
-                         const uint8_t* d_hasL, const uint8_t* d_hasU, const double* d_wl0, const double* d_wu0,
-                         const double* d_theta, const double* d_theta_min, const uint8_t* d_active,
-                         const double* d_delta_w, double* d_dwl, double* d_dzL, double* d_dzU, double* d_a_max,
-                         double* d_a_z, double* d_gd, uint8_t* d_switch_ok, const LsSetupArgs* ls, void* stream);
+int32_t ipm_post_step_ex(int64_t batch, const PostStepArgs& P, const LsSetupArgs* ls, void* stream);
+// cpl_ipm.hip: cpl_ipm_accept on the argument block the restoration entry also takes
+int32_t ipm_accept_ex(int64_t batch, const IpmAcceptArgs& a, void* stream);
 // cpl_ipm.hip: the optimality test + monotone barrier update with IPOPT's per-iteration rounds
 double ipm_mu_min(double tol);
 int32_t ipm_optimality_ex(int64_t batch, int32_t nw, int32_t m, int32_t fmax, int32_t nbounds, double tol,
@@ -89,6 +86,36 @@ constexpr int WPB = 4;            // instances per 256-thread workgroup (one wav
 
 inline unsigned blocks_for(int64_t batch) { return (unsigned)((batch + WPB - 1) / WPB); }
 inline unsigned blocks_elems(int64_t total) { return (unsigned)((total + 255) / 256); }
+
+// ---- the solver's buffers grouped by meaning: the wide kernels below take these groups inside one
+// by-value argument struct (built from the solver by the functions after `struct cpl_solver`), and
+// unpack a group with a structured binding — every buffer is named once per group, not once per
+// position of a 50-pointer list.  No member is __restrict__: several kernels store to the iterate or
+// the staged trial through one group and read it through another.
+struct Bounds {  // of w = [x_free, s]: which are finite, and their (relaxed) values
+  const uint8_t *hasL = nullptr, *hasU = nullptr;
+  const double *wl0 = nullptr, *wu0 = nullptr;
+};
+struct Iterate {  // the primal-dual iterate (the restoration phase's: its own bound multipliers)
+  double *w = nullptr, *y = nullptr, *zL = nullptr, *zU = nullptr;
+};
+struct Step {  // the Newton step
+  double *dw = nullptr, *dy = nullptr, *dzL = nullptr, *dzU = nullptr;
+};
+struct Staged {  // the accepted trial of the current search (p, n: the restoration phase's)
+  double *f = nullptr, *g = nullptr, *w = nullptr, *alpha = nullptr;
+  uint8_t* aug = nullptr;
+  double *p = nullptr, *n = nullptr;
+};
+struct Search {  // a line search's state: the regular one, and the restoration phase's own
+  uint8_t *act = nullptr, *searching = nullptr;
+  double *alpha = nullptr, *a_min = nullptr, *mu = nullptr, *theta = nullptr, *phi = nullptr, *gd = nullptr;
+  uint8_t* switch_ok = nullptr;
+  double *theta_max = nullptr, *filt_t = nullptr, *filt_p = nullptr;
+};
+struct RestoVars {  // the restoration problem's own variables and their multipliers
+  double *wR = nullptr, *pR = nullptr, *nR = nullptr, *zp = nullptr, *zn = nullptr;
+};
 
 __device__ __forceinline__ double wave_sum(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -140,57 +167,64 @@ __global__ void k_start_x(int64_t total, int n, const int32_t* __restrict__ free
 // the starting state of every instance (one wave each): w0 = push([x_free, g_I]), bound multipliers
 // 1, theta_0 and the filter's theta_max / theta_min, mu, flags; gw0 and the least-squares system's
 // right-hand side r1 = -(gw0 - zL0 + zU0) (the multiplier estimate is one KKT solve with M = I)
-__global__ __launch_bounds__(256) void k_init_state(
-    int64_t B, int n, int m, int nf, int nw, const int32_t* __restrict__ free_idx, const int32_t* __restrict__ ineq_row,
-    const int32_t* __restrict__ row_slack, const double* __restrict__ gl, const uint8_t* __restrict__ hasL,
-    const uint8_t* __restrict__ hasU, const double* __restrict__ wl0, const double* __restrict__ wu0, double mu_init,
-    const double* __restrict__ X, const double* __restrict__ g, const double* __restrict__ grad,
-    double* __restrict__ w, double* __restrict__ zL, double* __restrict__ zU, double* __restrict__ theta_max,
-    double* __restrict__ theta_min, double* __restrict__ mu, uint8_t* __restrict__ active,
-    int64_t* __restrict__ status, int64_t* __restrict__ iters, int64_t* __restrict__ acc, double* __restrict__ filt_t,
-    double* __restrict__ filt_p, int64_t* __restrict__ fcount, double* __restrict__ dwl, double* __restrict__ d_inf,
-    uint8_t* __restrict__ lm_cnt, uint8_t* __restrict__ lm_skip, double* __restrict__ r1, double* __restrict__ r2, double* __restrict__ M) {
+struct InitStateArgs {
+  int n = 0, m = 0, nf = 0, nw = 0;
+  double mu_init = 0.0;
+  const int32_t *free_idx = nullptr, *ineq_row = nullptr, *row_slack = nullptr;
+  const double *gl = nullptr, *X = nullptr, *g = nullptr, *grad = nullptr;
+  Bounds bd;
+  Iterate it;
+  double *theta_max = nullptr, *theta_min = nullptr, *mu = nullptr, *filt_t = nullptr, *filt_p = nullptr;
+  double *dwl = nullptr, *d_inf = nullptr, *r1 = nullptr, *r2 = nullptr, *M = nullptr;
+  uint8_t *active = nullptr, *lm_cnt = nullptr, *lm_skip = nullptr;
+  int64_t *status = nullptr, *iters = nullptr, *acc = nullptr, *fcount = nullptr;
+};
+__global__ __launch_bounds__(256) void k_init_state(int64_t B, const InitStateArgs a) {
   const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
   if (b >= B) return;
   const int lane = threadIdx.x & 63;
+  const int n = a.n, m = a.m, nf = a.nf, nw = a.nw;
+  const auto [hasL, hasU, wl0, wu0] = a.bd;
+  const auto [w, y, zL, zU] = a.it;
   double* wb = w + b * nw;
   for (int k = lane; k < nw; k += 64) {
-    const double v = k < nf ? X[b * n + free_idx[k]] : g[b * m + ineq_row[k - nf]];
+    const double v = k < nf ? a.X[b * n + a.free_idx[k]] : a.g[b * m + a.ineq_row[k - nf]];
     const bool hl = hasL[k], hu = hasU[k];
     wb[k] = push_into(v, hl, hu, wl0[k], wu0[k]);
     const double zl = hl ? 1.0 : 0.0, zu = hu ? 1.0 : 0.0;
     zL[b * nw + k] = zl;
     zU[b * nw + k] = zu;
-    const double gw = k < nf ? grad[b * n + free_idx[k]] : 0.0;
-    r1[b * nw + k] = -((gw - zl) + zu);
-    for (int j = 0; j < nw; ++j) M[(b * nw + k) * nw + j] = j == k ? 1.0 : 0.0;
+    const double gw = k < nf ? a.grad[b * n + a.free_idx[k]] : 0.0;
+    a.r1[b * nw + k] = -((gw - zl) + zu);
+    for (int j = 0; j < nw; ++j) a.M[(b * nw + k) * nw + j] = j == k ? 1.0 : 0.0;
   }
   double th = 0.0;
   for (int r = lane; r < m; r += 64) {  // (the slack recomputed: this lane did not write it)
-    const int sl = row_slack[r];
-    const double gv = g[b * m + r];
-    const double c = sl >= 0 ? gv - push_into(gv, hasL[nf + sl], hasU[nf + sl], wl0[nf + sl], wu0[nf + sl]) : gv - gl[r];
+    const int sl = a.row_slack[r];
+    const double gv = a.g[b * m + r];
+    const double c =
+        sl >= 0 ? gv - push_into(gv, hasL[nf + sl], hasU[nf + sl], wl0[nf + sl], wu0[nf + sl]) : gv - a.gl[r];
     th += fabs(c);
-    r2[b * m + r] = 0.0;
+    a.r2[b * m + r] = 0.0;
   }
   th = wave_sum(th);
   for (int k = lane; k < FMAX; k += 64) {
-    filt_t[b * FMAX + k] = INFINITY;
-    filt_p[b * FMAX + k] = INFINITY;
+    a.filt_t[b * FMAX + k] = INFINITY;
+    a.filt_p[b * FMAX + k] = INFINITY;
   }
   if (lane == 0) {
-    theta_max[b] = 1e4 * fmax(th, 1.0);
-    theta_min[b] = 1e-4 * fmax(th, 1.0);
-    mu[b] = mu_init;
-    active[b] = 1;
-    status[b] = CPL_SOLVE_MAX_ITER;
-    iters[b] = 0;
-    acc[b] = 0;
-    fcount[b] = 0;
-    dwl[b] = 0.0;
-    d_inf[b] = 0.0;
-    lm_cnt[b] = 0;
-    lm_skip[b] = 0;
+    a.theta_max[b] = 1e4 * fmax(th, 1.0);
+    a.theta_min[b] = 1e-4 * fmax(th, 1.0);
+    a.mu[b] = a.mu_init;
+    a.active[b] = 1;
+    a.status[b] = CPL_SOLVE_MAX_ITER;
+    a.iters[b] = 0;
+    a.acc[b] = 0;
+    a.fcount[b] = 0;
+    a.dwl[b] = 0.0;
+    a.d_inf[b] = 0.0;
+    a.lm_cnt[b] = 0;
+    a.lm_skip[b] = 0;
   }
 }
 
@@ -477,26 +511,41 @@ __global__ void k_halve2(int64_t B, uint8_t* __restrict__ searching, double* __r
 // IPOPT's soft restoration step, part 1 (BacktrackingLineSearch::TrySoftRestoStep): the instances
 // without an accepted trial (or in the soft phase, at most max_soft_resto_iters times) try the full
 // primal-dual step alpha = min(alpha_primal_max, alpha_dual_max): its point w + alpha dw and X
-__global__ __launch_bounds__(256) void k_soft_begin(
-    int64_t B, int n, int nf, int nw, const uint8_t* __restrict__ act, const uint8_t* __restrict__ tiny,
-    const uint8_t* __restrict__ soft_now, const int32_t* __restrict__ soft_cnt, const double* __restrict__ st_alpha,
-    const double* __restrict__ a_max, const double* __restrict__ a_z, const double* __restrict__ w,
-    const double* __restrict__ dw, const int32_t* __restrict__ freepos, const double* __restrict__ Xbase,
-    uint8_t* __restrict__ soft_try, double* __restrict__ a_soft, double* __restrict__ ws, double* __restrict__ X) {
+struct SoftStepArgs {  // the soft step's buffers: k_soft_begin starts it, k_soft_judge(_fail) judge it
+  int n = 0, m = 0, nf = 0, nw = 0, nnz_rec = 0;
+  const int32_t *amap = nullptr, *row_slack = nullptr, *free32 = nullptr, *freepos = nullptr;
+  const double *gl = nullptr, *Xbase = nullptr;
+  Bounds bd;
+  Iterate it;
+  Step sp;
+  Search ls;
+  Staged st;
+  const uint8_t *tiny = nullptr, *soft_now = nullptr;
+  uint8_t *soft_try = nullptr, *in_soft = nullptr;
+  int32_t* soft_cnt = nullptr;
+  double *a_soft = nullptr, *ws = nullptr, *Xs = nullptr;  // the step's length, its point, X = unpack(ws)
+  const double *f_s = nullptr, *grad_s = nullptr, *g_s = nullptr, *J_s = nullptr;  // the callbacks there
+  const double *A = nullptr, *gradw = nullptr, *c = nullptr;                       // ... and at the iterate
+  const double* a_max = nullptr;
+  double *a_z = nullptr, *cs_tmp = nullptr;
+};
+__global__ __launch_bounds__(256) void k_soft_begin(int64_t B, const SoftStepArgs a) {
   const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
   if (b >= B) return;
   const int lane = threadIdx.x & 63;
-  const bool t = act[b] && !tiny[b] &&
-                 ((soft_now[b] && soft_cnt[b] <= MAX_SOFT_RESTO) || (!soft_now[b] && !(st_alpha[b] > 0.0)));
-  const double as = fmin(a_max[b], a_z[b]);
-  for (int k = lane; k < nw; k += 64) ws[b * nw + k] = w[b * nw + k] + (t ? as : 0.0) * dw[b * nw + k];
+  const int n = a.n, nw = a.nw;
+  const double *w = a.it.w, *dw = a.sp.dw;
+  const bool t = a.ls.act[b] && !a.tiny[b] &&
+                 ((a.soft_now[b] && a.soft_cnt[b] <= MAX_SOFT_RESTO) || (!a.soft_now[b] && !(a.st.alpha[b] > 0.0)));
+  const double as = fmin(a.a_max[b], a.a_z[b]);
+  for (int k = lane; k < nw; k += 64) a.ws[b * nw + k] = w[b * nw + k] + (t ? as : 0.0) * dw[b * nw + k];
   for (int j = lane; j < n; j += 64) {
-    const int k = freepos[j];
-    X[b * n + j] = k >= 0 ? w[b * nw + k] + (t ? as : 0.0) * dw[b * nw + k] : Xbase[b * n + j];
+    const int k = a.freepos[j];
+    a.Xs[b * n + j] = k >= 0 ? w[b * nw + k] + (t ? as : 0.0) * dw[b * nw + k] : a.Xbase[b * n + j];
   }
   if (lane == 0) {
-    soft_try[b] = t ? 1 : 0;
-    a_soft[b] = as;
+    a.soft_try[b] = t ? 1 : 0;
+    a.a_soft[b] = as;
   }
 }
 
@@ -543,25 +592,19 @@ __device__ __forceinline__ double pd_error_wave(int m, int nf, int nw, const dou
 // part 2: the soft step is taken when the original filter / current iterate accept it (the soft
 // phase ends) or when it cuts the primal-dual error by soft_resto_pderror_reduction_factor (the
 // soft phase starts or continues); the step's alpha then also moves the bound multipliers
-__device__ __forceinline__ void soft_judge_wave(
-    int64_t b, int64_t B, int n, int m, int nf, int nw, int nnz_rec, const uint8_t* __restrict__ soft_try,
-    const uint8_t* __restrict__ soft_now, const double* __restrict__ a_soft, const int32_t* __restrict__ amap,
-    const int32_t* __restrict__ row_slack, const int32_t* __restrict__ free32, const double* __restrict__ gl,
-    const uint8_t* __restrict__ hasL, const uint8_t* __restrict__ hasU, const double* __restrict__ wl0,
-    const double* __restrict__ wu0, const double* __restrict__ ws, const double* __restrict__ f_s,
-    const double* __restrict__ grad_s, const double* __restrict__ g_s, const double* __restrict__ J_s,
-    const double* __restrict__ A, const double* __restrict__ gradw, const double* __restrict__ c,
-    const double* __restrict__ w, const double* __restrict__ y, const double* __restrict__ zL,
-    const double* __restrict__ zU, const double* __restrict__ dy, const double* __restrict__ dzL,
-    const double* __restrict__ dzU, const double* __restrict__ mu, const double* __restrict__ theta_k,
-    const double* __restrict__ phi_k, const double* __restrict__ gd, const uint8_t* __restrict__ switch_ok,
-    const double* __restrict__ theta_max, const double* __restrict__ ft, const double* __restrict__ fp,
-    double* __restrict__ cs_tmp, uint8_t* __restrict__ in_soft, int32_t* __restrict__ soft_cnt,
-    double* __restrict__ st_f, double* __restrict__ st_g, double* __restrict__ st_w, double* __restrict__ st_alpha,
-    uint8_t* __restrict__ st_aug, double* __restrict__ a_z) {
+__device__ __forceinline__ void soft_judge_wave(int64_t b, const SoftStepArgs& a) {
+  const int n = a.n, m = a.m, nf = a.nf, nw = a.nw, nnz_rec = a.nnz_rec;
+  const auto [hasL, hasU, wl0, wu0] = a.bd;
+  const auto [w, y, zL, zU] = a.it;
+  const auto [dw, dy, dzL, dzU] = a.sp;
+  const auto [act, searching, alpha, a_min, mu, theta_k, phi_k, gd, switch_ok, theta_max, ft, fp] = a.ls;
+  const auto [st_f, st_g, st_w, st_alpha, st_aug, st_p, st_n] = a.st;
+  const int32_t *amap = a.amap, *row_slack = a.row_slack, *free32 = a.free32;
+  const double *gl = a.gl, *ws = a.ws, *f_s = a.f_s, *grad_s = a.grad_s, *g_s = a.g_s, *J_s = a.J_s;
+  double* cs_tmp = a.cs_tmp;
   const int lane = threadIdx.x & 63;
   const double* wb = ws + b * nw;
-  const double mub = mu[b], as = a_soft[b];
+  const double mub = mu[b], as = a.a_soft[b];
   double th = 0.0, lg = 0.0;
   for (int r = lane; r < m; r += 64) {
     const double cr = cons_row(g_s + b * m, wb, nf, r, row_slack, gl);
@@ -582,8 +625,8 @@ __device__ __forceinline__ void soft_judge_wave(
   const double pd_t = pd_error_wave(m, nf, nw, nullptr, J_s + b * (int64_t)nnz_rec, amap, row_slack, grad_s + b * n, 1,
                                     free32, cs_tmp + b * m, wb, y + b * m, zL + b * nw, zU + b * nw, nullptr,
                                     dy + b * m, dzL + b * nw, dzU + b * nw, as, hasL, hasU, wl0, wu0, mub);
-  const double pd_c = pd_error_wave(m, nf, nw, A + b * (int64_t)m * nw, nullptr, amap, row_slack, gradw + b * nw, 0,
-                                    free32, c + b * m, w + b * nw, y + b * m, zL + b * nw, zU + b * nw, nullptr,
+  const double pd_c = pd_error_wave(m, nf, nw, a.A + b * (int64_t)m * nw, nullptr, amap, row_slack, a.gradw + b * nw, 0,
+                                    free32, a.c + b * m, w + b * nw, y + b * m, zL + b * nw, zU + b * nw, nullptr,
                                     nullptr, nullptr, nullptr, 0.0, hasL, hasU, wl0, wu0, mub);
   const bool ok = isfinite(th) && isfinite(ph) && (orig_ok || pd_t <= SOFT_RESTO_FACTOR * pd_c);
   if (ok) {
@@ -595,36 +638,19 @@ __device__ __forceinline__ void soft_judge_wave(
       st_f[b] = f_s[b];
       st_alpha[b] = as;
       st_aug[b] = 0;
-      a_z[b] = as;
+      a.a_z[b] = as;
     }
     const bool left = ok && orig_ok;
-    if (left) in_soft[b] = 0;
-    else if (ok) in_soft[b] = 1;
-    if (left || (ok && !soft_now[b])) soft_cnt[b] = 0;
+    if (left) a.in_soft[b] = 0;
+    else if (ok) a.in_soft[b] = 1;
+    if (left || (ok && !a.soft_now[b])) a.soft_cnt[b] = 0;
   }
 }
 
-__global__ __launch_bounds__(256) void k_soft_judge(
-    int64_t B, int n, int m, int nf, int nw, int nnz_rec, const uint8_t* __restrict__ soft_try,
-    const uint8_t* __restrict__ soft_now, const double* __restrict__ a_soft, const int32_t* __restrict__ amap,
-    const int32_t* __restrict__ row_slack, const int32_t* __restrict__ free32, const double* __restrict__ gl,
-    const uint8_t* __restrict__ hasL, const uint8_t* __restrict__ hasU, const double* __restrict__ wl0,
-    const double* __restrict__ wu0, const double* __restrict__ ws, const double* __restrict__ f_s,
-    const double* __restrict__ grad_s, const double* __restrict__ g_s, const double* __restrict__ J_s,
-    const double* __restrict__ A, const double* __restrict__ gradw, const double* __restrict__ c,
-    const double* __restrict__ w, const double* __restrict__ y, const double* __restrict__ zL,
-    const double* __restrict__ zU, const double* __restrict__ dy, const double* __restrict__ dzL,
-    const double* __restrict__ dzU, const double* __restrict__ mu, const double* __restrict__ theta_k,
-    const double* __restrict__ phi_k, const double* __restrict__ gd, const uint8_t* __restrict__ switch_ok,
-    const double* __restrict__ theta_max, const double* __restrict__ ft, const double* __restrict__ fp,
-    double* __restrict__ cs_tmp, uint8_t* __restrict__ in_soft, int32_t* __restrict__ soft_cnt,
-    double* __restrict__ st_f, double* __restrict__ st_g, double* __restrict__ st_w, double* __restrict__ st_alpha,
-    uint8_t* __restrict__ st_aug, double* __restrict__ a_z) {
+__global__ __launch_bounds__(256) void k_soft_judge(int64_t B, const SoftStepArgs a) {
   const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B || !soft_try[b]) return;
-  soft_judge_wave(b, B, n, m, nf, nw, nnz_rec, soft_try, soft_now, a_soft, amap, row_slack, free32, gl, hasL, hasU, wl0,
-                  wu0, ws, f_s, grad_s, g_s, J_s, A, gradw, c, w, y, zL, zU, dy, dzL, dzU, mu, theta_k, phi_k, gd,
-                  switch_ok, theta_max, ft, fp, cs_tmp, in_soft, soft_cnt, st_f, st_g, st_w, st_alpha, st_aug, a_z);
+  if (b >= B || !a.soft_try[b]) return;
+  soft_judge_wave(b, a);
 }
 
 // the end of the regular line search: failed = no accepted point (-> the restoration phase),
@@ -642,16 +668,28 @@ struct NearFeasible {
   const double *acc_w, *acc_y, *acc_zL, *acc_zU;
   double *w, *y, *zL, *zU;
 };
+// ... together with the accepted point's X = unpack(st_w): the end of the search
+struct FailTail {
+  int n = 0, nw = 0;
+  const int32_t* freepos = nullptr;
+  const double* Xbase = nullptr;
+  double* X = nullptr;
+  const uint8_t* act = nullptr;
+  Staged st;
+  const double* err0 = nullptr;
+  double acc_tol = 0.0;
+  uint8_t *failed = nullptr, *moved = nullptr, *in_soft = nullptr;
+  int32_t* soft_cnt = nullptr;
+  int64_t* status = nullptr;
+  uint8_t* active = nullptr;
+  NearFeasible nf;
+};
 // The bookkeeping of instance b:
-__device__ __forceinline__ void fail_book(int64_t b, const uint8_t* __restrict__ act,
-                                          const double* __restrict__ st_alpha, const double* __restrict__ err0,
-                                          double acc_tol, uint8_t* __restrict__ failed, uint8_t* __restrict__ moved,
-                                          uint8_t* __restrict__ in_soft, int32_t* __restrict__ soft_cnt,
-                                          int64_t* __restrict__ status, uint8_t* __restrict__ active,
-                                          const NearFeasible& nf) {
-  const bool a = act[b] != 0;
-  bool f = a && !(st_alpha[b] > 0.0);
-  const bool at_acc = f && err0[b] <= acc_tol;
+__device__ __forceinline__ void fail_book(int64_t b, const FailTail& t) {
+  const NearFeasible& nf = t.nf;
+  const bool a = t.act[b] != 0;
+  bool f = a && !(t.st.alpha[b] > 0.0);
+  const bool at_acc = f && t.err0[b] <= t.acc_tol;
   const bool near = f && !at_acc && nf.theta_k[b] <= nf.near_tol;
   if (at_acc || near) {
     const bool back = near && nf.has_acc[b] != 0;
@@ -665,36 +703,31 @@ __device__ __forceinline__ void fail_book(int64_t b, const uint8_t* __restrict__
       for (int r = 0; r < m; ++r) nf.y[b * m + r] = nf.acc_y[b * m + r];
       nf.has_acc[b] = 0;
     }
-    status[b] = (at_acc || back) ? CPL_SOLVE_ACCEPTABLE : CPL_SOLVE_RESTO_FAILED;
-    active[b] = 0;
-    failed[b] = 0;
-    moved[b] = 0;
+    t.status[b] = (at_acc || back) ? CPL_SOLVE_ACCEPTABLE : CPL_SOLVE_RESTO_FAILED;
+    t.active[b] = 0;
+    t.failed[b] = 0;
+    t.moved[b] = 0;
     return;
   }
-  failed[b] = f ? 1 : 0;
-  moved[b] = (a && !f) ? 1 : 0;
+  t.failed[b] = f ? 1 : 0;
+  t.moved[b] = (a && !f) ? 1 : 0;
   if (f) {
-    in_soft[b] = 0;
-    soft_cnt[b] = 0;
+    t.in_soft[b] = 0;
+    t.soft_cnt[b] = 0;
   }
 }
 
-// ... in the same launch as the accepted points' X = unpack(st_w) (an element per thread; the first
-// element of each instance also does that instance's bookkeeping — which does not touch st_w)
-__global__ void k_fail_unpack(int64_t total, int n, int nw, const int32_t* __restrict__ freepos,
-                              const double* __restrict__ Xbase, const double* __restrict__ st_w, double* __restrict__ X,
-                              const uint8_t* __restrict__ act, const double* __restrict__ st_alpha,
-                              const double* __restrict__ err0, double acc_tol, uint8_t* __restrict__ failed,
-                              uint8_t* __restrict__ moved, uint8_t* __restrict__ in_soft, int32_t* __restrict__ soft_cnt,
-                              int64_t* __restrict__ status, uint8_t* __restrict__ active, const NearFeasible nf) {
+// ... in one launch (an element per thread; the first element of each instance also does that
+// instance's bookkeeping — which does not touch st_w)
+__global__ void k_fail_unpack(int64_t total, const FailTail t) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= total) return;
-  const int64_t b = e / n;
-  const int j = (int)(e - b * n);
-  const int k = freepos[j];
-  X[e] = k >= 0 ? st_w[b * nw + k] : Xbase[e];
+  const int64_t b = e / t.n;
+  const int j = (int)(e - b * t.n);
+  const int k = t.freepos[j];
+  t.X[e] = k >= 0 ? t.st.w[b * t.nw + k] : t.Xbase[e];
   if (j != 0) return;
-  fail_book(b, act, st_alpha, err0, acc_tol, failed, moved, in_soft, soft_cnt, status, active, nf);
+  fail_book(b, t);
 }
 
 // The small-batch iteration (P_FUSED) runs the soft step's judge and the end of the search as one
@@ -702,52 +735,18 @@ __global__ void k_fail_unpack(int64_t total, int n, int nw, const int32_t* __res
 // written by the same wave, made visible to the wave's other lanes by a workgroup fence — the
 // accepted point's X = unpack(st_w) and the bookkeeping.  The same operations on the same values
 // as k_soft_judge + k_fail_unpack.
-struct FailTail {
-  const int32_t* freepos;
-  const double* Xbase;
-  double* X;
-  const uint8_t* act;
-  const double* err0;
-  double acc_tol;
-  uint8_t* failed;
-  uint8_t* moved;
-  int64_t* status;
-  uint8_t* active;
-  NearFeasible nf;
-};
-__global__ __launch_bounds__(256) void k_soft_judge_fail(
-    int64_t B, int n, int m, int nf, int nw, int nnz_rec, const uint8_t* __restrict__ soft_try,
-    const uint8_t* __restrict__ soft_now, const double* __restrict__ a_soft, const int32_t* __restrict__ amap,
-    const int32_t* __restrict__ row_slack, const int32_t* __restrict__ free32, const double* __restrict__ gl,
-    const uint8_t* __restrict__ hasL, const uint8_t* __restrict__ hasU, const double* __restrict__ wl0,
-    const double* __restrict__ wu0, const double* __restrict__ ws, const double* __restrict__ f_s,
-    const double* __restrict__ grad_s, const double* __restrict__ g_s, const double* __restrict__ J_s,
-    const double* __restrict__ A, const double* __restrict__ gradw, const double* __restrict__ c,
-    const double* __restrict__ w, const double* __restrict__ y, const double* __restrict__ zL,
-    const double* __restrict__ zU, const double* __restrict__ dy, const double* __restrict__ dzL,
-    const double* __restrict__ dzU, const double* __restrict__ mu, const double* __restrict__ theta_k,
-    const double* __restrict__ phi_k, const double* __restrict__ gd, const uint8_t* __restrict__ switch_ok,
-    const double* __restrict__ theta_max, const double* __restrict__ ft, const double* __restrict__ fp,
-    double* __restrict__ cs_tmp, uint8_t* __restrict__ in_soft, int32_t* __restrict__ soft_cnt,
-    double* __restrict__ st_f, double* __restrict__ st_g, double* __restrict__ st_w, double* __restrict__ st_alpha,
-    uint8_t* __restrict__ st_aug, double* __restrict__ a_z, const FailTail ft2) {
+__global__ __launch_bounds__(256) void k_soft_judge_fail(int64_t B, const SoftStepArgs a, const FailTail t) {
   const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
   if (b >= B) return;
-  if (soft_try[b])
-    soft_judge_wave(b, B, n, m, nf, nw, nnz_rec, soft_try, soft_now, a_soft, amap, row_slack, free32, gl, hasL, hasU,
-                    wl0, wu0, ws, f_s, grad_s, g_s, J_s, A, gradw, c, w, y, zL, zU, dy, dzL, dzU, mu, theta_k, phi_k,
-                    gd, switch_ok, theta_max, ft, fp, cs_tmp, in_soft, soft_cnt, st_f, st_g, st_w, st_alpha, st_aug,
-                    a_z);
+  if (a.soft_try[b]) soft_judge_wave(b, a);
   __threadfence_block();
   __builtin_amdgcn_wave_barrier();
-  const int lane = threadIdx.x & 63;
+  const int lane = threadIdx.x & 63, n = t.n, nw = t.nw;
   for (int j = lane; j < n; j += 64) {
-    const int k = ft2.freepos[j];
-    ft2.X[b * n + j] = k >= 0 ? st_w[b * nw + k] : ft2.Xbase[b * n + j];
+    const int k = t.freepos[j];
+    t.X[b * n + j] = k >= 0 ? t.st.w[b * nw + k] : t.Xbase[b * n + j];
   }
-  if (lane == 0)
-    fail_book(b, ft2.act, st_alpha, ft2.err0, ft2.acc_tol, ft2.failed, ft2.moved, in_soft, soft_cnt, ft2.status,
-              ft2.active, ft2.nf);
+  if (lane == 0) fail_book(b, t);
 }
 
 // IPOPT's limited-memory quasi-Newton model (LimMemQuasiNewtonUpdater [IPOPT] with the defaults
@@ -768,70 +767,76 @@ __global__ __launch_bounds__(256) void k_soft_judge_fail(
 constexpr int LM_HIST = 6, LM_MAX_SKIP = 2;
 // doubles per instance of the compact model: sigma, the number of pairs nv, U [LM_HIST][nf], W [LM_HIST][nf]
 __host__ __device__ constexpr int64_t LMC(int nf) { return 2 + 2 * (int64_t)LM_HIST * nf; }
-// NFX: the LDS row length of the pair vectors (64 for nf <= 64 — the 4-contact problem's 39 — else 128):
-// 28.5 -> 15.5 KiB of LDS per workgroup, twice the resident workgroups per CU
-template <int NFX>
-__global__ __launch_bounds__(256) void k_lbfgs(int64_t B, int m, int nf, int nw, int nnz_rec,
-                                               const int32_t* __restrict__ amap, const uint8_t* __restrict__ act,
-                                               const double* __restrict__ w_old, const double* __restrict__ w_new,
-                                               const double* __restrict__ y, const double* __restrict__ dy,
-                                               const double* __restrict__ alpha, const double* __restrict__ gw_old,
-                                               const double* __restrict__ J_old, const double* __restrict__ grad_new,
-                                               const int32_t* __restrict__ free_idx, int n,
-                                               const double* __restrict__ J_new, double* __restrict__ lm_s,
-                                               double* __restrict__ lm_y, uint8_t* __restrict__ lm_cnt,
-                                               uint8_t* __restrict__ lm_skip, const uint8_t* __restrict__ failed,
-                                               double* __restrict__ Hq) {
+struct LbfgsArgs {  // the update for the instances of `act`, from the old point to the new one
+  int n = 0, m = 0, nf = 0, nw = 0, nnz_rec = 0;
+  const int32_t *amap = nullptr, *free_idx = nullptr;
+  const uint8_t *act = nullptr, *failed = nullptr;
+  const double *w_old = nullptr, *w_new = nullptr, *y = nullptr, *dy = nullptr, *alpha = nullptr;
+  const double *gw_old = nullptr, *J_old = nullptr, *grad_new = nullptr, *J_new = nullptr;
+  double *lm_s = nullptr, *lm_y = nullptr;
+  uint8_t *lm_cnt = nullptr, *lm_skip = nullptr;
+  double* Hq = nullptr;
+};
+// Column k of J_free^T yn at both points over the rows part, part + parts, ..., straight from the
+// values-only Jacobian records (the entries of A = [J_free | -P] as cpl_ipm_dense_a forms them: amap
+// -1 = 0, -2 = constant 1, NaN = 0).  Rows in order, eight at a time: the eight amap indices, then
+// the eight record entries they name, are loads in flight together (one row at a time waited two
+// dependent L2 round trips per row); the accumulation is the plain loop's.  Both L-BFGS forms call
+// it, so their partial sums are the same bit for bit.
+__device__ __forceinline__ void lbfgs_jty_part(const int32_t* amap, const double* jnb, const double* job,
+                                               const double* yn, int m, int nf, int k, int part, int parts,
+                                               double& jn, double& jo) {
+  const int R = m > part ? (m - part + parts - 1) / parts : 0;
+  for (int t0 = 0; t0 < R; t0 += 8) {
+    int qv[8];
+    double anv[8], aov[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) qv[u] = t0 + u < R ? amap[(part + (t0 + u) * parts) * nf + k] : -1;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      anv[u] = qv[u] >= 0 ? jnb[qv[u]] : 1.0;
+      aov[u] = qv[u] >= 0 ? job[qv[u]] : 1.0;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      if (qv[u] == -1) continue;  // structural zero (or past the last row): A's entry is 0
+      double an = anv[u], ao = aov[u];
+      if (qv[u] >= 0) {
+        an = an == an ? an : 0.0;
+        ao = ao == ao ? ao : 0.0;
+      }
+      const int r = part + (t0 + u) * parts;
+      jn += an * yn[r];
+      jo += ao * yn[r];
+    }
+  }
+}
+// The workgroup form, for nf > 64 (nf <= 64 — the 4-contact problem's 39 — takes k_lbfgs_wave below):
+// the pair vectors in LDS rows of NFX = 128 doubles, 28.5 KiB per workgroup
+constexpr int NFX = 128;
+__global__ __launch_bounds__(256) void k_lbfgs(int64_t B, const LbfgsArgs L) {
+  const int n = L.n, m = L.m, nf = L.nf, nw = L.nw, nnz_rec = L.nnz_rec;
   const int64_t b = blockIdx.x;
-  if (b >= B || !act[b]) return;
+  if (b >= B || !L.act[b]) return;
   __shared__ double Ps[LM_HIST][NFX], Py[LM_HIST][NFX], yn[256], red[8];
   const int tid = threadIdx.x;
-  const double al = alpha[b];
-  for (int r = tid; r < m; r += blockDim.x) yn[r] = y[b * m + r] + al * dy[b * m + r];
+  const double al = L.alpha[b];
+  for (int r = tid; r < m; r += blockDim.x) yn[r] = L.y[b * m + r] + al * L.dy[b * m + r];
   // both counters read before any barrier: thread 0 rewrites them below
-  const int cnt = lm_cnt[b], skipped = lm_skip[b] + 1;
+  const int cnt = L.lm_cnt[b], skipped = L.lm_skip[b] + 1;
   __syncthreads();
   // the new pair goes to slot `last`; a full memory shifts down by one (the oldest dropped)
   const int shift = cnt == LM_HIST ? 1 : 0, last = cnt - shift;
-  double* gs = lm_s + b * (int64_t)LM_HIST * nf;
-  double* gy = lm_y + b * (int64_t)LM_HIST * nf;
-  {  // J_free^T y at both points, straight from the values-only Jacobian records (the entries of A =
-     // [J_free | -P] as cpl_ipm_dense_a forms them: amap -1 = 0, -2 = constant 1, NaN = 0); the rows
-     // split over `parts` thread groups, partials summed in fixed order
+  double* gs = L.lm_s + b * (int64_t)LM_HIST * nf;
+  double* gy = L.lm_y + b * (int64_t)LM_HIST * nf;
+  {  // J_free^T y at both points: the rows split over `parts` thread groups, partials summed in fixed order
     __shared__ double pjn[4][NFX], pjo[4][NFX];
     const int kp = nf <= 64 ? 64 : 128, parts = (int)blockDim.x / kp;
     const int k = tid % kp, part = tid / kp;
     if (k < nf && part < parts) {
-      const double* jnb = J_new + b * (int64_t)nnz_rec;
-      const double* job = J_old + b * (int64_t)nnz_rec;
       double jn = 0.0, jo = 0.0;
-      // rows r = part, part + parts, ... in order, eight at a time: the eight amap indices, then the
-      // eight record entries they name, are loads in flight together (one row at a time waited two
-      // dependent L2 round trips per row); the accumulation is the plain loop's
-      const int R = m > part ? (m - part + parts - 1) / parts : 0;
-      for (int t0 = 0; t0 < R; t0 += 8) {
-        int qv[8];
-        double anv[8], aov[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) qv[u] = t0 + u < R ? amap[(part + (t0 + u) * parts) * nf + k] : -1;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          anv[u] = qv[u] >= 0 ? jnb[qv[u]] : 1.0;
-          aov[u] = qv[u] >= 0 ? job[qv[u]] : 1.0;
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          if (qv[u] == -1) continue;  // structural zero (or past the last row): A's entry is 0
-          double an = anv[u], ao = aov[u];
-          if (qv[u] >= 0) {
-            an = an == an ? an : 0.0;
-            ao = ao == ao ? ao : 0.0;
-          }
-          const int r = part + (t0 + u) * parts;
-          jn += an * yn[r];
-          jo += ao * yn[r];
-        }
-      }
+      lbfgs_jty_part(L.amap, L.J_new + b * (int64_t)nnz_rec, L.J_old + b * (int64_t)nnz_rec, yn, m, nf, k, part, parts,
+                     jn, jo);
       pjn[part][k] = jn;
       pjo[part][k] = jo;
     }
@@ -842,10 +847,10 @@ __global__ __launch_bounds__(256) void k_lbfgs(int64_t B, int m, int nf, int nw,
         jn += pjn[q][k2];
         jo += pjo[q][k2];
       }
-      Ps[last][k2] = w_new[b * nw + k2] - w_old[b * nw + k2];
+      Ps[last][k2] = L.w_new[b * nw + k2] - L.w_old[b * nw + k2];
       // grad_w f at the new point: its free components (k_prep's gather), 0 without a cost (grad_new NULL)
-      const double gn = grad_new ? grad_new[b * n + free_idx[k2]] : 0.0;
-      Py[last][k2] = (gn + jn) - (gw_old[b * nw + k2] + jo);
+      const double gn = L.grad_new ? L.grad_new[b * n + L.free_idx[k2]] : 0.0;
+      Py[last][k2] = (gn + jn) - (L.gw_old[b * nw + k2] + jo);
       for (int j = 0; j < last; ++j) {
         Ps[j][k2] = gs[(j + shift) * nf + k2];
         Py[j][k2] = gy[(j + shift) * nf + k2];
@@ -867,18 +872,18 @@ __global__ __launch_bounds__(256) void k_lbfgs(int64_t B, int m, int nf, int nw,
   const double sy = block_dot(Ps[last], Py[last]);
   const double ss = block_dot(Ps[last], Ps[last]);
   const double yy = block_dot(Py[last], Py[last]);
-  double* hc = Hq + b * (int64_t)LMC(nf);  // the compact model: [sigma, nv, U, W]
+  double* hc = L.Hq + b * (int64_t)LMC(nf);  // the compact model: [sigma, nv, U, W]
   const bool skip = !(sy > sqrt(DBL_EPSILON) * sqrt(ss) * sqrt(yy));
-  if (skip || failed[b]) {  // (uniform branch)
-    if (!failed[b] && skipped <= LM_MAX_SKIP) {
-      if (tid == 0) lm_skip[b] = (uint8_t)skipped;
+  if (skip || L.failed[b]) {  // (uniform branch)
+    if (!L.failed[b] && skipped <= LM_MAX_SKIP) {
+      if (tid == 0) L.lm_skip[b] = (uint8_t)skipped;
       return;
     }
     if (tid == 0) {  // the model back to init_val I
       hc[0] = 1.0;
       hc[1] = 0.0;
-      lm_skip[b] = 0;
-      lm_cnt[b] = 0;
+      L.lm_skip[b] = 0;
+      L.lm_cnt[b] = 0;
     }
     return;
   }
@@ -889,8 +894,8 @@ __global__ __launch_bounds__(256) void k_lbfgs(int64_t B, int m, int nf, int nw,
       gy[j * nf + k] = Py[j][k];
     }
   if (tid == 0) {
-    lm_skip[b] = 0;
-    lm_cnt[b] = (uint8_t)nc;
+    L.lm_skip[b] = 0;
+    L.lm_cnt[b] = (uint8_t)nc;
   }
   const double sigma = fmin(fmax(sy / ss, 1e-8), 1e8);
   // The recursion unrolled onto vectors: a_j = B_j s_j = sigma s_j + sum_{i<j} [y_i (y_i's_j) / s_i'y_i
@@ -956,67 +961,37 @@ __global__ __launch_bounds__(256) void k_lbfgs(int64_t B, int m, int nf, int nw,
 
 // k_lbfgs for nf <= 64 with one wave per instance (four instances per workgroup) and the pair vectors
 // in registers (lane k holds entry k of every stored pair): the same operations in the same order as
-// k_lbfgs (the workgroup form, NFX = 64) — the J^T y row partials in its four row groups summed in its order, its block dots as
-// 0 + the wave sum, its recursion — so bitwise the same model, without its barriers and idle waves
-// (that form ran its recursion on one wave of four and kept 15.5 KiB of LDS per instance).
+// k_lbfgs runs for such a problem (its kp = 64 split) — the J^T y row partials in its four row groups
+// summed in its order, its block dots as 0 + the wave sum, its recursion — so bitwise the same model,
+// without its barriers and idle waves (that form runs its recursion on one wave of four).
 constexpr int LBW_WAVES = 4;
-__global__ __launch_bounds__(64 * LBW_WAVES) void k_lbfgs_wave(
-    int64_t B, int m, int nf, int nw, int nnz_rec, const int32_t* __restrict__ amap, const uint8_t* __restrict__ act,
-    const double* __restrict__ w_old, const double* __restrict__ w_new, const double* __restrict__ y,
-    const double* __restrict__ dy, const double* __restrict__ alpha, const double* __restrict__ gw_old,
-    const double* __restrict__ J_old, const double* __restrict__ grad_new, const int32_t* __restrict__ free_idx, int n,
-    const double* __restrict__ J_new, double* __restrict__ lm_s, double* __restrict__ lm_y, uint8_t* __restrict__ lm_cnt,
-    uint8_t* __restrict__ lm_skip, const uint8_t* __restrict__ failed, double* __restrict__ Hq) {
+__global__ __launch_bounds__(64 * LBW_WAVES) void k_lbfgs_wave(int64_t B, const LbfgsArgs L) {
+  const int n = L.n, m = L.m, nf = L.nf, nw = L.nw, nnz_rec = L.nnz_rec;
   extern __shared__ double ynw[];  // [LBW_WAVES][m]
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t b = (int64_t)blockIdx.x * LBW_WAVES + wv;
-  if (b >= B || !act[b]) return;
+  if (b >= B || !L.act[b]) return;
   double* yn = ynw + (size_t)wv * m;
-  const double al = alpha[b];
-  for (int r = lane; r < m; r += 64) yn[r] = y[b * m + r] + al * dy[b * m + r];
-  const int cnt = lm_cnt[b], skipped = lm_skip[b] + 1;
+  const double al = L.alpha[b];
+  for (int r = lane; r < m; r += 64) yn[r] = L.y[b * m + r] + al * L.dy[b * m + r];
+  const int cnt = L.lm_cnt[b], skipped = L.lm_skip[b] + 1;
   __builtin_amdgcn_wave_barrier();
   const int shift = cnt == LM_HIST ? 1 : 0, last = cnt - shift;
-  double* gs = lm_s + b * (int64_t)LM_HIST * nf;
-  double* gy = lm_y + b * (int64_t)LM_HIST * nf;
+  double* gs = L.lm_s + b * (int64_t)LM_HIST * nf;
+  double* gy = L.lm_y + b * (int64_t)LM_HIST * nf;
   const int k = lane;
   const bool hk = k < nf;
   double Ps[LM_HIST], Py[LM_HIST];
   {  // J_free^T y at both points: the workgroup form's four row groups (rows part, part + 4, ...), each in its
      // eight-row batches, the group partials summed in order
     constexpr int PARTS = 4;
-    const double* jnb = J_new + b * (int64_t)nnz_rec;
-    const double* job = J_old + b * (int64_t)nnz_rec;
+    const double* jnb = L.J_new + b * (int64_t)nnz_rec;
+    const double* job = L.J_old + b * (int64_t)nnz_rec;
     double pn[PARTS], po[PARTS];
 #pragma unroll
     for (int part = 0; part < PARTS; ++part) {
       double jn = 0.0, jo = 0.0;
-      const int R = m > part ? (m - part + PARTS - 1) / PARTS : 0;
-      if (hk) {
-        for (int t0 = 0; t0 < R; t0 += 8) {
-          int qv[8];
-          double anv[8], aov[8];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) qv[u] = t0 + u < R ? amap[(part + (t0 + u) * PARTS) * nf + k] : -1;
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            anv[u] = qv[u] >= 0 ? jnb[qv[u]] : 1.0;
-            aov[u] = qv[u] >= 0 ? job[qv[u]] : 1.0;
-          }
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            if (qv[u] == -1) continue;
-            double an = anv[u], ao = aov[u];
-            if (qv[u] >= 0) {
-              an = an == an ? an : 0.0;
-              ao = ao == ao ? ao : 0.0;
-            }
-            const int r = part + (t0 + u) * PARTS;
-            jn += an * yn[r];
-            jo += ao * yn[r];
-          }
-        }
-      }
+      if (hk) lbfgs_jty_part(L.amap, jnb, job, yn, m, nf, k, part, PARTS, jn, jo);
       pn[part] = jn;
       po[part] = jo;
     }
@@ -1036,9 +1011,9 @@ __global__ __launch_bounds__(64 * LBW_WAVES) void k_lbfgs_wave(
       }
     }
     if (hk) {
-      const double sl = w_new[b * nw + k] - w_old[b * nw + k];
-      const double gn = grad_new ? grad_new[b * n + free_idx[k]] : 0.0;
-      const double yl = (gn + jn) - (gw_old[b * nw + k] + jo);
+      const double sl = L.w_new[b * nw + k] - L.w_old[b * nw + k];
+      const double gn = L.grad_new ? L.grad_new[b * n + L.free_idx[k]] : 0.0;
+      const double yl = (gn + jn) - (L.gw_old[b * nw + k] + jo);
 #pragma unroll
       for (int j = 0; j < LM_HIST; ++j)
         if (j == last) {
@@ -1064,18 +1039,18 @@ __global__ __launch_bounds__(64 * LBW_WAVES) void k_lbfgs_wave(
   const double sy = wdot(sL, yL);
   const double ss = wdot(sL, sL);
   const double yy = wdot(yL, yL);
-  double* hc = Hq + b * (int64_t)LMC(nf);
+  double* hc = L.Hq + b * (int64_t)LMC(nf);
   const bool skip = !(sy > sqrt(DBL_EPSILON) * sqrt(ss) * sqrt(yy));
-  if (skip || failed[b]) {
-    if (!failed[b] && skipped <= LM_MAX_SKIP) {
-      if (lane == 0) lm_skip[b] = (uint8_t)skipped;
+  if (skip || L.failed[b]) {
+    if (!L.failed[b] && skipped <= LM_MAX_SKIP) {
+      if (lane == 0) L.lm_skip[b] = (uint8_t)skipped;
       return;
     }
     if (lane == 0) {
       hc[0] = 1.0;
       hc[1] = 0.0;
-      lm_skip[b] = 0;
-      lm_cnt[b] = 0;
+      L.lm_skip[b] = 0;
+      L.lm_cnt[b] = 0;
     }
     return;
   }
@@ -1089,8 +1064,8 @@ __global__ __launch_bounds__(64 * LBW_WAVES) void k_lbfgs_wave(
       }
   }
   if (lane == 0) {
-    lm_skip[b] = 0;
-    lm_cnt[b] = (uint8_t)nc;
+    L.lm_skip[b] = 0;
+    L.lm_cnt[b] = (uint8_t)nc;
   }
   const double sigma = fmin(fmax(sy / ss, 1e-8), 1e8);
   // the recursion (the workgroup form's, lane k0 = k; its second entry k1 = k + 64 >= nf contributes zeros)
@@ -1207,18 +1182,18 @@ __device__ __forceinline__ void resto_enter_one(const RestoEnterArgs& E, int64_t
   const int m = E.m, nw = E.nw;
   const uint8_t* __restrict__ failed = E.failed;
   const double* __restrict__ c = E.c;
-  const double* __restrict__ w = E.w;
-  const double* __restrict__ zL = E.zL;
-  const double* __restrict__ zU = E.zU;
+  const double* w = E.w;  // (w, zL, zU, the filter and the counts: stored to by ipm_accept_one below)
+  const double* zL = E.zL;
+  const double* zU = E.zU;
   const double* __restrict__ mu = E.mu;
   const double* __restrict__ theta_k = E.theta_k;
   const double* __restrict__ phi_k = E.phi_k;
   const uint8_t* __restrict__ hasL = E.hasL;
   const uint8_t* __restrict__ hasU = E.hasU;
-  double* __restrict__ filt_t = E.filt_t;
-  double* __restrict__ filt_p = E.filt_p;
-  int64_t* __restrict__ fcount = E.fcount;
-  int64_t* __restrict__ iters = E.iters;
+  double* filt_t = E.filt_t;
+  double* filt_p = E.filt_p;
+  int64_t* fcount = E.fcount;
+  int64_t* iters = E.iters;
   uint8_t* __restrict__ in_resto = E.in_resto;
   int64_t* __restrict__ n_resto = E.n_resto;
   double* __restrict__ wR = E.wR;
@@ -1321,44 +1296,55 @@ __global__ __launch_bounds__(256) void k_resto_enter(int64_t B, const RestoEnter
   resto_enter_one(E, b, threadIdx.x & 63);
 }
 
-// the least-squares estimate kept when |y|max <= constr_mult_init_max = 1e3
-__global__ __launch_bounds__(256) void k_resto_y0(int64_t B, int m, const uint8_t* __restrict__ failed,
-                                                  const double* __restrict__ dy, double* __restrict__ y) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B || !failed[b]) return;
-  const int lane = threadIdx.x & 63;
-  double mx = 0.0;
-  for (int r = lane; r < m; r += 64) mx = fmax(mx, fabs(dy[b * m + r]));
-  mx = wave_max(mx);
-  for (int r = lane; r < m; r += 64) y[b * m + r] = mx <= 1e3 ? dy[b * m + r] : 0.0;
-}
-
 // the restoration problem's optimality error, its monotone barrier update (resetting its filter) and
 // the proximity term's gradient over w.  The restoration problem converged (IPOPT's
 // RestoConvergenceCheck): a point of local infeasibility when the original problem's max |c| exceeds
 // 1e2 tol; otherwise the point is feasible but unacceptable to the original filter — the first time the
 // restoration tolerance is tightened to 1e-2 tol and the phase goes on (resto_tight), the second time
 // the solve ends as a restoration failure (IPOPT's RESTORATION_CONVERGED_TO_FEASIBLE_POINT)
-__global__ __launch_bounds__(256) void k_resto_prep1(
-    int64_t B, int m, int nf, int nw, int nbounds, double tol, double mu_min, uint8_t* __restrict__ active,
-    const uint8_t* __restrict__ in_resto, uint8_t* __restrict__ resto_tight, uint8_t* __restrict__ actR,
-    int64_t* __restrict__ status,
-    const double* __restrict__ A, const double* __restrict__ c, const double* __restrict__ w,
-    const double* __restrict__ y, const double* __restrict__ wR, const double* __restrict__ pR,
-    const double* __restrict__ nR, const double* __restrict__ zp, const double* __restrict__ zn,
-    const double* __restrict__ zLR, const double* __restrict__ zUR, const uint8_t* __restrict__ hasL,
-    const uint8_t* __restrict__ hasU, const double* __restrict__ wl0, const double* __restrict__ wu0,
-    double* __restrict__ muR, double* __restrict__ ftR, double* __restrict__ fpR, int64_t* __restrict__ fcR,
-    double* __restrict__ tauR, double* __restrict__ gfR) {
+// The restoration phase's buffers, for k_resto_prep1, k_resto_judge and k_resto_accept below (resto_args()
+// builds it once per phase).  k_resto_prep2 and k_resto_post keep positional __restrict__ parameters: as
+// struct members without the no-alias promise both compiled to more registers and lost occupancy.
+struct RestoArgs {
+  int m = 0, nf = 0, nw = 0, nbounds = 0;
+  double tol = 0.0, mu_min = 0.0;
+  int64_t lmc = 0;
+  const int32_t* row_slack = nullptr;
+  const double* gl = nullptr;
+  Bounds bd;
+  Iterate it;    // w, y and the restoration problem's bound multipliers zLR, zUR
+  RestoVars rv;
+  Step sp;
+  Search ls;     // the restoration problem's own search: mu_R, theta_R, phi_R, its filter
+  Staged st;
+  double *dp = nullptr, *dn = nullptr, *dzp = nullptr, *dzn = nullptr, *tauR = nullptr, *gfR = nullptr;
+  double* a_z = nullptr;                                        // the restoration step's dual step length
+  const double *A = nullptr, *c = nullptr;                      // at the iterate
+  const double *wt = nullptr, *f_t = nullptr, *g_t = nullptr;   // the first trial
+  const double *f_n = nullptr, *g_n = nullptr;                  // the accepted point
+  uint8_t *active = nullptr, *in_resto = nullptr, *resto_tight = nullptr, *movedR = nullptr;
+  int64_t *status = nullptr, *iters = nullptr, *fcR = nullptr, *acc = nullptr;
+  // the original problem's state the return test reads and the return resets
+  const double *mu = nullptr, *filt_t = nullptr, *filt_p = nullptr, *th_o0 = nullptr, *ph_o0 = nullptr;
+  double *zL = nullptr, *zU = nullptr;
+  uint8_t *lm_cnt = nullptr, *lm_skip = nullptr;
+  double* Hq = nullptr;
+};
+__global__ __launch_bounds__(256) void k_resto_prep1(int64_t B, const RestoArgs R) {
+  const int m = R.m, nf = R.nf, nw = R.nw;
+  const auto [hasL, hasU, wl0, wu0] = R.bd;
+  const auto [w, y, zLR, zUR] = R.it;
+  const auto [wR, pR, nR, zp, zn] = R.rv;
+  const auto [actR, searching, alpha, a_min, muR, thetaR, phiR, gdR, switchR, thmaxR, ftR, fpR] = R.ls;
   const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
   if (b >= B) return;
   const int lane = threadIdx.x & 63;
-  const bool a = active[b] && in_resto[b];
+  const bool a = R.active[b] && R.in_resto[b];
   if (!a) {
     if (lane == 0) actR[b] = 0;
     return;
   }
-  const double* Ab = A + b * (int64_t)m * nw;
+  const double* Ab = R.A + b * (int64_t)m * nw;
   double mu = muR[b];
   double eta = sqrt(mu);
   double dmax = 0.0, zs = 0.0, cmax = 0.0, ys = 0.0, crmax = 0.0;
@@ -1389,8 +1375,8 @@ __global__ __launch_bounds__(256) void k_resto_prep1(
       dmax = fmax(dmax, fmax(fabs(RHO_R - yr - zpv), fabs(RHO_R + yr - znv)));
       zs += fabs(zpv) + fabs(znv);
       ys += fabs(yr);
-      crmax = fmax(crmax, fabs(c[b * m + r] - pv + nv));
-      cinf = fmax(cinf, fabs(c[b * m + r]));
+      crmax = fmax(crmax, fabs(R.c[b * m + r] - pv + nv));
+      cinf = fmax(cinf, fabs(R.c[b * m + r]));
       cp[h] = pv * zpv;
       cn[h] = nv * znv;
       cmax = fmax(cmax, fmax(cp[h], cn[h]));
@@ -1401,24 +1387,24 @@ __global__ __launch_bounds__(256) void k_resto_prep1(
   crmax = wave_max(crmax);
   zs = wave_sum(zs);
   ys = wave_sum(ys);
-  const int nbR = nbounds + 2 * m;
+  const int nbR = R.nbounds + 2 * m;
   const double sd = fmax((ys + zs) / (double)max(m + nbR, 1), 100.0) / 100.0;
   const double sc = fmax(zs / (double)max(nbR, 1), 100.0) / 100.0;
   const double base = fmax(dmax / sd, crmax);
   const double err0 = fmax(base, cmax / sc);
-  const bool tight = resto_tight[b] != 0;
-  if (err0 <= (tight ? 1e-2 * tol : tol)) {  // the restoration problem converged
+  const bool tight = R.resto_tight[b] != 0;
+  if (err0 <= (tight ? 1e-2 * R.tol : R.tol)) {  // the restoration problem converged
     cinf = wave_max(cinf);
-    const bool feasible = cinf <= 1e2 * tol;
+    const bool feasible = cinf <= 1e2 * R.tol;
     if (!feasible || tight) {
       if (lane == 0) {
-        status[b] = feasible ? CPL_SOLVE_RESTO_FAILED : CPL_SOLVE_INFEASIBLE;
-        active[b] = 0;
+        R.status[b] = feasible ? CPL_SOLVE_RESTO_FAILED : CPL_SOLVE_INFEASIBLE;
+        R.active[b] = 0;
         actR[b] = 0;
       }
       return;
     }
-    if (lane == 0) resto_tight[b] = 1;  // once: the restoration tolerance 1e-2 tol, and on
+    if (lane == 0) R.resto_tight[b] = 1;  // once: the restoration tolerance 1e-2 tol, and on
   }
   bool reset = false;
   for (int round = 0; round < MU_ROUNDS; ++round) {
@@ -1433,8 +1419,8 @@ __global__ __launch_bounds__(256) void k_resto_prep1(
       if (lane + 64 * h < m) em = fmax(em, fmax(fabs(cp[h] - mu), fabs(cn[h] - mu)));
     }
     em = wave_max(em);
-    if (fmax(base, em / sc) <= 10.0 * mu && mu > mu_min) {
-      mu = fmax(fmin(0.2 * mu, pow(mu, 1.5)), mu_min);
+    if (fmax(base, em / sc) <= 10.0 * mu && mu > R.mu_min) {
+      mu = fmax(fmin(0.2 * mu, pow(mu, 1.5)), R.mu_min);
       reset = true;
     }
   }
@@ -1447,13 +1433,13 @@ __global__ __launch_bounds__(256) void k_resto_prep1(
   eta = sqrt(mu);
   for (int k = lane; k < nw; k += 64) {
     const double dr = k < nf ? 1.0 / fmax(fabs(wR[b * nw + k]), 1.0) : 0.0;
-    gfR[b * nw + k] = k < nf ? eta * (dr * dr) * (w[b * nw + k] - wR[b * nw + k]) : 0.0;
+    R.gfR[b * nw + k] = k < nf ? eta * (dr * dr) * (w[b * nw + k] - wR[b * nw + k]) : 0.0;
   }
   if (lane == 0) {
     actR[b] = 1;
     muR[b] = mu;
-    tauR[b] = fmax(1.0 - mu, 0.99);
-    if (reset) fcR[b] = 0;
+    R.tauR[b] = fmax(1.0 - mu, 0.99);
+    if (reset) R.fcR[b] = 0;
   }
 }
 
@@ -1619,27 +1605,21 @@ __global__ __launch_bounds__(256) void k_resto_post(
 }
 
 // the restoration line search's acceptance test at one trial point (p, n along with w) and the take
-__global__ __launch_bounds__(256) void k_resto_judge(
-    int64_t B, int m, int nf, int nw, const uint8_t* __restrict__ searching_in, const int32_t* __restrict__ row_slack,
-    const double* __restrict__ gl, const uint8_t* __restrict__ hasL, const uint8_t* __restrict__ hasU,
-    const double* __restrict__ wl0, const double* __restrict__ wu0, const double* __restrict__ wt,
-    const double* __restrict__ f_t, const double* __restrict__ g_t, const double* __restrict__ alpha,
-    const double* __restrict__ pR, const double* __restrict__ nR, const double* __restrict__ dp,
-    const double* __restrict__ dn, const double* __restrict__ wR, const double* __restrict__ muR,
-    const double* __restrict__ thetaR, const double* __restrict__ phiR, const double* __restrict__ gdR,
-    const uint8_t* __restrict__ switchR, const double* __restrict__ thmaxR, const double* __restrict__ ftR,
-    const double* __restrict__ fpR, uint8_t* __restrict__ searching, double* __restrict__ st_f,
-    double* __restrict__ st_g, double* __restrict__ st_w, double* __restrict__ st_p, double* __restrict__ st_n,
-    double* __restrict__ st_alpha, uint8_t* __restrict__ st_aug) {
+__global__ __launch_bounds__(256) void k_resto_judge(int64_t B, const RestoArgs R) {
+  const int m = R.m, nf = R.nf, nw = R.nw;
+  const auto [hasL, hasU, wl0, wu0] = R.bd;
+  const auto [wR, pR, nR, zp, zn] = R.rv;
+  const auto [actR, searching, alpha, a_min, muR, thetaR, phiR, gdR, switchR, thmaxR, ftR, fpR] = R.ls;
+  const auto [st_f, st_g, st_w, st_alpha, st_aug, st_p, st_n] = R.st;
   const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B || !searching_in[b]) return;
+  if (b >= B || !searching[b]) return;
   const int lane = threadIdx.x & 63;
   const double al = alpha[b], mu = muR[b], eta = sqrt(mu);
-  const double* wb = wt + b * nw;
+  const double* wb = R.wt + b * nw;
   double th = 0.0, pn = 0.0, lpn = 0.0, prox = 0.0, lg = 0.0;
   for (int r = lane; r < m; r += 64) {
-    const double pt = pR[b * m + r] + al * dp[b * m + r], nt = nR[b * m + r] + al * dn[b * m + r];
-    th += fabs(cons_row(g_t + b * m, wb, nf, r, row_slack, gl) - pt + nt);
+    const double pt = pR[b * m + r] + al * R.dp[b * m + r], nt = nR[b * m + r] + al * R.dn[b * m + r];
+    th += fabs(cons_row(R.g_t + b * m, wb, nf, r, R.row_slack, R.gl) - pt + nt);
     pn += pt + nt;
     lpn += log(pt) + log(nt);
   }
@@ -1663,13 +1643,13 @@ __global__ __launch_bounds__(256) void k_resto_judge(
                                   fpR + b * FMAX, &h);
   if (!ok) return;
   for (int r = lane; r < m; r += 64) {
-    st_g[b * m + r] = g_t[b * m + r];
-    st_p[b * m + r] = pR[b * m + r] + al * dp[b * m + r];
-    st_n[b * m + r] = nR[b * m + r] + al * dn[b * m + r];
+    st_g[b * m + r] = R.g_t[b * m + r];
+    st_p[b * m + r] = pR[b * m + r] + al * R.dp[b * m + r];
+    st_n[b * m + r] = nR[b * m + r] + al * R.dn[b * m + r];
   }
   for (int k = lane; k < nw; k += 64) st_w[b * nw + k] = wb[k];
   if (lane == 0) {
-    st_f[b] = f_t[b];
+    st_f[b] = R.f_t[b];
     st_alpha[b] = al;
     st_aug[b] = h ? 1 : 0;
     searching[b] = 0;
@@ -1682,29 +1662,19 @@ __global__ __launch_bounds__(256) void k_resto_judge(
 // kappa_resto of its value where the phase began, the point acceptable to the original filter and
 // to that iterate) and the return (ComputeBoundMultiplierStep for the original bound multipliers, a
 // reset to 1 when any exceeds 1000, y = 0, a fresh quasi-Newton model)
-__global__ __launch_bounds__(256) void k_resto_accept(
-    int64_t B, int m, int nf, int nw, const uint8_t* __restrict__ actR, uint8_t* __restrict__ movedR,
-    uint8_t* __restrict__ active, int64_t* __restrict__ status, int64_t* __restrict__ iters,
-    const double* __restrict__ st_alpha, const uint8_t* __restrict__ st_aug, const double* __restrict__ st_w,
-    const double* __restrict__ st_p, const double* __restrict__ st_n, const double* __restrict__ dy,
-    const double* __restrict__ dzL, const double* __restrict__ dzU, const double* __restrict__ dzp,
-    const double* __restrict__ dzn, const double* __restrict__ a_z, const double* __restrict__ muR,
-    const double* __restrict__ thetaR, const double* __restrict__ phiR, double* __restrict__ ftR,
-    double* __restrict__ fpR, int64_t* __restrict__ fcR, double* __restrict__ w, double* __restrict__ y,
-    double* __restrict__ pR, double* __restrict__ nR, double* __restrict__ zp, double* __restrict__ zn,
-    double* __restrict__ zLR, double* __restrict__ zUR, const uint8_t* __restrict__ hasL,
-    const uint8_t* __restrict__ hasU, const double* __restrict__ wl0, const double* __restrict__ wu0,
-    const int32_t* __restrict__ row_slack, const double* __restrict__ gl, const double* __restrict__ f_n,
-    const double* __restrict__ g_n, const double* __restrict__ mu, const double* __restrict__ filt_t,
-    const double* __restrict__ filt_p, const double* __restrict__ th_o0, const double* __restrict__ ph_o0,
-    const double* __restrict__ wR, double* __restrict__ zL, double* __restrict__ zU, uint8_t* __restrict__ in_resto,
-    int64_t* __restrict__ acc, uint8_t* __restrict__ lm_cnt, uint8_t* __restrict__ lm_skip, double* __restrict__ Hq,
-    int64_t lmc) {
+__global__ __launch_bounds__(256) void k_resto_accept(int64_t B, const RestoArgs R) {
+  const int m = R.m, nf = R.nf, nw = R.nw;
+  const auto [hasL, hasU, wl0, wu0] = R.bd;
+  const auto [w, y, zLR, zUR] = R.it;
+  const auto [wR, pR, nR, zp, zn] = R.rv;
+  const auto [dw, dy, dzL, dzU] = R.sp;
+  const auto [actR, searching, alpha, a_min, muR, thetaR, phiR, gdR, switchR, thmaxR, ftR, fpR] = R.ls;
+  const auto [st_f, st_g, st_w, st_alpha, st_aug, st_p, st_n] = R.st;
   const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
   if (b >= B) return;
   const int lane = threadIdx.x & 63;
   if (!actR[b]) {
-    if (lane == 0) movedR[b] = 0;
+    if (lane == 0) R.movedR[b] = 0;
     return;
   }
   const double al = st_alpha[b];
@@ -1716,24 +1686,24 @@ __global__ __launch_bounds__(256) void k_resto_accept(
     // the search state's point is the iterate when no trial was taken.)
     const double mur = muR[b];
     for (int r = lane; r < m; r += 64) {
-      const double c = cons_row(g_n + b * m, st_w + b * nw, nf, r, row_slack, gl);
+      const double c = cons_row(R.g_n + b * m, st_w + b * nw, nf, r, R.row_slack, R.gl);
       const double a = (mur - RHO_R * c) / (2.0 * RHO_R);
       const double nn = a + sqrt(a * a + mur * c / (2.0 * RHO_R));
       nR[b * m + r] = nn;
       pR[b * m + r] = c + nn;
     }
     if (lane == 0) {
-      movedR[b] = 0;
-      iters[b] += 1;
+      R.movedR[b] = 0;
+      R.iters[b] += 1;
     }
     return;
   }
-  const double mur = muR[b], az = a_z[b];
+  const double mur = muR[b], az = R.a_z[b];
   for (int r = lane; r < m; r += 64) {
     y[b * m + r] += al * dy[b * m + r];
     const double pn = st_p[b * m + r], nn = st_n[b * m + r];
-    zp[b * m + r] = fmin(fmax(zp[b * m + r] + az * dzp[b * m + r], mur / (KAPPA_SIGMA * pn)), KAPPA_SIGMA * mur / pn);
-    zn[b * m + r] = fmin(fmax(zn[b * m + r] + az * dzn[b * m + r], mur / (KAPPA_SIGMA * nn)), KAPPA_SIGMA * mur / nn);
+    zp[b * m + r] = fmin(fmax(zp[b * m + r] + az * R.dzp[b * m + r], mur / (KAPPA_SIGMA * pn)), KAPPA_SIGMA * mur / pn);
+    zn[b * m + r] = fmin(fmax(zn[b * m + r] + az * R.dzn[b * m + r], mur / (KAPPA_SIGMA * nn)), KAPPA_SIGMA * mur / nn);
     pR[b * m + r] = pn;
     nR[b * m + r] = nn;
   }
@@ -1750,21 +1720,21 @@ __global__ __launch_bounds__(256) void k_resto_accept(
     w[b * nw + k] = wn;
   }
   if (lane == 0) {
-    movedR[b] = 1;
-    iters[b] += 1;
+    R.movedR[b] = 1;
+    R.iters[b] += 1;
     if (st_aug[b]) {
-      const int64_t fc = fcR[b];
+      const int64_t fc = R.fcR[b];
       const int slot = (int)(fc % FMAX);
       const double tk = thetaR[b], pk = phiR[b];
       ftR[b * FMAX + slot] = (1.0 - GAMMA_TH) * tk;
       fpR[b * FMAX + slot] = pk - GAMMA_PHI * tk;
-      fcR[b] = fc + 1;
+      R.fcR[b] = fc + 1;
     }
   }
   // ---- back to the regular iteration?
-  const double mub = mu[b];
+  const double mub = R.mu[b];
   double th = 0.0, lg = 0.0;
-  for (int r = lane; r < m; r += 64) th += fabs(cons_row(g_n + b * m, st_w + b * nw, nf, r, row_slack, gl));
+  for (int r = lane; r < m; r += 64) th += fabs(cons_row(R.g_n + b * m, st_w + b * nw, nf, r, R.row_slack, R.gl));
   for (int k = lane; k < nw; k += 64) {
     const double wn = st_w[b * nw + k];
     if (hasL[k]) lg += log(wn - wl0[k]);
@@ -1772,12 +1742,12 @@ __global__ __launch_bounds__(256) void k_resto_accept(
   }
   th = wave_sum(th);
   lg = wave_sum(lg);
-  const double ph = f_n[b] - mub * lg;
+  const double ph = R.f_n[b] - mub * lg;
   bool rejected = false;
-  for (int k = lane; k < FMAX; k += 64) rejected |= !((th <= filt_t[b * FMAX + k]) || (ph <= filt_p[b * FMAX + k]));
+  for (int k = lane; k < FMAX; k += 64) rejected |= !((th <= R.filt_t[b * FMAX + k]) || (ph <= R.filt_p[b * FMAX + k]));
   const bool in_filter = __ballot(rejected) == 0;
-  const double t0 = th_o0[b];
-  const double p0 = ph_o0[b];
+  const double t0 = R.th_o0[b];
+  const double p0 = R.ph_o0[b];
   const bool vs_start = (th - (1.0 - GAMMA_TH) * t0 <= 10.0 * DBL_EPSILON * fabs(t0)) ||
                         ((ph - p0) - (-GAMMA_PHI * t0) <= 10.0 * DBL_EPSILON * fabs(p0));
   const bool back = isfinite(th) && isfinite(ph) && th <= KAPPA_RESTO * t0 && in_filter && vs_start;
@@ -1791,12 +1761,12 @@ __global__ __launch_bounds__(256) void k_resto_accept(
     if (k < nw) {
       const double wr = wR[b * nw + k], wn = st_w[b * nw + k];
       if (hasL[k]) {
-        const double s0 = wr - wl0[k], s1 = wn - wl0[k], z = zL[b * nw + k];
+        const double s0 = wr - wl0[k], s1 = wn - wl0[k], z = R.zL[b * nw + k];
         dzl[h] = (z * (s0 - s1) + mub) / s0 - z;
         if (dzl[h] < 0.0) ad = fmin(ad, -tau * z / dzl[h]);
       }
       if (hasU[k]) {
-        const double s0 = wu0[k] - wr, s1 = wu0[k] - wn, z = zU[b * nw + k];
+        const double s0 = wu0[k] - wr, s1 = wu0[k] - wn, z = R.zU[b * nw + k];
         dzu[h] = (z * (s0 - s1) + mub) / s0 - z;
         if (dzu[h] < 0.0) ad = fmin(ad, -tau * z / dzu[h]);
       }
@@ -1808,8 +1778,8 @@ __global__ __launch_bounds__(256) void k_resto_accept(
   for (int h = 0; h < 2; ++h) {
     const int k = lane + 64 * h;
     if (k < nw) {
-      zl_n[h] = hasL[k] ? zL[b * nw + k] + ad * dzl[h] : zL[b * nw + k];
-      zu_n[h] = hasU[k] ? zU[b * nw + k] + ad * dzu[h] : zU[b * nw + k];
+      zl_n[h] = hasL[k] ? R.zL[b * nw + k] + ad * dzl[h] : R.zL[b * nw + k];
+      zu_n[h] = hasU[k] ? R.zU[b * nw + k] + ad * dzu[h] : R.zU[b * nw + k];
       zmax = fmax(zmax, fmax(zl_n[h], zu_n[h]));
     }
   }
@@ -1819,19 +1789,19 @@ __global__ __launch_bounds__(256) void k_resto_accept(
   for (int h = 0; h < 2; ++h) {
     const int k = lane + 64 * h;
     if (k < nw) {
-      zL[b * nw + k] = (big && hasL[k]) ? 1.0 : zl_n[h];
-      zU[b * nw + k] = (big && hasU[k]) ? 1.0 : zu_n[h];
+      R.zL[b * nw + k] = (big && hasL[k]) ? 1.0 : zl_n[h];
+      R.zU[b * nw + k] = (big && hasU[k]) ? 1.0 : zu_n[h];
     }
   }
   for (int r = lane; r < m; r += 64) y[b * m + r] = 0.0;
   if (lane == 0) {
-    in_resto[b] = 0;
-    acc[b] = 0;
-    lm_cnt[b] = 0;
-    lm_skip[b] = 0;
-    if (Hq) {  // (limited-memory mode only)
-      Hq[b * lmc] = 1.0;
-      Hq[b * lmc + 1] = 0.0;
+    R.in_resto[b] = 0;
+    R.acc[b] = 0;
+    R.lm_cnt[b] = 0;
+    R.lm_skip[b] = 0;
+    if (R.Hq) {  // (limited-memory mode only)
+      R.Hq[b * R.lmc] = 1.0;
+      R.Hq[b * R.lmc + 1] = 0.0;
     }
   }
 }
@@ -1851,9 +1821,21 @@ struct TrackBest {  // (small batches) k_track_best's work inside k_count1; best
   double *best_w, *best_f;
   const double* dc;  // (scaled solves) the row factors: the violation is the unscaled g's; else NULL
 };
+// max violation of the constraint values g_b [m] against their original bounds (NaN: infinite), on
+// one wave.  dcb (scaled solves: the instance's row factors, else NULL): g_b holds the scaled problem's
+// values dc g, so the original constraint's value is g_b / dc (the bounds, 0 or infinite, are the
+// original ones either way) — fallback_viol_tol applies to the original constraints
 __device__ __forceinline__ double orig_violation_wave(int m, const double* __restrict__ gb,
                                                       const double* __restrict__ gl, const double* __restrict__ gu,
-                                                      const double* __restrict__ dcb);
+                                                      const double* __restrict__ dcb) {
+  double v = 0.0;
+  for (int r = threadIdx.x & 63; r < m; r += 64) {
+    const double gv = dcb ? gb[r] / dcb[r] : gb[r];
+    v = fmax(v, fmax(fmax(gl[r] - gv, gv - gu[r]), 0.0));
+    if (gv != gv) v = INFINITY;
+  }
+  return wave_max(v);
+}
 // k_track_best's work for instance b (one wave)
 __device__ __forceinline__ void track_best_one(const TrackBest& tb, const uint8_t* __restrict__ active, int m,
                                                int64_t b, int lane) {
@@ -1864,13 +1846,19 @@ __device__ __forceinline__ void track_best_one(const TrackBest& tb, const uint8_
   for (int k = lane; k < tb.nw; k += 64) tb.best_w[b * tb.nw + k] = tb.w[b * tb.nw + k];
   if (lane == 0) tb.best_f[b] = fb;
 }
-// k_resto_y0's work for a failed instance b (one wave)
+// the entry's least-squares estimate of a failed instance b, kept when |y|max <= constr_mult_init_max = 1e3
+// (one wave)
 __device__ __forceinline__ void resto_y0_one(int m, const double* __restrict__ dy, double* __restrict__ y, int64_t b,
                                              int lane) {
   double mx = 0.0;
   for (int r = lane; r < m; r += 64) mx = fmax(mx, fabs(dy[b * m + r]));
   mx = wave_max(mx);
   for (int r = lane; r < m; r += 64) y[b * m + r] = mx <= 1e3 ? dy[b * m + r] : 0.0;
+}
+__global__ __launch_bounds__(256) void k_resto_y0(int64_t B, int m, const uint8_t* __restrict__ failed,
+                                                  const double* __restrict__ dy, double* __restrict__ y) {
+  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
+  if (b < B && failed[b]) resto_y0_one(m, dy, y, b, threadIdx.x & 63);
 }
 // the two counts into count[0..1] and, with a mailbox, to the host behind the sequence number
 __device__ __forceinline__ void post_counts(int t, int tr, int32_t* __restrict__ count, int32_t* __restrict__ mail) {
@@ -1947,9 +1935,10 @@ struct QdSolveArgs {
 };
 __global__ __launch_bounds__(TAIL_THREADS) void k_tail_small(int64_t B, const RestoEnterArgs E, const QdSolveArgs Q,
                                                              const uint8_t* __restrict__ active,
-                                                             const uint8_t* __restrict__ in_resto,
-                                                             int32_t* __restrict__ count, int32_t* __restrict__ mail,
-                                                             double* __restrict__ y, const TrackBest tb) {
+                                                             const uint8_t* in_resto, int32_t* __restrict__ count,
+                                                             int32_t* __restrict__ mail, double* y,
+                                                             const TrackBest tb) {
+  // (in_resto and y without __restrict__: the entry stores to both through E)
   extern __shared__ __align__(16) double qd_lds[];
   const int64_t b = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -2069,31 +2058,38 @@ __global__ void k_gather_bytes(int64_t k, const int32_t* __restrict__ pos, const
 
 // the final state of every row that leaves the batch (finished, or at the end: all rows), written
 // to the instance's own position orig[r] of the full-batch result arrays
-__global__ __launch_bounds__(256) void k_scatter_final(int64_t rows, int n, int m, int nw, bool finished_only,
-                                                       const int32_t* __restrict__ orig, const uint8_t* __restrict__ active,
-                                                       const double* __restrict__ w, const double* __restrict__ y,
-                                                       const double* __restrict__ dc, const double* __restrict__ df,
-                                                       const double* __restrict__ Xbase, const double* __restrict__ d_inf,
-                                                       const int64_t* __restrict__ status, const int64_t* __restrict__ iters,
-                                                       const int64_t* __restrict__ n_resto,
-                                                       double* __restrict__ fw, double* __restrict__ fy,
-                                                       double* __restrict__ fX, double* __restrict__ fdinf,
-                                                       int64_t* __restrict__ fstatus, int64_t* __restrict__ fiters,
-                                                       int64_t* __restrict__ fresto) {
+struct LeaveArgs {  // rows leaving the batch: k_fallback, then k_scatter_final
+  int n = 0, m = 0, nw = 0;
+  double vtol = 0.0;
+  bool finished_only = false;
+  const int32_t* orig = nullptr;
+  const uint8_t* active = nullptr;
+  Iterate it;
+  const double *dc = nullptr, *df = nullptr, *Xbase = nullptr, *d_inf = nullptr;
+  const double *g = nullptr, *gl = nullptr, *gu = nullptr, *best_w = nullptr, *best_f = nullptr;
+  const int64_t *status = nullptr, *iters = nullptr, *n_resto = nullptr;
+  double *fw = nullptr, *fy = nullptr, *fX = nullptr, *fdinf = nullptr;
+  int64_t *fstatus = nullptr, *fiters = nullptr, *fresto = nullptr;
+  uint8_t* fbest = nullptr;
+};
+__global__ __launch_bounds__(256) void k_scatter_final(int64_t rows, const LeaveArgs a) {
+  const int n = a.n, m = a.m, nw = a.nw;
+  const auto [w, y, zL, zU] = a.it;
   const int64_t r = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
   if (r >= rows) return;
-  const int32_t o = orig[r];
-  if (o < 0 || (finished_only && active[r])) return;
+  const int32_t o = a.orig[r];
+  if (o < 0 || (a.finished_only && a.active[r])) return;
   const int lane = threadIdx.x & 63;
-  for (int k = lane; k < nw; k += 64) fw[(int64_t)o * nw + k] = w[r * nw + k];
+  for (int k = lane; k < nw; k += 64) a.fw[(int64_t)o * nw + k] = w[r * nw + k];
   // the multipliers of the unscaled problem: (dc y) / df (nlp_scaling; dc = nullptr: unscaled)
-  for (int k = lane; k < m; k += 64) fy[(int64_t)o * m + k] = dc ? (dc[r * m + k] * y[r * m + k]) / df[r] : y[r * m + k];
-  for (int k = lane; k < n; k += 64) fX[(int64_t)o * n + k] = Xbase[r * n + k];
+  for (int k = lane; k < m; k += 64)
+    a.fy[(int64_t)o * m + k] = a.dc ? (a.dc[r * m + k] * y[r * m + k]) / a.df[r] : y[r * m + k];
+  for (int k = lane; k < n; k += 64) a.fX[(int64_t)o * n + k] = a.Xbase[r * n + k];
   if (lane == 0) {
-    fdinf[o] = d_inf[r];
-    fstatus[o] = status[r];
-    fiters[o] = iters[r];
-    fresto[o] = n_resto[r];
+    a.fdinf[o] = a.d_inf[r];
+    a.fstatus[o] = a.status[r];
+    a.fiters[o] = a.iters[r];
+    a.fresto[o] = a.n_resto[r];
   }
 }
 
@@ -2121,62 +2117,32 @@ __global__ void k_iota(int64_t B, int32_t* __restrict__ orig) {
   if (b < B) orig[b] = (int32_t)b;
 }
 
-// max violation of the constraint values g_b [m] against their original bounds (NaN: infinite), on
-// one wave.  dcb (scaled solves: the instance's row factors, else NULL): g_b holds the scaled problem's
-// values dc g, so the original constraint's value is g_b / dc (the bounds, 0 or infinite, are the
-// original ones either way) — fallback_viol_tol applies to the original constraints
-__device__ __forceinline__ double orig_violation_wave(int m, const double* __restrict__ gb,
-                                                      const double* __restrict__ gl, const double* __restrict__ gu,
-                                                      const double* __restrict__ dcb) {
-  double v = 0.0;
-  for (int r = threadIdx.x & 63; r < m; r += 64) {
-    const double gv = dcb ? gb[r] / dcb[r] : gb[r];
-    v = fmax(v, fmax(fmax(gl[r] - gv, gv - gu[r]), 0.0));
-    if (gv != gv) v = INFINITY;
-  }
-  return wave_max(v);
-}
-
 // The best iterate of every active instance: after each iteration's acceptance, the current point
 // (w, f, g in sync) replaces the kept one when its original constraints hold to `vtol` and its
 // objective is lower.  (Not IPOPT: a solve that ends without convergence at an infeasible iterate
 // returns this one instead, k_fallback.)
-__global__ __launch_bounds__(256) void k_track_best(int64_t B, int m, int nw, double vtol,
-                                                    const uint8_t* __restrict__ active, const double* __restrict__ w,
-                                                    const double* __restrict__ f, const double* __restrict__ g,
-                                                    const double* __restrict__ gl, const double* __restrict__ gu,
-                                                    double* __restrict__ best_w, double* __restrict__ best_f,
-                                                    const double* __restrict__ dc) {
+__global__ __launch_bounds__(256) void k_track_best(int64_t B, int m, const uint8_t* __restrict__ active,
+                                                    const TrackBest tb) {
   const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B || !active[b]) return;
-  const double v = orig_violation_wave(m, g + b * m, gl, gu, dc ? dc + b * m : nullptr);
-  const double fb = f[b];
-  if (!(v <= vtol) || !(fb < best_f[b])) return;
-  const int lane = threadIdx.x & 63;
-  for (int k = lane; k < nw; k += 64) best_w[b * nw + k] = w[b * nw + k];
-  if (lane == 0) best_f[b] = fb;
+  if (b < B) track_best_one(tb, active, m, b, threadIdx.x & 63);
 }
 
 // Rows leaving the batch (finished ones, or every row at the end): an instance that stopped without
 // converging (max_iter, local infeasibility, restoration failure) at an iterate violating its
 // constraints by more than `vtol` returns its best feasible iterate (k_track_best) when it met one;
 // fbest[orig] records it
-__global__ __launch_bounds__(256) void k_fallback(int64_t rows, int m, int nw, double vtol, bool finished_only,
-                                                  const int32_t* __restrict__ orig, const uint8_t* __restrict__ active,
-                                                  const int64_t* __restrict__ status, const double* __restrict__ g,
-                                                  const double* __restrict__ gl, const double* __restrict__ gu,
-                                                  const double* __restrict__ best_w, const double* __restrict__ best_f,
-                                                  double* __restrict__ w, uint8_t* __restrict__ fbest,
-                                                  const double* __restrict__ dc) {
+__global__ __launch_bounds__(256) void k_fallback(int64_t rows, const LeaveArgs a) {
+  const int m = a.m, nw = a.nw;
+  const auto [w, y, zL, zU] = a.it;
   const int64_t r = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
   if (r >= rows) return;
-  const int32_t o = orig[r];
-  if (o < 0 || (finished_only && active[r]) || status[r] <= CPL_SOLVE_ACCEPTABLE) return;
-  const double v = orig_violation_wave(m, g + r * m, gl, gu, dc ? dc + r * m : nullptr);
-  if (v <= vtol || !(best_f[r] < INFINITY)) return;
+  const int32_t o = a.orig[r];
+  if (o < 0 || (a.finished_only && a.active[r]) || a.status[r] <= CPL_SOLVE_ACCEPTABLE) return;
+  const double v = orig_violation_wave(m, a.g + r * m, a.gl, a.gu, a.dc ? a.dc + r * m : nullptr);
+  if (v <= a.vtol || !(a.best_f[r] < INFINITY)) return;
   const int lane = threadIdx.x & 63;
-  for (int k = lane; k < nw; k += 64) w[r * nw + k] = best_w[r * nw + k];
-  if (lane == 0) fbest[o] = 1;
+  for (int k = lane; k < nw; k += 64) w[r * nw + k] = a.best_w[r * nw + k];
+  if (lane == 0) a.fbest[o] = 1;
 }
 
 __global__ void k_fill(int64_t B, double v, double* __restrict__ out) {
@@ -2448,9 +2414,145 @@ int32_t hessian_into(cpl_solver* S, const cpl_problem_desc* d, const uint8_t* ma
   return CPL_OK;
 }
 
-static NearFeasible near_feasible(cpl_solver* S, const cpl_solve_options& o) {
-  return NearFeasible{S->theta_k, 1e-2 * o.tol, S->nw, S->m, S->has_acc, S->acc_w, S->acc_y, S->acc_zL, S->acc_zU,
+// ---- the kernels' argument structs from the solver's buffers: each buffer is named here, once ----
+Bounds bounds_of(const cpl_solver* S) {
+  Bounds b;
+  b.hasL = S->hasL; b.hasU = S->hasU; b.wl0 = S->wl0; b.wu0 = S->wu0;
+  return b;
+}
+Iterate iterate_of(const cpl_solver* S) {
+  Iterate i;
+  i.w = S->w; i.y = S->y; i.zL = S->zL; i.zU = S->zU;
+  return i;
+}
+Step step_of(const cpl_solver* S) {
+  Step d;
+  d.dw = S->dw; d.dy = S->dy; d.dzL = S->dzL; d.dzU = S->dzU;
+  return d;
+}
+Staged staged_of(const cpl_solver* S) {
+  Staged t;
+  t.f = S->st_f; t.g = S->st_g; t.w = S->st_w; t.alpha = S->st_alpha; t.aug = S->st_aug; t.p = S->st_p; t.n = S->st_n;
+  return t;
+}
+Search search_of(const cpl_solver* S) {  // the regular search (mu, filter: after this iteration's barrier update)
+  Search q;
+  q.act = S->act; q.searching = S->searching; q.alpha = S->alpha; q.a_min = S->a_min; q.mu = S->mu_o;
+  q.theta = S->theta_k; q.phi = S->phi_k; q.gd = S->gd; q.switch_ok = S->switch_ok; q.theta_max = S->theta_max;
+  q.filt_t = S->ft; q.filt_p = S->fp;
+  return q;
+}
+Search resto_search_of(const cpl_solver* S) {  // the restoration problem's own search
+  Search q;
+  q.act = S->actR; q.searching = S->searchingR; q.alpha = S->alphaR; q.a_min = S->a_minR; q.mu = S->muR;
+  q.theta = S->thetaR; q.phi = S->phiR; q.gd = S->gdR; q.switch_ok = S->switchR; q.theta_max = S->thmaxR;
+  q.filt_t = S->ftR; q.filt_p = S->fpR;
+  return q;
+}
+InitStateArgs init_state_args(const cpl_solver* S) {
+  InitStateArgs a;
+  a.n = S->n; a.m = S->m; a.nf = S->nf; a.nw = S->nw; a.mu_init = S->opt.mu_init;
+  a.free_idx = S->free32; a.ineq_row = S->ineq_row; a.row_slack = S->row_slack; a.gl = S->gl;
+  a.X = S->X; a.g = S->g; a.grad = S->grad; a.bd = bounds_of(S); a.it = iterate_of(S);
+  a.theta_max = S->theta_max; a.theta_min = S->theta_min; a.mu = S->mu; a.filt_t = S->filt_t; a.filt_p = S->filt_p;
+  a.dwl = S->dwl; a.d_inf = S->d_inf; a.r1 = S->r1; a.r2 = S->r2; a.M = S->M;
+  a.active = S->active; a.lm_cnt = S->lm_cnt; a.lm_skip = S->lm_skip;
+  a.status = S->status; a.iters = S->iters; a.acc = S->acc; a.fcount = S->fcount;
+  return a;
+}
+SoftStepArgs soft_step_args(const cpl_solver* S) {  // (the soft step's callbacks land in the accepted point's buffers)
+  SoftStepArgs a;
+  a.n = S->n; a.m = S->m; a.nf = S->nf; a.nw = S->nw; a.nnz_rec = S->nnz_rec;
+  a.amap = S->amap; a.row_slack = S->row_slack; a.free32 = S->free32; a.freepos = S->freepos; a.gl = S->gl;
+  a.Xbase = S->Xbase; a.bd = bounds_of(S); a.it = iterate_of(S); a.sp = step_of(S); a.ls = search_of(S);
+  a.st = staged_of(S); a.tiny = S->tiny_now; a.soft_now = S->soft_now; a.soft_try = S->soft_try;
+  a.in_soft = S->in_soft; a.soft_cnt = S->soft_cnt; a.a_soft = S->a_soft; a.ws = S->ws_; a.Xs = S->Xs;
+  a.f_s = S->f_n; a.grad_s = S->grad_n; a.g_s = S->g_n; a.J_s = S->J_n; a.A = S->A; a.gradw = S->gradw; a.c = S->c;
+  a.a_max = S->a_max; a.a_z = S->a_z; a.cs_tmp = S->cs_tmp;
+  return a;
+}
+NearFeasible near_feasible(const cpl_solver* S) {
+  return NearFeasible{S->theta_k, 1e-2 * S->opt.tol, S->nw, S->m, S->has_acc, S->acc_w, S->acc_y, S->acc_zL, S->acc_zU,
                       S->w, S->y, S->zL, S->zU};
+}
+FailTail fail_tail(const cpl_solver* S) {
+  FailTail t;
+  t.n = S->n; t.nw = S->nw; t.freepos = S->freepos; t.Xbase = S->Xbase; t.X = S->Xn; t.act = S->act;
+  t.st = staged_of(S); t.err0 = S->err0; t.acc_tol = S->opt.acceptable_tol; t.failed = S->failed; t.moved = S->moved;
+  t.in_soft = S->in_soft; t.soft_cnt = S->soft_cnt; t.status = S->status; t.active = S->active;
+  t.nf = near_feasible(S);
+  return t;
+}
+RestoArgs resto_args(const cpl_solver* S) {
+  RestoArgs R;
+  R.m = S->m; R.nf = S->nf; R.nw = S->nw; R.nbounds = S->nbounds; R.tol = S->opt.tol; R.mu_min = S->mu_min;
+  R.lmc = S->bfgs ? LMC(S->nf) : 0; R.row_slack = S->row_slack; R.gl = S->gl; R.bd = bounds_of(S);
+  R.it.w = S->w; R.it.y = S->y; R.it.zL = S->zLR; R.it.zU = S->zUR;
+  R.rv.wR = S->wR; R.rv.pR = S->pR; R.rv.nR = S->nR; R.rv.zp = S->zp; R.rv.zn = S->zn;
+  R.sp = step_of(S); R.ls = resto_search_of(S); R.st = staged_of(S);
+  R.dp = S->dp; R.dn = S->dn; R.dzp = S->dzp; R.dzn = S->dzn; R.tauR = S->tauR; R.gfR = S->gfR;
+  R.a_z = S->a_zR; R.A = S->A; R.c = S->c;
+  R.wt = S->wt; R.f_t = S->f_t; R.g_t = S->g_t; R.f_n = S->f_n; R.g_n = S->g_n;
+  R.active = S->active; R.in_resto = S->in_resto; R.resto_tight = S->resto_tight; R.movedR = S->movedR;
+  R.status = S->status; R.iters = S->iters; R.fcR = S->fcR; R.acc = S->acc;
+  R.mu = S->mu; R.filt_t = S->filt_t; R.filt_p = S->filt_p; R.th_o0 = S->th_o0; R.ph_o0 = S->ph_o0;
+  R.zL = S->zL; R.zU = S->zU; R.lm_cnt = S->lm_cnt; R.lm_skip = S->lm_skip; R.Hq = S->bfgs ? S->Hq : nullptr;
+  return R;
+}
+LeaveArgs leave_args(const cpl_solver* S, bool finished_only) {
+  LeaveArgs a;
+  a.n = S->n; a.m = S->m; a.nw = S->nw; a.vtol = S->opt.fallback_viol_tol; a.finished_only = finished_only;
+  a.orig = S->orig; a.active = S->active; a.it = iterate_of(S); a.dc = S->scaled ? S->dc : nullptr; a.df = S->df;
+  a.Xbase = S->Xbase; a.d_inf = S->d_inf; a.g = S->g; a.gl = S->gl; a.gu = S->gu; a.best_w = S->best_w;
+  a.best_f = S->best_f; a.status = S->status; a.iters = S->iters; a.n_resto = S->n_resto;
+  a.fw = S->fw; a.fy = S->fy; a.fX = S->fX; a.fdinf = S->fdinf; a.fstatus = S->fstatus; a.fiters = S->fiters;
+  a.fresto = S->fresto; a.fbest = S->fbest;
+  return a;
+}
+TrackBest track_best(const cpl_solver* S) {
+  return TrackBest{S->nw, S->opt.fallback_viol_tol, S->w, S->f, S->g, S->gl, S->gu, S->best_w, S->best_f,
+                   S->scaled ? S->dc : nullptr};
+}
+static_assert(sizeof(RestoArgs) <= 1024 && sizeof(SoftStepArgs) + sizeof(FailTail) <= 1024,
+              "the widest kernel arguments stay far below the 4 KiB kernarg limit");
+
+// The L-BFGS update of the instances of `mask` from (w, gw_old, J) to the accepted point (st_w, grad_new,
+// J_n); grad_new == nullptr: no cost term (the restoration phase's model: the constraint curvature
+// alone).  nf <= 64 takes the one-wave form, larger problems the workgroup form.
+int32_t lbfgs_update(cpl_solver* S, const uint8_t* mask, const double* gw_old, const double* grad_new) {
+  LbfgsArgs L;
+  L.n = S->n; L.m = S->m; L.nf = S->nf; L.nw = S->nw; L.nnz_rec = S->nnz_rec; L.amap = S->amap; L.free_idx = S->free32;
+  L.act = mask; L.failed = S->zeros_u8; L.w_old = S->w; L.w_new = S->st_w; L.y = S->y; L.dy = S->dy;
+  L.alpha = S->st_alpha; L.gw_old = gw_old; L.J_old = S->J; L.grad_new = grad_new; L.J_new = S->J_n;
+  L.lm_s = S->lm_s; L.lm_y = S->lm_y; L.lm_cnt = S->lm_cnt; L.lm_skip = S->lm_skip; L.Hq = S->Hq;
+  const int64_t B = S->Bcur;
+  if (S->nf <= 64)
+    hipLaunchKernelGGL(k_lbfgs_wave, dim3((unsigned)((B + LBW_WAVES - 1) / LBW_WAVES)), dim3(64 * LBW_WAVES),
+                       sizeof(double) * LBW_WAVES * (size_t)S->m, S->stream, B, L);
+  else
+    hipLaunchKernelGGL(k_lbfgs, dim3((unsigned)B), dim3(256), 0, S->stream, B, L);
+  LAUNCHED("k_lbfgs");
+  return CPL_OK;
+}
+
+// The backtracking kernel's arguments common to its three uses, for the search `q` (the regular one or
+// the restoration phase's); a caller sets what differs: first / max_soc and the KKT buffers, the soft
+// step's buffers, with_post, resto / rho and the restoration variables
+LsBacktrackArgs ls_backtrack_args(const cpl_solver* S, const Search& q) {
+  LsBacktrackArgs la;
+  la.batch = S->Bcur; la.n = S->n; la.m = S->m; la.nf = S->nf; la.nw = S->nw; la.nfilt = FMAX;
+  la.max_trials = std::max(S->opt.max_ls - 1, 0);
+  la.act = q.act; la.tiny = S->tiny_now; la.soft_now = S->soft_now; la.soft_cnt = S->soft_cnt;
+  la.searching = q.searching; la.alpha = q.alpha; la.a_min = q.a_min;
+  la.w = S->w; la.dw = S->dw; la.Xbase = S->Xbase; la.freepos = S->freepos; la.row_slack = S->row_slack;
+  la.gl = S->gl; la.hasL = S->hasL; la.hasU = S->hasU; la.wl0 = S->wl0; la.wu0 = S->wu0;
+  la.mu = q.mu; la.theta_k = q.theta; la.phi_k = q.phi; la.gd = q.gd; la.switch_ok = q.switch_ok;
+  la.theta_max = q.theta_max; la.filt_t = q.filt_t; la.filt_p = q.filt_p;
+  la.mass = S->mass; la.env_tag = S->tag;
+  if (S->scaled) { la.df = S->df; la.dc = S->dc; }
+  la.st_f = S->st_f; la.st_g = S->st_g; la.st_w = S->st_w; la.st_alpha = S->st_alpha; la.st_aug = S->st_aug;
+  la.any = S->d_any;
+  return la;
 }
 
 int32_t step_phase(cpl_solver* S, int phase) {
@@ -2459,6 +2561,7 @@ int32_t step_phase(cpl_solver* S, int phase) {
   hipStream_t st = S->stream;
   const cpl_solve_options& o = S->opt;
   const int64_t lmc = S->bfgs ? LMC(nf) : 0;
+  const RestoArgs ra = resto_args(S);
   auto judge = [&](const double* wt, const double* ft_, const double* gt_, const double* al, const uint8_t* extra,
                    double* th, uint8_t* ok) {
     return cpl_ipm_judge_take(B, nw, m, nf, FMAX, S->row_slack, S->gl, S->hasL, S->hasU, S->wl0, S->wu0, wt, ft_, gt_,
@@ -2516,10 +2619,7 @@ int32_t step_phase(cpl_solver* S, int phase) {
     CK(cpl_ipm_trial_point(B, n, nf, nw, S->free64, S->fixed64, S->Xbase, S->w, S->dw, S->alphaR, S->searchingR,
                            S->st_w, S->wt, S->Xt, st));
     CK(eval_fg(S, S->Xt, S->f_t, S->g_t));
-    hipLaunchKernelGGL(k_resto_judge, dim3(blocks_for(B)), dim3(256), 0, st, B, m, nf, nw, S->searchingR, S->row_slack,
-                       S->gl, S->hasL, S->hasU, S->wl0, S->wu0, S->wt, S->f_t, S->g_t, S->alphaR, S->pR, S->nR, S->dp,
-                       S->dn, S->wR, S->muR, S->thetaR, S->phiR, S->gdR, S->switchR, S->thmaxR, S->ftR, S->fpR,
-                       S->searchingR, S->st_f, S->st_g, S->st_w, S->st_p, S->st_n, S->st_alpha, S->st_aug);
+    hipLaunchKernelGGL(k_resto_judge, dim3(blocks_for(B)), dim3(256), 0, st, B, ra);
     LAUNCHED("k_resto_judge");
     return halve(S->searchingR, S->alphaR, S->a_minR, 2, false);
   };
@@ -2572,38 +2672,22 @@ int32_t step_phase(cpl_solver* S, int phase) {
       ls.tiny_last = S->tiny_last; ls.tiny_flag = S->tiny_flag; ls.tiny_now = S->tiny_now; ls.soft_now = S->soft_now;
       ls.a_min = S->a_min; ls.searching = S->searching; ls.st_f = S->st_f; ls.st_g = S->st_g; ls.st_w = S->st_w;
       ls.st_alpha = S->st_alpha; ls.st_aug = S->st_aug; ls.alpha = S->alpha; ls.any = S->d_any;
-      const PostStepArgs post{nw, S->w, S->dw, S->zL, S->zU, S->gphi, S->mu_o, S->tau, S->hasL, S->hasU, S->wl0,
-                              S->wu0, S->theta_k, S->theta_min, S->act, S->delta_w, S->dwl, S->dzL, S->dzU,
-                              S->a_max, S->a_z, S->gd, S->switch_ok};
-      if (!post_in_ls)
-        CK(ipm_post_step_ex(B, nw, S->w, S->dw, S->zL, S->zU, S->gphi, S->mu_o, S->tau, S->hasL, S->hasU, S->wl0,
-                            S->wu0, S->theta_k, S->theta_min, S->act, S->delta_w, S->dwl, S->dzL, S->dzU, S->a_max,
-                            S->a_z, S->gd, S->switch_ok, &ls, st));
+      PostStepArgs post;
+      post.nw = nw; post.w = S->w; post.dw = S->dw; post.zL = S->zL; post.zU = S->zU; post.gphi = S->gphi;
+      post.mu = S->mu_o; post.tau = S->tau; post.hasL = S->hasL; post.hasU = S->hasU; post.wl0 = S->wl0;
+      post.wu0 = S->wu0; post.theta = S->theta_k; post.theta_min = S->theta_min; post.active = S->act;
+      post.delta_w = S->delta_w; post.dwl = S->dwl; post.dzL = S->dzL; post.dzU = S->dzU; post.a_max = S->a_max;
+      post.a_z = S->a_z; post.gd_out = S->gd; post.switch_ok = S->switch_ok;
+      if (!post_in_ls) CK(ipm_post_step_ex(B, post, &ls, st));
       if (!fused_ls) CK(first_trial());
-      if (fused && S->ls_fusable) {
-        LsBacktrackArgs la;
-        la.batch = B; la.n = n; la.m = m; la.nf = nf; la.nw = nw; la.nfilt = FMAX; la.max_trials = o.max_ls - 1;
-        if (la.max_trials < 0) la.max_trials = 0;
-        la.act = S->act; la.tiny = S->tiny_now; la.soft_now = S->soft_now; la.soft_cnt = S->soft_cnt;
-        la.searching = S->searching; la.alpha = S->alpha; la.a_min = S->a_min;
-        la.w = S->w; la.dw = S->dw; la.Xbase = S->Xbase; la.freepos = S->freepos; la.row_slack = S->row_slack;
-        la.gl = S->gl; la.hasL = S->hasL; la.hasU = S->hasU; la.wl0 = S->wl0; la.wu0 = S->wu0;
-        la.mu = S->mu_o; la.theta_k = S->theta_k; la.phi_k = S->phi_k; la.gd = S->gd; la.switch_ok = S->switch_ok;
-        la.theta_max = S->theta_max; la.filt_t = S->ft; la.filt_p = S->fp;
-        la.mass = S->mass; la.env_tag = S->tag;
-        if (S->scaled) { la.df = S->df; la.dc = S->dc; }
-        la.st_f = S->st_f; la.st_g = S->st_g; la.st_w = S->st_w; la.st_alpha = S->st_alpha; la.st_aug = S->st_aug;
-        la.any = S->d_any;
-        la.resto = 0;
-        la.rho = 0.0;
-        la.pR = la.nR = la.dp = la.dn = la.wR = nullptr;
-        la.st_p = la.st_n = nullptr;
+      if (!fused_ls && o.max_ls <= 1) return CPL_OK;
+      LsBacktrackArgs la = ls_backtrack_args(S, search_of(S));
+      if (fused_ls) {  // the whole search in one launch
         la.first = 1;
         la.max_soc = o.max_soc;
         la.c = S->c; la.M = S->M; la.r1 = S->r1; la.kkt_ws = S->ws; la.tau = S->tau;
         if (S->jreg) { la.aug_dc = S->delta_c; la.aug_ws = S->ws_aug; }  // (the regularised systems' re-solves)
         la.a_max = S->a_max; la.a_z = S->a_z;
-        la.soft_ws = la.soft_X = la.a_soft = nullptr; la.soft_try = nullptr;
         if (S->soft_fused) {
           la.soft_ws = S->ws_; la.soft_X = S->Xs; la.soft_try = S->soft_try; la.a_soft = S->a_soft;
           S->soft_begun = true;
@@ -2612,60 +2696,24 @@ int32_t step_phase(cpl_solver* S, int phase) {
         la.setup = ls;
         la.setup.any = nullptr;  // (cleared by the optimality kernel: other waves set them concurrently)
         la.with_post = post_in_ls ? 1 : 0;
-        CK(ls_backtrack(&S->desc, la, st));
-      } else if (o.max_ls > 1) {  // the remaining trials of every instance still searching, in one launch
+      } else {  // the remaining trials of every instance still searching, in one launch
         HK(hipMemsetAsync(S->d_any, 0, 2, st), "hipMemsetAsync flags");
-        LsBacktrackArgs la;
-        la.batch = B; la.n = n; la.m = m; la.nf = nf; la.nw = nw; la.nfilt = FMAX; la.max_trials = o.max_ls - 1;
-        la.act = S->act; la.tiny = S->tiny_now; la.soft_now = S->soft_now; la.soft_cnt = S->soft_cnt;
-        la.searching = S->searching; la.alpha = S->alpha; la.a_min = S->a_min;
-        la.w = S->w; la.dw = S->dw; la.Xbase = S->Xbase; la.freepos = S->freepos; la.row_slack = S->row_slack;
-        la.gl = S->gl; la.hasL = S->hasL; la.hasU = S->hasU; la.wl0 = S->wl0; la.wu0 = S->wu0;
-        la.mu = S->mu_o; la.theta_k = S->theta_k; la.phi_k = S->phi_k; la.gd = S->gd; la.switch_ok = S->switch_ok;
-        la.theta_max = S->theta_max; la.filt_t = S->ft; la.filt_p = S->fp;
-        la.mass = S->mass; la.env_tag = S->tag;
-        if (S->scaled) { la.df = S->df; la.dc = S->dc; }
-        la.st_f = S->st_f; la.st_g = S->st_g; la.st_w = S->st_w; la.st_alpha = S->st_alpha; la.st_aug = S->st_aug;
-        la.any = S->d_any;
-        la.resto = 0;
-        la.rho = 0.0;
-        la.pR = la.nR = la.dp = la.dn = la.wR = nullptr;
-        la.st_p = la.st_n = nullptr;
-        la.first = 0; la.max_soc = 0; la.c = la.M = la.r1 = la.kkt_ws = la.tau = nullptr;
-        la.with_post = 0;
-        la.a_max = la.a_z = nullptr; la.soft_ws = la.soft_X = la.a_soft = nullptr; la.soft_try = nullptr;
-        CK(ls_backtrack(&S->desc, la, st));
       }
-      return CPL_OK;
+      return ls_backtrack(&S->desc, la, st);
     }
     case P_SOFT: {
+      const SoftStepArgs soft = soft_step_args(S);
       if (!S->soft_begun) {  // (else the Newton phase's search kernel started the soft step)
-        hipLaunchKernelGGL(k_soft_begin, dim3(blocks_for(B)), dim3(256), 0, st, B, n, nf, nw, S->act, S->tiny_now,
-                           S->soft_now, S->soft_cnt, S->st_alpha, S->a_max, S->a_z, S->w, S->dw, S->freepos, S->Xbase,
-                           S->soft_try, S->a_soft, S->ws_, S->Xs);
+        hipLaunchKernelGGL(k_soft_begin, dim3(blocks_for(B)), dim3(256), 0, st, B, soft);
         LAUNCHED("k_soft_begin");
       }
       // (the fused search kernel raised d_any[1] exactly where it set soft_try: with no soft-step candidate
       // this evaluation's outputs are read by nobody, and its launch returns at once)
       CK(eval_full(S, S->Xs, S->f_n, S->grad_n, S->g_n, S->J_n, S->soft_begun ? S->d_any + 1 : nullptr));
-      if (S->tail_fused) {
-        const FailTail tail{S->freepos, S->Xbase, S->Xn, S->act, S->err0, o.acceptable_tol, S->failed, S->moved,
-                            S->status, S->active, near_feasible(S, o)};
-        hipLaunchKernelGGL(k_soft_judge_fail, dim3(blocks_for(B)), dim3(256), 0, st, B, n, m, nf, nw, S->nnz_rec,
-                           S->soft_try, S->soft_now, S->a_soft, S->amap, S->row_slack, S->free32, S->gl, S->hasL,
-                           S->hasU, S->wl0, S->wu0, S->ws_, S->f_n, S->grad_n, S->g_n, S->J_n, S->A, S->gradw, S->c,
-                           S->w, S->y, S->zL, S->zU, S->dy, S->dzL, S->dzU, S->mu_o, S->theta_k, S->phi_k, S->gd,
-                           S->switch_ok, S->theta_max, S->ft, S->fp, S->cs_tmp, S->in_soft, S->soft_cnt, S->st_f,
-                           S->st_g, S->st_w, S->st_alpha, S->st_aug, S->a_z, tail);
-        LAUNCHED("k_soft_judge_fail");
-        return CPL_OK;
-      }
-      hipLaunchKernelGGL(k_soft_judge, dim3(blocks_for(B)), dim3(256), 0, st, B, n, m, nf, nw, S->nnz_rec, S->soft_try,
-                         S->soft_now, S->a_soft, S->amap, S->row_slack, S->free32, S->gl, S->hasL, S->hasU, S->wl0,
-                         S->wu0, S->ws_, S->f_n, S->grad_n, S->g_n, S->J_n, S->A, S->gradw, S->c, S->w, S->y, S->zL,
-                         S->zU, S->dy, S->dzL, S->dzU, S->mu_o, S->theta_k, S->phi_k, S->gd, S->switch_ok,
-                         S->theta_max, S->ft, S->fp, S->cs_tmp, S->in_soft, S->soft_cnt, S->st_f, S->st_g, S->st_w,
-                         S->st_alpha, S->st_aug, S->a_z);
+      if (S->tail_fused)
+        hipLaunchKernelGGL(k_soft_judge_fail, dim3(blocks_for(B)), dim3(256), 0, st, B, soft, fail_tail(S));
+      else
+        hipLaunchKernelGGL(k_soft_judge, dim3(blocks_for(B)), dim3(256), 0, st, B, soft);
       LAUNCHED("k_soft_judge");
       return CPL_OK;
     }
@@ -2674,34 +2722,18 @@ int32_t step_phase(cpl_solver* S, int phase) {
       // the failed-search bookkeeping and the accepted points (done by the soft judge's launch in
       // P_FUSED), then one full evaluation there
       if (!S->tail_fused) {
-        hipLaunchKernelGGL(k_fail_unpack, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, n, nw, S->freepos,
-                           S->Xbase, S->st_w, S->Xn, S->act, S->st_alpha, S->err0, o.acceptable_tol, S->failed,
-                           S->moved, S->in_soft, S->soft_cnt, S->status, S->active, near_feasible(S, o));
+        hipLaunchKernelGGL(k_fail_unpack, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, fail_tail(S));
         LAUNCHED("k_fail_unpack");
       }
       CK(eval_full(S, S->Xn, S->f_n, S->grad_n, S->g_n, S->J_n));
-      if (S->bfgs) {
-        if (nf <= 64)
-          hipLaunchKernelGGL(k_lbfgs_wave, dim3((unsigned)((B + LBW_WAVES - 1) / LBW_WAVES)), dim3(64 * LBW_WAVES),
-                             sizeof(double) * LBW_WAVES * (size_t)m, st, B, m, nf, nw, S->nnz_rec, S->amap, S->moved,
-                             S->w, S->st_w, S->y, S->dy, S->st_alpha, S->gradw, S->J, S->grad_n, S->free32, n, S->J_n,
-                             S->lm_s, S->lm_y, S->lm_cnt, S->lm_skip, S->zeros_u8, S->Hq);
-        else
-          hipLaunchKernelGGL(k_lbfgs<128>, dim3((unsigned)B), dim3(256), 0, st, B, m, nf, nw, S->nnz_rec, S->amap, S->moved,
-                             S->w, S->st_w, S->y, S->dy, S->st_alpha, S->gradw, S->J, S->grad_n, S->free32, n, S->J_n,
-                             S->lm_s, S->lm_y, S->lm_cnt, S->lm_skip, S->zeros_u8, S->Hq);
-        LAUNCHED("k_lbfgs");
-      }
+      if (S->bfgs) CK(lbfgs_update(S, S->moved, S->gradw, S->grad_n));
       const IpmAcceptArgs acc{nw, m, FMAX, S->moved, S->st_aug, nullptr, nullptr, S->st_alpha, S->a_z, S->theta_k,
                               S->phi_k, S->ft, S->fp, S->fc, S->st_w, S->dy, S->dzL, S->dzU, S->mu_o, S->hasL,
                               S->hasU, S->wl0, S->wu0, S->w, S->y, S->zL, S->zU, S->mu, S->iters, S->filt_t,
                               S->filt_p, S->fcount};
       AcceptRows ar{S->moved, n, m, S->nnz_rec, S->f_n, S->grad_n, S->g_n, S->J_n, S->f, S->grad, S->g, S->J};
       if (phase == P_ACCEPT_NR) {  // no instance can have failed its search: no entry
-        CK(cpl_ipm_accept(B, nw, m, FMAX, S->moved, S->st_aug, nullptr, nullptr, S->st_alpha, S->a_z, S->theta_k,
-                          S->phi_k, S->ft, S->fp, S->fc, S->st_w, S->dy, S->dzL, S->dzU, S->mu_o, S->hasL, S->hasU,
-                          S->wl0, S->wu0, S->w, S->y, S->zL, S->zU, S->mu, S->iters, S->filt_t, S->filt_p, S->fcount,
-                          st));
+        CK(ipm_accept_ex(B, acc, st));
         hipLaunchKernelGGL(k_accept_rows, dim3(blocks_elems(B * (1 + n + m + S->nnz_rec))), dim3(256), 0, st, B, n,
                            m, S->nnz_rec, S->moved, S->f_n, S->grad_n, S->g_n, S->J_n, S->f, S->grad, S->g, S->J);
         LAUNCHED("k_accept_rows");
@@ -2716,10 +2748,7 @@ int32_t step_phase(cpl_solver* S, int phase) {
       if (B <= FUSE_ROWS && sizeof(double) * qd_lds_doubles(nw, m) <= 160 * 1024) {
         // the entry, its least-squares multipliers and the counts in one launch (k_tail_small)
         const QdSolveArgs Q{nw, m, S->M, S->A, S->Dinv, S->r1, S->r2, S->dwlR, S->dw, S->dy, S->scr1, S->Kqd};
-        TrackBest tb{};
-        if (o.fallback_viol_tol > 0.0)
-          tb = TrackBest{nw, o.fallback_viol_tol, S->w, S->f, S->g, S->gl, S->gu, S->best_w, S->best_f,
-                         S->scaled ? S->dc : nullptr};
+        const TrackBest tb = o.fallback_viol_tol > 0.0 ? track_best(S) : TrackBest{};
         hipLaunchKernelGGL(k_tail_small, dim3((unsigned)B), dim3(TAIL_THREADS), sizeof(double) * qd_lds_doubles(nw, m),
                            st, B, E, Q, S->active, S->in_resto, S->d_count, S->h_count, S->y, tb);
         LAUNCHED("k_tail_small (the entry, its multipliers, the counts)");
@@ -2736,12 +2765,9 @@ int32_t step_phase(cpl_solver* S, int phase) {
       }
     count:
       const bool track_fused = o.fallback_viol_tol > 0.0 && B <= TRACK_FUSE_ROWS;
-      TrackBest tb{};
-      if (track_fused) tb = TrackBest{nw, o.fallback_viol_tol, S->w, S->f, S->g, S->gl, S->gu, S->best_w, S->best_f,
-                         S->scaled ? S->dc : nullptr};
+      const TrackBest tb = track_fused ? track_best(S) : TrackBest{};
       if (o.fallback_viol_tol > 0.0 && !track_fused) {
-        hipLaunchKernelGGL(k_track_best, dim3(blocks_for(B)), dim3(256), 0, st, B, m, nw, o.fallback_viol_tol,
-                           S->active, S->w, S->f, S->g, S->gl, S->gu, S->best_w, S->best_f, S->scaled ? S->dc : nullptr);
+        hipLaunchKernelGGL(k_track_best, dim3(blocks_for(B)), dim3(256), 0, st, B, m, S->active, track_best(S));
         LAUNCHED("k_track_best");
       }
       if (B > COUNT1_MAX) {
@@ -2757,11 +2783,7 @@ int32_t step_phase(cpl_solver* S, int phase) {
       return CPL_OK;
     }
     case P_RNEWTON: {
-      hipLaunchKernelGGL(k_resto_prep1, dim3(blocks_for(B)), dim3(256), 0, st, B, m, nf, nw, S->nbounds, o.tol,
-                         S->mu_min, S->active, S->in_resto, S->resto_tight, S->actR, S->status, S->A, S->c, S->w, S->y,
-                         S->wR, S->pR,
-                         S->nR, S->zp, S->zn, S->zLR, S->zUR, S->hasL, S->hasU, S->wl0, S->wu0, S->muR, S->ftR,
-                         S->fpR, S->fcR, S->tauR, S->gfR);
+      hipLaunchKernelGGL(k_resto_prep1, dim3(blocks_for(B)), dim3(256), 0, st, B, ra);
       LAUNCHED("k_resto_prep1");
       hipLaunchKernelGGL(k_restore_acc, dim3(blocks_for(B)), dim3(256), 0, st, B, m, nw, S->status, S->has_acc,
                          S->acc_w, S->acc_y, S->acc_zL, S->acc_zU, S->w, S->y, S->zL, S->zU);
@@ -2792,25 +2814,11 @@ int32_t step_phase(cpl_solver* S, int phase) {
       CK(rtrial());
       if (o.max_ls > 1) {  // the restoration search's remaining trials, in one launch
         HK(hipMemsetAsync(S->d_any + 2, 0, 1, st), "hipMemsetAsync flag");
-        LsBacktrackArgs la;
-        la.batch = B; la.n = n; la.m = m; la.nf = nf; la.nw = nw; la.nfilt = FMAX; la.max_trials = o.max_ls - 1;
-        la.act = S->actR; la.tiny = S->tiny_now; la.soft_now = S->soft_now; la.soft_cnt = S->soft_cnt;
-        la.searching = S->searchingR; la.alpha = S->alphaR; la.a_min = S->a_minR;
-        la.w = S->w; la.dw = S->dw; la.Xbase = S->Xbase; la.freepos = S->freepos; la.row_slack = S->row_slack;
-        la.gl = S->gl; la.hasL = S->hasL; la.hasU = S->hasU; la.wl0 = S->wl0; la.wu0 = S->wu0;
-        la.mu = S->muR; la.theta_k = S->thetaR; la.phi_k = S->phiR; la.gd = S->gdR; la.switch_ok = S->switchR;
-        la.theta_max = S->thmaxR; la.filt_t = S->ftR; la.filt_p = S->fpR;
-        la.mass = S->mass; la.env_tag = S->tag;
-        if (S->scaled) { la.df = S->df; la.dc = S->dc; }
-        la.st_f = S->st_f; la.st_g = S->st_g; la.st_w = S->st_w; la.st_alpha = S->st_alpha; la.st_aug = S->st_aug;
-        la.any = S->d_any;
+        LsBacktrackArgs la = ls_backtrack_args(S, resto_search_of(S));
         la.resto = 1;
         la.rho = RHO_R;
         la.pR = S->pR; la.nR = S->nR; la.dp = S->dp; la.dn = S->dn; la.wR = S->wR;
         la.st_p = S->st_p; la.st_n = S->st_n;
-        la.first = 0; la.max_soc = 0; la.c = la.M = la.r1 = la.kkt_ws = la.tau = nullptr;
-        la.with_post = 0;
-        la.a_max = la.a_z = nullptr; la.soft_ws = la.soft_X = la.a_soft = nullptr; la.soft_try = nullptr;
         CK(ls_backtrack(&S->desc, la, st));
       }
       return step_phase(S, P_RACCEPT);
@@ -2823,23 +2831,9 @@ int32_t step_phase(cpl_solver* S, int phase) {
       if (S->bfgs) {  // the restoration phase's own model: pairs from J^T y (its constraint curvature)
         hipLaunchKernelGGL(k_moved_r, dim3(blocks_elems(B)), dim3(256), 0, st, B, S->actR, S->st_alpha, S->movedR);
         LAUNCHED("k_moved_r");
-        if (nf <= 64)
-          hipLaunchKernelGGL(k_lbfgs_wave, dim3((unsigned)((B + LBW_WAVES - 1) / LBW_WAVES)), dim3(64 * LBW_WAVES),
-                             sizeof(double) * LBW_WAVES * (size_t)m, st, B, m, nf, nw, S->nnz_rec, S->amap, S->movedR,
-                             S->w, S->st_w, S->y, S->dy, S->st_alpha, S->zeros_w, S->J, nullptr, S->free32, n, S->J_n,
-                             S->lm_s, S->lm_y, S->lm_cnt, S->lm_skip, S->zeros_u8, S->Hq);
-        else
-          hipLaunchKernelGGL(k_lbfgs<128>, dim3((unsigned)B), dim3(256), 0, st, B, m, nf, nw, S->nnz_rec, S->amap,
-                             S->movedR, S->w, S->st_w, S->y, S->dy, S->st_alpha, S->zeros_w, S->J, nullptr, S->free32, n,
-                             S->J_n, S->lm_s, S->lm_y, S->lm_cnt, S->lm_skip, S->zeros_u8, S->Hq);
-        LAUNCHED("k_lbfgs (resto)");
+        CK(lbfgs_update(S, S->movedR, S->zeros_w, nullptr));
       }
-      hipLaunchKernelGGL(k_resto_accept, dim3(blocks_for(B)), dim3(256), 0, st, B, m, nf, nw, S->actR, S->movedR,
-                         S->active, S->status, S->iters, S->st_alpha, S->st_aug, S->st_w, S->st_p, S->st_n, S->dy,
-                         S->dzL, S->dzU, S->dzp, S->dzn, S->a_zR, S->muR, S->thetaR, S->phiR, S->ftR, S->fpR, S->fcR,
-                         S->w, S->y, S->pR, S->nR, S->zp, S->zn, S->zLR, S->zUR, S->hasL, S->hasU, S->wl0, S->wu0,
-                         S->row_slack, S->gl, S->f_n, S->g_n, S->mu, S->filt_t, S->filt_p, S->th_o0, S->ph_o0, S->wR,
-                         S->zL, S->zU, S->in_resto, S->acc, S->lm_cnt, S->lm_skip, S->bfgs ? S->Hq : nullptr, lmc);
+      hipLaunchKernelGGL(k_resto_accept, dim3(blocks_for(B)), dim3(256), 0, st, B, ra);
       LAUNCHED("k_resto_accept");
       hipLaunchKernelGGL(k_accept_rows, dim3(blocks_elems(B * (1 + n + m + S->nnz_rec))), dim3(256), 0, st, B, n, m,
                          S->nnz_rec, S->movedR, S->f_n, S->grad_n, S->g_n, S->J_n, S->f, S->grad, S->g, S->J);
@@ -2934,16 +2928,12 @@ int32_t compact(cpl_solver* S, int64_t count, int64_t Bn) {
   hipStream_t st = S->stream;
   const int64_t Bc = S->Bcur;
   const int n = S->n, m = S->m, nw = S->nw;
+  const LeaveArgs leave = leave_args(S, true);
   if (S->opt.fallback_viol_tol > 0.0) {
-    hipLaunchKernelGGL(k_fallback, dim3(blocks_for(Bc)), dim3(256), 0, st, Bc, m, nw, S->opt.fallback_viol_tol, true,
-                       S->orig, S->active, S->status, S->g, S->gl, S->gu, S->best_w, S->best_f, S->w, S->fbest,
-                       S->scaled ? S->dc : nullptr);
+    hipLaunchKernelGGL(k_fallback, dim3(blocks_for(Bc)), dim3(256), 0, st, Bc, leave);
     LAUNCHED("k_fallback");
   }
-  hipLaunchKernelGGL(k_scatter_final, dim3(blocks_for(Bc)), dim3(256), 0, st, Bc, n, m, nw, true, S->orig, S->active,
-                     S->w, S->y, S->scaled ? S->dc : nullptr, S->df, S->Xbase, S->d_inf, S->status, S->iters, S->n_resto, S->fw, S->fy,
-                     S->fX, S->fdinf,
-                     S->fstatus, S->fiters, S->fresto);
+  hipLaunchKernelGGL(k_scatter_final, dim3(blocks_for(Bc)), dim3(256), 0, st, Bc, leave);
   LAUNCHED("k_scatter_final");
   hipLaunchKernelGGL(k_positions, dim3(1), dim3(1024), 0, st, Bc, S->active, S->pos);
   LAUNCHED("k_positions");
@@ -3405,10 +3395,7 @@ int32_t cpl_solver_solve(cpl_solver* S, const double* d_x0, const double* d_mass
   LAUNCHED("k_start_x");
   CK(eval_full(S, S->X, S->f, S->grad, S->g, S->J));
   ++evals;
-  hipLaunchKernelGGL(k_init_state, dim3(blocks_for(B)), dim3(256), 0, st, B, n, m, nf, nw, S->free32, S->ineq_row,
-                     S->row_slack, S->gl, S->hasL, S->hasU, S->wl0, S->wu0, S->opt.mu_init, S->X, S->g, S->grad, S->w,
-                     S->zL, S->zU, S->theta_max, S->theta_min, S->mu, S->active, S->status, S->iters, S->acc,
-                     S->filt_t, S->filt_p, S->fcount, S->dwl, S->d_inf, S->lm_cnt, S->lm_skip, S->r1, S->r2, S->M);
+  hipLaunchKernelGGL(k_init_state, dim3(blocks_for(B)), dim3(256), 0, st, B, init_state_args(S));
   LAUNCHED("k_init_state");
   CK(cpl_ipm_dense_a(B, m, nw, nf, S->nnz_rec, S->amap, S->row_slack, S->J, S->A, nullptr, st));
   CK(cpl_kkt_solve(0, B, nw, m, S->M, S->A, S->r1, S->r2, S->mu, S->zeros_B, nullptr, S->dw, S->dy, S->delta_w,
@@ -3480,17 +3467,13 @@ int32_t cpl_solver_solve(cpl_solver* S, const double* d_x0, const double* d_mass
                        S->gradw, S->c, S->w, S->y, S->zL, S->zU, S->hasL, S->hasU, S->wl0, S->wu0, S->mu, S->filt_t,
                        S->filt_p, S->fcount, S->active, S->status, S->acc, S->d_inf, S->err0, S->base, S->mu_o, S->ft,
                        S->fp, S->fc, MU_ROUNDS, S->mu_min, nullptr, S->in_resto, nullptr, st));
+  const LeaveArgs leave = leave_args(S, false);
   if (S->opt.fallback_viol_tol > 0.0) {
-    hipLaunchKernelGGL(k_fallback, dim3(blocks_for(Bc)), dim3(256), 0, st, Bc, m, nw, S->opt.fallback_viol_tol, false,
-                       S->orig, S->active, S->status, S->g, S->gl, S->gu, S->best_w, S->best_f, S->w, S->fbest,
-                       S->scaled ? S->dc : nullptr);
+    hipLaunchKernelGGL(k_fallback, dim3(blocks_for(Bc)), dim3(256), 0, st, Bc, leave);
     LAUNCHED("k_fallback");
   }
   // every row still in the batch to its instance's place in the full-batch results
-  hipLaunchKernelGGL(k_scatter_final, dim3(blocks_for(Bc)), dim3(256), 0, st, Bc, n, m, nw, false, S->orig, S->active,
-                     S->w, S->y, S->scaled ? S->dc : nullptr, S->df, S->Xbase, S->d_inf, S->status, S->iters, S->n_resto, S->fw, S->fy,
-                     S->fX, S->fdinf,
-                     S->fstatus, S->fiters, S->fresto);
+  hipLaunchKernelGGL(k_scatter_final, dim3(blocks_for(Bc)), dim3(256), 0, st, Bc, leave);
   LAUNCHED("k_scatter_final");
   // IPOPT honor_original_bounds: the final point projected into the original bounds, re-evaluated
   double* Xf = d_x ? d_x : S->Xn;
