@@ -15,7 +15,8 @@
 // own (2,2)-block regularisation with jacobian_regularization_value 1e-8 mu^(1/4).
 // One step of iterative refinement against the unregularised system follows when dC = 0.
 // The factors are kept in a per-instance workspace so second-order corrections re-solve with
-// another r2 without refactorising (mode 1).
+// another r2 without refactorising (mode 1; that re-solve does NOT refine — only the regularised
+// systems' cpl_kkt_aug_kernel re-solve does).
 //
 // No library calls: the per-instance data-dependent retry loops run on the device, so the host
 // never synchronises on them.  Sizes: nw <= KKT_MAX_NW (=128), m <= nw.
@@ -943,6 +944,12 @@ __global__ __launch_bounds__(W4 ? 256 : 64) __attribute__((amdgpu_waves_per_eu(2
       if (defl) QR[lane * NW + lane] = rjj < 0.0 ? rjj - dc : rjj + dc;
       dC = dc;
     }
+    // the image's padding — Z's alignment column, cp's spare slot — is never read, but it is kept with
+    // the factors: zeroed, so that a workspace row holds no uninitialised LDS
+    if constexpr (ZS > NZ) {
+      if (rw) Z[lane * ZS + NZ] = 0.0;
+    }
+    if (lane == 0) cp[NP] = 0.0;
     __builtin_amdgcn_wave_barrier();
   }
   // ---- reduced Hessian Hr = Z^T (M Z): M Z a lane per row through the global workspace (L2),

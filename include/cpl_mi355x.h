@@ -303,13 +303,17 @@ int32_t cpl_derivative_test(const cpl_problem_desc* d, int64_t batch, const doub
  * by the null-space method on a Householder QR of A^T, with IPOPT's inertia correction on the
  * device (delta_w on M until the reduced Hessian Z^T M Z is positive definite: first trial 1e-4 or
  * delta_w_last/3, growth x100 / x8; delta_c = 1e-8 mu^(1/4) |R|max on R's diagonal where A is
- * rank-deficient) and one step of iterative refinement.  One workgroup per instance; all of the
+ * rank-deficient) and, in mode 0 where A has full rank, one step of iterative refinement (taken when the
+ * residual exceeds 1e-13 of the right-hand side).  One workgroup per instance; all of the
  * step's matrices in LDS.  nw <= 128, 0 <= m <= nw, and the LDS image must fit 160 KiB.
  *   mode 0: factorise + solve; d_mu [batch] (barrier parameter), d_delta_w_last [batch] or NULL,
  *           outputs d_delta_w, d_delta_c [batch], d_info [batch] (0 ok, 1 inertia not corrected)
  *   mode 1: re-solve with the factors mode 0 left in d_ws (second-order corrections: same M, A,
- *           r1 up to the caller, another r2)
- *   d_active [batch] uint8 or NULL: inactive instances are skipped (dw = dy = 0)
+ *           r1 up to the caller, another r2); writes d_dw, d_dy only
+ *           mode 1 does NOT refine: its step is the plain null-space solve's (tests/test_gpu_kkt_precision.py)
+ *   d_active [batch] uint8 or NULL: inactive instances are not solved; unlike the cpl_ipm_* kernels
+ *           below, this one WRITES their outputs: dw = dy = 0 and, in mode 0, delta_w = delta_c = 0,
+ *           info = 0 (d_ws is left as it was)
  *   d_ws: cpl_kkt_workspace_doubles(nw, m) doubles per instance (device)
  * Asynchronous on `stream`.
  */
@@ -380,8 +384,8 @@ int32_t cpl_kkt_qd_solve(int64_t batch, int32_t nw, int32_t m, const double* d_W
  *   objective phi, filter of `nfilt` (theta, phi) entries per instance, switching condition /
  *   Armijo / sufficient decrease, theta_max); instances with searching & extra_mask (NULL: all)
  *   that pass copy (f_t, g_t, w_t, alpha, augment flag) into the line-search state and clear
- *   searching.  d_th_out / d_ok_out get theta and the test result of every instance.  mode 0: the
- *   filter test; 1: the feasibility step's test (theta cut by 10 %); 2: take unconditionally.
+ *   searching.  d_th_out / d_ok_out get theta and the test result of every instance.  mode must be 0
+ *   (the filter test; any other value is CPL_ERR_INVALID_ARGUMENT).
  *   row_slack[r] = slack index of inequality row r, -1 for an equality row.
  */
 int32_t cpl_ipm_trial_point(int64_t batch, int32_t n, int32_t nf, int32_t nw, const int64_t* d_free_idx,

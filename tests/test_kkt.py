@@ -2,10 +2,11 @@
 numpy solve of the same KKT systems (float64; tolerance 1e-9 relative to the solution's scale, the
 systems' condition numbers are ~1e3-1e5).
 
-The 4-contact size (nw 47, m 30) runs the one-wave kernel from 64 systems up and the workgroup kernel
-below (every other size: the workgroup kernel's generic instance): the (47, 30) cases run at B = 64 /
-300 and B = 4,096 (the dense check on a sample of the large batches), the small-batch cases and
-the other sizes cover the workgroup kernel."""
+The kernel is chosen by the system size alone: the 4-contact size (nw 47, m 30) runs the one-wave kernel
+at every batch size — batches of up to 256 systems factorise on four waves per system, larger ones on
+one — and every other size the workgroup kernel's generic instance.  The (47, 30) cases run at B = 16 /
+32 / 64 (four waves), 300 and 4,096 (one wave; the dense check on a sample of the large batches), the
+other sizes cover the workgroup kernel."""
 import ctypes
 
 import numpy as np
