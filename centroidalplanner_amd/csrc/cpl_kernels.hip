@@ -80,12 +80,9 @@ struct KParams {
   int32_t want_g, want_j, want_f, want_grad;
   int32_t want_norms;    // fused residual norms of g (cpl_eval_batch_norms)
   int32_t contact_rows;  // constraint rows per contact: 6 (environment) or 2
-  int32_t ablate;        // measurement-only ablation (cpl_set_tuning), 0 in production
   int32_t sq_ladder;     // every P_a is an integer in [2, 64]: double-double power ladders
   int32_t grid_cap;      // (entry kernel, the kind split's Ground half) the workgroups that walk the
                          // tiles while the Superquadric list is non-empty (0: every workgroup)
-  int32_t cw_prio;       // (entry kernel) the compute waves' wave priority (s_setprio; 0 = default)
-  int32_t list_prio;     // (tile kernel, LIST) the gather / copy-out at a raised wave priority (1 = yes)
   // fused Lagrangian gradient (cpl_eval_lagrangian_grad): grad f + J^T y of every instance from the
   // LDS tile image, through a CSC index of the fixed structure; instance b takes y[b / y_repeat]
   int32_t want_lgrad, y_repeat;
@@ -1459,7 +1456,7 @@ void cpl_eval_tile_kernel(const KParams K, int64_t batch,
     // element had cost the list tiles ~30 % more VALU instructions than the contiguous copy-in)
     // (Superquadric list tiles, the mixed split's Superquadric half: the gather and the copy-out at a
     // raised wave priority: mixed16 2.35 -> 2.28 ms with the 4-instance LDS-staged tiles, r6)
-    if (ENVK == CPL_ENV_SUPERQUADRIC && K.list_prio) __builtin_amdgcn_s_setprio(2);
+    if (ENVK == CPL_ENV_SUPERQUADRIC) __builtin_amdgcn_s_setprio(2);
     const int wave = tid >> 6, lane = tid & 63;
     constexpr int U = 4;  // (rows of up to 4 * 64 doubles in one pass)
     int bnext = spec_b;  // (row `wave`'s entry, loaded at the kernel's start)
@@ -1482,7 +1479,7 @@ void cpl_eval_tile_kernel(const KParams K, int64_t batch,
         }
       }
     }
-    if (ENVK == CPL_ENV_SUPERQUADRIC && K.list_prio) __builtin_amdgcn_s_setprio(0);
+    if (ENVK == CPL_ENV_SUPERQUADRIC) __builtin_amdgcn_s_setprio(0);
   } else {
     // Superquadric tiles of 8+ instances (sq8): the copy-in and the copy-out issued at a raised wave
     // priority, so that a workgroup's memory phases are not queued behind the other resident
@@ -1510,7 +1507,6 @@ void cpl_eval_tile_kernel(const KParams K, int64_t batch,
     __syncthreads();
     if (ENVK == CPL_ENV_MIXED) n_sq = lists[128];
     const int n_gr = valid - n_sq;
-    const bool compute = K.ablate != 1;
 
     // ---- phase 1: the Superquadric power ladders (into the LDS scratch); phase 2: the Superquadric
     // rows.  The items that do not read the scratch (Ground / no-env contacts, statics, cost) join
@@ -1568,75 +1564,69 @@ void cpl_eval_tile_kernel(const KParams K, int64_t batch,
     // Each phase as two loops over the same item -> thread mapping (Superquadric items, then the
     // others): one item function per loop body, so the register allocation of the two does not add up.
     const int items1 = r_ax + (OTHERS_FIRST ? r_oth : r_oth - r_gr);
-    if (compute) {
-      if (HAS_SQ && UAX)
-        for (int it = tid; it < r_ax; it += WG) {
-          const int a = __builtin_amdgcn_readfirstlane(it) / PA, kj = it - a * PA;
-          const int k = kj >> K.logT, r = kj & (T - 1);
-          if (kj < per_axis && r < valid) sq_axis_item<false>(K, X + r * n, k, a, L + r * K.LR + k * SQ_L, Gt + r * m);
-        }
-      else if (HAS_SQ)
-        for (int it = tid; it < r_ax; it += WG) {
-          const int a = it / per_axis, kj = it - a * per_axis;
-          const int k = kj / n_sq, j = kj - k * n_sq;
-          const int r = ENVK == CPL_ENV_MIXED ? lists[j] : j;
-          sq_axis_item<ENVK == CPL_ENV_MIXED>(K, X + r * n, k, a, L + r * K.LR + k * SQ_L, Gt + r * m);
-        }
-      for (int it = tid; it < items1; it += WG)
-        if (it >= r_ax) other_item(it - r_ax + (OTHERS_FIRST ? 0 : r_gr));
-    }
+    if (HAS_SQ && UAX)
+      for (int it = tid; it < r_ax; it += WG) {
+        const int a = __builtin_amdgcn_readfirstlane(it) / PA, kj = it - a * PA;
+        const int k = kj >> K.logT, r = kj & (T - 1);
+        if (kj < per_axis && r < valid) sq_axis_item<false>(K, X + r * n, k, a, L + r * K.LR + k * SQ_L, Gt + r * m);
+      }
+    else if (HAS_SQ)
+      for (int it = tid; it < r_ax; it += WG) {
+        const int a = it / per_axis, kj = it - a * per_axis;
+        const int k = kj / n_sq, j = kj - k * n_sq;
+        const int r = ENVK == CPL_ENV_MIXED ? lists[j] : j;
+        sq_axis_item<ENVK == CPL_ENV_MIXED>(K, X + r * n, k, a, L + r * K.LR + k * SQ_L, Gt + r * m);
+      }
+    for (int it = tid; it < items1; it += WG)
+      if (it >= r_ax) other_item(it - r_ax + (OTHERS_FIRST ? 0 : r_gr));
     // LDS-only barriers from here on: the phases exchange LDS data only, and a __syncthreads would
     // first wait for every global store the items issued (f, and with jdirect the Jacobian rows)
-    // (measurement only, ablation 8192: the phases' barriers skipped — wrong outputs, the barriers' cost)
-    const bool phase_bar = (K.ablate & 8192) == 0;
-    if (compute && HAS_SQ && n_sq > 0 && wgj && phase_bar) lds_barrier();
-    if (compute) {
-      const int r_rows = r_ax;
-      // Superquadric batches: the friction cones as items of their own in phase 2 (the workgroup's
-      // fourth wave, otherwise idle there: the row-1 items no longer carry them)
-      constexpr bool CONE_ITEMS = ENVK == CPL_ENV_SUPERQUADRIC;
-      const int r_cone = (CONE_ITEMS && wgj) ? (N << K.logT) : 0;  // (slots (contact, row) = (e >> logT, e & (T - 1)))
-      const int items2 = r_rows + (OTHERS_FIRST ? 0 : r_gr) + r_cone;
-      if (HAS_SQ && UAX)
-        for (int it = tid; it < r_rows; it += WG) {
-          const int a = __builtin_amdgcn_readfirstlane(it) / PA, kj = it - a * PA;
-          const int k = kj >> K.logT, r = kj & (T - 1);
-          if (kj < per_axis && r < valid) {  // a wave-uniform: the row item specialised on its axis — the
-            // three entries' chains in one basic block, interleaved (97 -> 127 VGPRs, still four waves
-            // per SIMD; bitwise; sq8 0.316 -> 0.299 ms, profiles/r5/sq_rowaf/)
-            double* const Lr = L + r * K.LR + k * SQ_L;
-            if (a == 0) sq_row_item<false, !CONE_ITEMS, 0>(K, X + r * n, k, a, Lr, Gt + r * m, JR(r));
-            else if (a == 1) sq_row_item<false, !CONE_ITEMS, 1>(K, X + r * n, k, a, Lr, Gt + r * m, JR(r));
-            else sq_row_item<false, !CONE_ITEMS, 2>(K, X + r * n, k, a, Lr, Gt + r * m, JR(r));
-          }
-        }
-      else if (HAS_SQ)
-        for (int it = tid; it < r_rows; it += WG) {
-          const int a = it / per_axis, kj = it - a * per_axis;
-          const int k = kj / n_sq, j = kj - k * n_sq;
-          const int r = ENVK == CPL_ENV_MIXED ? lists[j] : j;
-          // (the list tiles' waves also share one axis, but the axis-specialised row items cost their
-          // kernel 144-149 VGPRs (three waves per SIMD): 2.55 -> 2.84 ms for mixed16, 2.64 capped at
-          // four waves with 8-12 spilled VGPRs; profiles/r5/sq_rowaf/)
-          sq_row_item<ENVK == CPL_ENV_MIXED, !CONE_ITEMS>(K, X + r * n, k, a, L + r * K.LR + k * SQ_L, Gt + r * m,
-                                                          JR(r));
-        }
-      for (int it = tid; it < items2; it += WG) {
-        if (it < r_rows) continue;
-        if (CONE_ITEMS) {
-          const int e = it - r_rows, k = e >> K.logT, r = e & (T - 1);
-          if (r < valid) sq_cone_item(K, X + r * n, k, Gt + r * m, JR(r), SQST);
-        } else {
-          other_item(it - r_rows);
+    if (HAS_SQ && n_sq > 0 && wgj) lds_barrier();
+    const int r_rows = r_ax;
+    // Superquadric batches: the friction cones as items of their own in phase 2 (the workgroup's
+    // fourth wave, otherwise idle there: the row-1 items no longer carry them)
+    constexpr bool CONE_ITEMS = ENVK == CPL_ENV_SUPERQUADRIC;
+    const int r_cone = (CONE_ITEMS && wgj) ? (N << K.logT) : 0;  // (slots (contact, row) = (e >> logT, e & (T - 1)))
+    const int items2 = r_rows + (OTHERS_FIRST ? 0 : r_gr) + r_cone;
+    if (HAS_SQ && UAX)
+      for (int it = tid; it < r_rows; it += WG) {
+        const int a = __builtin_amdgcn_readfirstlane(it) / PA, kj = it - a * PA;
+        const int k = kj >> K.logT, r = kj & (T - 1);
+        if (kj < per_axis && r < valid) {  // a wave-uniform: the row item specialised on its axis — the
+          // three entries' chains in one basic block, interleaved (97 -> 127 VGPRs, still four waves
+          // per SIMD; bitwise; sq8 0.316 -> 0.299 ms, profiles/r5/sq_rowaf/)
+          double* const Lr = L + r * K.LR + k * SQ_L;
+          if (a == 0) sq_row_item<false, !CONE_ITEMS, 0>(K, X + r * n, k, a, Lr, Gt + r * m, JR(r));
+          else if (a == 1) sq_row_item<false, !CONE_ITEMS, 1>(K, X + r * n, k, a, Lr, Gt + r * m, JR(r));
+          else sq_row_item<false, !CONE_ITEMS, 2>(K, X + r * n, k, a, Lr, Gt + r * m, JR(r));
         }
       }
-      if (JD && K.want_j) {  // the statics Jacobian rows, lanes along each record
-        lds_barrier();  // (the CoM pairs of the values items)
-        for (int r = 0; r < valid; ++r) statics_rows_coop(K, X + r * n, com6 + 6 * r, JR(r), tid, WG);
+    else if (HAS_SQ)
+      for (int it = tid; it < r_rows; it += WG) {
+        const int a = it / per_axis, kj = it - a * per_axis;
+        const int k = kj / n_sq, j = kj - k * n_sq;
+        const int r = ENVK == CPL_ENV_MIXED ? lists[j] : j;
+        // (the list tiles' waves also share one axis, but the axis-specialised row items cost their
+        // kernel 144-149 VGPRs (three waves per SIMD): 2.55 -> 2.84 ms for mixed16, 2.64 capped at
+        // four waves with 8-12 spilled VGPRs; profiles/r5/sq_rowaf/)
+        sq_row_item<ENVK == CPL_ENV_MIXED, !CONE_ITEMS>(K, X + r * n, k, a, L + r * K.LR + k * SQ_L, Gt + r * m,
+                                                        JR(r));
+      }
+    for (int it = tid; it < items2; it += WG) {
+      if (it < r_rows) continue;
+      if (CONE_ITEMS) {
+        const int e = it - r_rows, k = e >> K.logT, r = e & (T - 1);
+        if (r < valid) sq_cone_item(K, X + r * n, k, Gt + r * m, JR(r), SQST);
+      } else {
+        other_item(it - r_rows);
       }
     }
-    if (phase_bar) lds_barrier();
-    if (ENVK == CPL_ENV_SUPERQUADRIC && (LIST ? K.list_prio != 0 : T >= 8)) __builtin_amdgcn_s_setprio(2);
+    if (JD && K.want_j) {  // the statics Jacobian rows, lanes along each record
+      lds_barrier();  // (the CoM pairs of the values items)
+      for (int r = 0; r < valid; ++r) statics_rows_coop(K, X + r * n, com6 + 6 * r, JR(r), tid, WG);
+    }
+    lds_barrier();
+    if (ENVK == CPL_ENV_SUPERQUADRIC && (LIST || T >= 8)) __builtin_amdgcn_s_setprio(2);
     // the residual partials first (from the LDS image), so that their stores are in flight with the
     // copy-out's instead of after them on every workgroup's tail; one partial slot per tile
     if (K.want_norms) {
@@ -1645,7 +1635,7 @@ void cpl_eval_tile_kernel(const KParams K, int64_t batch,
       nacc.add_tile(Gt, valid * m, tid, WG, m);
       partial_norms_waves(nacc, norms_ws + NORM_HDR, blockIdx.x);
     }
-    if (K.ablate != 2 && LIST) {  // records written in place: row by row (g, jac rows are 16-byte aligned)
+    if (LIST) {  // records written in place: row by row (g, jac rows are 16-byte aligned)
       if (K.want_g) copy_out_rows<WG, NT>(g_out, rowb, Gt, m, valid, tid);
       if (K.want_j && !JD) copy_out_rows<WG, NT>(jac_out, rowb, Jt, nnz, valid, tid);
       if (K.want_grad)
@@ -1653,17 +1643,19 @@ void cpl_eval_tile_kernel(const KParams K, int64_t batch,
           const int r = e / n;
           grad_out[rowb[r] * n + (e - r * n)] = Dt[e];
         }
-    } else if (K.ablate != 2 && K.soa) {
+    } else if (K.soa) {
       if (K.want_g) copy_out_soa<WG, NT>(g_out + b0, batch, Gt, m, valid, tid);
       if (K.want_j) copy_out_soa<WG, NT>(jac_out + b0, batch, Jt, nnz, valid, tid);
       if (K.want_grad) copy_out_soa<WG, NT>(grad_out + b0, batch, Dt, n, valid, tid);
-    } else if (K.ablate != 2) {
+    } else {
       if (K.want_g) copy_out<WG, NT>(g_out + b0 * m, Gt, valid * m, tid);
       if (K.want_j && !JD) copy_out<WG, NT>(jac_out + b0 * nnz, Jt, valid * nnz, tid);
       if (K.want_grad) copy_out<WG, NT>(grad_out + b0 * n, Dt, valid * n, tid);
     }
   }
 }
+using TileKernT = void (*)(const KParams, int64_t, const double*, const double*, const uint8_t*, const int32_t*,
+                           const int32_t*, double*, double*, double*, double*, double*);
 
 
 // ------------------------------------------------------------------------------------------
@@ -1840,58 +1832,54 @@ __global__ __launch_bounds__(64 * (NCW + 1)) void cpl_eval_pipe_kernel(const KPa
     // ---- phase 1: the Superquadric power ladders with every item that does not read their scratch
     // (contacts without Superquadric, statics, cost); phase 2: the Superquadric rows (as the tile
     // kernel; SQ items axis-major)
-    if (K.ablate != 1) {
-      const int r_ax = (HAS_SQ && wgj) ? 3 * N * n_sq : 0;
-      const int r_gr = (ENVK != CPL_ENV_SUPERQUADRIC && wgj) ? N * n_gr : 0;
-      const int r_st = wgj ? 4 * valid : 0;
-      const int r_co = K.cost_seg >= 0 ? valid : 0;
-      const int items1 = r_ax + r_gr + r_st + r_co;
-      const int per_axis = N * n_sq;
-      for (int it = tid; it < items1; it += CT) {
-        int e = it;
-        if (HAS_SQ && e < r_ax) {
-          const int a = e / per_axis, kj = e - a * per_axis;
+    const int r_ax = (HAS_SQ && wgj) ? 3 * N * n_sq : 0;
+    const int r_gr = (ENVK != CPL_ENV_SUPERQUADRIC && wgj) ? N * n_gr : 0;
+    const int r_st = wgj ? 4 * valid : 0;
+    const int r_co = K.cost_seg >= 0 ? valid : 0;
+    const int items1 = r_ax + r_gr + r_st + r_co;
+    const int per_axis = N * n_sq;
+    for (int it = tid; it < items1; it += CT) {
+      int e = it;
+      if (HAS_SQ && e < r_ax) {
+        const int a = e / per_axis, kj = e - a * per_axis;
+        const int k = kj / n_sq, j = kj - k * n_sq;
+        const int r = ENVK == CPL_ENV_MIXED ? lists[j] : j;
+        sq_axis_item<ENVK == CPL_ENV_MIXED>(K, X + r * n, k, a, L + r * K.LR + k * SQ_L, Gt + r * m);
+        continue;
+      }
+      e -= r_ax;
+      if (e < r_gr) {
+        const int j = e % n_gr, k = e / n_gr;
+        const int r = ENVK == CPL_ENV_MIXED ? lists[64 + j] : j;
+        if (!HAS_SQ && K.lg_active && !K.lg_active[(b0 + r) / K.y_repeat]) continue;
+        contact_item<ENVK == CPL_ENV_NONE ? CPL_ENV_NONE : CPL_ENV_GROUND>(K, X + r * n, CPL_ENV_GROUND, k,
+                                                                          Gt + r * m, Jt + r * nnz);
+        continue;
+      }
+      e -= r_gr;
+      if (e < r_st) {
+        const int r = e % valid, sg = e / valid;
+        if (!HAS_SQ && K.lg_active && !K.lg_active[(b0 + r) / K.y_repeat]) continue;
+        const double* xr = X + r * n;
+        if (sg == 0) statics_values_item(K, xr, MB(cur)[r], Gt + r * m, Jt + r * nnz);
+        else if (K.want_j) statics_row_item(K, xr, sg - 1, Jt + r * nnz);
+        continue;
+      }
+      e -= r_st;
+      if (!HAS_SQ && K.lg_active && !K.lg_active[(b0 + e) / K.y_repeat]) continue;
+      cost_item(K, X + e * n, f_out ? f_out + b0 + e : nullptr, Dt + e * n, SC ? K.sc_df + b0 + e : nullptr);
+    }
+    if (HAS_SQ) {
+      lds_barrier();
+      if (wgj) {
+        const int items2 = 3 * per_axis;
+        for (int it = tid; it < items2; it += CT) {
+          const int a = it / per_axis, kj = it - a * per_axis;
           const int k = kj / n_sq, j = kj - k * n_sq;
           const int r = ENVK == CPL_ENV_MIXED ? lists[j] : j;
-          sq_axis_item<ENVK == CPL_ENV_MIXED>(K, X + r * n, k, a, L + r * K.LR + k * SQ_L, Gt + r * m);
-          continue;
-        }
-        e -= r_ax;
-        if (e < r_gr) {
-          const int j = e % n_gr, k = e / n_gr;
-          const int r = ENVK == CPL_ENV_MIXED ? lists[64 + j] : j;
-          if (!HAS_SQ && K.lg_active && !K.lg_active[(b0 + r) / K.y_repeat]) continue;
-          contact_item<ENVK == CPL_ENV_NONE ? CPL_ENV_NONE : CPL_ENV_GROUND>(K, X + r * n, CPL_ENV_GROUND, k,
-                                                                            Gt + r * m, Jt + r * nnz);
-          continue;
-        }
-        e -= r_gr;
-        if (e < r_st) {
-          const int r = e % valid, sg = e / valid;
-          if (!HAS_SQ && K.lg_active && !K.lg_active[(b0 + r) / K.y_repeat]) continue;
-          const double* xr = X + r * n;
-          if (sg == 0) statics_values_item(K, xr, MB(cur)[r], Gt + r * m, Jt + r * nnz);
-          else if (K.want_j) statics_row_item(K, xr, sg - 1, Jt + r * nnz);
-          continue;
-        }
-        e -= r_st;
-        if (!HAS_SQ && K.lg_active && !K.lg_active[(b0 + e) / K.y_repeat]) continue;
-        cost_item(K, X + e * n, f_out ? f_out + b0 + e : nullptr, Dt + e * n, SC ? K.sc_df + b0 + e : nullptr);
-      }
-      if (HAS_SQ) {
-        lds_barrier();
-        if (wgj) {
-          const int items2 = 3 * per_axis;
-          for (int it = tid; it < items2; it += CT) {
-            const int a = it / per_axis, kj = it - a * per_axis;
-            const int k = kj / n_sq, j = kj - k * n_sq;
-            const int r = ENVK == CPL_ENV_MIXED ? lists[j] : j;
-            sq_row_item<ENVK == CPL_ENV_MIXED>(K, X + r * n, k, a, L + r * K.LR + k * SQ_L, Gt + r * m, Jt + r * nnz);
-          }
+          sq_row_item<ENVK == CPL_ENV_MIXED>(K, X + r * n, k, a, L + r * K.LR + k * SQ_L, Gt + r * m, Jt + r * nnz);
         }
       }
-    } else if (HAS_SQ) {
-      lds_barrier();
     }
     lds_barrier();  // the tile image is complete
     if (SC) {  // the scaled problem's values (the solve engine's k_apply_scaling, in the tile image)
@@ -1924,11 +1912,11 @@ __global__ __launch_bounds__(64 * (NCW + 1)) void cpl_eval_pipe_kernel(const KPa
         }
         grad_out[(b0 + r) * n + j] = s;
       }
-    } else if (K.ablate != 2 && K.soa) {
+    } else if (K.soa) {
       if (K.want_g) copy_out_soa<CT, NT>(g_out + b0, batch, Gt, m, valid, tid);
       if (K.want_j) copy_out_soa<CT, NT>(jac_out + b0, batch, Jt, nnz, valid, tid);
       if (K.want_grad) copy_out_soa<CT, NT>(grad_out + b0, batch, Dt, n, valid, tid);
-    } else if (K.ablate != 2) {
+    } else {
       if (K.want_g) copy_out_ct<CT, NT>(g_out + b0 * m, Gt, valid * m, tid);
       if (K.want_j) copy_out_ct<CT, NT>(jac_out + b0 * nnz, Jt, valid * nnz, tid);
       if (K.want_grad) copy_out_ct<CT, NT>(grad_out + b0 * n, Dt, valid * n, tid);
@@ -1940,6 +1928,8 @@ __global__ __launch_bounds__(64 * (NCW + 1)) void cpl_eval_pipe_kernel(const KPa
   }  // compute role
   if (K.want_norms) partial_norms(acc, norms_ws + NORM_HDR);  // the loader contributes zeros
 }
+using PipeKernT = void (*)(const KParams, int64_t, const double*, const double*, const uint8_t*, double*, double*,
+                           double*, double*, double*);
 
 
 // ------------------------------------------------------------------------------------------
@@ -2167,8 +2157,6 @@ __global__ __launch_bounds__(256) void cpl_eval_entry_kernel(const KParams K, in
       cur ^= 1;
     }
   } else {
-    if (K.cw_prio == 1) __builtin_amdgcn_s_setprio(1);
-    else if (K.cw_prio == 2) __builtin_amdgcn_s_setprio(2);
     acc.init(tid, CT, m);
     lds_barrier();
     int cur = 0;
@@ -2309,6 +2297,8 @@ __global__ __launch_bounds__(256) void cpl_eval_entry_kernel(const KParams K, in
   }
   if (K.want_norms) partial_norms(acc, norms_ws + NORM_HDR);  // the loader contributes zeros
 }
+using EntryKernT = void (*)(const KParams, int64_t, const double*, const double*, const int32_t*, const int32_t*,
+                            double*, double*, double*, double*, double*);
 
 
 // ------------------------------------------------------------------------------------------
@@ -2598,77 +2588,111 @@ __global__ __launch_bounds__(PART_BLOCK) void k_kind_write(int64_t batch, int nb
   else if (in) idx_gr[off_gr + (local - sq_rank)] = (int32_t)b;
 }
 
-// the kind lists' workspace, per (device, stream), grown on demand and never freed (a captured graph
-// keeps its pointers; see NormWs): [idx_gr | idx_sq | blk_sq | blk_off | counts]
-struct KindWs {
-  int32_t* ptr = nullptr;
-  int64_t cap = 0;
-  std::vector<int32_t*> old;
-};
 static int32_t hip_fail(hipError_t e, const char* what);
-static std::mutex g_kind_ws_mutex;
-static std::map<std::pair<int, hipStream_t>, KindWs> g_kind_ws;
+
+// The launch context of one (device, stream): every device allocation and runtime object that the
+// launches on that stream keep between calls, so that launches on different streams never share one.
+// A buffer is grown on demand and NEVER freed while the process runs: a HIP graph captured on the
+// stream keeps the pointer it saw, so a later, larger launch on the same stream must not release it
+// under the graph (the retired buffers are kept in `old`).  Growing needs hipMalloc, which a stream
+// capture forbids: warm the launch up on the stream (one eager launch of the largest batch) before
+// capturing it — a capture that would have to grow a buffer fails with CPL_ERR_RUNTIME instead.
+struct GrowBuf {
+  void* ptr = nullptr;
+  size_t cap = 0;  // in the buffer's own unit (instances, partial pairs)
+  std::vector<void*> old;
+};
+struct StreamCtx {
+  int cus = 256;      // the device's CU count
+  GrowBuf kind;       // the mixed split's kind lists: [idx_gr | idx_sq | blk_sq | blk_off | counts]
+  GrowBuf norms;      // the fused residual norms: NORM_HDR doubles, then the partial pairs
+  GrowBuf rn;         // the separate pass's partials (cpl_residual_norms), RN_GRID pairs
+  // the mixed split's second stream and its fork / join events, created on first use and kept (a
+  // captured graph may hold them)
+  hipStream_t side = nullptr;
+  hipEvent_t fork = nullptr, join = nullptr;
+};
+static std::mutex g_ctx_mutex;
+static std::map<std::pair<int, hipStream_t>, StreamCtx> g_ctx;
+
+static bool capturing(hipStream_t stream) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+
+// the context of `stream` on the current device (created empty; the map never moves or drops it)
+static int32_t stream_ctx(hipStream_t stream, StreamCtx** out) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
+  std::lock_guard<std::mutex> lk(g_ctx_mutex);
+  auto ins = g_ctx.try_emplace({dev, stream});
+  if (ins.second) (void)hipDeviceGetAttribute(&ins.first->second.cus, hipDeviceAttributeMultiprocessorCount, dev);
+  *out = &ins.first->second;
+  return CPL_OK;
+}
+
+// grow unless the stream is capturing, retire the old pointer, never free; `what` names the buffer
+static int32_t ctx_reserve(hipStream_t stream, GrowBuf& b, size_t cap, size_t bytes, const char* what) {
+  std::lock_guard<std::mutex> lk(g_ctx_mutex);
+  if (b.cap >= cap) return CPL_OK;
+  if (capturing(stream))
+    return fail(CPL_ERR_RUNTIME, std::string(what) + " must grow, which a stream capture forbids; "
+                                     "launch the largest batch once on this stream before capturing");
+  void* p = nullptr;
+  const hipError_t e = hipMalloc(&p, bytes);
+  if (e != hipSuccess) return hip_fail(e, (std::string("hipMalloc, ") + what).c_str());
+  if (b.ptr) b.old.push_back(b.ptr);  // possibly captured by a graph: kept alive
+  b.ptr = p;
+  b.cap = cap;
+  return CPL_OK;
+}
 
 struct KindLists {
   int32_t *idx_gr, *idx_sq, *blk_sq, *blk_off, *counts;
 };
-static int32_t kind_workspace(hipStream_t stream, int64_t batch, KindLists* out) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
-  std::lock_guard<std::mutex> lk(g_kind_ws_mutex);
-  KindWs& w = g_kind_ws[{dev, stream}];
-  if (w.cap < batch) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-      return fail(CPL_ERR_RUNTIME,
-                  "mixed batch: the per-stream kind-list workspace must grow, which a stream capture forbids; "
-                  "launch the largest batch once on this stream before capturing");
-    const int64_t nblk = (batch + PART_BLOCK - 1) / PART_BLOCK;
-    int32_t* p = nullptr;
-    e = hipMalloc(&p, sizeof(int32_t) * (size_t)(2 * batch + 2 * nblk + 4));
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc kind lists");
-    if (w.ptr) w.old.push_back(w.ptr);
-    w.ptr = p;
-    w.cap = batch;
-  }
-  const int64_t cap = w.cap, nblk = (cap + PART_BLOCK - 1) / PART_BLOCK;
-  out->idx_gr = w.ptr;
-  out->idx_sq = w.ptr + cap;
-  out->blk_sq = w.ptr + 2 * cap;
+static int32_t kind_workspace(StreamCtx& C, hipStream_t stream, int64_t batch, KindLists* out) {
+  const int64_t need = (batch + PART_BLOCK - 1) / PART_BLOCK;
+  if (int32_t st = ctx_reserve(stream, C.kind, (size_t)batch, sizeof(int32_t) * (size_t)(2 * batch + 2 * need + 4),
+                               "mixed batch: the per-stream kind-list workspace"))
+    return st;
+  const int64_t cap = (int64_t)C.kind.cap, nblk = (cap + PART_BLOCK - 1) / PART_BLOCK;
+  int32_t* p = static_cast<int32_t*>(C.kind.ptr);
+  out->idx_gr = p;
+  out->idx_sq = p + cap;
+  out->blk_sq = p + 2 * cap;
   out->blk_off = out->blk_sq + nblk;
   out->counts = out->blk_off + nblk;
   return CPL_OK;
 }
 
+// the fused norms' workspace with room for `pairs` partial pairs (4096 at the least)
+static int32_t norm_workspace(StreamCtx& C, hipStream_t stream, size_t pairs, double** out) {
+  const size_t cap = pairs < 4096 ? 4096 : pairs;
+  if (int32_t st = ctx_reserve(stream, C.norms, cap, sizeof(double) * (NORM_HDR + 4 * cap),
+                               "fused residual norms: the per-stream workspace"))
+    return st;
+  *out = static_cast<double*>(C.norms.ptr);
+  return CPL_OK;
+}
+
 // `part` must have room for nparts + nparts / RF_CHUNK + 1 pairs (the norm workspaces hold 2 cap)
 constexpr int RF_CHUNK = 8192;
-// a side stream (and a fork / join event pair) per (device, stream) for the mixed split's two halves,
-// created on first use and kept (a captured graph may hold them)
-struct SideStream {
+
+static int32_t side_stream(StreamCtx& C, hipStream_t stream) {
+  std::lock_guard<std::mutex> lk(g_ctx_mutex);
+  if (C.side) return CPL_OK;
+  if (capturing(stream))
+    return fail(CPL_ERR_RUNTIME, "mixed batch: launch once on this stream before capturing it (side stream)");
+  // (default priority: at the greatest stream priority the same-process A/B gained 0.2-2 %, but in the
+  // bench's default line, after the north-star loop, the mixed16 side field went 2.54 -> 3.02 ms and
+  // its 8-GPU shard 0.39 -> 0.55 ms; profiles/r5/side_prio/)
+  hipError_t e;
   hipStream_t side = nullptr;
-  hipEvent_t fork = nullptr, join = nullptr;
-};
-static std::mutex g_side_mutex;
-static std::map<std::pair<int, hipStream_t>, SideStream> g_side;
-static int32_t side_stream(hipStream_t stream, SideStream* out) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
-  std::lock_guard<std::mutex> lk(g_side_mutex);
-  SideStream& ss = g_side[{dev, stream}];
-  if (!ss.side) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-      return fail(CPL_ERR_RUNTIME, "mixed batch: launch once on this stream before capturing it (side stream)");
-    // (default priority: at the greatest stream priority the same-process A/B gained 0.2-2 %, but in the
-    // bench's default line, after the north-star loop, the mixed16 side field went 2.54 -> 3.02 ms and
-    // its 8-GPU shard 0.39 -> 0.55 ms; profiles/r5/side_prio/)
-    if ((e = hipStreamCreateWithFlags(&ss.side, hipStreamNonBlocking)) != hipSuccess) return hip_fail(e, "hipStreamCreate");
-    if ((e = hipEventCreateWithFlags(&ss.fork, hipEventDisableTiming)) != hipSuccess) return hip_fail(e, "hipEventCreate");
-    if ((e = hipEventCreateWithFlags(&ss.join, hipEventDisableTiming)) != hipSuccess) return hip_fail(e, "hipEventCreate");
-  }
-  *out = ss;
+  if ((e = hipEventCreateWithFlags(&C.fork, hipEventDisableTiming)) != hipSuccess) return hip_fail(e, "hipEventCreate");
+  if ((e = hipEventCreateWithFlags(&C.join, hipEventDisableTiming)) != hipSuccess) return hip_fail(e, "hipEventCreate");
+  if ((e = hipStreamCreateWithFlags(&side, hipStreamNonBlocking)) != hipSuccess) return hip_fail(e, "hipStreamCreate");
+  C.side = side;  // (last: a context with a side stream has its events)
   return CPL_OK;
 }
 
@@ -2676,23 +2700,10 @@ static int32_t side_stream(hipStream_t stream, SideStream* out) {
 // stream's kind-list workspace and side stream already exist at this size (the default then falls
 // back to the interleaved mixed kernel — bitwise the same records — instead of failing the capture:
 // the solve engine captures its first iteration directly)
-static bool split_ready(hipStream_t stream, int64_t batch) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs == hipStreamCaptureStatusNone) return true;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return false;
-  bool ws = false, side = false;
-  {
-    std::lock_guard<std::mutex> lk(g_kind_ws_mutex);
-    auto it = g_kind_ws.find({dev, stream});
-    ws = it != g_kind_ws.end() && it->second.cap >= batch;
-  }
-  {
-    std::lock_guard<std::mutex> lk(g_side_mutex);
-    auto it = g_side.find({dev, stream});
-    side = it != g_side.end() && it->second.side != nullptr;
-  }
-  return ws && side;
+static bool split_ready(StreamCtx& C, hipStream_t stream, int64_t batch) {
+  if (!capturing(stream)) return true;
+  std::lock_guard<std::mutex> lk(g_ctx_mutex);
+  return C.kind.cap >= (size_t)batch && C.side != nullptr;
 }
 
 static void launch_residual_final(int nparts, const double* part, double* out, hipStream_t s) {
@@ -2800,17 +2811,6 @@ static int g_variant = VAR_AUTO;
 static size_t g_lds_budget = 0;    // 0 = per-kernel default (tile 32 KiB, pipelined 48 KiB)
 static int g_wg = 256;             // threads per tile workgroup (128 or 256)
 static int g_nt = 1;               // non-temporal output stores
-static int g_ablate = 0;           // measurement-only: 1 = skip the compute phase, 2 = skip the stores,
-                                   // 4 = the kind split's halves one after the other on the launch stream,
-                                   // 8 = the split's Ground half issued before the Superquadric half,
-                                   // 16 / 64 / 128 = the split's Ground list at 48 / 36 / 32 KiB
-                                   // (default 40), 32 = its Superquadric tiles at 40 KiB (default 48),
-                                   // 256 / 512 = every Ground workgroup walking / two per CU
-                                   // (default one per CU while the Superquadric list is non-empty),
-                                   // 1024 / 2048 = the Ground half's compute waves at priority 1 / 2,
-                                   // 4096 = the 4-instance Superquadric list tiles at the default priority,
-                                   // 8192 = the tile kernel's phase barriers skipped (wrong outputs),
-                                   // 16384 = the split's Superquadric grid for half the batch
 
 static size_t tile_budget() { return g_lds_budget ? g_lds_budget : 48 * 1024; }
 static size_t pipe_budget() { return g_lds_budget ? g_lds_budget : 48 * 1024; }
@@ -2824,9 +2824,8 @@ static bool use_pipe(const KParams& K) {
 // size_without_j: the tile size is chosen as if the Jacobian were written straight to the records
 // (the layouts that cannot, SoA, then stage it in a larger LDS image) so that every layout of a batch
 // runs the same tiles and the fused per-tile residual partials reduce in the same order
-static int32_t plan_tile(KParams& K, bool g, bool j, bool f, bool grad, int t_max = 64, bool size_without_j = false,
-                         size_t budget = 0) {
-  if (!budget) budget = tile_budget();
+static int32_t plan_tile(KParams& K, bool g, bool j, bool f, bool grad, int t_max = 64, bool size_without_j = false) {
+  const size_t budget = tile_budget();
   K.want_g = g; K.want_j = j; K.want_f = f; K.want_grad = grad;
   const bool sq = K.env_kind == CPL_ENV_SUPERQUADRIC || K.env_kind == CPL_ENV_MIXED;
   K.LR = K.N * SQ_L + 1;  // odd instance stride of the SQ scratch: conflict-free LDS banks
@@ -2925,51 +2924,6 @@ static bool use_split(const KParams& K, int32_t flags, int64_t batch) {
          K.env_kind == CPL_ENV_MIXED && batch <= 0x7fffffffLL;
 }
 
-struct PipeLaunch {
-  const void* fn;
-  size_t lds;
-  int blocks_per_cu;
-};
-
-// Workspace of the fused residual norms: one partial pair per workgroup, per (device, stream) so
-// that launches on different streams never share it.  Grown on demand, and a buffer is NEVER freed
-// while the process runs: a HIP graph captured on the stream keeps the pointer it saw, so a later,
-// larger launch on the same stream must not release it under the graph (the retired buffers are
-// kept in `old`).  Growing needs hipMalloc, which a stream capture forbids: warm the launch up on
-// the stream (one eager launch of the largest batch) before capturing it — a capture that would
-// have to grow the workspace fails with CPL_ERR_RUNTIME instead.
-struct NormWs {
-  double* ptr = nullptr;
-  size_t cap = 0;  // partial pairs
-  std::vector<double*> old;
-};
-static std::mutex g_norm_ws_mutex;
-static std::map<std::pair<int, hipStream_t>, NormWs> g_norm_ws;
-
-static int32_t norm_workspace(hipStream_t stream, size_t blocks, double** out) {
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
-  std::lock_guard<std::mutex> lk(g_norm_ws_mutex);
-  NormWs& w = g_norm_ws[{dev, stream}];
-  if (w.cap < blocks) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-      return fail(CPL_ERR_RUNTIME,
-                  "fused residual norms: the per-stream workspace must grow, which a stream capture forbids; "
-                  "launch the largest batch once on this stream before capturing");
-    const size_t cap = blocks < 4096 ? 4096 : blocks;
-    double* p = nullptr;
-    e = hipMalloc(&p, sizeof(double) * (NORM_HDR + 4 * cap));
-    if (e != hipSuccess) return hip_fail(e, "hipMalloc norms workspace");
-    if (w.ptr) w.old.push_back(w.ptr);  // possibly captured by a graph: kept alive
-    w.ptr = p;
-    w.cap = cap;
-  }
-  *out = w.ptr;
-  return CPL_OK;
-}
-
 // Launch geometry of the persistent pipelined kernel, cached per (device, kernel, LDS bytes): the
 // CU count and the occupancy query cost host time on every launch otherwise (the single-instance
 // TNLP path makes one launch per callback).
@@ -3006,265 +2960,248 @@ struct EvalScale {
   const int32_t* row;
 };
 
-static int32_t launch_eval(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
-                           const uint8_t* d_env_tag, double* d_g, double* d_jac, double* d_f, double* d_grad,
-                           double* d_norms, hipStream_t stream, bool finish = true,
-                           const LGradArgs* lg = nullptr, int32_t flags = 0, const EvalScale* sc = nullptr,
-                           const uint8_t* gate = nullptr) {
+// one evaluation launch: the C entry points' arguments
+struct EvalCall {
+  const cpl_problem_desc* d;
+  int64_t batch;
+  const double *x, *mass;
+  const uint8_t* env_tag;
+  double *g, *jac, *f, *grad, *norms;
+  hipStream_t stream;
+  int32_t flags = 0;
+  bool finish = true;             // (norms) the partials reduced to the final pair
+  const LGradArgs* lg = nullptr;  // the fused Lagrangian gradient instead of the outputs
+  const EvalScale* sc = nullptr;  // the NLP-scaled evaluation (pipelined kernel only)
+  const uint8_t* gate = nullptr;  // KParams::gate
+};
+
+// a persistent kernel's grid: one workgroup per tile, at most the resident ones
+static unsigned persistent_grid(int64_t tiles, const void* kern, size_t lds) {
+  const int64_t want = resident_blocks(kern, lds);
+  return (unsigned)(tiles < want ? tiles : want);
+}
+
+// after a kernel launch: its error, then (norms, unless the caller finishes them) the partials' final pair
+static int32_t launched(const EvalCall& c, const char* what, size_t nparts = 0, const double* ws = nullptr) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, what);
+  if (!c.norms || !c.finish || !ws) return CPL_OK;
+  launch_residual_final((int)nparts, ws + NORM_HDR, c.norms, c.stream);
+  e = hipGetLastError();
+  return e != hipSuccess ? hip_fail(e, "cpl_residual_final launch") : CPL_OK;
+}
+
+// mixed batch split by kind: the stable partition, then the Ground instances through the entry
+// kernel and the Superquadric ones through the Superquadric tile kernel, records in place
+static int32_t launch_split(const EvalCall& c, const KParams& K, StreamCtx& C) {
+  const int64_t batch = c.batch;
+  int32_t st;
+  KindLists kl;
+  if ((st = kind_workspace(C, c.stream, batch, &kl))) return st;
+  const unsigned nblk = (unsigned)((batch + PART_BLOCK - 1) / PART_BLOCK);
+  hipLaunchKernelGGL(k_kind_count, dim3(nblk), dim3(PART_BLOCK), 0, c.stream, batch, c.env_tag, kl.blk_sq);
+  hipLaunchKernelGGL(k_kind_write, dim3(nblk), dim3(PART_BLOCK), 0, c.stream, batch, (int)nblk, c.env_tag, kl.blk_sq,
+                     kl.idx_gr, kl.idx_sq, kl.counts);
+  if ((st = launched(c, "mixed split partition launch"))) return st;
+  KParams Kg = K, Ks = K;
+  // the Ground list at 40 KiB (1 048 576 x 16 mixed: 2.600 against 2.626 ms at 48 KiB, profiles/r4/
+  // split_lds)
+  if ((st = plan_entry(Kg, c.g != nullptr, c.jac != nullptr, c.f != nullptr, c.grad != nullptr, true, 40 * 1024)))
+    return st;
+  Ks.jdirect = (g_variant == VAR_SPLIT_JD && c.jac) ? 1 : 0;
+  // (the Superquadric tiles at the default budget: 40 KiB instead of 48 was within the noise beside the
+  // capped Ground walkers below: 2.603 / 2.552 against 2.540 / 2.579 ms in two runs, profiles/r4/split_grid)
+  if ((st = plan_tile(Ks, c.g != nullptr, c.jac != nullptr, c.f != nullptr, c.grad != nullptr))) return st;
+  const EntryKernT ek = g_nt ? cpl_eval_entry_kernel<CPL_ENV_GROUND, true> : cpl_eval_entry_kernel<CPL_ENV_GROUND, false>;
+  const TileKernT tk = Ks.jdirect ? (g_nt ? cpl_eval_tile_kernel<CPL_ENV_SUPERQUADRIC, 256, true, true, true>
+                                          : cpl_eval_tile_kernel<CPL_ENV_SUPERQUADRIC, 256, false, true, true>)
+                                  : (g_nt ? cpl_eval_tile_kernel<CPL_ENV_SUPERQUADRIC, 256, true, false, true>
+                                          : cpl_eval_tile_kernel<CPL_ENV_SUPERQUADRIC, 256, false, false, true>);
+  const size_t lds_g = sizeof(double) * (size_t)Kg.offI;
+  const size_t lds_s = sizeof(double) * (size_t)(Ks.offRB + Ks.T);
+  // the Ground half's persistent grid at full residency, of which one workgroup per CU walks the tiles
+  // while the Superquadric list is non-empty (the other slots left to its tiles on the other stream:
+  // 1 048 576 x 16 mixed 2.54-2.58 against 2.61 ms with every workgroup walking, profiles/r4/split_grid);
+  // all of it when the batch is all Ground (the cap decided on the device, from the partition's
+  // counts: 1.31 ms for 524 288 all-Ground mixed instances, as uncapped; a cap fixed at launch had
+  // cost 2.37).
+  // Not below 262 144 instances: at the 8-GPU shard of configs[3] (131 072 x 16) the capped walkers ran
+  // ~90 us past the Superquadric half (0.432 ms capped against 0.394 uncapped; 262 144 / 524 288 /
+  // 1 048 576: within noise either way, profiles/r5/split_cap)
+  if (batch >= (int64_t)1 << 18) Kg.grid_cap = (int32_t)C.cus;
+  const unsigned grid_g = persistent_grid((batch + Kg.T - 1) / Kg.T, reinterpret_cast<const void*>(ek), lds_g);
+  // every tile the list may hold (a grid for half the batch, enough for the bench's alternating tags,
+  // priced the empty workgroups past the list: noise)
+  const unsigned grid_s = (unsigned)((batch + Ks.T - 1) / Ks.T);
+  const size_t nparts = (size_t)grid_g + (size_t)grid_s * 4;
+  double* ws = nullptr;
+  if (c.norms && (st = norm_workspace(C, c.stream, nparts, &ws))) return st;
+  // the two halves on two streams (fork after the partition, join before the norms' finish): the
+  // memory-bound Ground records and the latency-bound Superquadric tiles share the CUs; the
+  // Superquadric half issued first
+  if ((st = side_stream(C, c.stream))) return st;
+  hipError_t e = hipEventRecord(C.fork, c.stream);
+  if (e == hipSuccess) e = hipStreamWaitEvent(C.side, C.fork, 0);
+  if (e != hipSuccess) return hip_fail(e, "mixed split fork");
+  hipLaunchKernelGGL(tk, dim3(grid_s), dim3(256), lds_s, c.stream, Ks, batch, c.x, c.mass, c.env_tag, kl.idx_sq,
+                     kl.counts + 1, c.g, c.jac, c.f, c.grad, ws ? ws + 2 * (size_t)grid_g : nullptr);
+  hipLaunchKernelGGL(ek, dim3(grid_g), dim3(256), lds_g, C.side, Kg, batch, c.x, c.mass, kl.idx_gr, kl.counts, c.g,
+                     c.jac, c.f, c.grad, ws);
+  e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, "mixed split launch");
+  e = hipEventRecord(C.join, C.side);
+  if (e == hipSuccess) e = hipStreamWaitEvent(c.stream, C.join, 0);
+  if (e != hipSuccess) return hip_fail(e, "mixed split join");
+  return launched(c, "mixed split launch", nparts, ws);
+}
+
+static int32_t launch_entry(const EvalCall& c, KParams& K, StreamCtx* C) {
+  int32_t st = plan_entry(K, c.g != nullptr, c.jac != nullptr, c.f != nullptr, c.grad != nullptr);
+  if (st) return st;
+  const size_t lds = sizeof(double) * (size_t)K.offI;
+  static const EntryKernT table[2][2] = {
+      {cpl_eval_entry_kernel<CPL_ENV_NONE, false>, cpl_eval_entry_kernel<CPL_ENV_NONE, true>},
+      {cpl_eval_entry_kernel<CPL_ENV_GROUND, false>, cpl_eval_entry_kernel<CPL_ENV_GROUND, true>}};
+  const EntryKernT kern = table[K.env_kind == CPL_ENV_GROUND ? 1 : 0][g_nt ? 1 : 0];
+  const unsigned grid = persistent_grid((c.batch + K.T - 1) / K.T, reinterpret_cast<const void*>(kern), lds);
+  double* ws = nullptr;
+  if (c.norms && (st = norm_workspace(*C, c.stream, grid, &ws))) return st;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, c.stream, K, c.batch, c.x, c.mass, nullptr, nullptr, c.g, c.jac,
+                     c.f, c.grad, ws);
+  return launched(c, "cpl_eval_entry_kernel launch", grid, ws);
+}
+
+static int32_t launch_pipe(const EvalCall& c, KParams& K, StreamCtx* C) {
+  const LGradArgs* lg = c.lg;
+  // the fused Lagrangian gradient computes jac and grad into the tile image and stores only d_grad
+  // (the fused gradient also keeps the CSC index, (n + 1) + 2 nnz ints, in LDS)
+  const int csc_doubles = lg ? (K.n + 1 + 2 * K.nnz + 1) / 2 : 0;
+  int32_t st = lg ? plan_pipe(K, false, true, false, true, sizeof(double) * (size_t)csc_doubles)
+                  : plan_pipe(K, c.g != nullptr, c.jac != nullptr, c.f != nullptr, c.grad != nullptr);
+  if (st) return st;
+  K.offC = K.offI + 72;
+  if (lg) {
+    K.want_lgrad = 1;
+    K.y_repeat = lg->y_repeat;
+    K.col_ptr = lg->col_ptr;
+    K.csc_k = lg->csc_k;
+    K.csc_row = lg->csc_row;
+    K.ly = lg->y;
+    K.lg_active = lg->active;
+  }
+  const size_t lds = sizeof(double) * (size_t)(K.offC + csc_doubles);
+  static const PipeKernT table[4][2] = {
+      {cpl_eval_pipe_kernel<CPL_ENV_NONE, 3, false>, cpl_eval_pipe_kernel<CPL_ENV_NONE, 3, true>},
+      {cpl_eval_pipe_kernel<CPL_ENV_GROUND, 3, false>, cpl_eval_pipe_kernel<CPL_ENV_GROUND, 3, true>},
+      {cpl_eval_pipe_kernel<CPL_ENV_SUPERQUADRIC, 3, false>, cpl_eval_pipe_kernel<CPL_ENV_SUPERQUADRIC, 3, true>},
+      {cpl_eval_pipe_kernel<CPL_ENV_MIXED, 3, false>, cpl_eval_pipe_kernel<CPL_ENV_MIXED, 3, true>}};
+  static const PipeKernT table_sc[2][2] = {
+      {cpl_eval_pipe_kernel<CPL_ENV_NONE, 3, false, true>, cpl_eval_pipe_kernel<CPL_ENV_NONE, 3, true, true>},
+      {cpl_eval_pipe_kernel<CPL_ENV_GROUND, 3, false, true>, cpl_eval_pipe_kernel<CPL_ENV_GROUND, 3, true, true>}};
+  if (c.sc && K.env_kind != CPL_ENV_NONE && K.env_kind != CPL_ENV_GROUND) return CPL_ERR_UNSUPPORTED;
+  if (c.sc) {
+    K.sc_df = c.sc->df;
+    K.sc_dc = c.sc->dc;
+    K.sc_row = c.sc->row;
+  }
+  const PipeKernT kern =
+      c.sc ? table_sc[K.env_kind == CPL_ENV_GROUND ? 1 : 0][g_nt ? 1 : 0] : table[K.env_kind][g_nt ? 1 : 0];
+  const unsigned grid = persistent_grid((c.batch + K.T - 1) / K.T, reinterpret_cast<const void*>(kern), lds);
+  double* ws = nullptr;
+  if (c.norms && (st = norm_workspace(*C, c.stream, grid, &ws))) return st;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, c.stream, K, c.batch, c.x, c.mass, c.env_tag, c.g, c.jac, c.f,
+                     c.grad, ws);
+  return launched(c, "cpl_eval_pipe_kernel launch", grid, ws);  // per-workgroup partials -> final pair
+}
+
+// (the row-staged kernel writes IFOPT records only)
+static int32_t launch_rowstage(const EvalCall& c, const KParams& K) {
+  const size_t lds = eval_lds_bytes(K.n);
+  if (lds > 160 * 1024) return fail(CPL_ERR_UNSUPPORTED, "problem too large for one LDS tile");
+  const unsigned grid = (unsigned)((c.batch + TILE - 1) / TILE);
+  hipLaunchKernelGGL(cpl_eval_kernel, dim3(grid), dim3(TILE), lds, c.stream, K, c.batch, c.x, c.mass, c.env_tag, c.g,
+                     c.jac, c.f, c.grad);
+  if (int32_t st = launched(c, "cpl_eval_kernel launch")) return st;
+  // the row-staged kernel has no fused epilogue: a separate pass over g
+  return c.norms && c.finish ? cpl_residual_norms(c.d, c.batch, c.g, c.norms, c.stream) : CPL_OK;
+}
+
+static int32_t launch_tile(const EvalCall& c, KParams& K, StreamCtx* C) {
+  // records too large for 8 per 48 KiB tile (16 Superquadric / mixed contacts, ~10 KiB each) run as
+  // 4-instance tiles on 256 threads: 1 048 576 x 16 mixed 3.17 ms against 3.99 ms for the 2-instance
+  // tiles on 128 threads of round 1 and 4.18 ms for 8-instance tiles
+  // (profiles/r2_v7/sweep_tiles_mixed16_*.jsonl)
+  // mixed batches write the Jacobian straight to the output records (their ~10 KiB records leave
+  // 4 instances per 48 KiB tile otherwise; without the Jacobian image the tile holds 8): mixed16
+  // 4.23 -> 3.47 ms, interleaved A/B in one process (profiles/r3/abk_mixed16.jsonl); the
+  // Superquadric records are small enough that the staged copy-out wins there (0.32 vs 0.42 ms)
+  const bool jd = g_variant == VAR_TILE_JD || (g_variant == VAR_AUTO && K.env_kind == CPL_ENV_MIXED);
+  const int wg = g_wg;
+  K.jdirect = (jd && c.jac && !K.soa && wg == 256) ? 1 : 0;
+  int32_t st = plan_tile(K, c.g != nullptr, c.jac != nullptr, c.f != nullptr, c.grad != nullptr, 64, jd && c.jac);
+  if (st) return st;
+  const size_t lds = sizeof(double) * (size_t)(K.offRB + K.T);
+  const unsigned grid = (unsigned)((c.batch + K.T - 1) / K.T);
+  const size_t nparts = (size_t)grid * (wg / 64);  // one partial pair per wave
+  double* ws = nullptr;
+  if (c.norms && (st = norm_workspace(*C, c.stream, nparts, &ws))) return st;
+#define CPL_TILE_KERNELS(E) \
+  {cpl_eval_tile_kernel<E, 128, false, false>, cpl_eval_tile_kernel<E, 128, true, false>,        \
+   cpl_eval_tile_kernel<E, 256, false, false>, cpl_eval_tile_kernel<E, 256, true, false>,        \
+   cpl_eval_tile_kernel<E, 256, false, true>, cpl_eval_tile_kernel<E, 256, true, true>}
+  static const TileKernT table[4][6] = {CPL_TILE_KERNELS(CPL_ENV_NONE), CPL_TILE_KERNELS(CPL_ENV_GROUND),
+                                        CPL_TILE_KERNELS(CPL_ENV_SUPERQUADRIC), CPL_TILE_KERNELS(CPL_ENV_MIXED)};
+#undef CPL_TILE_KERNELS
+  const TileKernT kern = table[K.env_kind][(K.jdirect ? 4 : (wg == 256 ? 2 : 0)) + (g_nt ? 1 : 0)];
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(wg), lds, c.stream, K, c.batch, c.x, c.mass, c.env_tag, nullptr, nullptr,
+                     c.g, c.jac, c.f, c.grad, ws);
+  return launched(c, "cpl_eval_tile_kernel launch", nparts, ws);  // per-tile partials -> final pair
+}
+
+// validate, fill the kernel parameters, pick the launch path
+static int32_t launch_eval(const EvalCall& c) {
+  const cpl_problem_desc* d = c.d;
   int32_t st = validate_desc(d);
   if (st) return st;
-  if (flags & ~(CPL_EVAL_JAC_FOLDED | CPL_EVAL_SOA)) return fail(CPL_ERR_INVALID_ARGUMENT, "unknown eval flags");
-  if (batch < 0) return fail(CPL_ERR_INVALID_ARGUMENT, "negative batch");
-  if (batch == 0) {  // (an empty g may arrive as a null pointer)
-    if (d_norms) {
-      hipError_t e = hipMemsetAsync(d_norms, 0, 2 * sizeof(double), stream);
+  if (c.flags & ~(CPL_EVAL_JAC_FOLDED | CPL_EVAL_SOA)) return fail(CPL_ERR_INVALID_ARGUMENT, "unknown eval flags");
+  if (c.batch < 0) return fail(CPL_ERR_INVALID_ARGUMENT, "negative batch");
+  if (c.batch == 0) {  // (an empty g may arrive as a null pointer)
+    if (c.norms) {
+      hipError_t e = hipMemsetAsync(c.norms, 0, 2 * sizeof(double), c.stream);
       if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync norms");
     }
     return CPL_OK;
   }
-  if (d_norms && !d_g) return fail(CPL_ERR_INVALID_ARGUMENT, "residual norms need the g output");
-  if (!d_x) return fail(CPL_ERR_INVALID_ARGUMENT, "x is required");
-  if (d->env_kind == CPL_ENV_MIXED && !d_env_tag)
+  if (c.norms && !c.g) return fail(CPL_ERR_INVALID_ARGUMENT, "residual norms need the g output");
+  if (!c.x) return fail(CPL_ERR_INVALID_ARGUMENT, "x is required");
+  if (d->env_kind == CPL_ENV_MIXED && !c.env_tag)
     return fail(CPL_ERR_INVALID_ARGUMENT, "mixed environment batch needs a per-instance env tag array");
-  if ((batch + 7) / 8 > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "batch too large");
-  if (!d_g && !d_jac && !d_f && !d_grad) return CPL_OK;
+  if ((c.batch + 7) / 8 > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "batch too large");
+  if (!c.g && !c.jac && !c.f && !c.grad) return CPL_OK;
   KParams K;
-  fill_params(d, K, d_x);
-  K.gate = gate;  // (honoured by the pipelined kernel; the others evaluate regardless)
-  if (flags & CPL_EVAL_JAC_FOLDED) {  // values-only Jacobian records (cpl_layout.hpp)
+  fill_params(d, K, c.x);  // (zeroes every field it does not set)
+  K.gate = c.gate;  // (honoured by the pipelined kernel; the others evaluate regardless)
+  if (c.flags & CPL_EVAL_JAC_FOLDED) {  // values-only Jacobian records (cpl_layout.hpp)
     K.fold = fold_level(d->env_kind);
     K.nnz = folded_nnz(K.N, d->env_kind);
     K.jbase = 6 + 12 * K.N;
     K.cstride = folded_contact_nnz(d->env_kind);
   }
-  K.soa = (flags & CPL_EVAL_SOA) ? 1 : 0;
-  K.want_norms = d_norms != nullptr;
-  K.want_lgrad = 0;
+  K.soa = (c.flags & CPL_EVAL_SOA) ? 1 : 0;
+  K.want_norms = c.norms != nullptr;
   K.y_repeat = 1;
-  K.col_ptr = K.csc_k = K.csc_row = nullptr;
-  K.ly = nullptr;
-  K.lg_active = nullptr;
-  K.sc_df = K.sc_dc = nullptr;
-  K.sc_row = nullptr;
-  double* ws = nullptr;
+  const bool split = !c.lg && use_split(K, c.flags, c.batch), entry = !c.lg && use_entry(K, c.flags);
   // (the scaled evaluation: the pipelined path only; the caller scales the others itself)
-  if (sc && (lg || d_norms || K.soa || !use_pipe(K) || use_split(K, flags, batch) || use_entry(K, flags)))
-    return CPL_ERR_UNSUPPORTED;
-  if (lg && !use_pipe(K))
+  if (c.sc && (c.lg || c.norms || K.soa || !use_pipe(K) || split || entry)) return CPL_ERR_UNSUPPORTED;
+  if (c.lg && !use_pipe(K))
     return fail(CPL_ERR_UNSUPPORTED, "fused Lagrangian gradient: pipelined (Ground / no environment) path only");
-  if (!lg && use_split(K, flags, batch) && (g_variant != VAR_AUTO || split_ready(stream, batch))) {
-    // mixed batch split by kind: the stable partition, then the Ground instances through the entry
-    // kernel and the Superquadric ones through the Superquadric tile kernel, records in place
-    KindLists kl;
-    if ((st = kind_workspace(stream, batch, &kl))) return st;
-    const unsigned nblk = (unsigned)((batch + PART_BLOCK - 1) / PART_BLOCK);
-    hipLaunchKernelGGL(k_kind_count, dim3(nblk), dim3(PART_BLOCK), 0, stream, batch, d_env_tag, kl.blk_sq);
-    hipLaunchKernelGGL(k_kind_write, dim3(nblk), dim3(PART_BLOCK), 0, stream, batch, (int)nblk, d_env_tag, kl.blk_sq,
-                       kl.idx_gr, kl.idx_sq, kl.counts);
-    KParams Kg = K, Ks = K;
-    // the Ground list at 40 KiB (1 048 576 x 16 mixed: 2.600 against 2.626 ms at 48 KiB, profiles/r4/
-    // split_lds; measurement: ablation 16 gives it 48 KiB, 32 the Superquadric tiles 40 KiB)
-    const size_t list_kb = (g_ablate & 16) ? 48 : (g_ablate & 64) ? 36 : (g_ablate & 128) ? 32 : 40;
-    if ((st = plan_entry(Kg, d_g != nullptr, d_jac != nullptr, d_f != nullptr, d_grad != nullptr, true,
-                         list_kb * 1024)))
-      return st;
-    Ks.jdirect = (g_variant == VAR_SPLIT_JD && d_jac) ? 1 : 0;
-    // (measurement: ablation 32 = the Superquadric tiles at 40 KiB instead of 48 — within the noise beside
-    // the capped Ground walkers below: 2.603 / 2.552 against 2.540 / 2.579 ms in two runs,
-    // profiles/r4/split_grid)
-    if ((st = plan_tile(Ks, d_g != nullptr, d_jac != nullptr, d_f != nullptr, d_grad != nullptr, 64, false,
-                        (g_ablate & 32) ? 40 * 1024 : 0)))
-      return st;
-    Kg.ablate = Ks.ablate = g_ablate & 3;
-    const bool sequential = (g_ablate & 4) != 0;
-    using EntryT = void (*)(const KParams, int64_t, const double*, const double*, const int32_t*, const int32_t*,
-                            double*, double*, double*, double*, double*);
-    using TileT = void (*)(const KParams, int64_t, const double*, const double*, const uint8_t*, const int32_t*,
-                           const int32_t*, double*, double*, double*, double*, double*);
-    const EntryT ek = g_nt ? cpl_eval_entry_kernel<CPL_ENV_GROUND, true> : cpl_eval_entry_kernel<CPL_ENV_GROUND, false>;
-    const TileT tk = Ks.jdirect ? (g_nt ? cpl_eval_tile_kernel<CPL_ENV_SUPERQUADRIC, 256, true, true, true>
-                                        : cpl_eval_tile_kernel<CPL_ENV_SUPERQUADRIC, 256, false, true, true>)
-                                : (g_nt ? cpl_eval_tile_kernel<CPL_ENV_SUPERQUADRIC, 256, true, false, true>
-                                        : cpl_eval_tile_kernel<CPL_ENV_SUPERQUADRIC, 256, false, false, true>);
-    const size_t lds_g = sizeof(double) * (size_t)Kg.offI;
-    const size_t lds_s = sizeof(double) * (size_t)(Ks.offRB + Ks.T);
-    const int64_t ntg = (batch + Kg.T - 1) / Kg.T;
-    const int64_t want = resident_blocks(reinterpret_cast<const void*>(ek), lds_g);
-    // the Ground half's persistent grid at full residency, of which one workgroup per CU walks the tiles
-    // while the Superquadric list is non-empty (the other slots left to its tiles on the other stream:
-    // 1 048 576 x 16 mixed 2.54-2.58 against 2.61 ms with every workgroup walking, profiles/r4/split_grid);
-    // all of it when the batch is all Ground (the cap decided on the device, from the partition's
-    // counts: 1.31 ms for 524 288 all-Ground mixed instances, as uncapped; a cap fixed at launch had
-    // cost 2.37).  Measurement: ablation 256 = no cap, 512 = two per CU.
-    // Not below 262 144 instances: at the 8-GPU shard of configs[3] (131 072 x 16) the capped walkers ran
-    // ~90 us past the Superquadric half (0.432 ms capped against 0.394 uncapped; 262 144 / 524 288 /
-    // 1 048 576: within noise either way, profiles/r5/split_cap)
-    const int64_t want_g = want;
-    if (!(g_ablate & 256) && batch >= (int64_t)1 << 18) {
-      int dev = 0, cus = 256;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      Kg.grid_cap = (int32_t)((g_ablate & 512) ? 2 * cus : cus);
-    }
-    Kg.cw_prio = (g_ablate & 1024) ? 1 : (g_ablate & 2048) ? 2 : 0;
-    // the Superquadric list tiles' gather / copy-out at a raised wave priority (measurement: ablation
-    // 4096 leaves the 4-instance tiles at the default priority)
-    Ks.list_prio = ((g_ablate & 4096) && Ks.T < 8) ? 0 : 1;
-    const unsigned grid_g = (unsigned)(ntg < want_g ? ntg : want_g);
-    // every tile the list may hold (measurement only, ablation 16384: half of them — correct only for
-    // batches with at most half their instances Superquadric, e.g. the bench's alternating tags — to
-    // price the empty workgroups past the list)
-    const int64_t grid_inst = (g_ablate & 16384) ? (batch + 1) / 2 : batch;
-    const unsigned grid_s = (unsigned)((grid_inst + Ks.T - 1) / Ks.T);
-    const size_t nparts = (size_t)grid_g + (size_t)grid_s * 4;
-    if (K.want_norms && (st = norm_workspace(stream, nparts, &ws))) return st;
-    // the two halves on two streams (fork after the partition, join before the norms' finish): the
-    // memory-bound Ground records and the latency-bound Superquadric tiles share the CUs
-    SideStream ss;
-    if (!sequential) {
-      if ((st = side_stream(stream, &ss))) return st;
-      hipError_t e = hipEventRecord(ss.fork, stream);
-      if (e == hipSuccess) e = hipStreamWaitEvent(ss.side, ss.fork, 0);
-      if (e != hipSuccess) return hip_fail(e, "mixed split fork");
-    }
-    const bool ground_first = (g_ablate & 8) != 0;  // (measurement) the Ground half's launch issued first
-    auto launch_s = [&]() {
-      hipLaunchKernelGGL(tk, dim3(grid_s), dim3(256), lds_s, stream, Ks, batch, d_x, d_mass, d_env_tag, kl.idx_sq,
-                         kl.counts + 1, d_g, d_jac, d_f, d_grad, ws ? ws + 2 * (size_t)grid_g : nullptr);
-    };
-    if (!ground_first) launch_s();
-    hipLaunchKernelGGL(ek, dim3(grid_g), dim3(256), lds_g, sequential ? stream : ss.side, Kg, batch, d_x, d_mass,
-                       kl.idx_gr, kl.counts, d_g, d_jac, d_f, d_grad, ws);
-    if (ground_first) launch_s();
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "mixed split launch");
-    if (!sequential) {
-      e = hipEventRecord(ss.join, ss.side);
-      if (e == hipSuccess) e = hipStreamWaitEvent(stream, ss.join, 0);
-      if (e != hipSuccess) return hip_fail(e, "mixed split join");
-    }
-    if (K.want_norms && finish) launch_residual_final((int)nparts, ws + NORM_HDR, d_norms, stream);
-    return CPL_OK;
-  }
-  if (!lg && use_entry(K, flags)) {
-    st = plan_entry(K, d_g != nullptr, d_jac != nullptr, d_f != nullptr, d_grad != nullptr);
-    if (st) return st;
-    K.ablate = g_ablate;
-    const size_t lds = sizeof(double) * (size_t)K.offI;
-    using KernT = void (*)(const KParams, int64_t, const double*, const double*, const int32_t*, const int32_t*,
-                           double*, double*, double*, double*, double*);
-    static const KernT table[2][2] = {
-        {cpl_eval_entry_kernel<CPL_ENV_NONE, false>, cpl_eval_entry_kernel<CPL_ENV_NONE, true>},
-        {cpl_eval_entry_kernel<CPL_ENV_GROUND, false>, cpl_eval_entry_kernel<CPL_ENV_GROUND, true>}};
-    const KernT kern = table[K.env_kind == CPL_ENV_GROUND ? 1 : 0][g_nt ? 1 : 0];
-    const int64_t ntiles = (batch + K.T - 1) / K.T;
-    const int64_t want = resident_blocks(reinterpret_cast<const void*>(kern), lds);
-    const unsigned grid = (unsigned)(ntiles < want ? ntiles : want);
-    if (K.want_norms && (st = norm_workspace(stream, grid, &ws))) return st;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, K, batch, d_x, d_mass, nullptr, nullptr, d_g, d_jac,
-                       d_f, d_grad, ws);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "cpl_eval_entry_kernel launch");
-    if (K.want_norms && finish) launch_residual_final((int)grid, ws + NORM_HDR, d_norms, stream);
-    return CPL_OK;
-  }
-  if (use_pipe(K)) {
-    // the fused Lagrangian gradient computes jac and grad into the tile image and stores only d_grad
-    // (the fused gradient also keeps the CSC index, (n + 1) + 2 nnz ints, in LDS)
-    const int csc_doubles = lg ? (K.n + 1 + 2 * K.nnz + 1) / 2 : 0;
-    st = lg ? plan_pipe(K, false, true, false, true, sizeof(double) * (size_t)csc_doubles)
-            : plan_pipe(K, d_g != nullptr, d_jac != nullptr, d_f != nullptr, d_grad != nullptr);
-    if (st) return st;
-    K.offC = K.offI + 72;
-    if (lg) {
-      K.want_lgrad = 1;
-      K.y_repeat = lg->y_repeat;
-      K.col_ptr = lg->col_ptr;
-      K.csc_k = lg->csc_k;
-      K.csc_row = lg->csc_row;
-      K.ly = lg->y;
-      K.lg_active = lg->active;
-    }
-    K.ablate = g_ablate;
-    const size_t lds = sizeof(double) * (size_t)(K.offC + csc_doubles);
-    using KernT = void (*)(const KParams, int64_t, const double*, const double*, const uint8_t*, double*, double*,
-                           double*, double*, double*);
-    static const KernT table[4][2] = {
-        {cpl_eval_pipe_kernel<CPL_ENV_NONE, 3, false>, cpl_eval_pipe_kernel<CPL_ENV_NONE, 3, true>},
-        {cpl_eval_pipe_kernel<CPL_ENV_GROUND, 3, false>, cpl_eval_pipe_kernel<CPL_ENV_GROUND, 3, true>},
-        {cpl_eval_pipe_kernel<CPL_ENV_SUPERQUADRIC, 3, false>, cpl_eval_pipe_kernel<CPL_ENV_SUPERQUADRIC, 3, true>},
-        {cpl_eval_pipe_kernel<CPL_ENV_MIXED, 3, false>, cpl_eval_pipe_kernel<CPL_ENV_MIXED, 3, true>}};
-    static const KernT table_sc[2][2] = {
-        {cpl_eval_pipe_kernel<CPL_ENV_NONE, 3, false, true>, cpl_eval_pipe_kernel<CPL_ENV_NONE, 3, true, true>},
-        {cpl_eval_pipe_kernel<CPL_ENV_GROUND, 3, false, true>, cpl_eval_pipe_kernel<CPL_ENV_GROUND, 3, true, true>}};
-    if (sc && K.env_kind != CPL_ENV_NONE && K.env_kind != CPL_ENV_GROUND) return CPL_ERR_UNSUPPORTED;
-    if (sc) {
-      K.sc_df = sc->df;
-      K.sc_dc = sc->dc;
-      K.sc_row = sc->row;
-    }
-    const KernT kern = sc ? table_sc[K.env_kind == CPL_ENV_GROUND ? 1 : 0][g_nt ? 1 : 0] : table[K.env_kind][g_nt ? 1 : 0];
-    const int64_t ntiles = (batch + K.T - 1) / K.T;
-    const int64_t want = resident_blocks(reinterpret_cast<const void*>(kern), lds);
-    unsigned grid = (unsigned)(ntiles < want ? ntiles : want);
-    if (K.want_norms && (st = norm_workspace(stream, grid, &ws))) return st;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, K, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f,
-                       d_grad, ws);
-    if (K.want_norms) {  // per-workgroup partials -> final pair
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return hip_fail(e, "cpl_eval_pipe_kernel launch");
-      if (finish) launch_residual_final((int)grid, ws + NORM_HDR, d_norms, stream);
-    }
-  } else if (use_rowstage() && flags == 0) {  // (the row-staged kernel writes IFOPT records only)
-    const size_t lds = eval_lds_bytes(K.n);
-    if (lds > 160 * 1024) return fail(CPL_ERR_UNSUPPORTED, "problem too large for one LDS tile");
-    const unsigned grid = (unsigned)((batch + TILE - 1) / TILE);
-    hipLaunchKernelGGL(cpl_eval_kernel, dim3(grid), dim3(TILE), lds, stream, K, batch, d_x, d_mass, d_env_tag,
-                       d_g, d_jac, d_f, d_grad);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "cpl_eval_kernel launch");
-    // the row-staged kernel has no fused epilogue: a separate pass over g
-    return d_norms && finish ? cpl_residual_norms(d, batch, d_g, d_norms, stream) : CPL_OK;
-  } else {
-    // records too large for 8 per 48 KiB tile (16 Superquadric / mixed contacts, ~10 KiB each) run as
-    // 4-instance tiles on 256 threads: 1 048 576 x 16 mixed 3.17 ms against 3.99 ms for the 2-instance
-    // tiles on 128 threads of round 1 and 4.18 ms for 8-instance tiles
-    // (profiles/r2_v7/sweep_tiles_mixed16_*.jsonl)
-    // mixed batches write the Jacobian straight to the output records (their ~10 KiB records leave
-    // 4 instances per 48 KiB tile otherwise; without the Jacobian image the tile holds 8): mixed16
-    // 4.23 -> 3.47 ms, interleaved A/B in one process (profiles/r3/abk_mixed16.jsonl); the
-    // Superquadric records are small enough that the staged copy-out wins there (0.32 vs 0.42 ms)
-    const bool jd = g_variant == VAR_TILE_JD || (g_variant == VAR_AUTO && K.env_kind == CPL_ENV_MIXED);
-    K.jdirect = (jd && d_jac && !K.soa && g_wg == 256) ? 1 : 0;
-    st = plan_tile(K, d_g != nullptr, d_jac != nullptr, d_f != nullptr, d_grad != nullptr, 64, jd && d_jac);
-    const int wg = g_wg;
-    if (st) return st;
-    K.ablate = g_ablate;
-    const size_t lds = sizeof(double) * (size_t)(K.offRB + K.T);
-    const unsigned grid = (unsigned)((batch + K.T - 1) / K.T);
-    const size_t nparts = (size_t)grid * (wg / 64);  // one partial pair per wave
-    if (K.want_norms && (st = norm_workspace(stream, nparts, &ws))) return st;
-    using KernT = void (*)(const KParams, int64_t, const double*, const double*, const uint8_t*, const int32_t*,
-                           const int32_t*, double*, double*, double*, double*, double*);
-#define CPL_TILE_KERNELS(E) \
-  {cpl_eval_tile_kernel<E, 128, false, false>, cpl_eval_tile_kernel<E, 128, true, false>,        \
-   cpl_eval_tile_kernel<E, 256, false, false>, cpl_eval_tile_kernel<E, 256, true, false>,        \
-   cpl_eval_tile_kernel<E, 256, false, true>, cpl_eval_tile_kernel<E, 256, true, true>}
-    static const KernT table[4][6] = {CPL_TILE_KERNELS(CPL_ENV_NONE), CPL_TILE_KERNELS(CPL_ENV_GROUND),
-                                      CPL_TILE_KERNELS(CPL_ENV_SUPERQUADRIC), CPL_TILE_KERNELS(CPL_ENV_MIXED)};
-#undef CPL_TILE_KERNELS
-    const KernT kern = table[K.env_kind][(K.jdirect ? 4 : (wg == 256 ? 2 : 0)) + (g_nt ? 1 : 0)];
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(wg), lds, stream, K, batch, d_x, d_mass, d_env_tag, nullptr, nullptr,
-                       d_g, d_jac, d_f, d_grad, ws);
-    if (K.want_norms) {  // per-tile partials -> final pair
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return hip_fail(e, "cpl_eval_tile_kernel launch");
-      if (finish) launch_residual_final((int)nparts, ws + NORM_HDR, d_norms, stream);
-    }
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "cpl_eval_kernel launch");
-  return CPL_OK;
+  StreamCtx* C = nullptr;  // the stream's context, for the launches that keep something in it
+  if ((split || c.norms) && (st = stream_ctx(c.stream, &C))) return st;
+  if (split && (g_variant != VAR_AUTO || split_ready(*C, c.stream, c.batch))) return launch_split(c, K, *C);
+  if (entry) return launch_entry(c, K, C);
+  if (use_pipe(K)) return launch_pipe(c, K, C);
+  if (use_rowstage() && c.flags == 0) return launch_rowstage(c, K);
+  return launch_tile(c, K, C);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3568,10 +3505,6 @@ int32_t ls_backtrack(const cpl_problem_desc* d, const LsBacktrackArgs& a, hipStr
   return CPL_OK;
 }
 
-// per-device residual workspace (RN_GRID partial pairs), allocated once
-static std::mutex g_ws_mutex;
-static double* g_ws[64] = {nullptr};
-
 // (internal, the solve engine) cpl_eval_batch_ex of the NLP-scaled problem: f, grad times df[b], g, J
 // times dc[b, row]; CPL_ERR_UNSUPPORTED (nothing launched) where the evaluation does not take the
 // pipelined kernel — the caller then scales the outputs itself
@@ -3580,16 +3513,19 @@ int32_t eval_batch_scaled(const cpl_problem_desc* d, int64_t batch, const double
                           int32_t flags, const double* df, const double* dc, const int32_t* row, void* stream,
                           const uint8_t* gate) {
   const EvalScale sc{df, dc, row};
-  return launch_eval(d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, nullptr, (hipStream_t)stream, true,
-                     nullptr, flags, &sc, gate);
+  EvalCall c{d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, nullptr, (hipStream_t)stream, flags};
+  c.sc = &sc;
+  c.gate = gate;
+  return launch_eval(c);
 }
 
 // (internal, the solve engine) cpl_eval_batch_ex with a gate byte (KParams::gate)
 int32_t eval_batch_gated(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
                          const uint8_t* d_env_tag, double* d_g, double* d_jac, double* d_f, double* d_grad,
                          int32_t flags, void* stream, const uint8_t* gate) {
-  return launch_eval(d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, nullptr, (hipStream_t)stream, true,
-                     nullptr, flags, nullptr, gate);
+  EvalCall c{d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, nullptr, (hipStream_t)stream, flags};
+  c.gate = gate;
+  return launch_eval(c);
 }
 
 }  // namespace cpl
@@ -3601,7 +3537,7 @@ extern "C" {
 int32_t cpl_eval_batch(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
                        const uint8_t* d_env_tag, double* d_g, double* d_jac, double* d_f, double* d_grad,
                        void* stream) {
-  return launch_eval(d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, nullptr, (hipStream_t)stream);
+  return launch_eval(EvalCall{d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, nullptr, (hipStream_t)stream});
 }
 
 int32_t cpl_eval_lagrangian_grad(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
@@ -3613,8 +3549,9 @@ int32_t cpl_eval_lagrangian_grad(const cpl_problem_desc* d, int64_t batch, const
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_eval_lagrangian_grad: missing buffer");
   const LGradArgs lg{d_col_ptr, d_csc_k, d_csc_row, d_y, y_repeat, d_active};
   // jac and grad f are computed into the tile image; only grad f + J^T y is stored (to d_out)
-  return launch_eval(d, batch, d_x, d_mass, d_env_tag, nullptr, nullptr, nullptr, d_out, nullptr, (hipStream_t)stream,
-                     true, &lg);
+  EvalCall c{d, batch, d_x, d_mass, d_env_tag, nullptr, nullptr, nullptr, d_out, nullptr, (hipStream_t)stream};
+  c.lg = &lg;
+  return launch_eval(c);
 }
 
 int32_t cpl_lagrangian_hessian(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_y,
@@ -3640,22 +3577,20 @@ int32_t cpl_lagrangian_hessian(const cpl_problem_desc* d, int64_t batch, const d
 int32_t cpl_eval_batch_ex(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
                           const uint8_t* d_env_tag, double* d_g, double* d_jac, double* d_f, double* d_grad,
                           double* d_norms, int32_t flags, void* stream) {
-  return launch_eval(d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, d_norms, (hipStream_t)stream, true,
-                     nullptr, flags);
+  return launch_eval(EvalCall{d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, d_norms, (hipStream_t)stream, flags});
 }
 
 int32_t cpl_eval_batch_norms(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
                              const uint8_t* d_env_tag, double* d_g, double* d_jac, double* d_f, double* d_grad,
                              double* d_norms, void* stream) {
   if (!d_norms) return fail(CPL_ERR_INVALID_ARGUMENT, "d_norms is required");
-  return launch_eval(d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, d_norms, (hipStream_t)stream);
+  return launch_eval(EvalCall{d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, d_norms, (hipStream_t)stream});
 }
 
 int32_t cpl_set_tuning(int32_t kernel_variant, int32_t tile_lds_kb, int32_t wg_threads, int32_t nt_stores,
-                       int32_t ablate) {
-  if (ablate < 0 || (ablate > 2 && (ablate & ~(4 | 8 | 16 | 32 | 64 | 128 | 256 | 512 | 1024 | 2048 | 4096 | 8192 | 16384))))
-    return fail(CPL_ERR_INVALID_ARGUMENT, "unknown ablation");
-  g_ablate = ablate;
+                       int32_t reserved /* the removed ablate field */) {
+  // (every argument checked before any is stored: a rejected call changes nothing)
+  if (reserved != 0) return fail(CPL_ERR_INVALID_ARGUMENT, "the fifth tuning argument is reserved and must be 0");
   if (kernel_variant < VAR_AUTO || kernel_variant > VAR_SPLIT_JD) return fail(CPL_ERR_INVALID_ARGUMENT, "unknown kernel variant");
   if (tile_lds_kb != 0 && (tile_lds_kb < 8 || tile_lds_kb > 160))
     return fail(CPL_ERR_INVALID_ARGUMENT, "LDS budget out of [8, 160] KiB");
@@ -3671,28 +3606,20 @@ int32_t cpl_residual_norms(const cpl_problem_desc* d, int64_t batch, const doubl
   int32_t st = validate_desc(d);
   if (st) return st;
   if (batch < 0 || !d_out || (batch > 0 && !d_g)) return fail(CPL_ERR_INVALID_ARGUMENT, "bad residual arguments");
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
-  if (dev < 0 || dev >= 64) return fail(CPL_ERR_UNSUPPORTED, "device index out of range");
-  double* ws;
-  {
-    std::lock_guard<std::mutex> lk(g_ws_mutex);
-    if (!g_ws[dev]) {
-      e = hipMalloc(&g_ws[dev], sizeof(double) * 2 * RN_GRID);
-      if (e != hipSuccess) return hip_fail(e, "hipMalloc residual workspace");
-    }
-    ws = g_ws[dev];
-  }
+  hipStream_t s = (hipStream_t)stream;
+  StreamCtx* C = nullptr;  // the partials are the stream's own: two streams never share them
+  if ((st = stream_ctx(s, &C))) return st;
+  if ((st = ctx_reserve(s, C->rn, RN_GRID, sizeof(double) * 2 * RN_GRID, "residual norms: the per-stream workspace")))
+    return st;
+  double* ws = static_cast<double*>(C->rn.ptr);
   const Dims D = dims_of(d->n_contacts, d->env_kind);
   const int64_t total = batch * D.m;
   int64_t blocks = (total + RN_BLOCK - 1) / RN_BLOCK;
   if (blocks < 1) blocks = 1;
   if (blocks > RN_GRID) blocks = RN_GRID;
-  hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(cpl_residual_partial, dim3((unsigned)blocks), dim3(RN_BLOCK), 0, s, total, D.m, D.contact_rows,
                      d_g, ws);
-  e = hipGetLastError();
+  hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "cpl_residual_partial launch");
   launch_residual_final((int)blocks, ws, d_out, s);
   e = hipGetLastError();
@@ -3718,12 +3645,12 @@ int32_t cpl_time_eval_batch_ex(const cpl_problem_desc* d, int64_t batch, const d
   e = hipEventCreate(&e1);
   if (e != hipSuccess) { (void)hipEventDestroy(e0); return hip_fail(e, "hipEventCreate"); }
   int32_t st = CPL_OK;
+  EvalCall c{d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, d_norms, s, flags};
+  c.finish = false;
   (void)hipEventRecord(e0, s);
   // back-to-back eval kernels (with the fused per-workgroup norms when d_norms != NULL; the
   // one-workgroup finish, a separate kernel, is left out of the timed launches)
-  for (int32_t r = 0; r < reps && st == CPL_OK; ++r)
-    st = launch_eval(d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, d_norms, s, /*finish=*/false, nullptr,
-                     flags);
+  for (int32_t r = 0; r < reps && st == CPL_OK; ++r) st = launch_eval(c);
   (void)hipEventRecord(e1, s);
   e = hipEventSynchronize(e1);
   if (st == CPL_OK && e != hipSuccess) st = hip_fail(e, "hipEventSynchronize");
@@ -3736,8 +3663,8 @@ int32_t cpl_time_eval_batch_ex(const cpl_problem_desc* d, int64_t batch, const d
   (void)hipEventDestroy(e1);
   if (st == CPL_OK) *ms_per_launch = (double)ms / reps;
   // leave d_norms valid for the caller
-  if (st == CPL_OK && d_norms)
-    st = launch_eval(d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, d_norms, s, true, nullptr, flags);
+  c.finish = true;
+  if (st == CPL_OK && d_norms) st = launch_eval(c);
   return st;
 }
 

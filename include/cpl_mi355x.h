@@ -158,7 +158,9 @@ int32_t cpl_eval_batch(const cpl_problem_desc* d, int64_t batch, const double* d
  * Per-shard residual norms of g against the constraint bounds (the per-shard figure the
  * multi-GPU path all-gathers): d_out[0] = max_b max_r viol(b,r), d_out[1] = sum_b sum_r viol^2,
  * where viol = max(g_l - g, g - g_u, 0) and NaN counts as +inf.  d_g is [batch*m] from
- * cpl_eval_batch.  Device output, 2 doubles.  Asynchronous on `stream`.
+ * cpl_eval_batch.  Device output, 2 doubles.  Asynchronous on `stream`.  The partials live in a
+ * workspace of that stream's own (allocated by the first call on it, which therefore cannot be
+ * inside a stream capture).
  */
 int32_t cpl_residual_norms(const cpl_problem_desc* d, int64_t batch, const double* d_g,
                            double* d_out, void* stream);
@@ -234,18 +236,13 @@ int32_t cpl_time_eval_batch_ex(const cpl_problem_desc* d, int64_t batch, const d
  * tile_lds_kb = LDS budget of one workgroup (8..160 KiB; 0 = per-kernel
  * default: 48 KiB for both: the largest power-of-two tile that fits, e.g. 8 instances of 8
  * Superquadric contacts, 4 of 16); wg_threads = 128 or 256 for the tile kernel (default 256);
- * nt_stores = non-temporal output stores (default 1); ablate = measurement-only ablation
- * (0 = off, 1 = skip the compute phase, 2 = skip the output stores: results are then garbage; for
- * the kind split, bits 4 = its halves one after the other on one stream, 8 = the Ground half issued
- * first, 16 / 64 / 128 = the Ground list at 48 / 36 / 32 KiB instead of 40, 32 = the Superquadric tiles
- * at 40 KiB instead of 48, 256 / 512 = every Ground workgroup walking the tiles / two per CU instead of
- * one per CU while the Superquadric list is non-empty, 1024 / 2048 = the Ground half's compute waves at
- * wave priority 1 / 2, 4096 = the 4-instance Superquadric list tiles' gather / copy-out at the default
- * priority, 16384 = the Superquadric grid for half the batch (correct only when at most half the
- * instances are Superquadric); for the tile kernel, 8192 = its phase barriers skipped: garbage results).
- * Every variant computes bit-identical results.  Not thread-safe against concurrent launches. */
+ * nt_stores = non-temporal output stores (default 1); reserved = must be 0 (it selected
+ * measurement-only ablations of the kernels, since removed).
+ * Every variant computes bit-identical results.  An argument out of range returns
+ * CPL_ERR_INVALID_ARGUMENT and leaves every setting as it was.  Not thread-safe against concurrent
+ * launches. */
 int32_t cpl_set_tuning(int32_t kernel_variant, int32_t tile_lds_kb, int32_t wg_threads, int32_t nt_stores,
-                       int32_t ablate);
+                       int32_t reserved);
 
 /* ---- host-buffer entry points ------------------------------------------------------------ */
 /*

@@ -51,6 +51,8 @@ flags = (_abi.EVAL_JAC_FOLDED if args.folded else 0) | (_abi.EVAL_SOA if args.so
 stream = torch.cuda.current_stream()
 norms = torch.zeros(2, dtype=torch.float64, device=xt.device) if args.norms else None
 variants = [tuple(int(v) for v in s.split(":")) for s in args.variants.split(",")]
+if any(len(v) != 4 for v in variants):
+    ap.error("--variants: each entry is variant:lds_kb:wg:nt")
 times = {v: [] for v in variants}
 
 
@@ -60,7 +62,7 @@ def p(t):
 
 for _ in range(args.rounds):
     for v in variants:
-        _abi.check(_abi.lib.cpl_set_tuning(v[0], v[1], v[2], v[3], v[4] if len(v) > 4 else 0))
+        _abi.check(_abi.lib.cpl_set_tuning(*v, 0))
         ms = ctypes.c_double()
         _abi.check(_abi.lib.cpl_time_eval_batch_ex(ctypes.byref(prob.desc()), B, p(xt), p(mt), p(tt), p(out.get("g")),
                                                    p(out.get("jac")), p(out.get("f")), p(out.get("grad")), p(norms),
@@ -72,6 +74,6 @@ if args.folded and "jac" in outs:
     bpi -= 8 * (prob.nnz - out["jac"].shape[1 if not args.soa else 0])
 for v, ts in times.items():
     med = statistics.median(ts)
-    print(json.dumps({"config": args.config, "batch": B, "folded": args.folded, "soa": args.soa, "variant": v[0], "lds_kb": v[1], "wg": v[2], "nt": v[3], "ablate": v[4] if len(v) > 4 else 0, "median_ms": med,
+    print(json.dumps({"config": args.config, "batch": B, "folded": args.folded, "soa": args.soa, "variant": v[0], "lds_kb": v[1], "wg": v[2], "nt": v[3], "median_ms": med,
                       "min_ms": min(ts), "GBps": bpi * B / (med * 1e-3) / 1e9,
                       "rows_per_s": B * m / (med * 1e-3)}), flush=True)

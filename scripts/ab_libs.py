@@ -40,8 +40,10 @@ for tag in args.libs.split(","):
         fn.restype, fn.argtypes = res, sig
     if args.tuning:
         v = [int(t) for t in args.tuning.split(":")]
+        if len(v) != 4:
+            ap.error("--tuning is variant:lds_kb:wg:nt")
         lib.cpl_set_tuning.restype = ctypes.c_int32
-        _abi.check(lib.cpl_set_tuning(*[ctypes.c_int32(t) for t in (v + [0] * (5 - len(v)))]))
+        _abi.check(lib.cpl_set_tuning(*[ctypes.c_int32(t) for t in v + [0]]))
     libs[tag] = lib
 
 cfg = CONFIGS[args.config]

@@ -9,8 +9,9 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 AB="python3 -u scripts/ab_kernels.py"
 (cd /tmp && timeout -k 10 60 rocprofv3 -L) > "$out/counters_avail.txt" 2>&1
-# 0 = default split, 4 = halves one after the other on one stream, 256 = Ground walkers uncapped
-timeout -k 10 300 $AB --config mixed16 --rounds 3 --reps 10 --variants 0:0:256:1,0:0:256:1:4,0:0:256:1:256 > "$out/mixed16.jsonl" || exit $?
+# the default split (the sequential-halves and uncapped-walker runs used ablation bits since removed;
+# their figures: profiles/r6/split/)
+timeout -k 10 300 $AB --config mixed16 --rounds 3 --reps 10 --variants 0:0:256:1 > "$out/mixed16.jsonl" || exit $?
 timeout -k 10 200 $AB --config mixed16 --batch 524288 --tags all_sq --rounds 3 --reps 10 --variants 0:0:256:1 > "$out/list_sq_524k.jsonl" || exit $?
 timeout -k 10 200 $AB --config mixed16 --batch 524288 --tags all_ground --rounds 3 --reps 10 --variants 0:0:256:1 > "$out/list_ground_524k.jsonl" || exit $?
 timeout -k 10 200 $AB --config sq16 --rounds 3 --reps 10 --variants 0:0:256:1 > "$out/sq16.jsonl" || exit $?

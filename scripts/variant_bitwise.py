@@ -1,7 +1,7 @@
 """Eval-kernel variants (cpl_set_tuning) against the default on the same inputs: bitwise equality of g
 and the Jacobian values (NaN positions included), for a mixed batch with random tags and the two
 one-kind batches.  GPU box; one JSON line per (config, variant).
-    python scripts/variant_bitwise.py --config mixed16 --batch 20011 --variants 6:0:256:1,0:0:256:1:1024"""
+    python scripts/variant_bitwise.py --config mixed16 --batch 20011 --variants 6:0:256:1,7:0:256:0"""
 import argparse
 import ctypes
 import json
@@ -28,7 +28,7 @@ p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: 
 def run(prob, xt, mt, tt, v):
     n, m, nnz = prob.get_nlp_info()
     B = xt.shape[0]
-    _abi.check(_abi.lib.cpl_set_tuning(v[0], v[1], v[2], v[3], v[4] if len(v) > 4 else 0))
+    _abi.check(_abi.lib.cpl_set_tuning(*v, 0))
     g = torch.full((B, m), -7.0, dtype=torch.float64, device=dev)
     j = torch.full((B, nnz), -7.0, dtype=torch.float64, device=dev)
     _abi.check(_abi.lib.cpl_eval_batch(ctypes.byref(prob.desc()), B, p(xt), p(mt), p(tt), p(g), p(j), None, None, None))
@@ -51,9 +51,11 @@ ok_all = True
 for name, (xc, tc) in cases.items():
     xt, mt = torch.tensor(xc, device=dev), torch.tensor(mass, device=dev)
     tt = None if tc is None else torch.tensor(tc, device=dev)
-    ref = run(prob, xt, mt, tt, (0, 0, 256, 1, 0))
+    ref = run(prob, xt, mt, tt, (0, 0, 256, 1))
     for s in args.variants.split(","):
         v = tuple(int(q) for q in s.split(":"))
+        if len(v) != 4:
+            ap.error("--variants: each entry is variant:lds_kb:wg:nt")
         got = run(prob, xt, mt, tt, v)
         eq = same(ref[0], got[0]) and same(ref[1], got[1])
         ok_all &= eq

@@ -152,3 +152,45 @@ def test_mixed_default_split_under_graph_capture():
         s.synchronize()
         for k in ("g", "jac"):
             assert torch.equal(_bits(out[k]), _bits(ref[k])), (warm, k)
+
+
+@pytest.mark.gpu
+def test_mixed_split_workspaces_grow_after_capture():
+    """A graph captured on a stream keeps the stream's workspaces as it saw them: a later, larger eager
+    launch on the same stream (6 000 instances: kind lists past the 1 000 captured, 6 000-odd norm
+    partials past the 4 096-pair minimum) grows both without freeing the captured buffers, so the
+    replayed graph still gives the first launch's g, jac and norms bit for bit, and the larger launch
+    equals the oracle."""
+    N, B1, B2 = 16, 1000, 6000
+    prob = make_problem(N, "mixed")
+    x, mass, tag = generate(N, "mixed", B2, 4242 + N)  # (alternating tags)
+    assert tag[:4].tolist() in ([1, 2, 1, 2], [2, 1, 2, 1])
+    x2, _, _ = generate(N, "superquadric", B2, 4242 + N)  # Superquadric instances need points near the surface
+    x = np.where((tag == 2)[:, None], x2, x)
+    dev = torch.device("cuda:0")
+    xt, mt, tt = torch.tensor(x, device=dev), torch.tensor(mass, device=dev), torch.tensor(tag, device=dev)
+    small = (xt[:B1].contiguous(), mt[:B1].contiguous(), tt[:B1].contiguous())
+    outs = ("g", "jac", "norms")
+    s = torch.cuda.Stream(dev)
+    with torch.cuda.stream(s):
+        first = prob.eval_batch(*small, outputs=outs, stream=s)
+        s.synchronize()
+        first = {k: v.clone() for k, v in first.items()}
+        out = {k: torch.zeros_like(v) for k, v in first.items()}
+        s.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr, stream=s):
+            prob.eval_batch(*small, outputs=outs, out=out, stream=s)
+        big = prob.eval_batch(xt, mt, tt, outputs=outs, stream=s)
+        gr.replay()
+    s.synchronize()
+    for k in outs:
+        assert torch.equal(_bits(out[k]), _bits(first[k])), k
+    orc = pyoracle.eval_batch(prob.desc(), x, mass, tag, outputs=("g", "jac"))
+    got = {k: big[k].cpu().numpy() for k in ("g", "jac")}
+    check_outputs(prob, "mixed", x, got, orc, tag)
+    _, _, gl, gu = prob.get_bounds_info()
+    viol = np.maximum(np.maximum(gl - got["g"], got["g"] - gu), 0.0)
+    rn = big["norms"].cpu().numpy()
+    assert rn[0] == viol.max()
+    assert abs(rn[1] - (viol ** 2).sum()) <= 1e-12 * (viol ** 2).sum()  # (the fused norms' bound, test_gpu_parity)

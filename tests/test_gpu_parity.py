@@ -162,6 +162,31 @@ def test_residual_norms_match_host():
     assert abs(rn[1] - (viol ** 2).sum()) <= 1e-9 * (viol ** 2).sum()
 
 
+def test_residual_norms_two_streams():
+    """cpl_residual_norms keeps its partials per stream: two different g arrays (~10^6 entries each)
+    reduced alternately on two streams, 20 times, give each array's solo norms bit for bit every time.
+    With one workspace per device the two streams' partials could overwrite each other; that is a
+    race, so a tree with the shared workspace may also pass this by luck."""
+    from centroidalplanner_amd.workload import generate, make_problem
+
+    prob = make_problem(4, "ground")
+    dev = torch.device("cuda:0")
+    B = 33401
+    gs, solo = [], []
+    for seed in (3, 4):
+        x, mass, _ = generate(4, "ground", B, seed)
+        g = prob.eval_batch(torch.tensor(x, device=dev), torch.tensor(mass, device=dev), outputs=("g",))["g"]
+        gs.append(g)
+        solo.append(prob.residual_norms(g))
+    torch.cuda.synchronize()
+    assert not torch.equal(solo[0], solo[1])
+    streams = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]
+    got = [(i, prob.residual_norms(gs[i], stream=streams[i])) for _ in range(20) for i in (0, 1)]
+    torch.cuda.synchronize()
+    for i, rn in got:
+        assert torch.equal(rn.view(torch.int64), solo[i].view(torch.int64)), i
+
+
 @pytest.mark.parametrize("variant,lds_kb,wg,nt", [(1, 64, 256, 0), (3, 16, 128, 1), (3, 160, 256, 0), (3, 8, 128, 0),
                                                   (2, 32, 256, 1), (2, 64, 256, 0), (2, 8, 256, 1), (0, 0, 256, 1)])
 @pytest.mark.parametrize("env,N", [("ground", 4), ("superquadric", 8), ("mixed", 16), ("none", 3)])
@@ -178,6 +203,25 @@ def test_parity_kernel_variants(variant, lds_kb, wg, nt, env, N):
     finally:
         _abi.check(_abi.lib.cpl_set_tuning(0, 0, 256, 1, 0))
     _check(prob, env, x, got, ref, tag)
+
+
+def test_rejected_tuning_calls_change_nothing():
+    """cpl_set_tuning rejects a non-zero fifth (reserved) argument and an unknown variant with the
+    invalid-argument status, and a rejected call leaves every setting as it was: the default mixed and
+    Ground launches after it still equal the oracle."""
+    from centroidalplanner_amd import _abi
+    from centroidalplanner_amd.workload import generate, make_problem
+
+    cases = [(env, N, make_problem(N, env), generate(N, env, 333, 77 + N)) for env, N in (("mixed", 16), ("ground", 4))]
+    rejected = [(0, 0, 256, 1, k) for k in (1, 2, 4, 8192)] + [(8, 0, 256, 1, 0), (-1, 16, 128, 0, 0)]
+    try:
+        for args in rejected:
+            assert _abi.lib.cpl_set_tuning(*args) == _abi.ERR_INVALID_ARGUMENT, args
+            for env, N, prob, (x, mass, tag) in cases:
+                got, ref = _run(prob, x, mass, tag)
+                _check(prob, env, x, got, ref, tag)
+    finally:
+        _abi.check(_abi.lib.cpl_set_tuning(0, 0, 256, 1, 0))
 
 
 @pytest.mark.parametrize("env,N,B", [("ground", 4, 100003), ("superquadric", 8, 40001), ("mixed", 16, 20011)])
