@@ -114,6 +114,7 @@ class DerivativeReport(ctypes.Structure):
 HESSIAN_EXACT = 0
 HESSIAN_LIMITED_MEMORY = 1
 HESSIAN_FD = 2
+HESSIAN_ANALYTIC = 3
 
 # every symbol include/cpl_mi355x.h declares, with its ctypes signature
 _DESC_P = POINTER(ProblemDesc)
@@ -170,6 +171,8 @@ SIGNATURES = {
     "cpl_kkt_workspace_doubles": (c_int64, [c_int32, c_int32]),
     "cpl_lagrangian_hessian": (c_int32, [_DESC_P, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
                                          c_void_p]),
+    "cpl_lagrangian_hessian_ex": (c_int32, [_DESC_P, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                            c_void_p, c_void_p]),
     "cpl_eval_lagrangian_grad": (
         c_int32,
         [_DESC_P, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,

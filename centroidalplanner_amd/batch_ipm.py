@@ -143,6 +143,26 @@ class KernelEvaluator:
         self.calls += 1
         return out
 
+    def hessian(self, X, y, free, zero_cost=False):
+        """The analytic Hessian of f + y^T g over the variables `free` of every instance, [B, nf, nf]
+        (cpl_lagrangian_hessian_ex: every environment kind); zero_cost: of y^T g alone."""
+        import torch
+
+        desc = self.problem.desc()
+        if zero_cost:
+            desc = type(desc).from_buffer_copy(desc)  # (desc() is the problem's own record)
+            desc.W_com = 0.0
+            for i in range(len(desc.W_p)):
+                desc.W_p[i] = desc.W_F[i] = 0.0
+        X, y = X.contiguous(), y.contiguous()
+        fi = free.to(torch.int32).contiguous()
+        nf = int(fi.numel())
+        H = torch.empty(X.shape[0], nf, nf, dtype=torch.float64, device=X.device)
+        _abi.check(_abi.lib.cpl_lagrangian_hessian_ex(
+            ctypes.byref(desc), X.shape[0], _ptr(X), _ptr(y), None if self.env_tag is None else _ptr(self.env_tag), None,
+            _ptr(fi), nf, _ptr(H), ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)))
+        return H
+
 
 @dataclass
 class BatchSolveResult:
@@ -183,7 +203,7 @@ class NativeSolver:
         o.max_iter, o.max_ls, o.max_soc, o.acceptable_iter = int(max_iter), int(max_ls), int(max_soc), int(acceptable_iter)
         o.tol, o.acceptable_tol, o.mu_init, o.fd_step = float(tol), float(acceptable_tol), float(mu_init), float(fd_step)
         o.hessian = {"exact": _abi.HESSIAN_EXACT, "limited-memory": _abi.HESSIAN_LIMITED_MEMORY,
-                     "fd": _abi.HESSIAN_FD}[hessian]
+                     "fd": _abi.HESSIAN_FD, "analytic": _abi.HESSIAN_ANALYTIC}[hessian]
         o.use_graph = 1 if graph else 0
         o.compact = 1 if compact else 0
         o.ls_kernel = int(ls_kernel)
@@ -287,8 +307,12 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
     "g" [B, m], "jac" [B, nnz], on X's device; default KernelEvaluator(problem) (the HIP kernel).
     hessian: "exact" (the analytic Lagrangian Hessian, cpl_lagrangian_hessian, for Ground /
     no-environment problems on the device; batched central differences of the Lagrangian gradient
-    otherwise), "fd" (always the central differences) or "limited-memory"
-    (IPOPT's L-BFGS, 6 pairs).  graph: capture one iteration as a HIP graph (default: on for device tensors).
+    otherwise), "fd" (always the central differences), "limited-memory" (IPOPT's L-BFGS, 6 pairs) or
+    "analytic" (the analytic Hessian for every environment kind, cpl_lagrangian_hessian_ex: bitwise
+    "exact" on Ground / no-environment templates, the Superquadric contacts' closed-form p x p blocks
+    instead of "exact"'s central differences on Superquadric / mixed ones; the host restatement takes
+    the evaluator's `hessian(X, y, free, zero_cost)` and raises ValueError when it has none or it
+    returns None for the template).  graph: capture one iteration as a HIP graph (default: on for device tensors).
     max_ls / max_soc: at most this many backtracking trials per iteration (the search also stops below
     IPOPT's alpha_min) / second-order corrections on the first trial (IPOPT max_soc 4).
     ls_kernel (device engine): the whole line search (first trial, its corrections, backtracking) in
@@ -318,8 +342,8 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
     step judged against the kept iterate's references, a success ends it, the (trial_max + 1)-th failure
     restores the kept iterate and backtracks along its step from alpha_max / 2; a barrier change or the
     restoration phase ends it."""
-    if hessian not in ("exact", "fd", "limited-memory"):
-        raise ValueError("hessian must be 'exact', 'fd' or 'limited-memory'")
+    if hessian not in ("exact", "fd", "limited-memory", "analytic"):
+        raise ValueError("hessian must be 'exact', 'fd', 'limited-memory' or 'analytic'")
     if nlp_scaling not in ("gradient-based", "none"):
         raise ValueError("nlp_scaling must be 'gradient-based' or 'none'")
     if jacobian_regularization not in ("ipopt", "pivot"):
@@ -349,6 +373,8 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
     # of the device path over any evaluator's callbacks (tests drive it with the oracle's)
     ev = evaluator if evaluator is not None else KernelEvaluator(problem)
     dev, dt = X0.device, torch.float64
+    if hessian == "analytic" and not hasattr(ev, "hessian"):
+        raise ValueError("hessian='analytic': the evaluator has no hessian(X, y, free, zero_cost)")
     if graph:
         raise ValueError("graph capture needs device tensors")
     B = X0.shape[0]
@@ -502,11 +528,13 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
         one (hessian="exact"), else central differences; constraints_only: of y^T g alone (the
         restoration phase: its objective's curvature is the proximity term, added by the caller)."""
         Xc = unpack(wv)
-        if hessian == "exact" and hasattr(ev, "hessian"):
+        if hessian in ("exact", "analytic") and hasattr(ev, "hessian"):
             yr = y_raw(yv)
             Hb = ev.hessian(Xc, yr, free, zero_cost=True) if constraints_only else ev.hessian(Xc, yr, free)
             if Hb is not None:
                 return Hb * df[:, None, None] if scaled else Hb
+            if hessian == "analytic":
+                raise ValueError("hessian='analytic': the evaluator's hessian returned None for this template")
         return fd_hessian(Xc, yv, with_grad=not constraints_only)
 
     def chol_inertia(K, dwl, mask):

@@ -2388,28 +2388,95 @@ __device__ __forceinline__ double hessian_entry(const KParams& K, const double* 
   return h;
 }
 
+// Superquadric contacts (SQ instantiation; cpl_lagrangian_hessian_ex): the environment row S(p) - 1
+// (multiplier y_e) and the three normal rows n + nu(p) (multipliers y_k) are linear in everything
+// but p, so they add one 3 x 3 block per contact, on p_i x p_i.  With d_a = p_a - C_a,
+//   e_a = EJ_a d_a^(P_a-1), h_a = (P_a-1) EJ_a d_a^(P_a-2), t_a = (P_a-1)(P_a-2) EJ_a d_a^(P_a-3)
+//   (EJ_a = P_a / R_a^P_a, the eval kernels' host-computed factor; t_a exactly 0 at P_a == 2),
+//   r = |e|, nu = e / r, M_ka = delta_ka - nu_k nu_a, D_ka = M_ka h_a / r (the normal Jacobian),
+//   H[a][b] += delta_ab y_e h_a + sum_k y_k [ delta_ab M_ka t_a / r - (D_kb nu_a + nu_k D_ab) h_a / r
+//                                            - M_ka h_a nu_b h_b / r^2 ].
+// sq_axis_terms: one (contact, axis) lane's e, h, t; sq_pair_entry: one (contact, a <= b) lane's
+// entry, mirrored by the caller (the bracket is symmetric analytically, not in floating point).
+__device__ __forceinline__ void sq_axis_terms(const KParams& K, int a, double pa, double* __restrict__ o) {
+  const double d = -axv<false>(K, AX_C, a) + pa;
+  const double P = axv<false>(K, AX_P, a), Pm1 = axv<false>(K, AX_PM1, a), EJ = axv<false>(K, AX_EJ, a);
+  o[0] = EJ * cpow(d, Pm1);
+  o[1] = (EJ * Pm1) * cpow(d, P - 2.0);
+  o[2] = P == 2.0 ? 0.0 : ((EJ * Pm1) * (P - 2.0)) * cpow(d, P - 3.0);
+}
+__device__ __forceinline__ double sq_pair_entry(const double* __restrict__ ax, const double* __restrict__ ye, int a,
+                                                int b) {
+  const double e[3] = {ax[0], ax[3], ax[6]}, h[3] = {ax[1], ax[4], ax[7]};
+  const double r = sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+  if (!(r > 0.0 && r < INFINITY)) return NAN;  // (a degenerate contact: the caller drops the block)
+  const double nu[3] = {e[0] / r, e[1] / r, e[2] / r};
+  auto M = [&](int k, int c) { return (k == c ? 1.0 : 0.0) - nu[k] * nu[c]; };
+  auto D = [&](int k, int c) { return M(k, c) * h[c] / r; };
+  double v = a == b ? ye[0] * h[a] : 0.0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    double term = a == b ? M(k, a) * ax[3 * a + 2] / r : 0.0;
+    term -= (D(k, b) * nu[a] + nu[k] * D(a, b)) * h[a] / r;
+    term -= M(k, a) * h[a] * nu[b] * h[b] / (r * r);
+    v += ye[1 + k] * term;
+  }
+  return v;
+}
+
+// SQ: the Superquadric part compiled in (Superquadric / mixed templates); the Ground /
+// no-environment instantiation carries none of it.
+template <bool SQ>
 __global__ __launch_bounds__(256) void cpl_lagrangian_hessian_kernel(const KParams K, int64_t batch, int nf,
                                                                      const double* __restrict__ x,
                                                                      const double* __restrict__ y,
+                                                                     const uint8_t* __restrict__ env_tag,
                                                                      const uint8_t* __restrict__ active,
                                                                      const int32_t* __restrict__ free_idx,
                                                                      double* __restrict__ H) {
   __shared__ int s_pos[CPL_MAX_CONTACTS];          // block position (map order) of contact i
   __shared__ double s_cone[CPL_MAX_CONTACTS * 36];  // (F, n) x (F, n) entries of contact i
   __shared__ int s_col[3 + 9 * CPL_MAX_CONTACTS];   // free index -> column of x
+  __shared__ double s_ax[SQ ? CPL_MAX_CONTACTS * 9 : 1];  // (SQ) e, h, t of (contact i, axis a)
+  __shared__ double s_sq[SQ ? CPL_MAX_CONTACTS * 9 : 1];  // (SQ) the p x p block of contact i
+  __shared__ int s_sqok[SQ ? CPL_MAX_CONTACTS : 1];       // (SQ) every entry of the block is finite
   const int64_t b = blockIdx.x;
   if (b >= batch || (active && !active[b])) return;  // (uniform per workgroup)
   const int tid = threadIdx.x;
   if (tid < K.N) s_pos[K.map_order[tid]] = tid;
   for (int k = tid; k < nf; k += blockDim.x) s_col[k] = free_idx[k];
-  __syncthreads();
   const double* xb = x + b * (int64_t)K.n;
   const double* yb = y + b * (int64_t)K.m;
+  // (uniform per workgroup) this instance's contacts are Superquadric ones
+  const bool sq = SQ && (K.env_kind == CPL_ENV_SUPERQUADRIC || env_tag[b] == CPL_ENV_SUPERQUADRIC);
+  if (SQ && sq) {
+    for (int t = tid; t < 3 * K.N; t += blockDim.x) {
+      const int i = t / 3, a = t - 3 * i;
+      sq_axis_terms(K, a, xb[6 + 9 * i + a], s_ax + 3 * t);
+    }
+  }
+  __syncthreads();
   // (F, n) x (F, n) blocks: local index 0-2 F_a (column 3 + 9i + a), 3-5 n_a (column 9 + 9i + a)
   for (int t = tid; t < 36 * K.N; t += blockDim.x) {
     const int i = t / 36, r = t - 36 * i, u6 = r / 6, v6 = r - 6 * (r / 6);
     const int uu = 3 + 9 * i + (u6 < 3 ? u6 : 3 + u6), vv = 3 + 9 * i + (v6 < 3 ? v6 : 3 + v6);
     s_cone[t] = hessian_entry(K, xb, yb, s_pos, uu, vv);
+  }
+  if (SQ && sq) {
+    // the pairs a <= b of contact i: 0 (0,0), 1 (0,1), 2 (0,2), 3 (1,1), 4 (1,2), 5 (2,2)
+    for (int t = tid; t < 6 * K.N; t += blockDim.x) {
+      const int i = t / 6, q = t - 6 * i;
+      const int a = q < 3 ? 0 : (q < 5 ? 1 : 2), c = q < 3 ? q : (q < 5 ? q - 2 : 2);
+      const double v = sq_pair_entry(s_ax + 9 * i, yb + 6 + 6 * s_pos[i], a, c);
+      s_sq[9 * i + 3 * a + c] = v;
+      s_sq[9 * i + 3 * c + a] = v;
+    }
+    __syncthreads();
+    if (tid < K.N) {
+      bool ok = true;
+      for (int q = 0; q < 9; ++q) ok = ok && fabs(s_sq[9 * tid + q]) < INFINITY;
+      s_sqok[tid] = ok ? 1 : 0;
+    }
   }
   __syncthreads();
   double* Hb = H + b * (int64_t)nf * nf;
@@ -2425,6 +2492,8 @@ __global__ __launch_bounds__(256) void cpl_lagrangian_hessian_kernel(const KPara
       h = s_cone[36 * iu + 6 * (tu < 3 ? tu : tu - 3) + (tv < 3 ? tv : tv - 3)];
     else
       h = hessian_entry(K, xb, yb, s_pos, uu, vv);
+    if (SQ && sq && uu >= 3 && vv >= 3 && iu == iv && tu >= 3 && tu < 6 && tv >= 3 && tv < 6 && s_sqok[iu])
+      h += s_sq[9 * iu + 3 * (tu - 3) + (tv - 3)];
     Hb[e] = h;
     row += step_r;
     col += step_c;
@@ -3554,6 +3623,26 @@ int32_t cpl_eval_lagrangian_grad(const cpl_problem_desc* d, int64_t batch, const
   return launch_eval(c);
 }
 
+static int32_t launch_hessian(const char* who, const cpl_problem_desc* d, int64_t batch, const double* d_x,
+                              const double* d_y, const uint8_t* d_env_tag, const uint8_t* d_active,
+                              const int32_t* d_free_idx, int32_t nf, double* d_H, void* stream) {
+  const std::string w(who);
+  KParams K;
+  fill_params(d, K, d_x);
+  if (batch < 0 || nf <= 0 || nf > K.n) return fail(CPL_ERR_INVALID_ARGUMENT, w + ": bad sizes");
+  if (batch == 0) return CPL_OK;
+  if (!d_x || !d_y || !d_free_idx || !d_H) return fail(CPL_ERR_INVALID_ARGUMENT, w + ": missing buffer");
+  if (d->env_kind == CPL_ENV_MIXED && !d_env_tag) return fail(CPL_ERR_INVALID_ARGUMENT, w + ": mixed needs tags");
+  if (batch > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, w + ": batch too large");
+  const bool sq = d->env_kind == CPL_ENV_SUPERQUADRIC || d->env_kind == CPL_ENV_MIXED;
+  hipLaunchKernelGGL(sq ? cpl_lagrangian_hessian_kernel<true> : cpl_lagrangian_hessian_kernel<false>,
+                     dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, K, batch, (int)nf, d_x, d_y, d_env_tag,
+                     d_active, d_free_idx, d_H);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, (w + " launch").c_str());
+  return CPL_OK;
+}
+
 int32_t cpl_lagrangian_hessian(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_y,
                                const uint8_t* d_active, const int32_t* d_free_idx, int32_t nf, double* d_H,
                                void* stream) {
@@ -3561,17 +3650,16 @@ int32_t cpl_lagrangian_hessian(const cpl_problem_desc* d, int64_t batch, const d
   if (st) return st;
   if (d->env_kind != CPL_ENV_GROUND && d->env_kind != CPL_ENV_NONE)
     return fail(CPL_ERR_UNSUPPORTED, "cpl_lagrangian_hessian: Ground / no-environment problems only");
-  KParams K;
-  fill_params(d, K, d_x);
-  if (batch < 0 || nf <= 0 || nf > K.n) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_lagrangian_hessian: bad sizes");
-  if (batch == 0) return CPL_OK;
-  if (!d_x || !d_y || !d_free_idx || !d_H) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_lagrangian_hessian: missing buffer");
-  if (batch > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_lagrangian_hessian: batch too large");
-  hipLaunchKernelGGL(cpl_lagrangian_hessian_kernel, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, K, batch,
-                     (int)nf, d_x, d_y, d_active, d_free_idx, d_H);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return hip_fail(e, "cpl_lagrangian_hessian launch");
-  return CPL_OK;
+  return launch_hessian("cpl_lagrangian_hessian", d, batch, d_x, d_y, nullptr, d_active, d_free_idx, nf, d_H, stream);
+}
+
+int32_t cpl_lagrangian_hessian_ex(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_y,
+                                  const uint8_t* d_env_tag, const uint8_t* d_active, const int32_t* d_free_idx,
+                                  int32_t nf, double* d_H, void* stream) {
+  int32_t st = validate_desc(d);
+  if (st) return st;
+  return launch_hessian("cpl_lagrangian_hessian_ex", d, batch, d_x, d_y, d_env_tag, d_active, d_free_idx, nf, d_H,
+                        stream);
 }
 
 int32_t cpl_eval_batch_ex(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,

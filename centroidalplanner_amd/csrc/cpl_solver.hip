@@ -5,7 +5,8 @@
 // — whose host path (CPU tensors, the oracle's callbacks) is the checker of this engine — with every
 // per-instance quantity a row of a device buffer:
 //   * callbacks: cpl_eval_batch(_ex) (values-only Jacobian records), the analytic Lagrangian Hessian
-//     (cpl_lagrangian_hessian) or central differences (cpl_ipm_fd_points + cpl_eval_lagrangian_grad
+//     (cpl_lagrangian_hessian; cpl_lagrangian_hessian_ex under CPL_HESSIAN_ANALYTIC, every
+//     environment kind) or central differences (cpl_ipm_fd_points + cpl_eval_lagrangian_grad
 //     + cpl_ipm_fd_hessian_raw), or IPOPT's limited-memory BFGS model (6 pairs, scalar1; IFOPT's
 //     IpoptSolver default, the reference's configuration, src/CentroidalPlanner.cpp:22-29);
 //   * per-instance iteration work: cpl_ipm_optimality / newton_setup / post_step / trial_point /
@@ -2387,7 +2388,10 @@ int32_t hessian_into(cpl_solver* S, const cpl_problem_desc* d, const uint8_t* ma
     return CPL_OK;
   };
   if (S->analytic_H) {
-    CK(cpl_lagrangian_hessian(d, B, S->X, yh, mask, S->free32, nf, S->H, st));
+    if (o.hessian == CPL_HESSIAN_ANALYTIC)  // every environment kind (Ground / none: the same kernel)
+      CK(cpl_lagrangian_hessian_ex(d, B, S->X, yh, S->tag, mask, S->free32, nf, S->H, st));
+    else
+      CK(cpl_lagrangian_hessian(d, B, S->X, yh, mask, S->free32, nf, S->H, st));
     CK(scale_H());
     *Hblk = S->H;
     return CPL_OK;
@@ -3093,7 +3097,7 @@ int32_t cpl_solver_create(const cpl_problem_desc* d, int64_t batch, const cpl_so
   cpl_solve_options opt;
   cpl_solve_options_default(&opt);
   if (o) opt = *o;
-  if (opt.hessian < CPL_HESSIAN_EXACT || opt.hessian > CPL_HESSIAN_FD || opt.max_iter < 0 || opt.max_soc < 0 ||
+  if (opt.hessian < CPL_HESSIAN_EXACT || opt.hessian > CPL_HESSIAN_ANALYTIC || opt.max_iter < 0 || opt.max_soc < 0 ||
       opt.max_ls < 0 || !(opt.tol > 0.0) || opt.ls_kernel < 0 || opt.ls_kernel > 2 || opt.nlp_scaling < 0 ||
       opt.nlp_scaling > 1 || opt.jacobian_regularization < 0 || opt.jacobian_regularization > 1)
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_create: bad options");
@@ -3200,6 +3204,9 @@ int32_t cpl_solver_create(const cpl_problem_desc* d, int64_t batch, const cpl_so
   S->bfgs = opt.hessian == CPL_HESSIAN_LIMITED_MEMORY;
   S->analytic_H = opt.hessian == CPL_HESSIAN_EXACT && cpl_lagrangian_hessian(d, 0, nullptr, nullptr, nullptr, nullptr,
                                                                              nf > 0 ? nf : 1, nullptr, nullptr) == CPL_OK;
+  if (opt.hessian == CPL_HESSIAN_ANALYTIC)  // (the _ex entry supports every environment kind)
+    S->analytic_H = cpl_lagrangian_hessian_ex(d, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nf > 0 ? nf : 1,
+                                              nullptr, nullptr) == CPL_OK;
   S->fd = !S->bfgs && !S->analytic_H;
   auto bad = [&](hipError_t e, const char* what) {
     cpl_solver_destroy(S);

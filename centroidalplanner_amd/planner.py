@@ -96,7 +96,7 @@ class CentroidalPlanner:
         # IFOPT's IpoptSolver defaults the reference runs with (src/CentroidalPlanner.cpp:22-29)
         self.solver_tol = 1e-8
         self.solver_max_iter = 3000
-        self.solver_hessian = "limited-memory"
+        self.solver_hessian = "limited-memory"  # or "exact" / "analytic" (solver.solve's option)
         # a rank-deficient constraint Jacobian: "pivot" (the engine's default, delta_c on R's small
         # pivots) or "ipopt" (IPOPT's (2,2)-block regularisation, cpl_solve_options.jacobian_regularization)
         self.solver_jacobian_regularization = "pivot"

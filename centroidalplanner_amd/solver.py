@@ -64,7 +64,9 @@ def solve(problem, evaluator=None, x0: Optional[np.ndarray] = None, tol: float =
           hessian: str = "limited-memory", derivative_test: str = "none",
           jacobian_regularization: str = "pivot") -> SolveResult:
     """One instance through the batched solve loop.  hessian: "limited-memory" (IFOPT's default, as
-    the reference runs) or "exact" (the analytic Lagrangian Hessian).  derivative_test:
+    the reference runs), "exact" (the analytic Lagrangian Hessian on Ground / no-environment
+    templates, central differences otherwise) or "analytic" (the analytic one for every environment
+    kind; batch_ipm_solve's option).  derivative_test:
     "first-order" runs IPOPT's first-order derivative checker at the start point first, as the
     reference's solver option does (src/CentroidalPlanner.cpp:26); its report is returned.
     jacobian_regularization: "pivot" (default) or "ipopt" (batch_ipm_solve's option)."""

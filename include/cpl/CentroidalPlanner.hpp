@@ -31,6 +31,8 @@ class NlpSolver {
 
 // The native engine's options (cpl_solve_options), IFOPT's IpoptSolver defaults: limited-memory
 // Hessian (src/CentroidalPlanner.cpp:22-29 keeps IFOPT's setting), max_iter 3000, tol 1e-8.
+// hessian takes every CPL_HESSIAN_* value; CPL_HESSIAN_ANALYTIC is the analytic Hessian for every
+// environment kind (Superquadric and mixed templates included).
 struct SolveOptions : cpl_solve_options {
   SolveOptions() {
     cpl_solve_options_default(this);

@@ -348,6 +348,33 @@ int32_t cpl_eval_lagrangian_grad(const cpl_problem_desc* d, int64_t batch, const
 int32_t cpl_lagrangian_hessian(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_y,
                                const uint8_t* d_active, const int32_t* d_free_idx, int32_t nf, double* d_H,
                                void* stream);
+/*
+ * cpl_lagrangian_hessian_ex: cpl_lagrangian_hessian for every environment kind.  Ground and
+ * no-environment templates: bitwise cpl_lagrangian_hessian (the same kernel).  d_env_tag [batch]
+ * (CPL_ENV_GROUND / CPL_ENV_SUPERQUADRIC per instance) is required for CPL_ENV_MIXED
+ * (CPL_ERR_INVALID_ARGUMENT without it) and ignored otherwise; batch == 0 is the same probe as
+ * the plain entry's.  Superquadric contacts (Superquadric templates, Superquadric-tagged instances
+ * of a mixed batch) add the curvature of their environment row S(p) - 1 (multiplier y_e) and of
+ * their three normal rows n + nu(p) (multipliers y_k) to the p_i x p_i block of contact i; every
+ * other row is linear in everything but p.  With d_a = p_a - C_a,
+ *   e_a = P_a / R_a^P_a d_a^(P_a - 1),  h_a = (P_a - 1) P_a / R_a^P_a d_a^(P_a - 2),
+ *   t_a = (P_a - 1)(P_a - 2) P_a / R_a^P_a d_a^(P_a - 3)  (exactly 0 when P_a == 2),
+ *   r = |e|,  nu = e / r,  D_ka = (delta_ka - nu_k nu_a) h_a / r  (the normal Jacobian),
+ *   H[a][b] += delta_ab y_e h_a
+ *            + sum_k y_k [ (delta_ka - nu_k nu_a) delta_ab t_a / r - (D_kb nu_a + nu_k D_ab) h_a / r
+ *                          - (delta_ka - nu_k nu_a) h_a nu_b h_b / r^2 ],
+ * each pair evaluated once (a <= b) and mirrored, so H stays bitwise symmetric.  The powers of d
+ * are accurate to the evaluation kernels' standard (double-double for integer and half-integer
+ * exponents), not bitwise any reference's: tests/test_gpu_sq_hessian.py bounds the entries against
+ * an extended-precision derivative.  Degenerate contacts: where r is 0 or not finite, or any entry
+ * of the 3 x 3 block is not finite (a negative base under a non-integer exponent, overflow at a
+ * large exponent), the contact's whole environment / normal contribution counts as 0 (the cost's
+ * W_p diagonal stays) — the convention of the cone's |F_t| = 0 branch and of the engine's "NaN
+ * Jacobian entries count as 0".
+ */
+int32_t cpl_lagrangian_hessian_ex(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_y,
+                                  const uint8_t* d_env_tag, const uint8_t* d_active, const int32_t* d_free_idx,
+                                  int32_t nf, double* d_H, void* stream);
 int32_t cpl_kkt_solve(int32_t mode, int64_t batch, int32_t nw, int32_t m, const double* d_M, const double* d_A,
                       const double* d_r1, const double* d_r2, const double* d_mu, const double* d_delta_w_last,
                       const uint8_t* d_active, double* d_dw, double* d_dy, double* d_delta_w, double* d_delta_c,
@@ -486,6 +513,11 @@ int32_t cpl_ipm_dense_a(int64_t batch, int32_t m, int32_t nw, int32_t nf, int32_
 #define CPL_HESSIAN_EXACT 0          /* analytic Lagrangian Hessian (Ground / no environment), else FD */
 #define CPL_HESSIAN_LIMITED_MEMORY 1 /* IPOPT's L-BFGS (6 pairs, scalar1): IFOPT's IpoptSolver default */
 #define CPL_HESSIAN_FD 2             /* central differences of grad f + J^T y */
+#define CPL_HESSIAN_ANALYTIC 3       /* analytic Lagrangian Hessian for every environment kind
+                                        (cpl_lagrangian_hessian_ex): bitwise CPL_HESSIAN_EXACT on Ground /
+                                        no-environment templates; on Superquadric / mixed ones the closed
+                                        form replaces CPL_HESSIAN_EXACT's central differences (no
+                                        perturbed-point buffers are allocated) */
 
 #define CPL_SOLVE_OPTIMAL 0
 #define CPL_SOLVE_ACCEPTABLE 1
