@@ -2202,6 +2202,39 @@ struct Arena {
   }
 };
 
+// cpl_solver_create carves every device buffer through a call that names its class (DESIGN.md §5,
+// "Where the engine's buffers are declared"); compact(), the reset at the head of cpl_solver_solve and
+// the gather scratch's size know the buffers only by the records these calls leave:
+//   fixed  `count` elements, no batch factor (problem constants, flag and count words)
+//   state  [B, width] by batch row, live across iterations: gathered by the compaction when `when`
+//          holds (never at width 0: the limited-memory rows with the mode off)
+//   temp   [B, width] by batch row, written before it is read within an iteration
+//   full   [B, width] by original instance (results, constant zeros)
+// ZEROED: cleared at the start of every solve.
+enum MoveWhen : uint8_t { NEVER, ALWAYS, IF_SCALED, IF_MASS, IF_TAG };  // (the solve is scaled / has masses / tags)
+constexpr bool ZEROED = true;
+struct BufRec { void* ptr; size_t elem; int64_t width; MoveWhen when; bool zeroed; };  // elem: bytes; width: per row
+struct Carver {
+  Arena& a;
+  size_t B;
+  std::vector<BufRec>* recs;  // the state and the zeroed buffers, in carve order (null: the measuring pass)
+  size_t row_bytes = 0;       // the widest state row
+  bool ok = true;             // (the 1- and 4-byte gathers move one element per row)
+  template <typename T> T* fixed(size_t count) { return a.take<T>(count); }
+  template <typename T> T* temp(size_t width) { return a.take<T>(B * width); }
+  template <typename T> T* full(size_t width, bool zeroed = false) { return rows<T>(width, NEVER, zeroed); }
+  template <typename T> T* state(size_t width, MoveWhen when, bool zeroed = false) {
+    row_bytes = std::max(row_bytes, width * sizeof(T));
+    ok = ok && when != NEVER && (sizeof(T) == 8 || width == 1);
+    return rows<T>(width, when, zeroed);
+  }
+  template <typename T> T* rows(size_t width, MoveWhen when, bool zeroed) {
+    T* p = a.take<T>(B * width);
+    if (recs && (when != NEVER || zeroed)) recs->push_back({p, sizeof(T), (int64_t)width, when, zeroed});
+    return p;
+  }
+};
+
 }  // namespace
 }  // namespace cpl
 
@@ -2222,6 +2255,7 @@ struct cpl_solver {
   std::map<int64_t, std::pair<hipGraph_t, hipGraphExec_t>> graphs;  // (size, inputs, phase) -> graph
   uint8_t* h_flag = nullptr;  // pinned: the device's 4 flag bytes
   cpl::Arena arena;
+  std::vector<cpl::BufRec> bufs;  // the state buffers and the zeroed ones, in carve order (cpl::Carver)
   const double* mass = nullptr;       // per solve
   const uint8_t* tag = nullptr;
   // problem constants (device)
@@ -2271,7 +2305,6 @@ struct cpl_solver {
       *a_minR, *alphaR;
   uint8_t *actR, *movedR, *searchingR, *switchR;
   double *fin_f, *fin_g;
-  int32_t *st32, *it32;
   // compaction: original instance of each row, compacted masses / tags, full-batch results
   int32_t *orig, *pos, *d_count, *h_count = nullptr;
   bool tail_fused = false;  // P_FUSED: the soft judge launch also ends the search (k_soft_judge_fail)
@@ -2926,12 +2959,13 @@ int32_t read_flags(cpl_solver* S) {
 }
 
 // Active-set compaction: the finished rows' results go to the full-batch arrays, the `count` active
-// rows move to the front (every per-instance state buffer gathered), the batch shrinks to Bn rows
-// (the rows past `count` padded inactive), so later iterations cost what their active instances do.
+// rows move to the front (every buffer carved as `state` gathered: cpl::Carver), the batch shrinks to
+// Bn rows (the rows past `count` padded inactive), so later iterations cost what their active
+// instances do.
 int32_t compact(cpl_solver* S, int64_t count, int64_t Bn) {
   hipStream_t st = S->stream;
   const int64_t Bc = S->Bcur;
-  const int n = S->n, m = S->m, nw = S->nw;
+  const int nf = S->nf;
   const LeaveArgs leave = leave_args(S, true);
   if (S->opt.fallback_viol_tol > 0.0) {
     hipLaunchKernelGGL(k_fallback, dim3(blocks_for(Bc)), dim3(256), 0, st, Bc, leave);
@@ -2941,63 +2975,22 @@ int32_t compact(cpl_solver* S, int64_t count, int64_t Bn) {
   LAUNCHED("k_scatter_final");
   hipLaunchKernelGGL(k_positions, dim3(1), dim3(1024), 0, st, Bc, S->active, S->pos);
   LAUNCHED("k_positions");
-  auto move = [&](void* buf, int64_t words) -> int32_t {
-    if (!buf || words <= 0) return CPL_OK;
-    hipLaunchKernelGGL(k_gather_rows, dim3(blocks_elems(count * words)), dim3(256), 0, st, count, words, S->pos,
-                       (const uint64_t*)buf, S->scratch);
-    LAUNCHED("k_gather_rows");
-    HK(hipMemcpyAsync(buf, S->scratch, 8 * (size_t)(count * words), hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
-    return CPL_OK;
-  };
-  const int nf = S->nf;
-  CK(move(S->w, nw)); CK(move(S->y, m)); CK(move(S->zL, nw)); CK(move(S->zU, nw)); CK(move(S->mu, 1));
-  CK(move(S->filt_t, FMAX)); CK(move(S->filt_p, FMAX)); CK(move(S->dwl, 1)); CK(move(S->f, 1));
-  CK(move(S->grad, n)); CK(move(S->g, m)); CK(move(S->J, S->nnz_rec)); CK(move(S->d_inf, 1));
-  CK(move(S->theta_max, 1)); CK(move(S->theta_min, 1)); CK(move(S->Xbase, n));
-  CK(move(S->status, 1)); CK(move(S->iters, 1)); CK(move(S->acc, 1)); CK(move(S->fcount, 1)); CK(move(S->n_resto, 1));
-  // the restoration phase's state
-  CK(move(S->wR, nw)); CK(move(S->pR, m)); CK(move(S->nR, m)); CK(move(S->zp, m)); CK(move(S->zn, m));
-  CK(move(S->zLR, nw)); CK(move(S->zUR, nw)); CK(move(S->muR, 1)); CK(move(S->ftR, FMAX)); CK(move(S->fpR, FMAX));
-  CK(move(S->fcR, 1)); CK(move(S->th_o0, 1)); CK(move(S->ph_o0, 1)); CK(move(S->dwlR, 1)); CK(move(S->thmaxR, 1));
-  CK(move(S->thminR, 1)); CK(move(S->best_w, nw)); CK(move(S->best_f, 1));
-  CK(move(S->acc_w, nw)); CK(move(S->acc_y, m)); CK(move(S->acc_zL, nw)); CK(move(S->acc_zU, nw));
-  if (S->scaled) {
-    CK(move(S->df, 1));
-    CK(move(S->dc, m));
+  // every state buffer whose condition holds, gathered through the scratch and copied back
+  for (const BufRec& r : S->bufs) {
+    const bool moved = r.when == ALWAYS || (r.when == IF_SCALED && S->scaled) ||
+                       (r.when == IF_MASS && S->mass) || (r.when == IF_TAG && S->tag);
+    if (!moved || r.width <= 0) continue;
+    const dim3 grid(blocks_elems(count * r.width)), blk(256);
+    if (r.elem == 8)
+      hipLaunchKernelGGL(k_gather_rows, grid, blk, 0, st, count, r.width, S->pos, (const uint64_t*)r.ptr, S->scratch);
+    else if (r.elem == 4)
+      hipLaunchKernelGGL(k_gather_i32, grid, blk, 0, st, count, S->pos, (const int32_t*)r.ptr, (int32_t*)S->scratch);
+    else
+      hipLaunchKernelGGL(k_gather_bytes, grid, blk, 0, st, count, S->pos, (const uint8_t*)r.ptr, (uint8_t*)S->scratch);
+    LAUNCHED("k_gather");
+    HK(hipMemcpyAsync(r.ptr, S->scratch, r.elem * (size_t)(count * r.width), hipMemcpyDeviceToDevice, st),
+       "hipMemcpyAsync");
   }
-  if (S->bfgs) {
-    CK(move(S->Hq, LMC(nf)));
-    CK(move(S->lm_s, (int64_t)LM_HIST * nf));
-    CK(move(S->lm_y, (int64_t)LM_HIST * nf));
-  }
-  if (S->mass) CK(move(S->mass_c, 1));
-  // 1-byte and 4-byte rows
-  auto move_bytes = [&](uint8_t* buf) -> int32_t {
-    hipLaunchKernelGGL(k_gather_bytes, dim3(blocks_elems(count)), dim3(256), 0, st, count, S->pos, buf,
-                       (uint8_t*)S->scratch);
-    LAUNCHED("k_gather_bytes");
-    HK(hipMemcpyAsync(buf, S->scratch, (size_t)count, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
-    return CPL_OK;
-  };
-  CK(move_bytes(S->active));
-  CK(move_bytes(S->lm_cnt));
-  CK(move_bytes(S->lm_skip));
-  CK(move_bytes(S->in_soft));
-  CK(move_bytes(S->tiny_last));
-  CK(move_bytes(S->tiny_flag));
-  CK(move_bytes(S->in_resto));
-  CK(move_bytes(S->resto_tight));
-  CK(move_bytes(S->has_acc));
-  if (S->tag) CK(move_bytes(S->tag_c));
-  auto move_i32 = [&](int32_t* buf) -> int32_t {
-    hipLaunchKernelGGL(k_gather_i32, dim3(blocks_elems(count)), dim3(256), 0, st, count, S->pos, buf,
-                       (int32_t*)S->scratch);
-    LAUNCHED("k_gather_i32");
-    HK(hipMemcpyAsync(buf, S->scratch, 4 * (size_t)count, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
-    return CPL_OK;
-  };
-  CK(move_i32(S->orig));
-  CK(move_i32(S->soft_cnt));
   hipLaunchKernelGGL(k_pad, dim3(blocks_elems(Bn)), dim3(256), 0, st, count, Bn, S->active, S->orig);
   LAUNCHED("k_pad");
   S->Bcur = Bn;
@@ -3220,104 +3213,112 @@ int32_t cpl_solver_create(const cpl_problem_desc* d, int64_t batch, const cpl_so
     return bad(e, "hipHostMalloc");
   // every device buffer carved from one allocation: a measuring pass, then the real one
   const size_t Bz = (size_t)batch, kws = (size_t)cpl_kkt_workspace_doubles(nw, m);
-  const size_t nfd = S->fd ? Bz * 2 * nf : 0;
-  {  // the widest per-instance row the compaction moves
-    int64_t wmax = nnz_rec;
-    for (int64_t v : {(int64_t)n, (int64_t)nw, (int64_t)m, (int64_t)FMAX, S->bfgs ? LMC(nf) : 0}) wmax = std::max(wmax, v);
-    S->scratch_words = wmax;
-  }
-  auto carve = [&](Arena& a) {
+  const size_t fdw = S->fd ? 2 * (size_t)nf : 0;  // central-difference points per instance
+  const size_t lmc = S->bfgs ? (size_t)LMC(nf) : 0, lmh = S->bfgs ? (size_t)LM_HIST * nf : 0;  // limited-memory rows
+  // every line names its buffer's class (cpl::Carver): what compact() moves, what a solve starts by
+  // zeroing and the gather scratch's size follow from these lines alone
+  auto carve = [&](Carver& c) {
   // constants
-  S->free32 = a.take<int32_t>(nf); S->ineq_row = a.take<int32_t>(nI); S->row_slack = a.take<int32_t>(m);
-  S->freepos = a.take<int32_t>(n); S->amap = a.take<int32_t>((size_t)m * (nf ? nf : 1));
-  S->col_ptr = a.take<int32_t>(n + 1); S->csc_k = a.take<int32_t>(nnz); S->csc_row = a.take<int32_t>(nnz);
-  S->free64 = a.take<int64_t>(nf); S->fixed64 = a.take<int64_t>(fixed_idx.size());
-  S->is_fixed = a.take<uint8_t>(n); S->hasL = a.take<uint8_t>(nw); S->hasU = a.take<uint8_t>(nw);
-  S->zeros_u8 = a.take<uint8_t>(Bz);
-  S->xl = a.take<double>(n); S->xu = a.take<double>(n); S->gl = a.take<double>(m); S->gu = a.take<double>(m);
-  S->wl0 = a.take<double>(nw); S->wu0 = a.take<double>(nw);
+  S->free32 = c.fixed<int32_t>(nf); S->ineq_row = c.fixed<int32_t>(nI); S->row_slack = c.fixed<int32_t>(m);
+  S->freepos = c.fixed<int32_t>(n); S->amap = c.fixed<int32_t>((size_t)m * (nf ? nf : 1));
+  S->col_ptr = c.fixed<int32_t>(n + 1); S->csc_k = c.fixed<int32_t>(nnz); S->csc_row = c.fixed<int32_t>(nnz);
+  S->free64 = c.fixed<int64_t>(nf); S->fixed64 = c.fixed<int64_t>(fixed_idx.size());
+  S->is_fixed = c.fixed<uint8_t>(n); S->hasL = c.fixed<uint8_t>(nw); S->hasU = c.fixed<uint8_t>(nw);
+  S->zeros_u8 = c.full<uint8_t>(1);
+  S->xl = c.fixed<double>(n); S->xu = c.fixed<double>(n); S->gl = c.fixed<double>(m); S->gu = c.fixed<double>(m);
+  S->wl0 = c.fixed<double>(nw); S->wu0 = c.fixed<double>(nw);
   // state
-  S->Xbase = a.take<double>(Bz * n); S->w = a.take<double>(Bz * nw); S->y = a.take<double>(Bz * m);
-  S->zL = a.take<double>(Bz * nw); S->zU = a.take<double>(Bz * nw); S->mu = a.take<double>(Bz);
-  S->filt_t = a.take<double>(Bz * FMAX); S->filt_p = a.take<double>(Bz * FMAX); S->dwl = a.take<double>(Bz);
-  S->f = a.take<double>(Bz); S->grad = a.take<double>(Bz * n); S->g = a.take<double>(Bz * m);
-  S->J = a.take<double>(Bz * nnz_rec); S->d_inf = a.take<double>(Bz); S->Hq = a.take<double>(S->bfgs ? Bz * LMC(nf) : 0);
-  S->lm_s = a.take<double>(S->bfgs ? Bz * LM_HIST * nf : 0); S->lm_y = a.take<double>(S->bfgs ? Bz * LM_HIST * nf : 0);
-  S->theta_max = a.take<double>(Bz); S->theta_min = a.take<double>(Bz);
-  S->status = a.take<int64_t>(Bz); S->iters = a.take<int64_t>(Bz); S->acc = a.take<int64_t>(Bz);
-  S->fcount = a.take<int64_t>(Bz); S->fc = a.take<int64_t>(Bz); S->n_resto = a.take<int64_t>(Bz);
-  S->active = a.take<uint8_t>(Bz); S->lm_cnt = a.take<uint8_t>(Bz); S->lm_skip = a.take<uint8_t>(Bz); S->d_any = a.take<uint8_t>(4);
-  S->in_soft = a.take<uint8_t>(Bz); S->tiny_last = a.take<uint8_t>(Bz); S->tiny_flag = a.take<uint8_t>(Bz);
-  S->in_resto = a.take<uint8_t>(Bz); S->soft_cnt = a.take<int32_t>(Bz); S->resto_tight = a.take<uint8_t>(Bz);
-  S->best_w = a.take<double>(Bz * nw); S->best_f = a.take<double>(Bz); S->fbest = a.take<uint8_t>(Bz);
-  S->acc_w = a.take<double>(Bz * nw); S->acc_y = a.take<double>(Bz * m); S->acc_zL = a.take<double>(Bz * nw);
-  S->acc_zU = a.take<double>(Bz * nw); S->has_acc = a.take<uint8_t>(Bz);
+  S->Xbase = c.state<double>(n, ALWAYS); S->w = c.state<double>(nw, ALWAYS); S->y = c.state<double>(m, ALWAYS);
+  S->zL = c.state<double>(nw, ALWAYS); S->zU = c.state<double>(nw, ALWAYS); S->mu = c.state<double>(1, ALWAYS);
+  S->filt_t = c.state<double>(FMAX, ALWAYS); S->filt_p = c.state<double>(FMAX, ALWAYS); S->dwl = c.state<double>(1, ALWAYS);
+  S->f = c.state<double>(1, ALWAYS); S->grad = c.state<double>(n, ALWAYS); S->g = c.state<double>(m, ALWAYS);
+  S->J = c.state<double>(nnz_rec, ALWAYS); S->d_inf = c.state<double>(1, ALWAYS); S->Hq = c.state<double>(lmc, ALWAYS);
+  S->lm_s = c.state<double>(lmh, ALWAYS); S->lm_y = c.state<double>(lmh, ALWAYS);
+  S->theta_max = c.state<double>(1, ALWAYS); S->theta_min = c.state<double>(1, ALWAYS);
+  S->status = c.state<int64_t>(1, ALWAYS); S->iters = c.state<int64_t>(1, ALWAYS); S->acc = c.state<int64_t>(1, ALWAYS);
+  S->fcount = c.state<int64_t>(1, ALWAYS); S->fc = c.temp<int64_t>(1); S->n_resto = c.state<int64_t>(1, ALWAYS, ZEROED);
+  S->active = c.state<uint8_t>(1, ALWAYS); S->lm_cnt = c.state<uint8_t>(1, ALWAYS); S->lm_skip = c.state<uint8_t>(1, ALWAYS);
+  S->d_any = c.fixed<uint8_t>(4);
+  S->in_soft = c.state<uint8_t>(1, ALWAYS, ZEROED); S->tiny_last = c.state<uint8_t>(1, ALWAYS, ZEROED);
+  S->tiny_flag = c.state<uint8_t>(1, ALWAYS, ZEROED); S->in_resto = c.state<uint8_t>(1, ALWAYS, ZEROED);
+  S->soft_cnt = c.state<int32_t>(1, ALWAYS, ZEROED); S->resto_tight = c.state<uint8_t>(1, ALWAYS, ZEROED);
+  S->best_w = c.state<double>(nw, ALWAYS); S->best_f = c.state<double>(1, ALWAYS); S->fbest = c.full<uint8_t>(1, ZEROED);
+  S->acc_w = c.state<double>(nw, ALWAYS); S->acc_y = c.state<double>(m, ALWAYS); S->acc_zL = c.state<double>(nw, ALWAYS);
+  S->acc_zU = c.state<double>(nw, ALWAYS); S->has_acc = c.state<uint8_t>(1, ALWAYS, ZEROED);
   // the restoration phase's state
-  S->wR = a.take<double>(Bz * nw); S->pR = a.take<double>(Bz * m); S->nR = a.take<double>(Bz * m);
-  S->zp = a.take<double>(Bz * m); S->zn = a.take<double>(Bz * m); S->zLR = a.take<double>(Bz * nw);
-  S->zUR = a.take<double>(Bz * nw); S->muR = a.take<double>(Bz); S->ftR = a.take<double>(Bz * FMAX);
-  S->fpR = a.take<double>(Bz * FMAX); S->fcR = a.take<int64_t>(Bz); S->th_o0 = a.take<double>(Bz);
-  S->ph_o0 = a.take<double>(Bz); S->dwlR = a.take<double>(Bz); S->thmaxR = a.take<double>(Bz);
-  S->thminR = a.take<double>(Bz);
+  S->wR = c.state<double>(nw, ALWAYS); S->pR = c.state<double>(m, ALWAYS); S->nR = c.state<double>(m, ALWAYS);
+  S->zp = c.state<double>(m, ALWAYS); S->zn = c.state<double>(m, ALWAYS); S->zLR = c.state<double>(nw, ALWAYS);
+  S->zUR = c.state<double>(nw, ALWAYS); S->muR = c.state<double>(1, ALWAYS); S->ftR = c.state<double>(FMAX, ALWAYS);
+  S->fpR = c.state<double>(FMAX, ALWAYS); S->fcR = c.state<int64_t>(1, ALWAYS); S->th_o0 = c.state<double>(1, ALWAYS);
+  S->ph_o0 = c.state<double>(1, ALWAYS); S->dwlR = c.state<double>(1, ALWAYS); S->thmaxR = c.state<double>(1, ALWAYS);
+  S->thminR = c.state<double>(1, ALWAYS);
   // temporaries
-  S->A = a.take<double>(Bz * m * nw);
-  S->gradw = a.take<double>(Bz * nw); S->c = a.take<double>(Bz * m);
-  S->err0 = a.take<double>(Bz); S->base = a.take<double>(Bz); S->mu_o = a.take<double>(Bz);
-  S->ft = a.take<double>(Bz * FMAX); S->fp = a.take<double>(Bz * FMAX); S->tau = a.take<double>(Bz);
-  S->X = a.take<double>(Bz * n); S->H = a.take<double>(Bz * nf * nf); S->M = a.take<double>(Bz * nw * nw);
-  S->Kqd = a.take<double>(Bz * nw * nw); S->r1 = a.take<double>(Bz * nw); S->r2 = a.take<double>(Bz * m);
-  S->gphi = a.take<double>(Bz * nw); S->mr_diag = a.take<double>(Bz * nw); S->theta_k = a.take<double>(Bz);
-  S->phi_k = a.take<double>(Bz); S->dw = a.take<double>(Bz * nw); S->dy = a.take<double>(Bz * m);
-  S->delta_w = a.take<double>(Bz); S->delta_c = a.take<double>(Bz); S->dzL = a.take<double>(Bz * nw);
-  S->dzU = a.take<double>(Bz * nw); S->a_max = a.take<double>(Bz); S->a_z = a.take<double>(Bz);
-  S->gd = a.take<double>(Bz); S->ws = a.take<double>(Bz * kws);
-  S->ws_aug = a.take<double>(S->jreg ? Bz * (size_t)kkt_aug_workspace_doubles(nw, m) : 0); S->info = a.take<int32_t>(Bz);
-  S->a_min = a.take<double>(Bz); S->a_soft = a.take<double>(Bz); S->cs_tmp = a.take<double>(Bz * m);
-  S->scr1 = a.take<double>(2 * Bz); S->scr2 = a.take<double>(Bz * m);
-  S->act = a.take<uint8_t>(Bz); S->switch_ok = a.take<uint8_t>(Bz); S->searching = a.take<uint8_t>(Bz);
-  S->st_aug = a.take<uint8_t>(Bz); S->ok = a.take<uint8_t>(Bz); S->soc = a.take<uint8_t>(Bz);
-  S->ok_s = a.take<uint8_t>(Bz); S->failed = a.take<uint8_t>(Bz); S->moved = a.take<uint8_t>(Bz);
-  S->tiny_now = a.take<uint8_t>(Bz); S->soft_now = a.take<uint8_t>(Bz); S->soft_try = a.take<uint8_t>(Bz);
-  S->st_f = a.take<double>(Bz); S->st_g = a.take<double>(Bz * m); S->st_w = a.take<double>(Bz * nw);
-  S->st_alpha = a.take<double>(Bz); S->alpha = a.take<double>(Bz);
-  S->th = a.take<double>(Bz); S->wt = a.take<double>(Bz * nw); S->Xt = a.take<double>(Bz * n);
-  S->f_t = a.take<double>(Bz); S->g_t = a.take<double>(Bz * m);
-  S->c_soc = a.take<double>(Bz * m); S->a_soc = a.take<double>(Bz); S->th_old = a.take<double>(Bz);
-  S->r2s = a.take<double>(Bz * m); S->dws = a.take<double>(Bz * nw); S->dys = a.take<double>(Bz * m);
-  S->ws_ = a.take<double>(Bz * nw); S->Xs = a.take<double>(Bz * n); S->f_s = a.take<double>(Bz);
-  S->g_s = a.take<double>(Bz * m); S->th_s = a.take<double>(Bz);
-  S->Xn = a.take<double>(Bz * n); S->f_n = a.take<double>(Bz); S->grad_n = a.take<double>(Bz * n);
-  S->g_n = a.take<double>(Bz * m); S->J_n = a.take<double>(Bz * nnz_rec);
-  S->zeros_w = a.take<double>(Bz * nw); S->zeros_B = a.take<double>(Bz);
+  S->A = c.temp<double>((size_t)m * nw);
+  S->gradw = c.temp<double>(nw); S->c = c.temp<double>(m);
+  S->err0 = c.temp<double>(1); S->base = c.temp<double>(1); S->mu_o = c.temp<double>(1);
+  S->ft = c.temp<double>(FMAX); S->fp = c.temp<double>(FMAX); S->tau = c.temp<double>(1);
+  S->X = c.temp<double>(n); S->H = c.temp<double>((size_t)nf * nf); S->M = c.temp<double>((size_t)nw * nw);
+  S->Kqd = c.temp<double>((size_t)nw * nw); S->r1 = c.temp<double>(nw); S->r2 = c.temp<double>(m);
+  S->gphi = c.temp<double>(nw); S->mr_diag = c.temp<double>(nw); S->theta_k = c.temp<double>(1);
+  S->phi_k = c.temp<double>(1); S->dw = c.temp<double>(nw); S->dy = c.temp<double>(m);
+  S->delta_w = c.temp<double>(1); S->delta_c = c.temp<double>(1); S->dzL = c.temp<double>(nw);
+  S->dzU = c.temp<double>(nw); S->a_max = c.temp<double>(1); S->a_z = c.temp<double>(1);
+  S->gd = c.temp<double>(1); S->ws = c.temp<double>(kws);
+  S->ws_aug = c.temp<double>(S->jreg ? (size_t)kkt_aug_workspace_doubles(nw, m) : 0); S->info = c.temp<int32_t>(1);
+  S->a_min = c.temp<double>(1); S->a_soft = c.temp<double>(1); S->cs_tmp = c.temp<double>(m);
+  S->scr1 = c.temp<double>(2); S->scr2 = c.temp<double>(m);
+  S->act = c.temp<uint8_t>(1); S->switch_ok = c.temp<uint8_t>(1); S->searching = c.temp<uint8_t>(1);
+  S->st_aug = c.temp<uint8_t>(1); S->ok = c.temp<uint8_t>(1); S->soc = c.temp<uint8_t>(1);
+  S->ok_s = c.temp<uint8_t>(1); S->failed = c.temp<uint8_t>(1); S->moved = c.temp<uint8_t>(1);
+  S->tiny_now = c.temp<uint8_t>(1); S->soft_now = c.temp<uint8_t>(1); S->soft_try = c.temp<uint8_t>(1);
+  S->st_f = c.temp<double>(1); S->st_g = c.temp<double>(m); S->st_w = c.temp<double>(nw);
+  S->st_alpha = c.temp<double>(1); S->alpha = c.temp<double>(1);
+  S->th = c.temp<double>(1); S->wt = c.temp<double>(nw); S->Xt = c.temp<double>(n);
+  S->f_t = c.temp<double>(1); S->g_t = c.temp<double>(m);
+  S->c_soc = c.temp<double>(m); S->a_soc = c.temp<double>(1); S->th_old = c.temp<double>(1);
+  S->r2s = c.temp<double>(m); S->dws = c.temp<double>(nw); S->dys = c.temp<double>(m);
+  S->ws_ = c.temp<double>(nw); S->Xs = c.temp<double>(n); S->f_s = c.temp<double>(1);
+  S->g_s = c.temp<double>(m); S->th_s = c.temp<double>(1);
+  S->Xn = c.temp<double>(n); S->f_n = c.temp<double>(1); S->grad_n = c.temp<double>(n);
+  S->g_n = c.temp<double>(m); S->J_n = c.temp<double>(nnz_rec);
+  S->zeros_w = c.full<double>(nw); S->zeros_B = c.full<double>(1);
   // the restoration phase's temporaries
-  S->gfR = a.take<double>(Bz * nw); S->tauR = a.take<double>(Bz); S->rp = a.take<double>(Bz * m);
-  S->rn = a.take<double>(Bz * m); S->Dinv = a.take<double>(Bz * m); S->dp = a.take<double>(Bz * m);
-  S->dn = a.take<double>(Bz * m); S->dzp = a.take<double>(Bz * m); S->dzn = a.take<double>(Bz * m);
-  S->st_p = a.take<double>(Bz * m); S->st_n = a.take<double>(Bz * m); S->thetaR = a.take<double>(Bz);
-  S->phiR = a.take<double>(Bz); S->gdR = a.take<double>(Bz); S->a_maxR = a.take<double>(Bz);
-  S->a_zR = a.take<double>(Bz); S->a_minR = a.take<double>(Bz); S->alphaR = a.take<double>(Bz);
-  S->actR = a.take<uint8_t>(Bz); S->movedR = a.take<uint8_t>(Bz); S->searchingR = a.take<uint8_t>(Bz);
-  S->switchR = a.take<uint8_t>(Bz);
-  S->fin_f = a.take<double>(Bz); S->fin_g = a.take<double>(Bz * m);
-  S->st32 = a.take<int32_t>(Bz); S->it32 = a.take<int32_t>(Bz);
-  S->Xp = a.take<double>(nfd * n); S->gL = a.take<double>(nfd * n); S->hfd = a.take<double>(Bz * nf);
-  S->mass_fd = a.take<double>(nfd); S->jac_fd = a.take<double>(nfd * nnz); S->grad_fd = a.take<double>(nfd * n);
-  S->tag_fd = a.take<uint8_t>(nfd);
-  S->orig = a.take<int32_t>(Bz); S->pos = a.take<int32_t>(Bz); S->d_count = a.take<int32_t>(6);
-  S->mass_c = a.take<double>(Bz); S->tag_c = a.take<uint8_t>(Bz);
-  S->fw = a.take<double>(Bz * nw); S->fy = a.take<double>(Bz * m); S->fX = a.take<double>(Bz * n);
-  S->fdinf = a.take<double>(Bz); S->fstatus = a.take<int64_t>(Bz); S->fiters = a.take<int64_t>(Bz);
-  S->fresto = a.take<int64_t>(Bz);
-  S->scratch = a.take<uint64_t>(Bz * (size_t)S->scratch_words);
-  S->df = a.take<double>(Bz); S->dc = a.take<double>(Bz * m); S->ytil = a.take<double>(S->bfgs ? 0 : Bz * m);
-  S->rrow = a.take<int32_t>(nnz_rec); S->srp = a.take<int32_t>(m + 1); S->srq = a.take<int32_t>(srq.size());
-  S->sc_any = a.take<uint8_t>(4); S->nan_cnt = a.take<int32_t>(Bz);
+  S->gfR = c.temp<double>(nw); S->tauR = c.temp<double>(1); S->rp = c.temp<double>(m);
+  S->rn = c.temp<double>(m); S->Dinv = c.temp<double>(m); S->dp = c.temp<double>(m);
+  S->dn = c.temp<double>(m); S->dzp = c.temp<double>(m); S->dzn = c.temp<double>(m);
+  S->st_p = c.temp<double>(m); S->st_n = c.temp<double>(m); S->thetaR = c.temp<double>(1);
+  S->phiR = c.temp<double>(1); S->gdR = c.temp<double>(1); S->a_maxR = c.temp<double>(1);
+  S->a_zR = c.temp<double>(1); S->a_minR = c.temp<double>(1); S->alphaR = c.temp<double>(1);
+  S->actR = c.temp<uint8_t>(1); S->movedR = c.temp<uint8_t>(1); S->searchingR = c.temp<uint8_t>(1);
+  S->switchR = c.temp<uint8_t>(1);
+  S->fin_f = c.full<double>(1); S->fin_g = c.full<double>(m);
+  S->Xp = c.temp<double>(fdw * n); S->gL = c.temp<double>(fdw * n); S->hfd = c.temp<double>(nf);
+  S->mass_fd = c.temp<double>(fdw); S->jac_fd = c.temp<double>(fdw * nnz); S->grad_fd = c.temp<double>(fdw * n);
+  S->tag_fd = c.temp<uint8_t>(fdw);
+  // compaction: each row's original instance, the gather's positions, this solve's masses / tags
+  S->orig = c.state<int32_t>(1, ALWAYS); S->pos = c.temp<int32_t>(1); S->d_count = c.fixed<int32_t>(6);
+  S->mass_c = c.state<double>(1, IF_MASS); S->tag_c = c.state<uint8_t>(1, IF_TAG);
+  S->fw = c.full<double>(nw); S->fy = c.full<double>(m); S->fX = c.full<double>(n);
+  S->fdinf = c.full<double>(1); S->fstatus = c.full<int64_t>(1); S->fiters = c.full<int64_t>(1);
+  S->fresto = c.full<int64_t>(1);
+  S->df = c.state<double>(1, IF_SCALED); S->dc = c.state<double>(m, IF_SCALED); S->ytil = c.temp<double>(S->bfgs ? 0 : m);
+  S->rrow = c.fixed<int32_t>(nnz_rec); S->srp = c.fixed<int32_t>(m + 1); S->srq = c.fixed<int32_t>(srq.size());
+  S->sc_any = c.fixed<uint8_t>(4); S->nan_cnt = c.full<int32_t>(1);
+  // last: the gather scratch holds the widest state row of every instance, in 8-byte words
+  S->scratch_words = (int64_t)((c.row_bytes + 7) / 8);
+  S->scratch = c.temp<uint64_t>((size_t)S->scratch_words);
   };
-  Arena probe;
+  Arena probe_arena;
+  Carver probe{probe_arena, Bz, nullptr};
   carve(probe);
-  if ((e = hipMalloc(&S->arena.base, probe.used)) != hipSuccess) return bad(e, "hipMalloc solver arena");
-  S->arena.cap = probe.used;
-  carve(S->arena);
+  if ((e = hipMalloc(&S->arena.base, probe_arena.used)) != hipSuccess) return bad(e, "hipMalloc solver arena");
+  S->arena.cap = probe_arena.used;
+  Carver real{S->arena, Bz, &S->bufs};
+  carve(real);
+  if (S->arena.used != probe_arena.used || !real.ok) {
+    cpl_solver_destroy(S);
+    return fail(CPL_ERR_RUNTIME, "cpl_solver_create: the buffer carve is inconsistent");
+  }
   // constants up, zero buffers
   std::vector<int64_t> f64(free_idx.begin(), free_idx.end()), x64(fixed_idx.begin(), fixed_idx.end());
   struct Up { void* dst; const void* src; size_t bytes; };
@@ -3361,18 +3362,12 @@ int32_t cpl_solver_solve(cpl_solver* S, const double* d_x0, const double* d_mass
   if (d_env_tag) HK(hipMemcpyAsync(S->tag_c, d_env_tag, (size_t)B, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync tag");
   hipLaunchKernelGGL(k_iota, dim3(blocks_elems(B)), dim3(256), 0, st, B, S->orig);
   LAUNCHED("k_iota");
-  // per-instance flags of the line search and the restoration phase start cleared
-  HK(hipMemsetAsync(S->in_soft, 0, (size_t)B, st), "hipMemsetAsync");
-  HK(hipMemsetAsync(S->tiny_last, 0, (size_t)B, st), "hipMemsetAsync");
-  HK(hipMemsetAsync(S->tiny_flag, 0, (size_t)B, st), "hipMemsetAsync");
-  HK(hipMemsetAsync(S->in_resto, 0, (size_t)B, st), "hipMemsetAsync");
-  HK(hipMemsetAsync(S->resto_tight, 0, (size_t)B, st), "hipMemsetAsync");
-  HK(hipMemsetAsync(S->fbest, 0, (size_t)B, st), "hipMemsetAsync");
-  HK(hipMemsetAsync(S->has_acc, 0, (size_t)B, st), "hipMemsetAsync");
+  // the buffers carved ZEROED (per-instance flags and counts of the line search and the restoration
+  // phase) start cleared; the best iterate's objective starts at +inf
+  for (const BufRec& r : S->bufs)
+    if (r.zeroed) HK(hipMemsetAsync(r.ptr, 0, r.elem * (size_t)(B * r.width), st), "hipMemsetAsync");
   hipLaunchKernelGGL(k_fill, dim3(blocks_elems(B)), dim3(256), 0, st, B, INFINITY, S->best_f);
   LAUNCHED("k_fill best_f");
-  HK(hipMemsetAsync(S->soft_cnt, 0, 4 * (size_t)B, st), "hipMemsetAsync");
-  HK(hipMemsetAsync(S->n_resto, 0, 8 * (size_t)B, st), "hipMemsetAsync");
   int64_t evals = 0;
   if (S->fd && (d_mass || d_env_tag)) {
     hipLaunchKernelGGL(k_repeat, dim3(blocks_elems(B * 2 * nf)), dim3(256), 0, st, B, 2 * nf, S->mass, S->mass_fd,

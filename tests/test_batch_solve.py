@@ -410,24 +410,121 @@ def test_batch_solve_gpu_limited_memory_eight_contacts():
     np.testing.assert_allclose(obj, objc, rtol=1e-6)
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("hessian", ["exact", "limited-memory"])
-def test_active_set_compaction_is_exact(hessian):
-    """The native engine's active-set compaction (the lock-step batch shrinks to its active
-    instances) leaves every instance's iterates untouched: the same x, y, status and iteration
-    counts, bit for bit, as the solve that keeps every row to the end."""
+_SOLVE_FIELDS = ("x", "y", "status", "iterations", "objective", "primal_inf", "dual_inf", "restorations")
+
+
+def _assert_compaction_is_exact(prob, X0, mass, tag=None, fields=_SOLVE_FIELDS, **kw):
+    """The same inputs solved with and without compaction: at least one compaction in the first run,
+    none in the second, every field of `fields` bitwise equal.  Returns the two results."""
     from centroidalplanner_amd.batch_ipm import KernelEvaluator
 
-    cpl = solve_problem()
-    prob = cpl.GetCplProblem()
-    B = 1024
-    X0, mass = solve_inputs(prob, B, seed=13)
     dev = torch.device("cuda:0")
     X0t, mt = torch.as_tensor(X0, device=dev), torch.as_tensor(mass, device=dev)
-    a = batch_ipm_solve(prob, X0t, mt, evaluator=KernelEvaluator(prob), max_iter=1000, hessian=hessian, compact=True)
-    b = batch_ipm_solve(prob, X0t, mt, evaluator=KernelEvaluator(prob), max_iter=1000, hessian=hessian, compact=False)
+    tt = None if tag is None else torch.as_tensor(tag, device=dev)
+    a, b = (batch_ipm_solve(prob, X0t, mt, evaluator=KernelEvaluator(prob, env_tag=tt), max_iter=1000, compact=c, **kw)
+            for c in (True, False))
+    print("compactions", a.compactions, b.compactions, "final rows", a.final_rows, "iterations run", a.iterations_run,
+          "iterations", np.bincount(a.iterations.cpu().numpy()).nonzero()[0])
     assert a.compactions >= 1 and b.compactions == 0
-    for k in ("x", "y", "status", "iterations", "objective", "primal_inf", "dual_inf"):
+    for k in fields:
+        assert torch.equal(getattr(a, k), getattr(b, k)), k
+    return a, b
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hessian,fallback_viol_tol", [("exact", 0.0), ("limited-memory", 0.0), ("exact", 1e-6)],
+                         ids=["exact", "limited-memory", "exact-fallback"])
+def test_active_set_compaction_is_exact(hessian, fallback_viol_tol):
+    """The native engine's active-set compaction (the lock-step batch shrinks to its active
+    instances) leaves every instance's iterates untouched: the same x, y, status and iteration
+    counts, bit for bit, as the solve that keeps every row to the end.  With fallback_viol_tol the best
+    feasible iterate travels with its row (best_w, best_f) and the full-batch flag does not (fbest):
+    a mistake in the class of either (state / full) shows in `fallback` or in x."""
+    prob = solve_problem().GetCplProblem()
+    X0, mass = solve_inputs(prob, 1024, seed=13)
+    fields = _SOLVE_FIELDS + (("fallback",) if fallback_viol_tol > 0.0 else ())
+    _assert_compaction_is_exact(prob, X0, mass, fields=fields, hessian=hessian, fallback_viol_tol=fallback_viol_tol)
+
+
+def _resto_batch():
+    """The Superquadric TestBasic scenario, B = 512 (the smallest batch that can compact: more than 256
+    rows, at most half of them active): 496 rows from the scenario's own start, which finish early, and
+    16 rows from x = 0, which enter the restoration phase in their first iteration and run far longer
+    (masses spread between the two of test_gpu_solve_engine's test_restoration_phase_device_matches_host)
+    — the x = 0 rows are among those a compaction moves."""
+    prob, x0, _ = _scenario("superquadric")
+    xl, xu, _, _ = prob.get_bounds_info()
+    X0 = np.tile(x0, (512, 1))
+    X0[-16:] = np.clip(np.zeros(prob.n), xl, xu)
+    mass = np.concatenate([np.random.default_rng(4).uniform(80.0, 150.0, 496), np.linspace(96.57673546, 100.0, 16)])
+    return prob, X0, mass
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hessian", ["analytic", "limited-memory"])
+def test_compaction_moves_live_restoration_state(hessian):
+    """Rows inside the restoration phase (wR, pR, nR, its multipliers, filter and references, in_resto,
+    resto_tight, the backup acceptable point) move in a compaction without a bit changing; with
+    "limited-memory" the model's rows (Hq, lm_s, lm_y, lm_cnt, lm_skip) move too.  A restoration or
+    limited-memory buffer carved as `temp` instead of `state` (so never gathered) fails here."""
+    prob, X0, mass = _resto_batch()
+    for r in _assert_compaction_is_exact(prob, X0, mass, hessian=hessian):
+        print("restorations of the x = 0 rows", r.restorations[-16:].cpu().numpy())
+        assert bool((r.restorations[-16:] >= 1).all())
+
+
+def _mixed_batch(B):
+    """test_gpu_sq_hessian's test_engine_mixed_analytic_converges template (the Superquadric scenario's
+    surface and position box, a ground plane at z = 0.6, force weight 1e-3), alternating tags, Ground
+    rows from the Ground workload's start and Superquadric rows from their scenario's own."""
+    import sq_hessian_ref as R
+    from centroidalplanner_amd import CentroidalPlanner
+    from centroidalplanner_amd.problem import Ground, MixedEnvironment, Superquadric
+    from centroidalplanner_amd.workload import ENV_GROUND, ENV_SUPERQUADRIC
+
+    names = ["contact1", "contact2", "contact3", "contact4"]
+    g, s = Ground(), Superquadric()
+    g.SetGroundZ(0.6)
+    s.SetParameters(*(np.array(v) for v in R.PARAM_SETS["testbasic"]))
+    env = MixedEnvironment(g, s)
+    env.SetMu(MU)
+    cpl = CentroidalPlanner(names, 100.0, env)
+    cpl.SetForceWeight(1e-3)
+    for c in names:
+        cpl.SetPosBounds(c, np.array([-0.5, -0.5, 0.5]), np.array([0.5, 0.5, 1.5]))
+    cpl.SetManipulationWrench(WRENCH)
+    prob = cpl.GetCplProblem()
+    tag = np.where(np.arange(B) % 2 == 0, ENV_GROUND, ENV_SUPERQUADRIC).astype(np.uint8)
+    Xg, mass = solve_inputs(prob, B, seed=12)
+    _, xs, _ = _scenario("superquadric")
+    xl, xu, _, _ = prob.get_bounds_info()
+    X0 = np.where((tag == ENV_SUPERQUADRIC)[:, None], np.clip(xs, xl, xu)[None], Xg)
+    return prob, X0, mass, tag
+
+
+@pytest.mark.gpu
+def test_compaction_moves_tags_and_masses():
+    """A mixed batch of 512 (alternating tags: the 1 : 1 mix) with per-instance masses under "analytic":
+    after a compaction every remaining row must still be evaluated with its own environment and mass
+    (tag_c, mass_c).  Either carved without its condition (IF_TAG / IF_MASS), or as `temp`, fails here."""
+    prob, X0, mass, tag = _mixed_batch(512)
+    _assert_compaction_is_exact(prob, X0, mass, tag=tag, hessian="analytic")
+
+
+@pytest.mark.gpu
+def test_solver_handle_is_reusable():
+    """One engine handle, the restoration batch solved twice: the second solve must not see what the
+    first left behind (the x = 0 rows leave in_resto, has_acc, resto_tight, soft_cnt and n_resto
+    dirty).  A buffer that lost its ZEROED mark where it is carved fails here."""
+    from centroidalplanner_amd.batch_ipm import NativeSolver
+
+    prob, X0, mass = _resto_batch()
+    dev = torch.device("cuda:0")
+    X0t, mt = torch.as_tensor(X0, device=dev), torch.as_tensor(mass, device=dev)
+    ns = NativeSolver(prob, 512, max_iter=1000, hessian="analytic")
+    a, b = ns.solve(X0t, mt), ns.solve(X0t, mt)
+    assert bool((a.restorations[-16:] >= 1).all())
+    for k in _SOLVE_FIELDS:
         assert torch.equal(getattr(a, k), getattr(b, k)), k
 
 
