@@ -96,6 +96,17 @@ class SolveOptions(ctypes.Structure):
     ]
 
 
+class InstanceDataC(ctypes.Structure):
+    """cpl_instance_data (include/cpl_mi355x.h): device pointers, any may be NULL."""
+
+    _fields_ = [
+        ("d_wrench", c_void_p),
+        ("d_com_ref", c_void_p),
+        ("d_p_ref", c_void_p),
+        ("d_F_ref", c_void_p),
+    ]
+
+
 class DerivativeReport(ctypes.Structure):
     """cpl_derivative_report (include/cpl_mi355x.h)."""
 
@@ -152,6 +163,12 @@ SIGNATURES = {
         c_int32,
         [_DESC_P, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
          c_void_p],
+    ),
+    "cpl_instance_data_sizeof": (c_size_t, []),
+    "cpl_eval_batch_inst": (
+        c_int32,
+        [_DESC_P, c_int64, c_void_p, c_void_p, c_void_p, POINTER(InstanceDataC), c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_int32, c_void_p],
     ),
     "cpl_jac_fold_info": (c_int32, [_DESC_P, _IP, _IP, _IP, _IP, _DP]),
     "cpl_time_eval_batch_ex": (
@@ -214,6 +231,8 @@ SIGNATURES = {
     "cpl_solver_create": (c_int32, [_DESC_P, c_int64, POINTER(SolveOptions), POINTER(c_void_p)]),
     "cpl_solver_destroy": (c_int32, [c_void_p]),
     "cpl_solver_solve": (c_int32, [c_void_p] + [c_void_p] * 10 + [POINTER(c_int32), POINTER(c_int64), c_void_p]),
+    "cpl_solver_solve_inst": (c_int32, [c_void_p] * 4 + [POINTER(InstanceDataC), c_int32] + [c_void_p] * 7
+                              + [POINTER(c_int32), POINTER(c_int64), c_void_p]),
     "cpl_solver_dims": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
     "cpl_solver_stats": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int64)]),
     "cpl_solver_restorations": (c_int32, [c_void_p, c_void_p, c_void_p]),

@@ -65,6 +65,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import INF
+from .problem import InstanceData
 
 EPS = float(np.finfo(np.float64).eps)
 LM_HIST, LM_MAX_SKIP = 6, 2  # IPOPT limited_memory_max_history / limited_memory_max_skipping
@@ -112,23 +113,26 @@ class KernelEvaluator:
     cpl_eval_batch launch on device-resident tensors (CplProblem.eval_batch raises unless the
     inputs are CUDA tensors and the HIP library is loaded — there is no CPU fallback)."""
 
-    def __init__(self, problem, env_tag=None):
+    def __init__(self, problem, env_tag=None, instance=None):
         self.problem = problem
         self.env_tag = env_tag
+        self.instance = instance  # per-instance wrench / references (InstanceData, cpl_eval_batch_inst)
         self.calls = 0
 
     def __call__(self, X, mass, outputs=("g", "jac", "f", "grad"), jac_folded=False):
         """jac_folded: values-only Jacobian records (CPL_EVAL_JAC_FOLDED; CplProblem.jac_fold_info)."""
         self.calls += 1
-        return self.problem.eval_batch(X, mass, self.env_tag, outputs=outputs, jac_folded=jac_folded)
+        return self.problem.eval_batch(X, mass, self.env_tag, outputs=outputs, jac_folded=jac_folded,
+                                       instance=self.instance)
 
     def lagrangian_grad(self, X, mass, y, y_repeat, csc, active=None):
         """grad f + J^T y of every instance in one fused launch (cpl_eval_lagrangian_grad: the
         Jacobian stays in LDS); None where the fused path does not exist (Superquadric / mixed
-        batches: the caller takes eval + cpl_lagrangian_grad, the same result)."""
+        batches: the caller takes eval + cpl_lagrangian_grad, the same result) — nor with instance data:
+        cpl_eval_lagrangian_grad evaluates the template, and the unfused evaluation honours `instance`."""
         import torch
 
-        if getattr(self, "_no_fused", False):
+        if getattr(self, "_no_fused", False) or (self.instance is not None and self.instance):
             return None
         out = torch.empty(X.shape[0], X.shape[1], dtype=torch.float64, device=X.device)
         st = _abi.lib.cpl_eval_lagrangian_grad(
@@ -222,7 +226,10 @@ class NativeSolver:
             _abi.lib.cpl_solver_destroy(h)
             self.handle = None
 
-    def solve(self, X0, mass=None, env_tag=None) -> "BatchSolveResult":
+    def solve(self, X0, mass=None, env_tag=None, instance=None, fixed_from_x0=False) -> "BatchSolveResult":
+        """instance: per-instance wrench / cost references (InstanceData); fixed_from_x0: every variable
+        the template fixes (lb == ub) takes instance b's value from X0[b] instead of the template's
+        bound (cpl_solver_solve_inst)."""
         import torch
 
         n, m, _ = self.problem.get_nlp_info()
@@ -247,10 +254,19 @@ class NativeSolver:
         obj, pinf, dinf = (torch.empty(B, dtype=torch.float64, device=dev) for _ in range(3))
         it = ctypes.c_int32()
         ev = ctypes.c_int64()
-        _abi.check(_abi.lib.cpl_solver_solve(
-            self.handle, _ptr(X0), None if mass is None else _ptr(mass), None if env_tag is None else _ptr(env_tag),
-            _ptr(x), _ptr(y), _ptr(status), _ptr(iters), _ptr(obj), _ptr(pinf), _ptr(dinf), ctypes.byref(it),
-            ctypes.byref(ev), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        if (instance is not None and instance) or fixed_from_x0:
+            inst = (instance if instance is not None else InstanceData()).validated(B, len(self.problem.contact_names), dev)
+            cs = inst.c_struct()
+            _abi.check(_abi.lib.cpl_solver_solve_inst(
+                self.handle, _ptr(X0), None if mass is None else _ptr(mass), None if env_tag is None else _ptr(env_tag),
+                ctypes.byref(cs), 1 if fixed_from_x0 else 0, _ptr(x), _ptr(y), _ptr(status), _ptr(iters), _ptr(obj),
+                _ptr(pinf), _ptr(dinf), ctypes.byref(it), ctypes.byref(ev),
+                ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        else:
+            _abi.check(_abi.lib.cpl_solver_solve(
+                self.handle, _ptr(X0), None if mass is None else _ptr(mass), None if env_tag is None else _ptr(env_tag),
+                _ptr(x), _ptr(y), _ptr(status), _ptr(iters), _ptr(obj), _ptr(pinf), _ptr(dinf), ctypes.byref(it),
+                ctypes.byref(ev), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         g = ctypes.c_int32()
         _abi.check(_abi.lib.cpl_solver_dims(self.handle, None, None, ctypes.byref(g)))
         nc, rows = ctypes.c_int32(), ctypes.c_int64()
@@ -299,7 +315,7 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
                     ls_kernel: int = 2, fallback_viol_tol: float = 0.0,
                     nlp_scaling: str = "gradient-based", jacobian_regularization: str = "pivot",
                     watchdog: bool = False, watchdog_trigger: int = 10,
-                    watchdog_trial_max: int = 3) -> BatchSolveResult:
+                    watchdog_trial_max: int = 3, instance=None, fixed_from_x0: bool = False) -> BatchSolveResult:
     """Solve B instances of `problem`'s template from the starting points X0 [B, n] (torch float64,
     device tensor), per-instance robot masses `mass` [B] (None: the template's).
 
@@ -341,7 +357,11 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
     consecutive shortened steps the iterate and its step are kept; the next iterations take their full
     step judged against the kept iterate's references, a success ends it, the (trial_max + 1)-th failure
     restores the kept iterate and backtracks along its step from alpha_max / 2; a barrier change or the
-    restoration phase ends it."""
+    restoration phase ends it.
+    instance / fixed_from_x0 (device engine only): per-instance wrench and cost references
+    (InstanceData) and per-instance values of the variables the template fixes, taken from X0
+    (NativeSolver.solve, cpl_solver_solve_inst).  The host restatement is one template per call and
+    raises ValueError for either."""
     if hessian not in ("exact", "fd", "limited-memory", "analytic"):
         raise ValueError("hessian must be 'exact', 'fd', 'limited-memory' or 'analytic'")
     if nlp_scaling not in ("gradient-based", "none"):
@@ -364,11 +384,17 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
                      fd_step=fd_step, graph=True if graph is None else bool(graph), compact=compact,
                      ls_kernel=ls_kernel, fallback_viol_tol=fallback_viol_tol, nlp_scaling=nlp_scaling,
                      jacobian_regularization=jacobian_regularization)
-        r = ns.solve(X0, mass, None if evaluator is None else evaluator.env_tag)
+        if instance is None and evaluator is not None:
+            instance = evaluator.instance
+        r = ns.solve(X0, mass, None if evaluator is None else evaluator.env_tag, instance=instance,
+                     fixed_from_x0=fixed_from_x0)
         if evaluator is not None:
             evaluator.calls += r.evaluations
         return r
 
+    if (instance is not None and instance) or fixed_from_x0:
+        raise ValueError("instance / fixed_from_x0: the device engine only (the host restatement solves one "
+                         "template per call: loop over the instances)")
     # host tensors: this module's restatement, step for step, of the engine's iteration — the checker
     # of the device path over any evaluator's callbacks (tests drive it with the oracle's)
     ev = evaluator if evaluator is not None else KernelEvaluator(problem)

@@ -235,6 +235,14 @@ struct LsBacktrackArgs {
   // 2 the marked — large batches run the two in separate instantiations (the default one keeps its
   // occupancy), small ones all in the AUGR one
   int32_t aug_sel = 0;
+  // a solve with instance data (set by ls_backtrack, read by the per-instance instantiations only):
+  // the solver's copies of cpl_instance_data's arrays in the rows' order (null: the template's values)
+  // and the doubles offset of the instance's 6 + 3 + 6N values in the kernel's LDS image
+  const double* inst_wrench = nullptr;
+  const double* inst_com_ref = nullptr;
+  const double* inst_p_ref = nullptr;
+  const double* inst_F_ref = nullptr;
+  int32_t inst_off = 0;
 };
 
 // s + sum_{r < m} a[r * stride] * v[r], accumulated in r order exactly as the plain loop

@@ -994,14 +994,36 @@ __device__ __forceinline__ void contact_item(const KParams& K, const double* __r
   }
 }
 
+// Where the statics / cost items read the manipulation wrench and the cost references from.
+// TemplateSrc (the default of every item): the kernarg template, one value for the whole batch.
+// InstSrc: one instance's own values, staged by the caller (LDS): wrench [6], com_ref [3], p_ref and
+// F_ref [N][3] in contact_names (vector) order — cpl_instance_data's records.
+struct TemplateSrc {
+  __device__ __forceinline__ double wrench(const KParams& K, int t) const { return K.wrench[t]; }
+  __device__ __forceinline__ double com_ref(const KParams& K, int a) const { return K.com_ref[a]; }
+  __device__ __forceinline__ double p_ref(const KParams& K, int i, int a) const { return K.p_ref[i][a]; }
+  __device__ __forceinline__ double F_ref(const KParams& K, int i, int a) const { return K.F_ref[i][a]; }
+};
+struct InstSrc {
+  const double* w;
+  const double* c;
+  const double* p;
+  const double* F;
+  __device__ __forceinline__ double wrench(const KParams&, int t) const { return w[t]; }
+  __device__ __forceinline__ double com_ref(const KParams&, int a) const { return c[a]; }
+  __device__ __forceinline__ double p_ref(const KParams&, int i, int a) const { return p[3 * i + a]; }
+  __device__ __forceinline__ double F_ref(const KParams&, int i, int a) const { return F[3 * i + a]; }
+};
+
 // CentroidalStatics::GetValues (src/Constraints/CentroidalStatics.cpp:37-61) and Jacobian rows 0-2
 // (the I3 of every F_i, :93-95)
 // pairs_j: the torque rows' CoM pairs written straight to their Jacobian entries (row q's first two)
 // instead of com6 — the Superquadric tile, whose cone items write the rows' per-contact entries
+template <class SRC = TemplateSrc>
 __device__ __forceinline__ void statics_values_item(const KParams& K, const double* __restrict__ xr, double m_i,
                                                     double* __restrict__ Gr, double* __restrict__ Jr,
                                                     bool with_j = true, double* __restrict__ com6 = nullptr,
-                                                    bool pairs_j = false) {
+                                                    bool pairs_j = false, const SRC& src = SRC()) {
   const int N = K.N;
   if (pairs_j && K.want_j) {
     com6 = Jr + (K.fold == FOLD_NONE ? 3 * N : 0);  // row q's pair at com6[q * (2 + 4N) + {0, 1}]
@@ -1052,8 +1074,8 @@ __device__ __forceinline__ void statics_values_item(const KParams& K, const doub
       }
     }
     if (vals) {
-      v0 -= K.wrench[0]; v1 -= K.wrench[1]; v2 -= K.wrench[2];
-      v3 -= K.wrench[3]; v4 -= K.wrench[4]; v5 -= K.wrench[5];
+      v0 -= src.wrench(K, 0); v1 -= src.wrench(K, 1); v2 -= src.wrench(K, 2);
+      v3 -= src.wrench(K, 3); v4 -= src.wrench(K, 4); v5 -= src.wrench(K, 5);
       v0 += m_i * K.gravity[0]; v1 += m_i * K.gravity[1]; v2 += m_i * K.gravity[2];
       Gr[0] = v0; Gr[1] = v1; Gr[2] = v2; Gr[3] = v3; Gr[4] = v4; Gr[5] = v5;
     }
@@ -1130,39 +1152,42 @@ __device__ __forceinline__ void statics_row_item(const KParams& K, const double*
 }
 
 // MinimizeCentroidalVariables::GetCost / FillJacobianBlock, src/MinimizeCentroidalVariables.cpp:124-192
-__device__ __forceinline__ double cost_value(const KParams& K, const double* __restrict__ xr) {
+template <class SRC = TemplateSrc>
+__device__ __forceinline__ double cost_value(const KParams& K, const double* __restrict__ xr, const SRC& src = SRC()) {
   const int N = K.N;
   double value = 0;
   for (int k = 0; k < N; ++k) {
     const int i = s_ct.map_order[k];
     const double* q = xr + 3 + 9 * i;
-    const double e0 = q[3] - K.p_ref[i][0], e1 = q[4] - K.p_ref[i][1], e2 = q[5] - K.p_ref[i][2];
-    const double h0 = q[0] - K.F_ref[i][0], h1 = q[1] - K.F_ref[i][1], h2 = q[2] - K.F_ref[i][2];
+    const double e0 = q[3] - src.p_ref(K, i, 0), e1 = q[4] - src.p_ref(K, i, 1), e2 = q[5] - src.p_ref(K, i, 2);
+    const double h0 = q[0] - src.F_ref(K, i, 0), h1 = q[1] - src.F_ref(K, i, 1), h2 = q[2] - src.F_ref(K, i, 2);
     value += 0.5 * K.W_p[i] * ((e0 * e0 + e1 * e1) + e2 * e2) + 0.5 * K.W_F[i] * ((h0 * h0 + h1 * h1) + h2 * h2);
   }
-  const double r0 = xr[0] - K.com_ref[0], r1 = xr[1] - K.com_ref[1], r2 = xr[2] - K.com_ref[2];
+  const double r0 = xr[0] - src.com_ref(K, 0), r1 = xr[1] - src.com_ref(K, 1), r2 = xr[2] - src.com_ref(K, 2);
   value += 0.5 * K.W_com * ((r0 * r0 + r1 * r1) + r2 * r2);
   return value;
 }
 
+template <class SRC = TemplateSrc>
 __device__ __forceinline__ void cost_item(const KParams& K, const double* __restrict__ xr, double* __restrict__ f,
-                                          double* __restrict__ Dr, const double* __restrict__ fscale = nullptr) {
+                                          double* __restrict__ Dr, const double* __restrict__ fscale = nullptr,
+                                          const SRC& src = SRC()) {
   const int N = K.N;
   const double c0 = xr[0], c1 = xr[1], c2 = xr[2];
-  if (K.want_f) *f = fscale ? cost_value(K, xr) * *fscale : cost_value(K, xr);
+  if (K.want_f) *f = fscale ? cost_value(K, xr, src) * *fscale : cost_value(K, xr, src);
   if (K.want_grad) {
-    Dr[0] = K.W_com * (c0 - K.com_ref[0]);
-    Dr[1] = K.W_com * (c1 - K.com_ref[1]);
-    Dr[2] = K.W_com * (c2 - K.com_ref[2]);
+    Dr[0] = K.W_com * (c0 - src.com_ref(K, 0));
+    Dr[1] = K.W_com * (c1 - src.com_ref(K, 1));
+    Dr[2] = K.W_com * (c2 - src.com_ref(K, 2));
     for (int i = 0; i < N; ++i) {
       const double* q = xr + 3 + 9 * i;
       double* d = Dr + 3 + 9 * i;
-      d[0] = K.W_F[i] * (q[0] - K.F_ref[i][0]);
-      d[1] = K.W_F[i] * (q[1] - K.F_ref[i][1]);
-      d[2] = K.W_F[i] * (q[2] - K.F_ref[i][2]);
-      d[3] = K.W_p[i] * (q[3] - K.p_ref[i][0]);
-      d[4] = K.W_p[i] * (q[4] - K.p_ref[i][1]);
-      d[5] = K.W_p[i] * (q[5] - K.p_ref[i][2]);
+      d[0] = K.W_F[i] * (q[0] - src.F_ref(K, i, 0));
+      d[1] = K.W_F[i] * (q[1] - src.F_ref(K, i, 1));
+      d[2] = K.W_F[i] * (q[2] - src.F_ref(K, i, 2));
+      d[3] = K.W_p[i] * (q[3] - src.p_ref(K, i, 0));
+      d[4] = K.W_p[i] * (q[4] - src.p_ref(K, i, 1));
+      d[5] = K.W_p[i] * (q[5] - src.p_ref(K, i, 2));
       d[6] = 0.0; d[7] = 0.0; d[8] = 0.0;
     }
   }
@@ -3274,6 +3299,141 @@ static int32_t launch_eval(const EvalCall& c) {
 }
 
 // ------------------------------------------------------------------------------------------
+// The instance overlay (cpl_eval_batch_inst, the solve engine with instance data): the outputs that
+// depend on cpl_instance_data — the six statics values g[0:6], f and grad f — of every instance, from
+// x, the mass and the instance's own wrench / references, through the same items as the evaluation
+// kernels with the per-instance source (InstSrc).  It runs after the template's evaluation on the
+// same stream and overwrites that kernel's six template statics values per instance; the Jacobian
+// and the other rows of g do not depend on the instance data.
+// One 256-thread workgroup per tile of T consecutive instances (T even, at most 64, sized by the host to
+// the tile kernel's LDS budget: 8 (2n + 16 + 6N) bytes per instance, so 52 instances of 4 contacts and
+// 14 of 16 in the default 48 KiB): the tile's x records and instance data copied into LDS with 16-byte accesses,
+// one item per thread (instance r's statics values, instance r's cost), the tile's grad / f images
+// copied out linearly and the six g values of each record as three 16-byte stores (m is even).
+// A NULL instance array is staged from the template, so every item reads LDS.
+struct InstPtrs {
+  const double *wrench, *com_ref, *p_ref, *F_ref;  // cpl_instance_data's arrays (device; any may be null)
+  bool any() const { return wrench || com_ref || p_ref || F_ref; }
+};
+
+template <bool NT>
+__global__ __launch_bounds__(256) void cpl_inst_overlay_kernel(const KParams K, int64_t batch,
+                                                               const double* __restrict__ x,
+                                                               const double* __restrict__ mass, const InstPtrs I,
+                                                               double* __restrict__ g_out, double* __restrict__ f_out,
+                                                               double* __restrict__ grad_out) {
+  extern __shared__ __align__(16) double smem[];
+  if (K.gate && *K.gate == 0) return;  // (every thread of every workgroup: the same byte)
+  const int tid = threadIdx.x;
+  const int T = K.T, n = K.n, m = K.m, N = K.N;
+  const int64_t b0 = (int64_t)blockIdx.x * T;
+  if (b0 >= batch) return;
+  const int valid = (int)((batch - b0) < T ? (batch - b0) : T);
+  double* X = smem;              // [T][n]
+  double* Dt = X + T * n;        // [T][n]   grad f
+  double* G6 = Dt + T * n;       // [T][6]   statics values
+  double* Fv = G6 + T * 6;       // [T]      f
+  double* Wl = Fv + T;           // [T][6]   wrench
+  double* Cl = Wl + T * 6;       // [T][3]   com_ref
+  double* Pl = Cl + T * 3;       // [T][3N]  p_ref
+  double* Fl = Pl + T * 3 * N;   // [T][3N]  F_ref
+  load_ctab(K);
+  auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  // (T even: every tile's first record of every array is 16-byte aligned when the array is)
+  copy_in<256>(X, x + b0 * n, valid * n, tid, aligned(x));
+  if (I.wrench) copy_in<256>(Wl, I.wrench + b0 * 6, valid * 6, tid, aligned(I.wrench));
+  else for (int e = tid; e < valid * 6; e += 256) Wl[e] = K.wrench[e % 6];
+  if (I.com_ref) copy_in<256>(Cl, I.com_ref + b0 * 3, valid * 3, tid, aligned(I.com_ref));
+  else for (int e = tid; e < valid * 3; e += 256) Cl[e] = K.com_ref[e % 3];
+  if (I.p_ref) copy_in<256>(Pl, I.p_ref + b0 * 3 * N, valid * 3 * N, tid, aligned(I.p_ref));
+  else for (int e = tid; e < valid * 3 * N; e += 256) Pl[e] = K.p_ref[(e % (3 * N)) / 3][e % 3];
+  if (I.F_ref) copy_in<256>(Fl, I.F_ref + b0 * 3 * N, valid * 3 * N, tid, aligned(I.F_ref));
+  else for (int e = tid; e < valid * 3 * N; e += 256) Fl[e] = K.F_ref[(e % (3 * N)) / 3][e % 3];
+  __syncthreads();
+  // one item per thread: (instance r, statics values | cost) — 2 T <= 128 items: half the workgroup
+  // computes, all of it copies (the kernel is its copies: 2 n + 16 + 6 N doubles moved per instance)
+  for (int e = tid; e < 2 * valid; e += 256) {
+    const int r = e >> 1;
+    const InstSrc src{Wl + r * 6, Cl + r * 3, Pl + r * 3 * N, Fl + r * 3 * N};
+    const double* xr = X + r * n;
+    if ((e & 1) == 0) {
+      if (K.want_g)
+        statics_values_item<InstSrc>(K, xr, mass ? mass[b0 + r] : K.mass_default, G6 + r * 6, nullptr, false, nullptr,
+                                     false, src);
+    } else {
+      cost_item<InstSrc>(K, xr, Fv + r, Dt + r * n, nullptr, src);
+    }
+  }
+  __syncthreads();
+  if (K.want_grad) copy_out<256, NT>(grad_out + b0 * n, Dt, valid * n, tid);
+  if (K.want_f) copy_out<256, NT>(f_out + b0, Fv, valid, tid);
+  if (K.want_g) {
+    if (aligned(g_out)) {  // (m even: g[0:6] of every record is three aligned pairs)
+      for (int e = tid; e < valid * 3; e += 256) {
+        const int r = e / 3, q = e - r * 3;
+        const double2 v = reinterpret_cast<const double2*>(G6)[e];
+        double2* dst = reinterpret_cast<double2*>(g_out + (b0 + r) * m) + q;
+        if (NT) {
+          __builtin_nontemporal_store(v.x, &dst->x);
+          __builtin_nontemporal_store(v.y, &dst->y);
+        } else {
+          *dst = v;
+        }
+      }
+    } else {
+      for (int e = tid; e < valid * 6; e += 256) g_out[(b0 + e / 6) * m + e % 6] = G6[e];
+    }
+  }
+}
+
+// the overlay's launch: g (its first six values per record), f, grad — any may be null
+static int32_t launch_overlay(const cpl_problem_desc* d, int64_t batch, const double* x, const double* mass,
+                              const InstPtrs& I, double* g, double* f, double* grad, hipStream_t stream,
+                              const uint8_t* gate) {
+  if (batch <= 0 || (!g && !f && !grad)) return CPL_OK;
+  KParams K;
+  fill_params(d, K, x);
+  K.gate = gate;
+  K.want_g = g != nullptr; K.want_j = 0; K.want_f = f != nullptr; K.want_grad = grad != nullptr;
+  const size_t per = sizeof(double) * (size_t)(2 * K.n + 6 + 1 + 9 + 6 * K.N);
+  int T = (int)(tile_budget() / per) & ~1;  // (the tile kernel's LDS budget: 48 KiB by default)
+  K.T = T > 64 ? 64 : (T < 2 ? 2 : T);
+  const size_t lds = per * (size_t)K.T;
+  const int64_t grid = (batch + K.T - 1) / K.T;
+  if (grid > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "batch too large");
+  hipLaunchKernelGGL(g_nt ? cpl_inst_overlay_kernel<true> : cpl_inst_overlay_kernel<false>, dim3((unsigned)grid),
+                     dim3(256), lds, stream, K, batch, x, mass, I, g, f, grad);
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? hip_fail(e, "cpl_inst_overlay_kernel launch") : CPL_OK;
+}
+
+// the evaluation with instance data: the template's evaluation (whichever path launch_eval picks) with
+// f and grad switched off, the overlay on the same stream, then (norms) a pass over the finished g —
+// the fused norms would see the template's statics rows
+static int32_t launch_eval_inst(const EvalCall& c, const InstPtrs& I) {
+  if (!I.any()) return launch_eval(c);
+  if (c.flags & CPL_EVAL_SOA)
+    return fail(CPL_ERR_UNSUPPORTED, "instance data: entry-major (CPL_EVAL_SOA) outputs are not supported");
+  EvalCall t = c;
+  t.f = nullptr;
+  t.grad = nullptr;
+  t.norms = nullptr;
+  if (c.norms && !c.g) return fail(CPL_ERR_INVALID_ARGUMENT, "residual norms need the g output");
+  if (!c.g && !c.jac) {  // (launch_eval launches nothing without an output: its argument checks only)
+    int32_t st = validate_desc(c.d);
+    if (st) return st;
+    if (c.flags & ~(CPL_EVAL_JAC_FOLDED | CPL_EVAL_SOA)) return fail(CPL_ERR_INVALID_ARGUMENT, "unknown eval flags");
+    if (c.batch < 0) return fail(CPL_ERR_INVALID_ARGUMENT, "negative batch");
+    if (c.batch > 0 && !c.x) return fail(CPL_ERR_INVALID_ARGUMENT, "x is required");
+  } else if (int32_t st = launch_eval(t)) {
+    return st;
+  }
+  if (c.batch == 0) return c.norms ? launch_eval(c) : CPL_OK;  // (the empty batch's zero norms)
+  if (int32_t st = launch_overlay(c.d, c.batch, c.x, c.mass, I, c.g, c.f, c.grad, c.stream, c.gate)) return st;
+  return c.norms && c.finish ? cpl_residual_norms(c.d, c.batch, c.g, c.norms, c.stream) : CPL_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // The solve engine's backtracking line search after the first trial (cpl_accept.hpp
 // LsBacktrackArgs): one wave per instance, the instances not searching leave at once.  A trial point
 // x_t = unpack(w + alpha dw) is evaluated (f and g) by the eval work items of the tile kernel on this
@@ -3288,8 +3448,18 @@ static int32_t launch_eval(const EvalCall& c) {
 // AUGR (with FIRST; IPOPT's Jacobian regularisation on): a system marked rank deficient re-solves its
 // corrections with the augmented factors (kkt_aug_resolve_wave) — its own instantiation, because the
 // call raises the kernel's registers past two waves per SIMD; the default search keeps its occupancy
-template <int ENVK, bool RESTO, bool FIRST, bool GF = false, bool AUGR = false>
+// ENVKI = the environment kind, plus LS_INST for a solve with instance data (launched only then):
+// the instance's 6 + 3 + 6N doubles (wrench, com_ref, p_ref, F_ref; a null array: the template's
+// values) are staged once, before the first trial, into the LDS image at A.inst_off, lanes along the
+// records, and the trial points' statics / cost items read them there (InstSrc).  A bit of the first
+// argument instead of a new parameter: the instantiations without it keep their symbols and their
+// code (profiles/instance_data/resource_usage.txt).
+constexpr int LS_INST = 8;
+template <int ENVKI, bool RESTO, bool FIRST, bool GF = false, bool AUGR = false>
 __global__ __launch_bounds__(64) void cpl_ls_backtrack_kernel(const KParams K, const LsBacktrackArgs A) {
+  constexpr int ENVK = ENVKI & ~LS_INST;
+  constexpr bool INST = (ENVKI & LS_INST) != 0;
+  using SRC = typename std::conditional<INST, InstSrc, TemplateSrc>::type;
   extern __shared__ __align__(16) double smem[];
   __shared__ double s_f;
   const int64_t b = blockIdx.x;
@@ -3318,6 +3488,17 @@ __global__ __launch_bounds__(64) void cpl_ls_backtrack_kernel(const KParams K, c
     double* Dv = L + nL;  // (FIRST) the second-order correction's step
     double* kk = smem + ((n + m + 2 * nw + nL + 1) & ~1);  // (FIRST) the KKT re-solve's LDS image
     load_ctab(K);
+    SRC src;
+    if constexpr (INST) {
+      double* Q = smem + A.inst_off;
+      for (int e = lane; e < 6; e += 64) Q[e] = A.inst_wrench ? A.inst_wrench[b * 6 + e] : K.wrench[e];
+      for (int e = lane; e < 3; e += 64) Q[6 + e] = A.inst_com_ref ? A.inst_com_ref[b * 3 + e] : K.com_ref[e];
+      for (int e = lane; e < 3 * N; e += 64) {
+        Q[9 + e] = A.inst_p_ref ? A.inst_p_ref[b * 3 * N + e] : K.p_ref[e / 3][e % 3];
+        Q[9 + 3 * N + e] = A.inst_F_ref ? A.inst_F_ref[b * 3 * N + e] : K.F_ref[e / 3][e % 3];
+      }
+      src = InstSrc{Q, Q + 6, Q + 9, Q + 9 + 3 * N};  // (published by the barrier below)
+    }
     __syncthreads();
     const double* wb = A.w + b * nw;
     const double* db = A.dw + b * nw;
@@ -3345,8 +3526,8 @@ __global__ __launch_bounds__(64) void cpl_ls_backtrack_kernel(const KParams K, c
       if (ENVK != CPL_ENV_NONE && ENVK != CPL_ENV_GROUND && sq) {
         for (int it = lane; it < 3 * N + 2; it += 64) {
           if (it < 3 * N) sq_axis_item<ENVK == CPL_ENV_MIXED>(K, X, it / 3, it % 3, L + (it / 3) * SQ_L, G);
-          else if (it == 3 * N) statics_values_item(K, X, m_i, G, G);
-          else cost_item(K, X, &s_f, nullptr);
+          else if (it == 3 * N) statics_values_item<SRC>(K, X, m_i, G, G, true, nullptr, false, src);
+          else cost_item<SRC>(K, X, &s_f, nullptr, nullptr, src);
         }
         __syncthreads();
         for (int it = lane; it < 3 * N; it += 64) sq_row_item<ENVK == CPL_ENV_MIXED>(K, X, it / 3, it % 3, L + (it / 3) * SQ_L, G, G);
@@ -3354,8 +3535,8 @@ __global__ __launch_bounds__(64) void cpl_ls_backtrack_kernel(const KParams K, c
         for (int it = lane; it < N + 2; it += 64) {
           if (it < N)
             contact_item<ENVK == CPL_ENV_NONE ? CPL_ENV_NONE : CPL_ENV_GROUND>(K, X, CPL_ENV_GROUND, it, G, G);
-          else if (it == N) statics_values_item(K, X, m_i, G, G);
-          else cost_item(K, X, &s_f, nullptr);
+          else if (it == N) statics_values_item<SRC>(K, X, m_i, G, G, true, nullptr, false, src);
+          else cost_item<SRC>(K, X, &s_f, nullptr, nullptr, src);
         }
       }
       __syncthreads();
@@ -3524,7 +3705,10 @@ constexpr int64_t LS_GF_MIN = 2048;  // batches from this size re-solve from the
 // global-factor form it would cost that kernel its second wave per SIMD (238 VGPRs + 24 AGPRs)
 bool ls_post_prologue(int64_t batch) { return batch < LS_GF_MIN; }
 
-int32_t ls_backtrack(const cpl_problem_desc* d, const LsBacktrackArgs& a, hipStream_t stream) {
+// inst (optional): the solve's instance data, [batch] rows in the rows' current order — the search then
+// runs the per-instance instantiations
+int32_t ls_backtrack(const cpl_problem_desc* d, const LsBacktrackArgs& a, hipStream_t stream,
+                     const cpl_instance_data* inst) {
   if (a.batch <= 0) return CPL_OK;
   if (a.batch > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "ls_backtrack: batch too large");
   KParams K;
@@ -3556,6 +3740,28 @@ int32_t ls_backtrack(const cpl_problem_desc* d, const LsBacktrackArgs& a, hipStr
                                     CPL_LS_KERNELS(false, true, false, false), CPL_LS_KERNELS(false, true, true, false),
                                     CPL_LS_KERNELS(false, true, false, true), CPL_LS_KERNELS(false, true, true, true)};
 #undef CPL_LS_KERNELS
+#define CPL_LS_KERNELS(R, F, G, AG)                                                \
+  {cpl_ls_backtrack_kernel<CPL_ENV_NONE | LS_INST, R, F, G, AG>,                   \
+   cpl_ls_backtrack_kernel<CPL_ENV_GROUND | LS_INST, R, F, G, AG>,                 \
+   cpl_ls_backtrack_kernel<CPL_ENV_SUPERQUADRIC | LS_INST, R, F, G, AG>,           \
+   cpl_ls_backtrack_kernel<CPL_ENV_MIXED | LS_INST, R, F, G, AG>}
+  static const KernT table_inst[6][4] = {
+      CPL_LS_KERNELS(false, false, false, false), CPL_LS_KERNELS(true, false, false, false),
+      CPL_LS_KERNELS(false, true, false, false),  CPL_LS_KERNELS(false, true, true, false),
+      CPL_LS_KERNELS(false, true, false, true),   CPL_LS_KERNELS(false, true, true, true)};
+#undef CPL_LS_KERNELS
+  const InstPtrs I = inst ? InstPtrs{inst->d_wrench, inst->d_com_ref, inst->d_p_ref, inst->d_F_ref} : InstPtrs{};
+  const bool with_inst = I.any();
+  const int inst_off = (int)((lds / sizeof(double) + 1) & ~(size_t)1);  // the instance's values past the image
+  if (with_inst) lds = sizeof(double) * ((size_t)inst_off + 9 + 6 * (size_t)K.N);
+  auto launch = [&](int row, LsBacktrackArgs args) {
+    if (with_inst) {
+      args.inst_wrench = I.wrench; args.inst_com_ref = I.com_ref; args.inst_p_ref = I.p_ref; args.inst_F_ref = I.F_ref;
+      args.inst_off = inst_off;
+    }
+    hipLaunchKernelGGL((with_inst ? table_inst : table)[row][K.env_kind], dim3((unsigned)a.batch), dim3(64), lds, stream,
+                       K, args);
+  };
   const bool augr = first && a.aug_ws && a.aug_dc;
   if (a.resto && (!a.pR || !a.nR || !a.dp || !a.dn || !a.wR || !a.st_p || !a.st_n))
     return fail(CPL_ERR_INVALID_ARGUMENT, "ls_backtrack: restoration search without its buffers");
@@ -3563,11 +3769,10 @@ int32_t ls_backtrack(const cpl_problem_desc* d, const LsBacktrackArgs& a, hipStr
     LsBacktrackArgs a1 = a, a2 = a;
     a1.aug_sel = 1;
     a2.aug_sel = 2;
-    hipLaunchKernelGGL(table[3][K.env_kind], dim3((unsigned)a.batch), dim3(64), lds, stream, K, a1);
-    hipLaunchKernelGGL(table[5][K.env_kind], dim3((unsigned)a.batch), dim3(64), lds, stream, K, a2);
+    launch(3, a1);
+    launch(5, a2);
   } else {
-    hipLaunchKernelGGL(table[first ? (gf ? 3 : 2) + (augr ? 2 : 0) : (a.resto ? 1 : 0)][K.env_kind],
-                       dim3((unsigned)a.batch), dim3(64), lds, stream, K, a);
+    launch(first ? (gf ? 3 : 2) + (augr ? 2 : 0) : (a.resto ? 1 : 0), a);
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, "cpl_ls_backtrack_kernel launch");
@@ -3597,11 +3802,30 @@ int32_t eval_batch_gated(const cpl_problem_desc* d, int64_t batch, const double*
   return launch_eval(c);
 }
 
+// (internal, the solve engine) the instance overlay alone: g[0:6], f, grad of every row from the
+// solver's own copies of the instance data; honours the gate byte
+int32_t eval_overlay(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
+                     const cpl_instance_data* inst, double* d_g, double* d_f, double* d_grad, void* stream,
+                     const uint8_t* gate) {
+  return launch_overlay(d, batch, d_x, d_mass, InstPtrs{inst->d_wrench, inst->d_com_ref, inst->d_p_ref, inst->d_F_ref},
+                        d_g, d_f, d_grad, (hipStream_t)stream, gate);
+}
+
 }  // namespace cpl
 
 using namespace cpl;
 
 extern "C" {
+
+size_t cpl_instance_data_sizeof(void) { return sizeof(cpl_instance_data); }
+
+int32_t cpl_eval_batch_inst(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
+                            const uint8_t* d_env_tag, const cpl_instance_data* inst, double* d_g, double* d_jac,
+                            double* d_f, double* d_grad, double* d_norms, int32_t flags, void* stream) {
+  const InstPtrs I = inst ? InstPtrs{inst->d_wrench, inst->d_com_ref, inst->d_p_ref, inst->d_F_ref} : InstPtrs{};
+  return launch_eval_inst(
+      EvalCall{d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, d_norms, (hipStream_t)stream, flags}, I);
+}
 
 int32_t cpl_eval_batch(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
                        const uint8_t* d_env_tag, double* d_g, double* d_jac, double* d_f, double* d_grad,

@@ -40,7 +40,13 @@ int32_t ipm_newton_setup_lm(int64_t batch, int32_t nw, int32_t m, int32_t nf, co
                             int32_t lm_pairs, double* d_M, double* d_r1, double* d_r2, double* d_gphi,
                             double* d_mr_diag, double* d_theta, double* d_phi, const uint8_t* d_active, void* stream);
 // cpl_kernels.hip: the backtracking line search after the first trial, one wave per instance
-int32_t ls_backtrack(const cpl_problem_desc* d, const LsBacktrackArgs& a, hipStream_t stream);
+// (inst: the solve's instance data in the rows' current order, or null — then the template's search)
+int32_t ls_backtrack(const cpl_problem_desc* d, const LsBacktrackArgs& a, hipStream_t stream,
+                     const cpl_instance_data* inst = nullptr);
+// cpl_kernels.hip: the instance overlay — g[0:6], f, grad of every row from its instance data
+int32_t eval_overlay(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
+                     const cpl_instance_data* inst, double* d_g, double* d_f, double* d_grad, void* stream,
+                     const uint8_t* gate);
 // cpl_kernels.hip: the NLP-scaled evaluation (pipelined kernel; CPL_ERR_UNSUPPORTED: not that path)
 int32_t eval_batch_scaled(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
                           const uint8_t* d_env_tag, double* d_g, double* d_jac, double* d_f, double* d_grad,
@@ -388,6 +394,19 @@ __global__ void k_unpack_tau(int64_t total, int n, int nw, const int32_t* __rest
     tau[b] = fmax(1.0 - mu[b], 0.99);
     act[b] = active[b] && !in_resto[b];  // the restoration phase's instances take their own step
   }
+}
+
+// X = unpack(w), the free variables clamped into [xl, xu]; the fixed ones keep Xbase's value (the
+// instance's own under fixed_from_x0, where the template's bound is not theirs)
+__global__ void k_unpack_free(int64_t total, int n, int nw, const int32_t* __restrict__ freepos,
+                              const double* __restrict__ Xbase, const double* __restrict__ w,
+                              const double* __restrict__ xl, const double* __restrict__ xu, double* __restrict__ X) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const int64_t b = e / n;
+  const int j = (int)(e - b * n);
+  const int k = freepos[j];
+  X[e] = k >= 0 ? fmin(fmax(w[b * nw + k], xl[j]), xu[j]) : Xbase[e];
 }
 
 // X = unpack(w) (optionally clamped into [xl, xu]: IPOPT honor_original_bounds)
@@ -2211,7 +2230,8 @@ struct Arena {
 //   temp   [B, width] by batch row, written before it is read within an iteration
 //   full   [B, width] by original instance (results, constant zeros)
 // ZEROED: cleared at the start of every solve.
-enum MoveWhen : uint8_t { NEVER, ALWAYS, IF_SCALED, IF_MASS, IF_TAG };  // (the solve is scaled / has masses / tags)
+// (the solve is scaled / has masses / tags / instance data)
+enum MoveWhen : uint8_t { NEVER, ALWAYS, IF_SCALED, IF_MASS, IF_TAG, IF_INST };
 constexpr bool ZEROED = true;
 struct BufRec { void* ptr; size_t elem; int64_t width; MoveWhen when; bool zeroed; };  // elem: bytes; width: per row
 struct Carver {
@@ -2252,7 +2272,7 @@ struct cpl_solver {
   double mu_min = 0.0;
   hipStream_t stream = nullptr;
   bool captured = false;  // an iteration graph exists
-  std::map<int64_t, std::pair<hipGraph_t, hipGraphExec_t>> graphs;  // (size, inputs, phase) -> graph
+  std::map<int64_t, std::pair<hipGraph_t, hipGraphExec_t>> graphs;  // (size, inputs given, phase) -> graph
   uint8_t* h_flag = nullptr;  // pinned: the device's 4 flag bytes
   cpl::Arena arena;
   std::vector<cpl::BufRec> bufs;  // the state buffers and the zeroed ones, in carve order (cpl::Carver)
@@ -2312,6 +2332,12 @@ struct cpl_solver {
   bool soft_begun = false;  // ... and the Newton phase's search kernel did (P_SOFT skips k_soft_begin)
   double *mass_c, *fw, *fy, *fX, *fdinf;
   uint8_t* tag_c;
+  // this solve's instance data (cpl_solver_solve_inst): the solver's own copies, by batch row (moved by
+  // the compaction with their rows); inst's pointers name them, null where the caller gave no array
+  // (the kernels then read the template's value)
+  double *inst_w, *inst_c, *inst_p, *inst_F;
+  cpl_instance_data inst = {nullptr, nullptr, nullptr, nullptr};
+  bool has_inst = false;
   int64_t *fstatus, *fiters, *fresto;
   uint64_t* scratch;
   int64_t scratch_words = 0;
@@ -2351,7 +2377,14 @@ int32_t apply_scaling(cpl_solver* S, double* fo, double* grado, double* go, doub
 }
 // (scaled: the pipelined evaluation applies the factors in its tile image — one launch fewer per
 // evaluation; other paths evaluate, then k_apply_scaling)
+// (instance data: the unfused route — the template's evaluation without f / grad, the overlay, then
+// k_apply_scaling; the overlay needs no scaling arguments)
 int32_t eval_fg(cpl_solver* S, const double* X, double* fo, double* go) {
+  if (S->has_inst) {
+    CK(cpl_eval_batch(&S->desc, S->Bcur, X, S->mass, S->tag, go, nullptr, nullptr, nullptr, S->stream));
+    CK(eval_overlay(&S->desc, S->Bcur, X, S->mass, &S->inst, go, fo, nullptr, S->stream, nullptr));
+    return apply_scaling(S, fo, nullptr, go, nullptr);
+  }
   if (S->scaled && S->sc_fused) {
     const int32_t rc = eval_batch_scaled(&S->desc, S->Bcur, X, S->mass, S->tag, go, nullptr, fo, nullptr, 0, S->df,
                                          S->dc, S->rrow, S->stream);
@@ -2366,6 +2399,12 @@ int32_t eval_fg(cpl_solver* S, const double* X, double* fo, double* go) {
 // an evaluation whose outputs nobody reads when the byte is 0)
 int32_t eval_full(cpl_solver* S, const double* X, double* fo, double* grado, double* go, double* jo,
                   const uint8_t* gate = nullptr) {
+  if (S->has_inst) {
+    CK(eval_batch_gated(&S->desc, S->Bcur, X, S->mass, S->tag, go, jo, nullptr, nullptr, CPL_EVAL_JAC_FOLDED, S->stream,
+                        gate));
+    CK(eval_overlay(&S->desc, S->Bcur, X, S->mass, &S->inst, go, fo, grado, S->stream, gate));
+    return apply_scaling(S, fo, grado, go, jo);
+  }
   if (S->scaled && S->sc_fused) {
     const int32_t rc = eval_batch_scaled(&S->desc, S->Bcur, X, S->mass, S->tag, go, jo, fo, grado,
                                          CPL_EVAL_JAC_FOLDED, S->df, S->dc, S->rrow, S->stream, gate);
@@ -2736,7 +2775,7 @@ int32_t step_phase(cpl_solver* S, int phase) {
       } else {  // the remaining trials of every instance still searching, in one launch
         HK(hipMemsetAsync(S->d_any, 0, 2, st), "hipMemsetAsync flags");
       }
-      return ls_backtrack(&S->desc, la, st);
+      return ls_backtrack(&S->desc, la, st, S->has_inst ? &S->inst : nullptr);
     }
     case P_SOFT: {
       const SoftStepArgs soft = soft_step_args(S);
@@ -2856,7 +2895,7 @@ int32_t step_phase(cpl_solver* S, int phase) {
         la.rho = RHO_R;
         la.pR = S->pR; la.nR = S->nR; la.dp = S->dp; la.dn = S->dn; la.wR = S->wR;
         la.st_p = S->st_p; la.st_n = S->st_n;
-        CK(ls_backtrack(&S->desc, la, st));
+        CK(ls_backtrack(&S->desc, la, st, S->has_inst ? &S->inst : nullptr));
       }
       return step_phase(S, P_RACCEPT);
     }
@@ -2906,7 +2945,12 @@ int32_t step_phase(cpl_solver* S, int phase) {
 // replayed); without graphs the phase is launched directly
 int32_t run_phase(cpl_solver* S, int phase) {
   if (!S->opt.use_graph) return step_phase(S, phase);
-  const int64_t key = ((S->Bcur * 8 + (S->scaled ? 4 : 0) + (S->mass ? 2 : 0) + (S->tag ? 1 : 0)) * 16) + phase;
+  // (a graph holds the pointers its launches were given: one bit per input that may be absent — the
+  // masses, the tags and each of the four instance arrays, whose slot is null when the caller gave none)
+  const int inst_bits = (S->inst.d_wrench ? 1 : 0) | (S->inst.d_com_ref ? 2 : 0) | (S->inst.d_p_ref ? 4 : 0) |
+                        (S->inst.d_F_ref ? 8 : 0);
+  const int64_t key =
+      ((S->Bcur * 128 + inst_bits * 8 + (S->scaled ? 4 : 0) + (S->mass ? 2 : 0) + (S->tag ? 1 : 0)) * 16) + phase;
   auto it = S->graphs.find(key);
   if (it == S->graphs.end()) {
     HK(hipStreamBeginCapture(S->stream, hipStreamCaptureModeRelaxed), "hipStreamBeginCapture");
@@ -2978,7 +3022,8 @@ int32_t compact(cpl_solver* S, int64_t count, int64_t Bn) {
   // every state buffer whose condition holds, gathered through the scratch and copied back
   for (const BufRec& r : S->bufs) {
     const bool moved = r.when == ALWAYS || (r.when == IF_SCALED && S->scaled) ||
-                       (r.when == IF_MASS && S->mass) || (r.when == IF_TAG && S->tag);
+                       (r.when == IF_MASS && S->mass) || (r.when == IF_TAG && S->tag) ||
+                       (r.when == IF_INST && S->has_inst);
     if (!moved || r.width <= 0) continue;
     const dim3 grid(blocks_elems(count * r.width)), blk(256);
     if (r.elem == 8)
@@ -3298,6 +3343,9 @@ int32_t cpl_solver_create(const cpl_problem_desc* d, int64_t batch, const cpl_so
   // compaction: each row's original instance, the gather's positions, this solve's masses / tags
   S->orig = c.state<int32_t>(1, ALWAYS); S->pos = c.temp<int32_t>(1); S->d_count = c.fixed<int32_t>(6);
   S->mass_c = c.state<double>(1, IF_MASS); S->tag_c = c.state<uint8_t>(1, IF_TAG);
+  S->inst_w = c.state<double>(6, IF_INST); S->inst_c = c.state<double>(3, IF_INST);
+  S->inst_p = c.state<double>(3 * (size_t)d->n_contacts, IF_INST);
+  S->inst_F = c.state<double>(3 * (size_t)d->n_contacts, IF_INST);
   S->fw = c.full<double>(nw); S->fy = c.full<double>(m); S->fX = c.full<double>(n);
   S->fdinf = c.full<double>(1); S->fstatus = c.full<int64_t>(1); S->fiters = c.full<int64_t>(1);
   S->fresto = c.full<int64_t>(1);
@@ -3344,9 +3392,22 @@ int32_t cpl_solver_create(const cpl_problem_desc* d, int64_t batch, const cpl_so
 int32_t cpl_solver_solve(cpl_solver* S, const double* d_x0, const double* d_mass, const uint8_t* d_env_tag, double* d_x,
                          double* d_y, int32_t* d_status, int32_t* d_iters, double* d_obj, double* d_primal_inf,
                          double* d_dual_inf, int32_t* iterations_run, int64_t* evaluations, void* stream) {
+  return cpl_solver_solve_inst(S, d_x0, d_mass, d_env_tag, nullptr, 0, d_x, d_y, d_status, d_iters, d_obj, d_primal_inf,
+                               d_dual_inf, iterations_run, evaluations, stream);
+}
+
+int32_t cpl_solver_solve_inst(cpl_solver* S, const double* d_x0, const double* d_mass, const uint8_t* d_env_tag,
+                              const cpl_instance_data* inst, int32_t fixed_from_x0, double* d_x, double* d_y,
+                              int32_t* d_status, int32_t* d_iters, double* d_obj, double* d_primal_inf,
+                              double* d_dual_inf, int32_t* iterations_run, int64_t* evaluations, void* stream) {
   if (!S || !d_x0) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_solve: missing solver or x0");
   if (S->desc.env_kind == CPL_ENV_MIXED && !d_env_tag)
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_solve: mixed batches need the env tags");
+  const bool has_inst = inst && (inst->d_wrench || inst->d_com_ref || inst->d_p_ref || inst->d_F_ref);
+  if (has_inst && S->fd)  // (the 2 nf perturbed points of every instance would need the arrays replicated)
+    return fail(CPL_ERR_UNSUPPORTED,
+                "cpl_solver_solve_inst: instance data needs a Hessian that is not central differences: create the "
+                "solver with CPL_HESSIAN_ANALYTIC or CPL_HESSIAN_LIMITED_MEMORY");
   const int64_t B = S->B;
   const int n = S->n, m = S->m, nf = S->nf, nw = S->nw;
   hipStream_t st = S->stream;
@@ -3360,6 +3421,20 @@ int32_t cpl_solver_solve(cpl_solver* S, const double* d_x0, const double* d_mass
   S->tag = d_env_tag ? S->tag_c : nullptr;
   if (d_mass) HK(hipMemcpyAsync(S->mass_c, d_mass, 8 * (size_t)B, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync mass");
   if (d_env_tag) HK(hipMemcpyAsync(S->tag_c, d_env_tag, (size_t)B, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync tag");
+  // ... and of the instance data, array by array (an array not given stays the template's value)
+  S->has_inst = has_inst;
+  S->inst = cpl_instance_data{nullptr, nullptr, nullptr, nullptr};
+  if (has_inst) {
+    const size_t N3 = 3 * (size_t)S->desc.n_contacts;
+    const struct { const double* src; double* dst; const double** slot; size_t width; } arrays[] = {
+        {inst->d_wrench, S->inst_w, &S->inst.d_wrench, 6}, {inst->d_com_ref, S->inst_c, &S->inst.d_com_ref, 3},
+        {inst->d_p_ref, S->inst_p, &S->inst.d_p_ref, N3}, {inst->d_F_ref, S->inst_F, &S->inst.d_F_ref, N3}};
+    for (const auto& a : arrays) {
+      if (!a.src) continue;
+      HK(hipMemcpyAsync(a.dst, a.src, 8 * (size_t)B * a.width, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync instance data");
+      *a.slot = a.dst;
+    }
+  }
   hipLaunchKernelGGL(k_iota, dim3(blocks_elems(B)), dim3(256), 0, st, B, S->orig);
   LAUNCHED("k_iota");
   // the buffers carved ZEROED (per-instance flags and counts of the line search and the restoration
@@ -3375,8 +3450,12 @@ int32_t cpl_solver_solve(cpl_solver* S, const double* d_x0, const double* d_mass
     LAUNCHED("k_repeat");
   }
   // starting point: x pushed into its bounds, slacks = g_I(x) pushed into theirs, least-squares y
-  hipLaunchKernelGGL(k_xbase, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, n, d_x0, S->is_fixed, S->xl, S->Xbase);
-  LAUNCHED("k_xbase");
+  if (fixed_from_x0) {  // k_xbase with the fixed entries from x0 as well: the copy
+    HK(hipMemcpyAsync(S->Xbase, d_x0, 8 * (size_t)(B * n), hipMemcpyDeviceToDevice, st), "hipMemcpyAsync x0");
+  } else {
+    hipLaunchKernelGGL(k_xbase, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, n, d_x0, S->is_fixed, S->xl, S->Xbase);
+    LAUNCHED("k_xbase");
+  }
   // IPOPT's gradient-based NLP scaling from the callbacks at the starting point (fixed variables at
   // their value); the iteration runs on the scaled problem when any instance has a factor != 1
   // (and the NaN Jacobian entries there: cpl_solver_nan_jacobian)
@@ -3479,10 +3558,16 @@ int32_t cpl_solver_solve(cpl_solver* S, const double* d_x0, const double* d_mass
   LAUNCHED("k_scatter_final");
   // IPOPT honor_original_bounds: the final point projected into the original bounds, re-evaluated
   double* Xf = d_x ? d_x : S->Xn;
-  hipLaunchKernelGGL(k_unpack, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, n, nw, S->freepos, S->fX, S->fw,
-                     S->xl, S->xu, Xf);
+  // (fixed_from_x0: the projection skips the fixed entries — the template's bound is not the instance's value)
+  hipLaunchKernelGGL(fixed_from_x0 ? k_unpack_free : k_unpack, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, n, nw,
+                     S->freepos, S->fX, S->fw, S->xl, S->xu, Xf);
   LAUNCHED("k_unpack (final)");
-  CK(cpl_eval_batch(&S->desc, B, Xf, d_mass, d_env_tag, S->fin_g, nullptr, d_obj ? d_obj : S->fin_f, nullptr, st));
+  // (the full batch in the instances' own order: the caller's masses, tags and instance data)
+  if (has_inst)
+    CK(cpl_eval_batch_inst(&S->desc, B, Xf, d_mass, d_env_tag, inst, S->fin_g, nullptr, d_obj ? d_obj : S->fin_f, nullptr,
+                           nullptr, 0, st));
+  else
+    CK(cpl_eval_batch(&S->desc, B, Xf, d_mass, d_env_tag, S->fin_g, nullptr, d_obj ? d_obj : S->fin_f, nullptr, st));
   ++evals;
   hipLaunchKernelGGL(k_final, dim3(blocks_for(B)), dim3(256), 0, st, B, m, S->fin_g, S->gl, S->gu, S->fstatus,
                      S->fiters, d_primal_inf, d_status, d_iters);

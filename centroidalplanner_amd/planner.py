@@ -118,6 +118,22 @@ class CentroidalPlanner:
             out.contact_values_map[name] = ContactValues(cv["force"], cv["position"], cv["normal"])
         return out
 
+    def SolveBatch(self, X0, mass=None, instance=None, fixed_from_x0: bool = False, **solve_options):
+        """Solve B instances of this planner's problem in one batched solve on the GPU (no reference
+        counterpart: B Solve() calls).  X0 [B, n]: float64 CUDA start points; mass [B]: per-instance
+        robot masses (None: the planner's); instance: per-instance manipulation wrench and cost
+        references (InstanceData); fixed_from_x0: every variable this planner fixes (lb == ub) takes
+        instance b's value from X0[b].  solve_options go to batch_ipm_solve (default hessian: the
+        planner's).  Returns the BatchSolveResult; the planner's own variables are left as they were."""
+        from .batch_ipm import batch_ipm_solve
+
+        opts = {"tol": self.solver_tol, "max_iter": self.solver_max_iter, "hessian": self.solver_hessian,
+                "jacobian_regularization": self.solver_jacobian_regularization}
+        opts.update(solve_options)
+        if not getattr(X0, "is_cuda", False):
+            raise ValueError("SolveBatch: X0 must be a float64 CUDA tensor [B, n]")
+        return batch_ipm_solve(self._cpl_problem, X0, mass=mass, instance=instance, fixed_from_x0=fixed_from_x0, **opts)
+
     # ---- validation helpers ------------------------------------------------------------------
     def HasContact(self, contact_name: str) -> bool:  # :359-370
         return contact_name in self._contact_names
@@ -315,6 +331,55 @@ class CoMPlanner:
     # using CentroidalPlanner::... (include/CentroidalPlanner/CoMPlanner.h:67-78)
     def Solve(self):
         return self._cp.Solve()
+
+    def SolveBatch(self, positions, normals=None, com_ref=None, wrench=None, mass=None, **solve_options):
+        """The stance query, batched: are these B candidate stances statically feasible, and with what
+        forces and CoM?  The batched form of B x (SetContactPosition / SetContactNormal / SetCoMRef /
+        Solve).  positions [B, N, 3] (contact_names order), normals [B, N, 3] (None: the planner's),
+        com_ref [B, 3], wrench [B, 6], mass [B] (None: the planner's values): float64 CUDA tensors.
+        Every contact's position and normal must be fixed in the planner (as SetContactPosition /
+        SetContactNormal leave them); the start point is the CoM at its reference, F_i = (1, 1, m g / N)
+        clipped to the force bounds, and the given positions and normals.  Returns the
+        BatchSolveResult of the solve with fixed_from_x0."""
+        import torch
+
+        from .problem import InstanceData
+
+        prob = self._cp.GetCplProblem()
+        N = len(self._contact_names)
+        if (not torch.is_tensor(positions) or positions.dtype != torch.float64 or not positions.is_cuda
+                or positions.dim() != 3 or tuple(positions.shape[1:]) != (N, 3)):
+            raise ValueError(f"positions must be a float64 CUDA tensor [B, {N}, 3]")
+        B, dev = positions.shape[0], positions.device
+        for c in self._contact_names:  # (raise like GetContactPosition / GetContactNormal when not set)
+            self.GetContactPosition(c)
+            self.GetContactNormal(c)
+
+        def per_batch(t, shape, name):
+            if t is None:
+                return None
+            if not torch.is_tensor(t) or t.dtype != torch.float64 or t.device != dev or tuple(t.shape) != shape:
+                raise ValueError(f"{name} must be a float64 tensor {list(shape)} on {dev}")
+            return t
+
+        normals = per_batch(normals, (B, N, 3), "normals")
+        com_ref = per_batch(com_ref, (B, 3), "com_ref")
+        mass = per_batch(mass, (B,), "mass")
+        d = prob.desc()
+        X0 = torch.empty(B, 3 + 9 * N, dtype=torch.float64, device=dev)
+        X0[:, 0:3] = com_ref if com_ref is not None else torch.tensor(list(d.com_ref), dtype=torch.float64, device=dev)
+        blocks = X0[:, 3:].view(B, N, 9)
+        g = -float(d.gravity[2])
+        fz = (mass if mass is not None else torch.full((B,), float(d.mass), dtype=torch.float64, device=dev)) * g / N
+        F0 = torch.stack([torch.ones_like(fz), torch.ones_like(fz), fz], dim=1)  # [B, 3]
+        F_lb = torch.tensor([list(d.F_lb[i]) for i in range(N)], dtype=torch.float64, device=dev)
+        F_ub = torch.tensor([list(d.F_ub[i]) for i in range(N)], dtype=torch.float64, device=dev)
+        blocks[:, :, 0:3] = torch.minimum(torch.maximum(F0[:, None, :], F_lb[None]), F_ub[None])
+        blocks[:, :, 3:6] = positions
+        blocks[:, :, 6:9] = normals if normals is not None else torch.tensor(
+            [list(d.n_lb[i]) for i in range(N)], dtype=torch.float64, device=dev)[None]
+        inst = InstanceData(wrench=wrench, com_ref=com_ref)
+        return self._cp.SolveBatch(X0, mass=mass, instance=inst if inst else None, fixed_from_x0=True, **solve_options)
 
     def SetCoMWeight(self, w):
         self._cp.SetCoMWeight(w)

@@ -105,6 +105,46 @@ class MixedEnvironment(EnvironmentClass):
 # --------------------------------------------------------------------------------------------
 # CplProblem  (src/CplProblem.cpp)
 # --------------------------------------------------------------------------------------------
+class InstanceData:
+    """Per-instance problem data of a batch (cpl_instance_data): what a user of the reference changes
+    from one problem to the next — SetManipulationWrench, SetCoMRef, SetPosRef, SetForceRef — as
+    float64 CUDA tensors wrench [B, 6], com_ref [B, 3], p_ref [B, N, 3], F_ref [B, N, 3] (contacts in
+    contact_names order).  A field left None takes the template's value for every instance."""
+
+    FIELDS = ("wrench", "com_ref", "p_ref", "F_ref")
+
+    def __init__(self, wrench=None, com_ref=None, p_ref=None, F_ref=None):
+        self.wrench, self.com_ref, self.p_ref, self.F_ref = wrench, com_ref, p_ref, F_ref
+
+    def __bool__(self):
+        return any(getattr(self, k) is not None for k in self.FIELDS)
+
+    def validated(self, batch: int, n_contacts: int, device) -> "InstanceData":
+        """The fields checked against the batch (ValueError naming the field) and made contiguous."""
+        import torch
+
+        shapes = {"wrench": (batch, 6), "com_ref": (batch, 3), "p_ref": (batch, n_contacts, 3),
+                  "F_ref": (batch, n_contacts, 3)}
+        out = InstanceData()
+        for k in self.FIELDS:
+            t = getattr(self, k)
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or t.dtype != torch.float64:
+                raise ValueError(f"InstanceData.{k} must be a float64 tensor")
+            if tuple(t.shape) != shapes[k]:
+                raise ValueError(f"InstanceData.{k} must have shape {shapes[k]}, not {tuple(t.shape)}")
+            if not t.is_cuda or t.device != device:
+                raise ValueError(f"InstanceData.{k} must be a CUDA tensor on the batch's device {device}, not {t.device}")
+            setattr(out, k, t.contiguous())
+        return out
+
+    def c_struct(self) -> "_abi.InstanceDataC":
+        """The C record over these tensors (which must stay alive while it is in use)."""
+        return _abi.InstanceDataC(*(None if getattr(self, k) is None else getattr(self, k).data_ptr()
+                                    for k in self.FIELDS))
+
+
 class CplProblem:
     """One CentroidalPlanner problem template; evaluates single instances (TNLP hooks) or batches.
 
@@ -419,7 +459,7 @@ class CplProblem:
 
     # ---- the batched hot path ---------------------------------------------------------------
     def eval_batch(self, x, mass=None, env_tag=None, outputs: Iterable[str] = ("g", "jac"), out=None,
-                   stream=None, jac_folded: bool = False, soa: bool = False):
+                   stream=None, jac_folded: bool = False, soa: bool = False, instance: Optional[InstanceData] = None):
         """Evaluate B instances on the GPU in one launch.
 
         x: torch.float64 CUDA tensor [B, n] (contiguous).  mass: [B] or None.  env_tag: uint8 [B]
@@ -430,6 +470,9 @@ class CplProblem:
         ``stream`` (default: torch's current stream).
         jac_folded: values-only Jacobian records (structural constants skipped, see jac_fold_info);
         soa: entry-major outputs g [m, B], jac [nnz, B], grad [n, B] (cpl_eval_batch_ex).
+        instance: per-instance wrench / cost references (InstanceData, cpl_eval_batch_inst: the
+        template's evaluation, then the instance overlay's launch for g[0:6], f and grad; "norms" is
+        then a separate pass over g); not with soa.
         """
         import torch
 
@@ -480,6 +523,13 @@ class CplProblem:
             elif tuple(t.shape) != (2,) or t.dtype != torch.float64 or t.device != x.device or not t.is_contiguous():
                 raise InvalidArgument(_abi.ERR_INVALID_ARGUMENT, f"output 'norms' must be a contiguous float64 (2,) tensor on {x.device}")
             res["norms"] = t
+        if instance is not None and instance:
+            inst = instance.validated(B, len(self._contact_names), x.device)
+            cs = inst.c_struct()
+            check(lib.cpl_eval_batch_inst(ctypes.byref(self.desc()), B, p(x), p(mass), p(env_tag), ctypes.byref(cs),
+                                          p(res.get("g")), p(res.get("jac")), p(res.get("f")), p(res.get("grad")),
+                                          p(res.get("norms")), flags, ctypes.c_void_p(s.cuda_stream)))
+            return res
         if flags or want_norms:
             check(lib.cpl_eval_batch_ex(ctypes.byref(self.desc()), B, p(x), p(mass), p(env_tag), p(res.get("g")),
                                         p(res.get("jac")), p(res.get("f")), p(res.get("grad")), p(res.get("norms")),

@@ -201,6 +201,36 @@ int32_t cpl_eval_batch_ex(const cpl_problem_desc* d, int64_t batch, const double
                           int32_t flags, void* stream);
 
 /*
+ * Per-instance problem data: the quantities a user of the reference changes from one problem to the
+ * next, per instance of the batch instead of once in the template.  Device pointers, instance-major;
+ * any may be NULL = the template's value (cpl_problem_desc.wrench / com_ref / p_ref / F_ref) for
+ * every instance.  Per-contact arrays are in contact_names (vector) order.
+ */
+typedef struct cpl_instance_data {
+  const double* d_wrench;   /* [batch][6]      CentroidalStatics::SetManipulationWrench */
+  const double* d_com_ref;  /* [batch][3]      MinimizeCentroidalVariables::SetCoMRef   */
+  const double* d_p_ref;    /* [batch][N][3]   SetPosRef,   contact_names (vector) order */
+  const double* d_F_ref;    /* [batch][N][3]   SetForceRef, contact_names (vector) order */
+} cpl_instance_data;
+size_t cpl_instance_data_sizeof(void); /* sizeof(cpl_instance_data), for FFI layout checks */
+
+/*
+ * cpl_eval_batch_ex with per-instance data.  inst == NULL or every pointer in it NULL: exactly
+ * cpl_eval_batch_ex.  Otherwise the template's evaluation runs with f and grad switched off (the
+ * Jacobian does not depend on the four arrays) and an overlay launch on the same stream computes the
+ * six statics values g[0:6], f and grad of every instance from x, the mass and the instance data (the
+ * wrench subtracted after the contact sums and before m * gravity, as CentroidalStatics::GetValues
+ * does: row b is bitwise cpl_eval_batch_ex on a batch of one whose template carries instance b's
+ * values); d_norms then come from a cpl_residual_norms pass over the finished g.
+ * CPL_EVAL_JAC_FOLDED is supported; CPL_EVAL_SOA with instance data returns CPL_ERR_UNSUPPORTED
+ * before any launch.  cpl_eval_lagrangian_grad's fused form has no instance argument: it is the
+ * template's; with instance data take jac and grad from this call, then cpl_lagrangian_grad.
+ */
+int32_t cpl_eval_batch_inst(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
+                            const uint8_t* d_env_tag, const cpl_instance_data* inst, double* d_g, double* d_jac,
+                            double* d_f, double* d_grad, double* d_norms, int32_t flags, void* stream);
+
+/*
  * The folded Jacobian layout of `d` (host only): *nnz_folded values per record; var_k[j] = the
  * CSR position (0..nnz-1, cpl_structure order) of folded value j; const_k[c] / const_val[c] = the
  * CSR position and value of skipped constant c, *n_const of them (nnz = nnz_folded + n_const).
@@ -599,6 +629,23 @@ int32_t cpl_solver_solve(cpl_solver* s, const double* d_x0, const double* d_mass
                          double* d_x, double* d_y, int32_t* d_status, int32_t* d_iters, double* d_obj,
                          double* d_primal_inf, double* d_dual_inf, int32_t* iterations_run, int64_t* evaluations,
                          void* stream);
+/*
+ * cpl_solver_solve with per-instance data (copied into buffers of the solver's own, which the
+ * active-set compaction moves with their rows) and, with fixed_from_x0 != 0, per-instance values of
+ * the fixed variables: a variable with lb == ub in the template (cpl_solver_create's test) takes its
+ * value for instance b from d_x0[b][j] instead of the template's bound — the template then only says
+ * WHICH variables are fixed; the returned d_x carries the instance's value there and the final
+ * projection onto the original bounds skips those entries.  The batched form of
+ * CoMPlanner::SetContactPosition / SetContactNormal and CentroidalPlanner::SetPosBounds(p, p).
+ * inst == NULL (or all NULL) and fixed_from_x0 == 0: exactly cpl_solver_solve.
+ * Instance data needs a Hessian that is not central differences: with CPL_HESSIAN_FD, or
+ * CPL_HESSIAN_EXACT on a Superquadric / mixed template, the call returns CPL_ERR_UNSUPPORTED before
+ * any launch (use CPL_HESSIAN_ANALYTIC or CPL_HESSIAN_LIMITED_MEMORY).
+ */
+int32_t cpl_solver_solve_inst(cpl_solver* s, const double* d_x0, const double* d_mass, const uint8_t* d_env_tag,
+                              const cpl_instance_data* inst, int32_t fixed_from_x0, double* d_x, double* d_y,
+                              int32_t* d_status, int32_t* d_iters, double* d_obj, double* d_primal_inf,
+                              double* d_dual_inf, int32_t* iterations_run, int64_t* evaluations, void* stream);
 /* dims of the solver's primal-slack system: nf free variables, nI inequality rows (nw = nf + nI) */
 int32_t cpl_solver_dims(const cpl_solver* s, int32_t* nf, int32_t* n_ineq, int32_t* graph_captured);
 /* the last solve's active-set compactions and its final lock-step batch size */
