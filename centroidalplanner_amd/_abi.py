@@ -93,6 +93,47 @@ class SolveOptions(ctypes.Structure):
         ("fallback_viol_tol", c_double),
         ("nlp_scaling", c_int32),
         ("jacobian_regularization", c_int32),
+        ("termination", c_int32),
+        ("reserved_term", c_int32),
+        ("dual_inf_tol", c_double),
+        ("constr_viol_tol", c_double),
+        ("compl_inf_tol", c_double),
+        ("acceptable_dual_inf_tol", c_double),
+        ("acceptable_constr_viol_tol", c_double),
+        ("acceptable_compl_inf_tol", c_double),
+        ("acceptable_obj_change_tol", c_double),
+        ("diverging_iterates_tol", c_double),
+        ("max_wall_time", c_double),
+    ]
+
+
+class TermArgs(ctypes.Structure):
+    """cpl_term_args (include/cpl_mi355x.h): cpl_ipm_optimality_ex's termination block."""
+
+    _fields_ = [
+        ("termination", c_int32),
+        ("nf", c_int32),
+        ("dual_inf_tol", c_double),
+        ("constr_viol_tol", c_double),
+        ("compl_inf_tol", c_double),
+        ("acceptable_dual_inf_tol", c_double),
+        ("acceptable_constr_viol_tol", c_double),
+        ("acceptable_compl_inf_tol", c_double),
+        ("acceptable_obj_change_tol", c_double),
+        ("diverging_iterates_tol", c_double),
+        ("d_g", c_void_p),
+        ("d_dc", c_void_p),
+        ("d_df", c_void_p),
+        ("d_gl", c_void_p),
+        ("d_gu", c_void_p),
+        ("d_slack_row", c_void_p),
+        ("d_f", c_void_p),
+        ("d_f_prev", c_void_p),
+        ("d_acceptable", c_void_p),
+        ("d_dual_inf", c_void_p),
+        ("d_constr_viol", c_void_p),
+        ("d_compl_inf", c_void_p),
+        ("d_skip", c_void_p),
     ]
 
 
@@ -126,6 +167,11 @@ HESSIAN_EXACT = 0
 HESSIAN_LIMITED_MEMORY = 1
 HESSIAN_FD = 2
 HESSIAN_ANALYTIC = 3
+
+TERM_SCALED = 0
+TERM_IPOPT = 1
+SOLVE_DIVERGING = 5
+SOLVE_TIME_LIMIT = 6
 
 # every symbol include/cpl_mi355x.h declares, with its ctypes signature
 _DESC_P = POINTER(ProblemDesc)
@@ -218,6 +264,11 @@ SIGNATURES = {
         c_int32,
         [c_int64, c_int32, c_int32, c_int32, c_int32, c_double, c_double, c_int32] + [c_void_p] * 26,
     ),
+    "cpl_ipm_optimality_ex": (
+        c_int32,
+        [c_int64, c_int32, c_int32, c_int32, c_int32, c_double, c_double, c_int32] + [c_void_p] * 25
+        + [POINTER(TermArgs), c_void_p],
+    ),
     "cpl_ipm_max_step": (c_int32, [c_int64, c_int32] + [c_void_p] * 11),
     "cpl_ipm_newton_setup": (c_int32, [c_int64, c_int32, c_int32, c_int32] + [c_void_p] * 14 + [c_int32]
                              + [c_void_p] * 9),
@@ -228,6 +279,8 @@ SIGNATURES = {
     "cpl_ipm_masked_rows": (c_int32, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cpl_ipm_dense_a": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 6),
     "cpl_solve_options_default": (None, [POINTER(SolveOptions)]),
+    "cpl_solve_options_ifopt": (None, [POINTER(SolveOptions)]),
+    "cpl_solve_options_sizeof": (c_int64, []),
     "cpl_solver_create": (c_int32, [_DESC_P, c_int64, POINTER(SolveOptions), POINTER(c_void_p)]),
     "cpl_solver_destroy": (c_int32, [c_void_p]),
     "cpl_solver_solve": (c_int32, [c_void_p] + [c_void_p] * 10 + [POINTER(c_int32), POINTER(c_int64), c_void_p]),
@@ -238,6 +291,8 @@ SIGNATURES = {
     "cpl_solver_restorations": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "cpl_solver_fallbacks": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "cpl_solver_nan_jacobian": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "cpl_solver_unscaled_errors": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cpl_solver_final_iterate": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 
@@ -315,3 +370,5 @@ def iptr(a) -> ctypes.POINTER(c_int32):
 
 if lib.cpl_desc_sizeof() != ctypes.sizeof(ProblemDesc):  # pragma: no cover - layout guard
     raise ImportError("cpl_problem_desc layout mismatch between header and ctypes mirror")
+if lib.cpl_solve_options_sizeof() != ctypes.sizeof(SolveOptions):  # pragma: no cover - layout guard
+    raise ImportError("cpl_solve_options layout mismatch between header and ctypes mirror")

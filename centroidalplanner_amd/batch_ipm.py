@@ -58,6 +58,7 @@ from __future__ import annotations
 
 import ctypes
 import math
+import time
 from dataclasses import dataclass
 from typing import Callable, Optional
 
@@ -78,8 +79,20 @@ STATUS_MAX_ITER = 2
 STATUS_INFEASIBLE = 3     # the restoration phase converged: a point of local infeasibility
 STATUS_RESTO_FAILED = 4   # the restoration phase converged twice to a feasible point the filter rejects, or
                           # it was called at an almost feasible point without a backup acceptable point
+STATUS_DIVERGING = 5      # termination="ipopt": max |x| exceeded diverging_iterates_tol
+STATUS_TIME_LIMIT = 6     # max_wall_time passed: the instance's current iterate is returned
 STATUS_NAMES = {STATUS_OPTIMAL: "optimal", STATUS_ACCEPTABLE: "acceptable", STATUS_MAX_ITER: "max_iter",
-                STATUS_INFEASIBLE: "local_infeasibility", STATUS_RESTO_FAILED: "restoration_failed"}
+                STATUS_INFEASIBLE: "local_infeasibility", STATUS_RESTO_FAILED: "restoration_failed",
+                STATUS_DIVERGING: "diverging_iterates", STATUS_TIME_LIMIT: "time_limit"}
+
+# IPOPT's defaults of the termination tests the scaled optimality error does not cover (termination="ipopt")
+TERMINATION_DEFAULTS = dict(dual_inf_tol=1.0, constr_viol_tol=1e-4, compl_inf_tol=1e-4, acceptable_dual_inf_tol=1e10,
+                            acceptable_constr_viol_tol=1e-2, acceptable_compl_inf_tol=1e-2,
+                            acceptable_obj_change_tol=1e20, diverging_iterates_tol=1e20)
+# [IFOPT-ext] the option set IFOPT's IpoptSolver constructor runs with (ifopt_ipopt/src/ipopt_solver.cc as
+# VERDICT.md cites it; IFOPT's source is not part of this repository) — cpl_solve_options_ifopt; keyword
+# arguments of batch_ipm_solve / solver.solve / the planners' SetSolverOptions
+IFOPT_OPTIONS = dict(hessian="limited-memory", tol=1e-3, termination="ipopt", max_wall_time=40.0)
 
 # IPOPT's defaults (Waechter & Biegler 2006; IpFilterLSAcceptor / IpBacktrackingLineSearch /
 # IpMonotoneMuUpdate / IpRestoMinC_1Nrm option defaults) that the iteration restates
@@ -185,6 +198,16 @@ class BatchSolveResult:
     restorations: object = None  # [B] int: restoration-phase entries per instance
     fallback: object = None  # [B] bool: x is the best feasible iterate, not the last (fallback_viol_tol)
     nan_jacobian: object = None  # [B] int: NaN Jacobian entries at the start point (taken as 0)
+    # termination="ipopt": the last regular test's unscaled measures [B] (None under "scaled")
+    unscaled_dual_inf: object = None
+    unscaled_constr_viol: object = None
+    unscaled_compl_inf: object = None
+    # ... and the last iterate w [B, nw] (the free variables in index order, then the inequality rows' slacks
+    # in row order; x is w's free part projected onto the original bounds) with its bound multipliers of
+    # the scaled problem
+    w: object = None
+    z_L: object = None
+    z_U: object = None
 
     @property
     def success(self):
@@ -201,7 +224,11 @@ class NativeSolver:
 
     def __init__(self, problem, batch, tol=1e-8, max_iter=3000, mu_init=0.1, acceptable_tol=1e-6,
                  acceptable_iter=15, max_ls=40, max_soc=4, hessian="exact", fd_step=1e-6, graph=True, compact=True,
-                 ls_kernel=2, fallback_viol_tol=0.0, nlp_scaling="gradient-based", jacobian_regularization="pivot"):
+                 ls_kernel=2, fallback_viol_tol=0.0, nlp_scaling="gradient-based", jacobian_regularization="pivot",
+                 termination="scaled", max_wall_time=0.0, **term_tols):
+        unknown = set(term_tols) - set(TERMINATION_DEFAULTS)
+        if unknown:
+            raise TypeError(f"NativeSolver: unknown options {sorted(unknown)}")
         o = _abi.SolveOptions()
         _abi.lib.cpl_solve_options_default(ctypes.byref(o))
         o.max_iter, o.max_ls, o.max_soc, o.acceptable_iter = int(max_iter), int(max_ls), int(max_soc), int(acceptable_iter)
@@ -214,6 +241,11 @@ class NativeSolver:
         o.fallback_viol_tol = float(fallback_viol_tol)
         o.nlp_scaling = {"gradient-based": 1, "none": 0}[nlp_scaling]
         o.jacobian_regularization = {"pivot": 0, "ipopt": 1}[jacobian_regularization]
+        o.termination = {"scaled": _abi.TERM_SCALED, "ipopt": _abi.TERM_IPOPT}[termination]
+        o.max_wall_time = float(max_wall_time)
+        for k, v in term_tols.items():
+            setattr(o, k, float(v))
+        self.termination = termination
         self.problem, self.batch = problem, int(batch)
         self.desc = problem.desc()
         self.handle = ctypes.c_void_p()
@@ -281,10 +313,22 @@ class NativeSolver:
         nanj = torch.empty(B, dtype=torch.int32, device=dev)
         _abi.check(_abi.lib.cpl_solver_nan_jacobian(self.handle, _ptr(nanj),
                                                     ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        return BatchSolveResult(x=x, y=y, status=status.to(torch.int64), iterations=iters.to(torch.int64),
-                                objective=obj, primal_inf=pinf, dual_inf=dinf, evaluations=int(ev.value),
-                                iterations_run=int(it.value), graph=bool(g.value), compactions=int(nc.value),
-                                final_rows=int(rows.value), restorations=resto, fallback=fb.bool(), nan_jacobian=nanj.to(torch.int64))
+        res = BatchSolveResult(x=x, y=y, status=status.to(torch.int64), iterations=iters.to(torch.int64),
+                               objective=obj, primal_inf=pinf, dual_inf=dinf, evaluations=int(ev.value),
+                               iterations_run=int(it.value), graph=bool(g.value), compactions=int(nc.value),
+                               final_rows=int(rows.value), restorations=resto, fallback=fb.bool(), nan_jacobian=nanj.to(torch.int64))
+        if self.termination == "ipopt":
+            u = [torch.empty(B, dtype=torch.float64, device=dev) for _ in range(3)]
+            _abi.check(_abi.lib.cpl_solver_unscaled_errors(self.handle, _ptr(u[0]), _ptr(u[1]), _ptr(u[2]),
+                                                           ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            res.unscaled_dual_inf, res.unscaled_constr_viol, res.unscaled_compl_inf = u
+            nf_, nI_ = ctypes.c_int32(), ctypes.c_int32()
+            _abi.check(_abi.lib.cpl_solver_dims(self.handle, ctypes.byref(nf_), ctypes.byref(nI_), None))
+            res.w, res.z_L, res.z_U = (torch.empty(B, nf_.value + nI_.value, dtype=torch.float64, device=dev)
+                                       for _ in range(3))
+            _abi.check(_abi.lib.cpl_solver_final_iterate(self.handle, _ptr(res.w), _ptr(res.z_L), _ptr(res.z_U),
+                                                         ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return res
 
 
 _NATIVE_CACHE = {}
@@ -315,7 +359,12 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
                     ls_kernel: int = 2, fallback_viol_tol: float = 0.0,
                     nlp_scaling: str = "gradient-based", jacobian_regularization: str = "pivot",
                     watchdog: bool = False, watchdog_trigger: int = 10,
-                    watchdog_trial_max: int = 3, instance=None, fixed_from_x0: bool = False) -> BatchSolveResult:
+                    watchdog_trial_max: int = 3, instance=None, fixed_from_x0: bool = False,
+                    termination: str = "scaled", dual_inf_tol: float = 1.0, constr_viol_tol: float = 1e-4,
+                    compl_inf_tol: float = 1e-4, acceptable_dual_inf_tol: float = 1e10,
+                    acceptable_constr_viol_tol: float = 1e-2, acceptable_compl_inf_tol: float = 1e-2,
+                    acceptable_obj_change_tol: float = 1e20, diverging_iterates_tol: float = 1e20,
+                    max_wall_time: float = 0.0) -> BatchSolveResult:
     """Solve B instances of `problem`'s template from the starting points X0 [B, n] (torch float64,
     device tensor), per-instance robot masses `mass` [B] (None: the template's).
 
@@ -361,7 +410,33 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
     instance / fixed_from_x0 (device engine only): per-instance wrench and cost references
     (InstanceData) and per-instance values of the variables the template fixes, taken from X0
     (NativeSolver.solve, cpl_solver_solve_inst).  The host restatement is one template per call and
-    raises ValueError for either."""
+    raises ValueError for either.
+    termination: "scaled" (default) — the scaled optimality error alone decides (err0 <= tol, or
+    <= acceptable_tol for acceptable_iter iterations); the eight tolerances below are ignored.  "ipopt" —
+    IPOPT's OptimalityErrorConvergenceCheck, restated from its published semantics: "optimal" also needs
+    the unscaled dual infeasibility (|dual| / df on x, |dual| dc_r / df on the slack of row r), the
+    unscaled constraint violation of d(x) = g / dc against its bounds (not d(x) - s; a NaN row: inf) and
+    the unscaled complementarity max(comp) / df within dual_inf_tol / constr_viol_tol / compl_inf_tol;
+    "acceptable" (the consecutive count, the backup acceptable point, a failed search at an acceptable
+    point) needs err0 <= acceptable_tol, the three within their acceptable_* limits and the objective
+    change |f - f_prev| / max(1, |f|) <= acceptable_obj_change_tol (f_prev starts at -1e50); an instance
+    that stopped on neither with max |x| > diverging_iterates_tol ends STATUS_DIVERGING; the barrier
+    floor is min(tol, compl_inf_tol) / 11.  The result's unscaled_* carry the last regular test's measures.
+    max_wall_time (seconds, 0: none; either termination): checked once per lock-step iteration; when it
+    has passed every still-active instance ends STATUS_TIME_LIMIT with its current iterate.
+    IFOPT_OPTIONS is the set IFOPT's IpoptSolver runs with."""
+    if termination not in ("scaled", "ipopt"):
+        raise ValueError("termination must be 'scaled' or 'ipopt'")
+    term_tols = dict(dual_inf_tol=dual_inf_tol, constr_viol_tol=constr_viol_tol, compl_inf_tol=compl_inf_tol,
+                     acceptable_dual_inf_tol=acceptable_dual_inf_tol,
+                     acceptable_constr_viol_tol=acceptable_constr_viol_tol,
+                     acceptable_compl_inf_tol=acceptable_compl_inf_tol,
+                     acceptable_obj_change_tol=acceptable_obj_change_tol,
+                     diverging_iterates_tol=diverging_iterates_tol)
+    for k, v in list(term_tols.items()) + [("max_wall_time", max_wall_time)]:
+        if not (float(v) >= 0.0):
+            raise ValueError(f"{k} must be >= 0")
+    ipopt_term = termination == "ipopt"
     if hessian not in ("exact", "fd", "limited-memory", "analytic"):
         raise ValueError("hessian must be 'exact', 'fd', 'limited-memory' or 'analytic'")
     if nlp_scaling not in ("gradient-based", "none"):
@@ -383,7 +458,8 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
                      acceptable_iter=acceptable_iter, max_ls=max_ls, max_soc=max_soc, hessian=hessian,
                      fd_step=fd_step, graph=True if graph is None else bool(graph), compact=compact,
                      ls_kernel=ls_kernel, fallback_viol_tol=fallback_viol_tol, nlp_scaling=nlp_scaling,
-                     jacobian_regularization=jacobian_regularization)
+                     jacobian_regularization=jacobian_regularization, termination=termination,
+                     max_wall_time=max_wall_time, **term_tols)
         if instance is None and evaluator is not None:
             instance = evaluator.instance
         r = ns.solve(X0, mass, None if evaluator is None else evaluator.env_tag, instance=instance,
@@ -446,7 +522,8 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
     eye_f = torch.eye(nf, dtype=dt, device=dev)
     fslot = torch.arange(FMAX, device=dev)[None, :]
     fd_cols = torch.arange(nf, device=dev)
-    mu_min = min(tol, COMPL_INF_TOL) / (BARRIER_TOL_FACTOR + 1.0)  # IPOPT MonotoneMuUpdate's floor
+    # IPOPT MonotoneMuUpdate's floor (compl_inf_tol: the option under termination="ipopt", else its default)
+    mu_min = min(tol, compl_inf_tol if ipopt_term else COMPL_INF_TOL) / (BARRIER_TOL_FACTOR + 1.0)
     xmask = torch.cat([torch.ones(nf, dtype=torch.bool, device=dev), torch.zeros(nI, dtype=torch.bool, device=dev)])
 
     def push(v):  # IPOPT bound_push = bound_frac = 1e-2 (absolute and relative to the range)
@@ -754,8 +831,17 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
         d_inf = dual.abs().amax(1)
         c_inf = c_.abs().amax(1) if m else zeros_B
         base = torch.maximum(d_inf / sd, c_inf)
-        return {"A": A_, "gw": gw, "c": c_, "d_inf": d_inf, "c_inf": c_inf, "base": base, "cl": cl, "cu": cu,
-                "sc": sc, "err0": torch.maximum(base, torch.maximum(cl.amax(1), cu.amax(1)) / sc)}
+        E = {"A": A_, "gw": gw, "c": c_, "d_inf": d_inf, "c_inf": c_inf, "base": base, "cl": cl, "cu": cu,
+             "sc": sc, "err0": torch.maximum(base, torch.maximum(cl.amax(1), cu.amax(1)) / sc)}
+        if ipopt_term:  # the unscaled measures of IPOPT's termination tests (cpl_term_args) and max |x|
+            ad = dual.abs()
+            ad = torch.cat([ad[:, :nf], ad[:, nf:] * dc[:, I]], 1) / df[:, None]
+            E["u_dual"] = ad.amax(1)
+            E["u_viol"] = orig_violation(o["g"])
+            E["u_compl"] = torch.maximum(cl.amax(1), cu.amax(1)) / df
+            E["xmax"] = wv[:, :nf].abs().amax(1) if nf else zeros_B
+            E["f"] = o["f"]
+        return E
 
     def err_mu(E, muv):
         comp_mu = torch.maximum((E["cl"] - torch.where(hasL, muv[:, None], 0.0)).abs().amax(1),
@@ -878,6 +964,8 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
         # IPOPT's backup acceptable point (BacktrackingLineSearch::StoreAcceptablePoint): the last
         # regular iterate at the acceptable level, restored when the restoration phase fails
         "acc_w": zBw(), "acc_y": zBm(), "acc_zL": zBw(), "acc_zU": zBw(), "has_acc": bool_B(),
+        # termination="ipopt": the previous test's objective (IPOPT's last_obj_val) and the last test's measures
+        "f_prev": torch.full((B,), -1e50, dtype=dt, device=dev), "u_dual": zB(), "u_viol": zB(), "u_compl": zB(),
     }
     if watchdog:  # IPOPT's watchdog: its state, the kept iterate, its step, evaluation and references
         S.update({"in_wd": bool_B(), "wd_cnt": torch.zeros(B, dtype=torch.int64, device=dev),
@@ -903,17 +991,42 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
         S["best_w"].copy_(torch.where(upd[:, None], S["w"], S["best_w"]))
         S["best_f"].copy_(torch.where(upd, S["f"], S["best_f"]))
 
-    def check(E, mask):
-        """Convergence test at the current iterate of the instances in `mask`; updates status /
-        active / acc."""
-        active = S["active"]
+    def levels(E, f_prev):
+        """IPOPT's "optimal" and CurrentIsAcceptable predicates at the measures E (f_prev None: without the
+        objective change — the watchdog's restored iterate, whose test already ran)."""
         e0 = E["err0"]
+        opt_lvl, acc_lvl = e0 <= tol, e0 <= acceptable_tol
+        if ipopt_term:
+            opt_lvl = opt_lvl & (E["u_dual"] <= dual_inf_tol) & (E["u_viol"] <= constr_viol_tol) & \
+                (E["u_compl"] <= compl_inf_tol)
+            acc_lvl = acc_lvl & (E["u_dual"] <= acceptable_dual_inf_tol) & (E["u_viol"] <= acceptable_constr_viol_tol) & \
+                (E["u_compl"] <= acceptable_compl_inf_tol)
+            if f_prev is not None:
+                fv = E["f"]
+                acc_lvl = acc_lvl & ((fv - f_prev).abs() / torch.clamp(fv.abs(), min=1.0) <= acceptable_obj_change_tol)
+        return opt_lvl, acc_lvl
+
+    def check(E, mask, final=False):
+        """Convergence test at the current iterate of the instances in `mask`; updates status /
+        active / acc.  E["acc_lvl"]: IPOPT's CurrentIsAcceptable.  final: the test after max_iter
+        iterations (IPOPT tests max_iter before the diverging iterates)."""
+        active = S["active"]
         act = active & mask
-        done_now = act & (e0 <= tol)
-        acc = torch.where(act & (e0 <= acceptable_tol), S["acc"] + 1, torch.where(act, 0, S["acc"]))
+        opt_lvl, acc_lvl = levels(E, S["f_prev"])
+        if ipopt_term:
+            S["f_prev"].copy_(torch.where(act, E["f"], S["f_prev"]))
+            for k in ("u_dual", "u_viol", "u_compl"):
+                S[k].copy_(torch.where(act, E[k], S[k]))
+        E["acc_lvl"] = acc_lvl
+        done_now = act & opt_lvl
+        acc = torch.where(act & acc_lvl, S["acc"] + 1, torch.where(act, 0, S["acc"]))
         acc_now = act & ~done_now & (acc >= acceptable_iter)
         status = torch.where(done_now, torch.full_like(S["status"], STATUS_OPTIMAL),
                              torch.where(acc_now, torch.full_like(S["status"], STATUS_ACCEPTABLE), S["status"]))
+        if ipopt_term and not final:
+            div_now = act & ~done_now & ~acc_now & (E["xmax"] > diverging_iterates_tol)
+            status = torch.where(div_now, torch.full_like(status, STATUS_DIVERGING), status)
+            acc_now = acc_now | div_now  # (leaves the batch like the other two)
         S["acc"].copy_(acc)
         S["status"].copy_(status)
         S["active"].copy_(active & ~done_now & ~acc_now)
@@ -996,7 +1109,7 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
         A, gradw, c = E["A"], E["gw"], E["c"]
         # IPOPT stores the current iterate as the backup acceptable point when it is at the
         # acceptable level (FindAcceptableTrialPoint: CurrentIsAcceptable -> StoreAcceptablePoint)
-        store = act & (E["err0"] <= acceptable_tol)
+        store = act & E["acc_lvl"]
         for k, v in (("acc_w", w), ("acc_y", y), ("acc_zL", zL), ("acc_zU", zU)):
             S[k].copy_(torch.where(store[:, None], v, S[k]))
         S["has_acc"].copy_(S["has_acc"] | store)
@@ -1108,6 +1221,7 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
                 dzL = torch.where(R[:, None], S["wd_dzL"], dzL)
                 dzU = torch.where(R[:, None], S["wd_dzU"], dzU)
                 E = errors(cur, w, y, zL, zU)
+                E["acc_lvl"] = levels(E, None)[1]
                 A, gradw, c = E["A"], E["gw"], E["c"]
                 a_max = torch.where(R, primal_step(dw), a_max)
                 a_z = torch.where(R, torch.minimum(max_step(zL, dzL, hasL, 0.0, tau), max_step(zU, dzU, hasU, 0.0, tau)),
@@ -1189,7 +1303,7 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
         failed = act & ~tiny & ~st["found"]  # -> the restoration phase
         # IPOPT calls no restoration phase at an acceptable point (BacktrackingLineSearch: "Restoration
         # phase called at acceptable point" -> STOP_AT_ACCEPTABLE_POINT): the solve ends there
-        at_acc = failed & (E["err0"] <= acceptable_tol)
+        at_acc = failed & E["acc_lvl"]
         # nor at an almost feasible point (theta <= 1e-2 tol): the backup acceptable point is restored
         # and the solve stops there as acceptable (RestoreAcceptablePoint), or without one it ends as a
         # restoration failure ("Restoration phase called, but point is almost feasible")
@@ -1544,16 +1658,22 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
 
     # ---- drive the iterations
     it_run = 0
+    t_start = time.monotonic()
     while it_run < max_iter:
         if it_run % max(1, check_every) == 0 and not bool(S["active"].any()):
             break
         step()
         it_run += 1
+        # max_wall_time, once per lock-step iteration (the engine: at its host synchronisation)
+        if max_wall_time > 0 and bool(S["active"].any()) and time.monotonic() - t_start > max_wall_time:
+            S["status"].copy_(torch.where(S["active"], STATUS_TIME_LIMIT, S["status"]))
+            S["active"].fill_(False)
+            break
         if verbose:
             print(f"it {it_run:4d} active {int(S['active'].sum())} resto {int((S['resto'] & S['active']).sum())}")
     # final convergence test at the last iterate (instances still in the restoration phase keep max_iter)
     check(errors({"f": S["f"], "grad": S["grad"], "g": S["g"], "J": S["J"]}, S["w"], S["y"], S["zL"], S["zU"]),
-          ~S["resto"])
+          ~S["resto"], final=True)
     fallback = bool_B()
     if fallback_viol_tol > 0:  # an unconverged instance stopped at an infeasible iterate: its best feasible one
         fallback = (S["status"] > STATUS_ACCEPTABLE) & (orig_violation(S["g"]) > fallback_viol_tol) & \
@@ -1573,4 +1693,7 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
     res.restorations = S["n_resto"]
     res.nan_jacobian = nan_jacobian
     res.fallback = fallback
+    if ipopt_term:
+        res.unscaled_dual_inf, res.unscaled_constr_viol, res.unscaled_compl_inf = S["u_dual"], S["u_viol"], S["u_compl"]
+        res.w, res.z_L, res.z_U = S["w"], S["zL"], S["zU"]
     return res

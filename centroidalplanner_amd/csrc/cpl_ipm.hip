@@ -105,7 +105,28 @@ __global__ __launch_bounds__(256) void cpl_ipm_judge_take_kernel(
 //   acc_iter consecutive iterations) / still active;
 //   two rounds of mu <- max(min(0.2 mu, mu^1.5), tol/10) while err_mu <= 10 mu and mu > tol/10, each
 //   resetting the instance's filter.  Writes status/acc/active/d_inf in place; mu, filter -> *_out.
-__global__ __launch_bounds__(256) void cpl_ipm_optimality_kernel(
+// TERM (a compile-time variant, cpl_ipm_optimality_term_kernel): IPOPT's full termination tests
+// (OptimalityErrorConvergenceCheck, cpl_term_args in include/cpl_mi355x.h) in the same pass — the lanes'
+// dual / complementarity entries also give the unscaled dual infeasibility and complementarity, one
+// more strided loop over the rows the unscaled constraint violation of d(x), the free entries of w
+// max |x|; "optimal" and "acceptable" take the unscaled tolerances (and the objective change), an
+// instance that stopped on neither and has max |x| > diverging_iterates_tol stops as diverging.
+struct IpmTerm {
+  int nf;
+  double dual_inf_tol, constr_viol_tol, compl_inf_tol;
+  double acc_dual_inf_tol, acc_constr_viol_tol, acc_compl_inf_tol, acc_obj_change_tol;
+  double diverging_tol;
+  const double *g, *dc, *df, *gl, *gu;
+  const int32_t* slack_row;
+  const double* f;
+  double* f_prev;
+  uint8_t* acceptable;
+  double *dual_inf, *constr_viol, *compl_inf;
+};
+struct IpmNoTerm {};
+
+template <bool TERM, typename TermT>
+__device__ __forceinline__ void ipm_optimality_body(
     int64_t batch, int nw, int m, int nfilt, int nbounds, double tol, double acc_tol, int acc_iter,
     const double* __restrict__ A, const double* __restrict__ gw, const double* __restrict__ c,
     const double* __restrict__ w, const double* __restrict__ y, const double* __restrict__ zL,
@@ -116,7 +137,7 @@ __global__ __launch_bounds__(256) void cpl_ipm_optimality_kernel(
     double* __restrict__ d_inf_out, double* __restrict__ err0_out, double* __restrict__ base_out,
     double* __restrict__ mu_out, double* __restrict__ filt_t_out, double* __restrict__ filt_p_out,
     int64_t* __restrict__ fcount_out, int mu_rounds, double mu_min, const uint8_t* __restrict__ tiny_flag,
-    const uint8_t* __restrict__ skip, const IpmUnpack up) {
+    const uint8_t* __restrict__ skip, const IpmUnpack& up, const TermT& T) {
   const int64_t b = (int64_t)blockIdx.x * IPM_WAVES + (threadIdx.x >> 6);
   if (b >= batch) return;
   const int lane = threadIdx.x & 63;
@@ -151,6 +172,8 @@ __global__ __launch_bounds__(256) void cpl_ipm_optimality_kernel(
   // lanes own w entries k = lane, lane + 64 (nw <= 128)
   double cl[2] = {0.0, 0.0}, cu[2] = {0.0, 0.0};
   double dmax = 0.0, zs = 0.0, clmax = 0.0, cumax = 0.0;
+  double du = 0.0, cv = 0.0, xmax = 0.0, dfv = 1.0;  // TERM: the unscaled dual infeasibility, violation, max |x|
+  if constexpr (TERM) dfv = T.df ? T.df[b] : 1.0;
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const int k = lane + 64 * h;
@@ -160,6 +183,12 @@ __global__ __launch_bounds__(256) void cpl_ipm_optimality_kernel(
       const double zl = zL[b * nw + k], zu = zU[b * nw + k], wk = w[b * nw + k];
       dual = dual - zl + zu;
       dmax = fmax(dmax, fabs(dual));
+      if constexpr (TERM) {  // x part: / df; the slack of row r: dc_r / df
+        double a = fabs(dual);
+        if (k >= T.nf) a = a * (T.dc ? T.dc[b * m + T.slack_row[k - T.nf]] : 1.0);
+        else xmax = fmax(xmax, fabs(wk));
+        du = fmax(du, a / dfv);
+      }
       zs += fabs(zl) + fabs(zu);
       cl[h] = hasL[k] ? (wk - wl0[k]) * zl : 0.0;
       cu[h] = hasU[k] ? (wu0[k] - wk) * zu : 0.0;
@@ -171,6 +200,16 @@ __global__ __launch_bounds__(256) void cpl_ipm_optimality_kernel(
   for (int r = lane; r < m; r += 64) {
     ys += fabs(yb[r]);
     cmax = fmax(cmax, fabs(c[b * m + r]));
+  }
+  if constexpr (TERM) {  // the violation of d(x) = g / dc against the original bounds (a NaN row: +inf)
+    for (int r = lane; r < m; r += 64) {
+      const double gv = T.g[b * m + r] / (T.dc ? T.dc[b * m + r] : 1.0);
+      cv = fmax(cv, fmax(fmax(T.gl[r] - gv, gv - T.gu[r]), 0.0));
+      if (gv != gv) cv = INFINITY;
+    }
+    du = wave_max(du);
+    cv = wave_max(cv);
+    xmax = wave_max(xmax);
   }
   // wave reductions (DPP, cpl_wave.hpp; all lanes end with the totals)
   dmax = wave_max(dmax);
@@ -186,11 +225,27 @@ __global__ __launch_bounds__(256) void cpl_ipm_optimality_kernel(
   const double err0 = fmax(base, fmax(clmax, cumax) / sc);
   // convergence test
   bool act = active[b] != 0;
-  const bool done_now = act && err0 <= tol;
-  const int64_t acc_new = (act && err0 <= acc_tol) ? acc[b] + 1 : 0;
+  const bool act_in = act;
+  bool opt_lvl = err0 <= tol, acc_lvl = err0 <= acc_tol;  // (CurrentIsAcceptable: acc_lvl)
+  double cp = 0.0, fv = 0.0;
+  if constexpr (TERM) {
+    cp = fmax(clmax, cumax) / dfv;
+    fv = T.f[b];
+    const double oc = fabs(fv - T.f_prev[b]) / fmax(1.0, fabs(fv));
+    opt_lvl = opt_lvl && du <= T.dual_inf_tol && cv <= T.constr_viol_tol && cp <= T.compl_inf_tol;
+    acc_lvl = acc_lvl && du <= T.acc_dual_inf_tol && cv <= T.acc_constr_viol_tol && cp <= T.acc_compl_inf_tol &&
+              oc <= T.acc_obj_change_tol;
+  }
+  const bool done_now = act && opt_lvl;
+  const int64_t acc_new = (act && acc_lvl) ? acc[b] + 1 : 0;
   const bool acc_now = act && !done_now && acc_new >= acc_iter;
   act = act && !done_now && !acc_now;
-  if (up.acc_w && act && err0 <= acc_tol) {  // the backup acceptable point (CurrentIsAcceptable)
+  bool div_now = false;
+  if constexpr (TERM) {
+    div_now = act && xmax > T.diverging_tol;
+    act = act && !div_now;
+  }
+  if (up.acc_w && act && acc_lvl) {  // the backup acceptable point (CurrentIsAcceptable)
     for (int k = lane; k < nw; k += 64) {
       up.acc_w[b * nw + k] = w[b * nw + k];
       up.acc_zL[b * nw + k] = zL[b * nw + k];
@@ -229,6 +284,16 @@ __global__ __launch_bounds__(256) void cpl_ipm_optimality_kernel(
     acc[b] = acc_new;
     if (done_now) status[b] = 0;
     else if (acc_now) status[b] = 1;
+    if constexpr (TERM) {
+      if (div_now) status[b] = CPL_SOLVE_DIVERGING;
+      T.acceptable[b] = acc_lvl ? 1 : 0;
+      if (act_in) {
+        T.f_prev[b] = fv;
+        T.dual_inf[b] = du;
+        T.constr_viol[b] = cv;
+        T.compl_inf[b] = cp;
+      }
+    }
     active[b] = act ? 1 : 0;
     d_inf_out[b] = dmax;
     err0_out[b] = err0;
@@ -238,6 +303,30 @@ __global__ __launch_bounds__(256) void cpl_ipm_optimality_kernel(
     if (reset && up.in_soft) up.in_soft[b] = 0;  // (the line search's Reset: the soft restoration phase ends)
   }
   unpack(mu, act);
+}
+
+#define IPM_OPT_PARAMS                                                                                          \
+  int64_t batch, int nw, int m, int nfilt, int nbounds, double tol, double acc_tol, int acc_iter,               \
+      const double *__restrict__ A, const double *__restrict__ gw, const double *__restrict__ c,                \
+      const double *__restrict__ w, const double *__restrict__ y, const double *__restrict__ zL,                \
+      const double *__restrict__ zU, const uint8_t *__restrict__ hasL, const uint8_t *__restrict__ hasU,        \
+      const double *__restrict__ wl0, const double *__restrict__ wu0, const double *__restrict__ mu_in,         \
+      const double *__restrict__ filt_t, const double *__restrict__ filt_p, const int64_t *__restrict__ fcount, \
+      uint8_t *__restrict__ active, int64_t *__restrict__ status, int64_t *__restrict__ acc,                    \
+      double *__restrict__ d_inf_out, double *__restrict__ err0_out, double *__restrict__ base_out,             \
+      double *__restrict__ mu_out, double *__restrict__ filt_t_out, double *__restrict__ filt_p_out,            \
+      int64_t *__restrict__ fcount_out, int mu_rounds, double mu_min, const uint8_t *__restrict__ tiny_flag,    \
+      const uint8_t *__restrict__ skip, const IpmUnpack up
+#define IPM_OPT_ARGS                                                                                             \
+  batch, nw, m, nfilt, nbounds, tol, acc_tol, acc_iter, A, gw, c, w, y, zL, zU, hasL, hasU, wl0, wu0, mu_in,     \
+      filt_t, filt_p, fcount, active, status, acc, d_inf_out, err0_out, base_out, mu_out, filt_t_out, filt_p_out, \
+      fcount_out, mu_rounds, mu_min, tiny_flag, skip, up
+
+__global__ __launch_bounds__(256) void cpl_ipm_optimality_kernel(IPM_OPT_PARAMS) {
+  ipm_optimality_body<false>(IPM_OPT_ARGS, IpmNoTerm{});
+}
+__global__ __launch_bounds__(256) void cpl_ipm_optimality_term_kernel(IPM_OPT_PARAMS, const IpmTerm T) {
+  ipm_optimality_body<true>(IPM_OPT_ARGS, T);
 }
 
 // Fraction-to-the-boundary step (batch_ipm.py max_step, both sides): the largest alpha <= 1 with
@@ -591,11 +680,26 @@ int32_t ipm_optimality_ex(int64_t batch, int32_t nw, int32_t m, int32_t nfilt, i
                           uint8_t* d_active, int64_t* d_status, int64_t* d_acc, double* d_d_inf, double* d_err0,
                           double* d_base, double* d_mu_out, double* d_filt_t_out, double* d_filt_p_out,
                           int64_t* d_fcount_out, int32_t mu_rounds, double mu_min, const uint8_t* d_tiny_flag,
-                          const uint8_t* d_skip, const IpmUnpack* unpack, void* stream) {
+                          const uint8_t* d_skip, const IpmUnpack* unpack, void* stream, const cpl_term_args* term) {
   const int64_t blocks = (batch + IPM_WAVES - 1) / IPM_WAVES;
   IpmUnpack up{};
   if (unpack) up = *unpack;
   if (batch == 0) return CPL_OK;
+  if (term && term->termination == CPL_TERM_IPOPT) {  // the compile-time variant with IPOPT's full tests
+    const IpmTerm T{(int)term->nf, term->dual_inf_tol, term->constr_viol_tol, term->compl_inf_tol,
+                    term->acceptable_dual_inf_tol, term->acceptable_constr_viol_tol, term->acceptable_compl_inf_tol,
+                    term->acceptable_obj_change_tol, term->diverging_iterates_tol, term->d_g, term->d_dc, term->d_df,
+                    term->d_gl, term->d_gu, term->d_slack_row, term->d_f, term->d_f_prev, term->d_acceptable,
+                    term->d_dual_inf, term->d_constr_viol, term->d_compl_inf};
+    hipLaunchKernelGGL(cpl_ipm_optimality_term_kernel, dim3((unsigned)blocks), dim3(64 * IPM_WAVES), 0,
+                       (hipStream_t)stream, batch, (int)nw, (int)m, (int)nfilt, (int)nbounds, tol, acc_tol,
+                       (int)acc_iter, d_A, d_gw, d_c, d_w, d_y, d_zL, d_zU, d_hasL, d_hasU, d_wl0, d_wu0, d_mu, d_filt_t,
+                       d_filt_p, d_fcount, d_active, d_status, d_acc, d_d_inf, d_err0, d_base, d_mu_out, d_filt_t_out,
+                       d_filt_p_out, d_fcount_out, (int)mu_rounds, mu_min, d_tiny_flag, d_skip, up, T);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(CPL_ERR_HIP, std::string("cpl_ipm_optimality_ex launch: ") + hipGetErrorString(e));
+    return CPL_OK;
+  }
   hipLaunchKernelGGL(cpl_ipm_optimality_kernel, dim3((unsigned)blocks), dim3(64 * IPM_WAVES), 0, (hipStream_t)stream,
                      batch, (int)nw, (int)m, (int)nfilt, (int)nbounds, tol, acc_tol, (int)acc_iter, d_A, d_gw, d_c, d_w,
                      d_y, d_zL, d_zU, d_hasL, d_hasU, d_wl0, d_wu0, d_mu, d_filt_t, d_filt_p, d_fcount, d_active,
@@ -680,7 +784,50 @@ int32_t cpl_ipm_optimality(int64_t batch, int32_t nw, int32_t m, int32_t nfilt, 
   return ipm_optimality_ex(batch, nw, m, nfilt, nbounds, tol, acc_tol, acc_iter, d_A, d_gw, d_c, d_w, d_y, d_zL, d_zU,
                            d_hasL, d_hasU, d_wl0, d_wu0, d_mu, d_filt_t, d_filt_p, d_fcount, d_active, d_status, d_acc,
                            d_d_inf, d_err0, d_base, d_mu_out, d_filt_t_out, d_filt_p_out, d_fcount_out, IPM_MU_ROUNDS,
-                           ipm_mu_min(tol), nullptr, nullptr, nullptr, stream);
+                           ipm_mu_min(tol), nullptr, nullptr, nullptr, stream, nullptr);
+}
+
+int32_t cpl_ipm_optimality_ex(int64_t batch, int32_t nw, int32_t m, int32_t nfilt, int32_t nbounds, double tol,
+                              double acc_tol, int32_t acc_iter, const double* d_A, const double* d_gw,
+                              const double* d_c, const double* d_w, const double* d_y, const double* d_zL,
+                              const double* d_zU, const uint8_t* d_hasL, const uint8_t* d_hasU, const double* d_wl0,
+                              const double* d_wu0, const double* d_mu, const double* d_filt_t, const double* d_filt_p,
+                              const int64_t* d_fcount, uint8_t* d_active, int64_t* d_status, int64_t* d_acc,
+                              double* d_d_inf, double* d_err0, double* d_base, double* d_mu_out, double* d_filt_t_out,
+                              double* d_filt_p_out, int64_t* d_fcount_out, const cpl_term_args* term, void* stream) {
+  if (!term || (term->termination == CPL_TERM_SCALED && !term->d_skip))
+    return cpl_ipm_optimality(batch, nw, m, nfilt, nbounds, tol, acc_tol, acc_iter, d_A, d_gw, d_c, d_w, d_y, d_zL,
+                              d_zU, d_hasL, d_hasU, d_wl0, d_wu0, d_mu, d_filt_t, d_filt_p, d_fcount, d_active,
+                              d_status, d_acc, d_d_inf, d_err0, d_base, d_mu_out, d_filt_t_out, d_filt_p_out,
+                              d_fcount_out, stream);
+  const bool scaled_only = term->termination == CPL_TERM_SCALED;
+  if (!scaled_only && term->termination != CPL_TERM_IPOPT)
+    return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_optimality_ex: termination must be CPL_TERM_SCALED or CPL_TERM_IPOPT");
+  if (batch < 0 || nw <= 0 || nw > 128 || m < 0 || nfilt < 0 || nbounds < 0 ||
+      (!scaled_only && (term->nf < 0 || term->nf > nw)))
+    return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_optimality_ex: need 0 < nw <= 128, m >= 0, 0 <= nf <= nw");
+  const double tols[] = {term->dual_inf_tol, term->constr_viol_tol, term->compl_inf_tol,
+                         term->acceptable_dual_inf_tol, term->acceptable_constr_viol_tol,
+                         term->acceptable_compl_inf_tol, term->acceptable_obj_change_tol, term->diverging_iterates_tol};
+  for (double t : tols)
+    if (!scaled_only && !(t >= 0.0))
+      return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_optimality_ex: a tolerance is negative or NaN");
+  if (batch == 0) return CPL_OK;
+  if ((m > 0 && (!d_A || !d_c || !d_y)) ||
+      (!scaled_only && ((m > 0 && (!term->d_g || !term->d_gl || !term->d_gu)) ||
+                        (nw > term->nf && !term->d_slack_row) || !term->d_f || !term->d_f_prev ||
+                        !term->d_acceptable || !term->d_dual_inf || !term->d_constr_viol || !term->d_compl_inf)) ||
+      !d_gw || !d_w || !d_zL || !d_zU || !d_hasL || !d_hasU || !d_wl0 ||
+      !d_wu0 || !d_mu || (nfilt > 0 && (!d_filt_t || !d_filt_p || !d_filt_t_out || !d_filt_p_out)) || !d_fcount ||
+      !d_active || !d_status || !d_acc || !d_d_inf || !d_err0 || !d_base || !d_mu_out || !d_fcount_out)
+    return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_optimality_ex: missing buffer");
+  const int64_t blocks = (batch + IPM_WAVES - 1) / IPM_WAVES;
+  if (blocks > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_optimality_ex: batch too large");
+  return ipm_optimality_ex(batch, nw, m, nfilt, nbounds, tol, acc_tol, acc_iter, d_A, d_gw, d_c, d_w, d_y, d_zL, d_zU,
+                           d_hasL, d_hasU, d_wl0, d_wu0, d_mu, d_filt_t, d_filt_p, d_fcount, d_active, d_status, d_acc,
+                           d_d_inf, d_err0, d_base, d_mu_out, d_filt_t_out, d_filt_p_out, d_fcount_out, IPM_MU_ROUNDS,
+                           scaled_only ? ipm_mu_min(tol) : fmin(tol, term->compl_inf_tol) / 11.0, nullptr, term->d_skip,
+                           nullptr, stream, term);
 }
 
 int32_t cpl_ipm_max_step(int64_t batch, int32_t nw, const double* d_v, const double* d_dir, const double* d_v2,

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <algorithm>
@@ -78,7 +79,7 @@ int32_t ipm_optimality_ex(int64_t batch, int32_t nw, int32_t m, int32_t fmax, in
                           uint8_t* d_active, int64_t* d_status, int64_t* d_acc, double* d_dinf, double* d_err0,
                           double* d_base, double* d_mu_o, double* d_ft, double* d_fp, int64_t* d_fc,
                           int32_t mu_rounds, double mu_min, const uint8_t* d_tiny_flag, const uint8_t* d_skip,
-                          const IpmUnpack* unpack, void* stream);
+                          const IpmUnpack* unpack, void* stream, const cpl_term_args* term);
 namespace {
 
 constexpr int FMAX = 64;          // filter entries kept per instance (a ring), as batch_ipm.FMAX
@@ -698,6 +699,7 @@ struct FailTail {
   Staged st;
   const double* err0 = nullptr;
   double acc_tol = 0.0;
+  const uint8_t* acc_ok = nullptr;  // CPL_TERM_IPOPT: the optimality kernel's CurrentIsAcceptable byte (else err0 <= acc_tol)
   uint8_t *failed = nullptr, *moved = nullptr, *in_soft = nullptr;
   int32_t* soft_cnt = nullptr;
   int64_t* status = nullptr;
@@ -709,7 +711,7 @@ __device__ __forceinline__ void fail_book(int64_t b, const FailTail& t) {
   const NearFeasible& nf = t.nf;
   const bool a = t.act[b] != 0;
   bool f = a && !(t.st.alpha[b] > 0.0);
-  const bool at_acc = f && t.err0[b] <= t.acc_tol;
+  const bool at_acc = f && (t.acc_ok ? t.acc_ok[b] != 0 : t.err0[b] <= t.acc_tol);
   const bool near = f && !at_acc && nf.theta_k[b] <= nf.near_tol;
   if (at_acc || near) {
     const bool back = near && nf.has_acc[b] != 0;
@@ -2170,6 +2172,36 @@ __global__ void k_fill(int64_t B, double v, double* __restrict__ out) {
   if (b < B) out[b] = v;
 }
 
+// max_wall_time: every still-active row stops with its current iterate
+__global__ void k_time_limit(int64_t B, uint8_t* __restrict__ active, int64_t* __restrict__ status) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B || !active[b]) return;
+  status[b] = CPL_SOLVE_TIME_LIMIT;
+  active[b] = 0;
+}
+
+// CPL_TERM_IPOPT: the unscaled measures and the bound multipliers of the rows leaving the batch, beside
+// k_scatter_final's results (an element of z per thread; the row's first also copies the measures)
+__global__ void k_scatter_term(int64_t total, int nw, bool finished_only, const int32_t* __restrict__ orig,
+                               const uint8_t* __restrict__ active, const double* __restrict__ du,
+                               const double* __restrict__ cv, const double* __restrict__ cp,
+                               const double* __restrict__ zL, const double* __restrict__ zU, double* __restrict__ fdu,
+                               double* __restrict__ fcv, double* __restrict__ fcp, double* __restrict__ fzL,
+                               double* __restrict__ fzU) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const int64_t r = e / nw;
+  const int k = (int)(e - r * nw);
+  const int32_t o = orig[r];
+  if (o < 0 || (finished_only && active[r])) return;
+  fzL[(int64_t)o * nw + k] = zL[e];
+  fzU[(int64_t)o * nw + k] = zU[e];
+  if (k != 0) return;
+  fdu[o] = du[r];
+  fcv[o] = cv[r];
+  fcp[o] = cp[r];
+}
+
 // results: max violation of g against its bounds, int32 copies of status / iterations
 __global__ __launch_bounds__(256) void k_final(int64_t B, int m, const double* __restrict__ g, const double* __restrict__ gl,
                                                const double* __restrict__ gu, const int64_t* __restrict__ status,
@@ -2349,6 +2381,12 @@ struct cpl_solver {
   double *df, *dc, *ytil;
   int32_t *rrow, *srp, *srq;
   int32_t* nan_cnt;  // [B] full batch: NaN Jacobian entries at each instance's start point
+  // CPL_TERM_IPOPT (cpl_term_args): the previous test's objective, the CurrentIsAcceptable byte, the last
+  // regular test's unscaled measures by batch row and by original instance
+  bool term = false;
+  bool term_done = false;  // the last solve ran with it (cpl_solver_unscaled_errors)
+  double *f_prev, *u_dinf, *u_cviol, *u_compl, *fu_dinf, *fu_cviol, *fu_compl, *fzL, *fzU;
+  uint8_t* acc_ok;
   uint8_t* sc_any;
   bool scaled = false;
   bool sc_fused = true;  // the evaluations apply the scaling themselves (until a path says unsupported)
@@ -2547,6 +2585,21 @@ SoftStepArgs soft_step_args(const cpl_solver* S) {  // (the soft step's callback
   a.a_max = S->a_max; a.a_z = S->a_z; a.cs_tmp = S->cs_tmp;
   return a;
 }
+// diverging: false at the final test after max_iter iterations (IPOPT tests max_iter first)
+cpl_term_args term_args(const cpl_solver* S, bool diverging) {
+  const cpl_solve_options& o = S->opt;
+  cpl_term_args t;
+  t.termination = o.termination; t.nf = S->nf;
+  t.dual_inf_tol = o.dual_inf_tol; t.constr_viol_tol = o.constr_viol_tol; t.compl_inf_tol = o.compl_inf_tol;
+  t.acceptable_dual_inf_tol = o.acceptable_dual_inf_tol; t.acceptable_constr_viol_tol = o.acceptable_constr_viol_tol;
+  t.acceptable_compl_inf_tol = o.acceptable_compl_inf_tol; t.acceptable_obj_change_tol = o.acceptable_obj_change_tol;
+  t.diverging_iterates_tol = diverging ? o.diverging_iterates_tol : INFINITY;
+  t.d_g = S->g; t.d_dc = S->scaled ? S->dc : nullptr; t.d_df = S->scaled ? S->df : nullptr;
+  t.d_gl = S->gl; t.d_gu = S->gu; t.d_slack_row = S->ineq_row; t.d_f = S->f; t.d_f_prev = S->f_prev;
+  t.d_acceptable = S->acc_ok; t.d_dual_inf = S->u_dinf; t.d_constr_viol = S->u_cviol; t.d_compl_inf = S->u_compl;
+  t.d_skip = nullptr;  // (the engine passes in_resto as the kernel's skip itself)
+  return t;
+}
 NearFeasible near_feasible(const cpl_solver* S) {
   return NearFeasible{S->theta_k, 1e-2 * S->opt.tol, S->nw, S->m, S->has_acc, S->acc_w, S->acc_y, S->acc_zL, S->acc_zU,
                       S->w, S->y, S->zL, S->zU};
@@ -2555,6 +2608,7 @@ FailTail fail_tail(const cpl_solver* S) {
   FailTail t;
   t.n = S->n; t.nw = S->nw; t.freepos = S->freepos; t.Xbase = S->Xbase; t.X = S->Xn; t.act = S->act;
   t.st = staged_of(S); t.err0 = S->err0; t.acc_tol = S->opt.acceptable_tol; t.failed = S->failed; t.moved = S->moved;
+  t.acc_ok = S->term ? S->acc_ok : nullptr;
   t.in_soft = S->in_soft; t.soft_cnt = S->soft_cnt; t.status = S->status; t.active = S->active;
   t.nf = near_feasible(S);
   return t;
@@ -2720,10 +2774,12 @@ int32_t step_phase(cpl_solver* S, int phase) {
       const IpmUnpack unp{n, S->freepos, S->Xbase, S->in_resto, S->X, S->tau, S->act,
                           S->acc_w, S->acc_y, S->acc_zL, S->acc_zU, S->has_acc, post_in_ls ? S->d_any : nullptr,
                           S->in_soft};
+      const cpl_term_args term = S->term ? term_args(S, true) : cpl_term_args{};
       CK(ipm_optimality_ex(B, nw, m, FMAX, S->nbounds, o.tol, o.acceptable_tol, o.acceptable_iter, S->A, S->gradw,
                            S->c, S->w, S->y, S->zL, S->zU, S->hasL, S->hasU, S->wl0, S->wu0, S->mu, S->filt_t,
                            S->filt_p, S->fcount, S->active, S->status, S->acc, S->d_inf, S->err0, S->base, S->mu_o,
-                           S->ft, S->fp, S->fc, MU_ROUNDS, S->mu_min, S->tiny_flag, S->in_resto, &unp, st));
+                           S->ft, S->fp, S->fc, MU_ROUNDS, S->mu_min, S->tiny_flag, S->in_resto, &unp, st,
+                           S->term ? &term : nullptr));
       const double* Hblk = nullptr;
       int h_sym = 0;
       CK(hessian_into(S, &S->desc, S->act, &Hblk, &h_sym));
@@ -3017,6 +3073,12 @@ int32_t compact(cpl_solver* S, int64_t count, int64_t Bn) {
   }
   hipLaunchKernelGGL(k_scatter_final, dim3(blocks_for(Bc)), dim3(256), 0, st, Bc, leave);
   LAUNCHED("k_scatter_final");
+  if (S->term) {
+    hipLaunchKernelGGL(k_scatter_term, dim3(blocks_elems(Bc * S->nw)), dim3(256), 0, st, Bc * S->nw, S->nw, true,
+                       S->orig, S->active, S->u_dinf, S->u_cviol, S->u_compl, S->zL, S->zU, S->fu_dinf, S->fu_cviol,
+                       S->fu_compl, S->fzL, S->fzU);
+    LAUNCHED("k_scatter_term");
+  }
   hipLaunchKernelGGL(k_positions, dim3(1), dim3(1024), 0, st, Bc, S->active, S->pos);
   LAUNCHED("k_positions");
   // every state buffer whose condition holds, gathered through the scratch and copied back
@@ -3073,7 +3135,29 @@ void cpl_solve_options_default(cpl_solve_options* o) {
   o->fallback_viol_tol = 0.0;  // off: IPOPT returns its last iterate
   o->nlp_scaling = 1;          // IPOPT's default nlp_scaling_method gradient-based
   o->jacobian_regularization = 0;  // R's pivots (the restatements' default); 1: IPOPT's (2,2) block
+  o->termination = CPL_TERM_SCALED;  // the scaled optimality error alone; the tolerances below: IPOPT's defaults
+  o->dual_inf_tol = 1.0;
+  o->constr_viol_tol = 1e-4;
+  o->compl_inf_tol = 1e-4;
+  o->acceptable_dual_inf_tol = 1e10;
+  o->acceptable_constr_viol_tol = 1e-2;
+  o->acceptable_compl_inf_tol = 1e-2;
+  o->acceptable_obj_change_tol = 1e20;
+  o->diverging_iterates_tol = 1e20;
+  o->max_wall_time = 0.0;  // none
 }
+
+// [IFOPT-ext] the option set of IFOPT's IpoptSolver constructor (ifopt_ipopt/src/ipopt_solver.cc, as VERDICT.md cites it)
+void cpl_solve_options_ifopt(cpl_solve_options* o) {
+  if (!o) return;
+  cpl_solve_options_default(o);
+  o->hessian = CPL_HESSIAN_LIMITED_MEMORY;
+  o->tol = 1e-3;
+  o->termination = CPL_TERM_IPOPT;
+  o->max_wall_time = 40.0;  // its max_cpu_time
+}
+
+int64_t cpl_solve_options_sizeof(void) { return (int64_t)sizeof(cpl_solve_options); }
 
 int32_t cpl_solver_destroy(cpl_solver* S) {
   if (!S) return CPL_OK;
@@ -3119,6 +3203,36 @@ int32_t cpl_solver_nan_jacobian(const cpl_solver* S, int32_t* d_out, void* strea
   return CPL_OK;
 }
 
+int32_t cpl_solver_unscaled_errors(const cpl_solver* S, double* d_dual_inf, double* d_constr_viol, double* d_compl_inf,
+                                   void* stream) {
+  if (!S) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_unscaled_errors: null solver");
+  if (!S->term_done)
+    return fail(CPL_ERR_UNSUPPORTED, "cpl_solver_unscaled_errors: the last solve did not run with CPL_TERM_IPOPT");
+  const struct { double* dst; const double* src; } outs[] = {
+      {d_dual_inf, S->fu_dinf}, {d_constr_viol, S->fu_cviol}, {d_compl_inf, S->fu_compl}};
+  for (const auto& o : outs)
+    if (o.dst)
+      HK(hipMemcpyAsync(o.dst, o.src, 8 * (size_t)S->B, hipMemcpyDeviceToDevice, (hipStream_t)stream),
+         "hipMemcpyAsync unscaled errors");
+  return CPL_OK;
+}
+
+int32_t cpl_solver_final_iterate(const cpl_solver* S, double* d_w, double* d_zL, double* d_zU, void* stream) {
+  if (!S) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_final_iterate: null solver");
+  if (!S->term_done)
+    return fail(CPL_ERR_UNSUPPORTED, "cpl_solver_final_iterate: the last solve did not run with CPL_TERM_IPOPT");
+  if (d_w)
+    HK(hipMemcpyAsync(d_w, S->fw, 8 * (size_t)S->B * S->nw, hipMemcpyDeviceToDevice, (hipStream_t)stream),
+       "hipMemcpyAsync w");
+  if (d_zL)
+    HK(hipMemcpyAsync(d_zL, S->fzL, 8 * (size_t)S->B * S->nw, hipMemcpyDeviceToDevice, (hipStream_t)stream),
+       "hipMemcpyAsync zL");
+  if (d_zU)
+    HK(hipMemcpyAsync(d_zU, S->fzU, 8 * (size_t)S->B * S->nw, hipMemcpyDeviceToDevice, (hipStream_t)stream),
+       "hipMemcpyAsync zU");
+  return CPL_OK;
+}
+
 int32_t cpl_solver_restorations(const cpl_solver* S, int64_t* d_out, void* stream) {
   if (!S || !d_out) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_restorations: null argument");
   HK(hipMemcpyAsync(d_out, S->fresto, 8 * (size_t)S->B, hipMemcpyDeviceToDevice, (hipStream_t)stream),
@@ -3139,6 +3253,15 @@ int32_t cpl_solver_create(const cpl_problem_desc* d, int64_t batch, const cpl_so
       opt.max_ls < 0 || !(opt.tol > 0.0) || opt.ls_kernel < 0 || opt.ls_kernel > 2 || opt.nlp_scaling < 0 ||
       opt.nlp_scaling > 1 || opt.jacobian_regularization < 0 || opt.jacobian_regularization > 1)
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_create: bad options");
+  if (opt.termination != CPL_TERM_SCALED && opt.termination != CPL_TERM_IPOPT)
+    return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_create: termination must be CPL_TERM_SCALED or CPL_TERM_IPOPT");
+  {
+    const double tols[] = {opt.dual_inf_tol, opt.constr_viol_tol, opt.compl_inf_tol, opt.acceptable_dual_inf_tol,
+                           opt.acceptable_constr_viol_tol, opt.acceptable_compl_inf_tol, opt.acceptable_obj_change_tol,
+                           opt.diverging_iterates_tol, opt.max_wall_time, opt.acceptable_tol};
+    for (double t : tols)
+      if (!(t >= 0.0)) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_create: a tolerance is negative or NaN");
+  }
   int32_t n, m, nnz;
   CK(cpl_dims(d, &n, &m, &nnz));
   std::vector<int32_t> iRow(nnz), jCol(nnz);
@@ -3238,7 +3361,8 @@ int32_t cpl_solver_create(const cpl_problem_desc* d, int64_t batch, const cpl_so
     return fail(CPL_ERR_UNSUPPORTED, "cpl_solver_create: jacobian_regularization needs nw + m <= 128");
   }
   S->ls_fusable = kkt_wave_size(nw, m);
-  S->mu_min = ipm_mu_min(opt.tol);
+  S->term = opt.termination == CPL_TERM_IPOPT;
+  S->mu_min = S->term ? std::fmin(opt.tol, opt.compl_inf_tol) / 11.0 : ipm_mu_min(opt.tol);
   S->bfgs = opt.hessian == CPL_HESSIAN_LIMITED_MEMORY;
   S->analytic_H = opt.hessian == CPL_HESSIAN_EXACT && cpl_lagrangian_hessian(d, 0, nullptr, nullptr, nullptr, nullptr,
                                                                              nf > 0 ? nf : 1, nullptr, nullptr) == CPL_OK;
@@ -3352,6 +3476,12 @@ int32_t cpl_solver_create(const cpl_problem_desc* d, int64_t batch, const cpl_so
   S->df = c.state<double>(1, IF_SCALED); S->dc = c.state<double>(m, IF_SCALED); S->ytil = c.temp<double>(S->bfgs ? 0 : m);
   S->rrow = c.fixed<int32_t>(nnz_rec); S->srp = c.fixed<int32_t>(m + 1); S->srq = c.fixed<int32_t>(srq.size());
   S->sc_any = c.fixed<uint8_t>(4); S->nan_cnt = c.full<int32_t>(1);
+  // CPL_TERM_IPOPT's per-instance state (width 0 with the mode off: never moved, never read)
+  const size_t tw = S->term ? 1 : 0;
+  S->f_prev = c.state<double>(tw, ALWAYS); S->acc_ok = S->term ? c.state<uint8_t>(1, ALWAYS, ZEROED) : nullptr;
+  S->u_dinf = c.state<double>(tw, ALWAYS); S->u_cviol = c.state<double>(tw, ALWAYS); S->u_compl = c.state<double>(tw, ALWAYS);
+  S->fu_dinf = c.full<double>(tw); S->fu_cviol = c.full<double>(tw); S->fu_compl = c.full<double>(tw);
+  S->fzL = c.full<double>(tw * nw); S->fzU = c.full<double>(tw * nw);
   // last: the gather scratch holds the widest state row of every instance, in 8-byte words
   S->scratch_words = (int64_t)((c.row_bytes + 7) / 8);
   S->scratch = c.temp<uint64_t>((size_t)S->scratch_words);
@@ -3443,6 +3573,14 @@ int32_t cpl_solver_solve_inst(cpl_solver* S, const double* d_x0, const double* d
     if (r.zeroed) HK(hipMemsetAsync(r.ptr, 0, r.elem * (size_t)(B * r.width), st), "hipMemsetAsync");
   hipLaunchKernelGGL(k_fill, dim3(blocks_elems(B)), dim3(256), 0, st, B, INFINITY, S->best_f);
   LAUNCHED("k_fill best_f");
+  S->term_done = S->term;
+  if (S->term) {  // IPOPT's last_obj_val starts at -1e50; the measures of an instance never tested read 0
+    hipLaunchKernelGGL(k_fill, dim3(blocks_elems(B)), dim3(256), 0, st, B, -1e50, S->f_prev);
+    LAUNCHED("k_fill f_prev");
+    for (double* p : {S->u_dinf, S->u_cviol, S->u_compl})
+      HK(hipMemsetAsync(p, 0, 8 * (size_t)B, st), "hipMemsetAsync unscaled errors");
+  }
+  const auto t_start = std::chrono::steady_clock::now();
   int64_t evals = 0;
   if (S->fd && (d_mass || d_env_tag)) {
     hipLaunchKernelGGL(k_repeat, dim3(blocks_elems(B * 2 * nf)), dim3(256), 0, st, B, 2 * nf, S->mass, S->mass_fd,
@@ -3531,6 +3669,13 @@ int32_t cpl_solver_solve_inst(cpl_solver* S, const double* d_x0, const double* d
     const int64_t cnt = ((volatile int32_t*)S->h_count)[0];
     resto_rows = ((volatile int32_t*)S->h_count)[1];
     if (cnt == 0) break;
+    // max_wall_time, at the iteration's host synchronisation: the active rows stop where they are
+    if (S->opt.max_wall_time > 0.0 &&
+        std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count() > S->opt.max_wall_time) {
+      hipLaunchKernelGGL(k_time_limit, dim3(blocks_elems(S->Bcur)), dim3(256), 0, st, S->Bcur, S->active, S->status);
+      LAUNCHED("k_time_limit");
+      break;
+    }
     if (compacting && S->Bcur > min_rows && 2 * cnt <= S->Bcur) {
       // shrink to the smallest halving of the current size that holds the active instances
       int64_t Bn = S->Bcur;
@@ -3544,10 +3689,18 @@ int32_t cpl_solver_solve_inst(cpl_solver* S, const double* d_x0, const double* d
   hipLaunchKernelGGL(k_prep, dim3(blocks_for(Bc)), dim3(256), 0, st, Bc, n, m, nf, nw, S->free32, S->row_slack, S->gl,
                      S->grad, S->g, S->w, S->gradw, S->c);
   LAUNCHED("k_prep");
+  const cpl_term_args term_fin = S->term ? term_args(S, false) : cpl_term_args{};
   CK(ipm_optimality_ex(Bc, nw, m, FMAX, S->nbounds, S->opt.tol, S->opt.acceptable_tol, S->opt.acceptable_iter, S->A,
                        S->gradw, S->c, S->w, S->y, S->zL, S->zU, S->hasL, S->hasU, S->wl0, S->wu0, S->mu, S->filt_t,
                        S->filt_p, S->fcount, S->active, S->status, S->acc, S->d_inf, S->err0, S->base, S->mu_o, S->ft,
-                       S->fp, S->fc, MU_ROUNDS, S->mu_min, nullptr, S->in_resto, nullptr, st));
+                       S->fp, S->fc, MU_ROUNDS, S->mu_min, nullptr, S->in_resto, nullptr, st,
+                       S->term ? &term_fin : nullptr));
+  if (S->term) {
+    hipLaunchKernelGGL(k_scatter_term, dim3(blocks_elems(Bc * nw)), dim3(256), 0, st, Bc * nw, nw, false, S->orig,
+                       S->active, S->u_dinf, S->u_cviol, S->u_compl, S->zL, S->zU, S->fu_dinf, S->fu_cviol, S->fu_compl,
+                       S->fzL, S->fzU);
+    LAUNCHED("k_scatter_term");
+  }
   const LeaveArgs leave = leave_args(S, false);
   if (S->opt.fallback_viol_tol > 0.0) {
     hipLaunchKernelGGL(k_fallback, dim3(blocks_for(Bc)), dim3(256), 0, st, Bc, leave);

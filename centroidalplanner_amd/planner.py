@@ -3,8 +3,9 @@
 Mirrors include/CentroidalPlanner/CentroidalPlanner.h and CoMPlanner.h: same method names, same
 argument meaning, same validation and error kinds (std::invalid_argument -> InvalidArgument,
 std::runtime_error -> CplError(ERR_RUNTIME)).  Solve() runs the batched interior-point solve loop on
-one instance (centroidalplanner_amd.solver: IPOPT's method with IFOPT's defaults — limited-memory
-Hessian, max_iter 3000, tol 1e-8) over the GPU callbacks; like the reference's persistent problem,
+one instance (centroidalplanner_amd.solver: IPOPT's method with the engine's defaults — limited-memory
+Hessian, max_iter 3000, tol 1e-8; SetSolverOptions(**batch_ipm.IFOPT_OPTIONS) selects the set IFOPT's
+IpoptSolver runs with) over the GPU callbacks; like the reference's persistent problem,
 the variables keep the last solution between solves (warm start).
 """
 from __future__ import annotations
@@ -93,7 +94,8 @@ class CentroidalPlanner:
         self._env = env
         self._cpl_problem = CplProblem(self._contact_names, self._robot_mass, env)
         self.evaluator = None  # None: GPU callbacks; tests may inject the oracle
-        # IFOPT's IpoptSolver defaults the reference runs with (src/CentroidalPlanner.cpp:22-29)
+        # the engine's defaults (IFOPT's own option set — tol 1e-3, IPOPT's full termination tests, a 40 s
+        # limit — is the preset batch_ipm.IFOPT_OPTIONS: SetSolverOptions(**IFOPT_OPTIONS))
         self.solver_tol = 1e-8
         self.solver_max_iter = 3000
         self.solver_hessian = "limited-memory"  # or "exact" / "analytic" (solver.solve's option)
@@ -104,12 +106,28 @@ class CentroidalPlanner:
         # first derivatives at the start point of every solve; the report lands here
         self.solver_derivative_test = "first-order"
         self.last_derivative_report = None
+        self._solver_options = {}  # SetSolverOptions: further batch_ipm_solve options of Solve / SolveBatch
+
+    def SetSolverOptions(self, **options):
+        """Options of batch_ipm_solve (tol, hessian, termination and its tolerances, max_wall_time, ...)
+        merged into every later Solve() and SolveBatch(); no arguments: back to none (the default).
+        SetSolverOptions(**batch_ipm.IFOPT_OPTIONS) runs the option set of IFOPT's IpoptSolver."""
+        self._solver_options = dict(options)
+
+    def GetSolverOptions(self) -> dict:
+        return dict(self._solver_options)
+
+    def _solve_kwargs(self) -> dict:
+        opts = {"tol": self.solver_tol, "max_iter": self.solver_max_iter, "hessian": self.solver_hessian,
+                "jacobian_regularization": self.solver_jacobian_regularization}
+        opts.update(self._solver_options)
+        return opts
 
     # ---- Solve (src/CentroidalPlanner.cpp:22-34) ------------------------------------------
     def Solve(self) -> Solution:
-        res = solve(self._cpl_problem, evaluator=self.evaluator, tol=self.solver_tol, max_iter=self.solver_max_iter,
-                    hessian=self.solver_hessian, jacobian_regularization=self.solver_jacobian_regularization,
-                    derivative_test=self.solver_derivative_test if self.evaluator is None else "none")
+        res = solve(self._cpl_problem, evaluator=self.evaluator,
+                    derivative_test=self.solver_derivative_test if self.evaluator is None else "none",
+                    **self._solve_kwargs())
         self.last_derivative_report = res.derivative_report
         sol = self._cpl_problem.GetSolution()
         out = Solution(com_sol=sol["com"], success=res.success, message=res.status, iterations=res.iterations,
@@ -127,8 +145,7 @@ class CentroidalPlanner:
         planner's).  Returns the BatchSolveResult; the planner's own variables are left as they were."""
         from .batch_ipm import batch_ipm_solve
 
-        opts = {"tol": self.solver_tol, "max_iter": self.solver_max_iter, "hessian": self.solver_hessian,
-                "jacobian_regularization": self.solver_jacobian_regularization}
+        opts = self._solve_kwargs()
         opts.update(solve_options)
         if not getattr(X0, "is_cuda", False):
             raise ValueError("SolveBatch: X0 must be a float64 CUDA tensor [B, n]")
@@ -331,6 +348,12 @@ class CoMPlanner:
     # using CentroidalPlanner::... (include/CentroidalPlanner/CoMPlanner.h:67-78)
     def Solve(self):
         return self._cp.Solve()
+
+    def SetSolverOptions(self, **options):
+        self._cp.SetSolverOptions(**options)
+
+    def GetSolverOptions(self) -> dict:
+        return self._cp.GetSolverOptions()
 
     def SolveBatch(self, positions, normals=None, com_ref=None, wrench=None, mass=None, **solve_options):
         """The stance query, batched: are these B candidate stances statically feasible, and with what

@@ -1,8 +1,11 @@
 """Solve() plumbing of the facade: the batched interior-point solve loop on a batch of one.
 
 The reference drives each solve with ifopt::IpoptSolver (src/CentroidalPlanner.cpp:22-34): IPOPT
-with IFOPT's defaults — exact constraint Jacobian, limited-memory Hessian, max_iter 3000, tol 1e-8
-— from the problem's current variables (x = 0 initially, src/Variable3D.cpp:8-10).  IPOPT is not in
+from the problem's current variables.  The defaults here are the engine's — exact constraint Jacobian,
+limited-memory Hessian, max_iter 3000, tol 1e-8, the scaled optimality error as the only test; the set
+IFOPT's IpoptSolver constructor itself runs with (tol 1e-3, IPOPT's full termination tests, a 40 s
+limit) is the preset batch_ipm.IFOPT_OPTIONS, passed as ``solve(..., **IFOPT_OPTIONS)``.  The start is
+the problem's current variables (x = 0 initially, src/Variable3D.cpp:8-10).  IPOPT is not in
 this image; the same method runs here as the batched solve loop (batch_ipm.py, the driver of the
 8,192-instance solves) with B = 1: on the GPU (HIP kernels, the iteration captured as a HIP graph)
 when no evaluator is given, else on the host over the evaluator's callbacks (tests inject the
@@ -62,8 +65,10 @@ class _HostBatchEvaluator:
 
 def solve(problem, evaluator=None, x0: Optional[np.ndarray] = None, tol: float = 1e-8, max_iter: int = 3000,
           hessian: str = "limited-memory", derivative_test: str = "none",
-          jacobian_regularization: str = "pivot") -> SolveResult:
-    """One instance through the batched solve loop.  hessian: "limited-memory" (IFOPT's default, as
+          jacobian_regularization: str = "pivot", **options) -> SolveResult:
+    """One instance through the batched solve loop.  options: further keyword arguments of
+    batch_ipm_solve (termination, its tolerances, max_wall_time, ...; batch_ipm.IFOPT_OPTIONS is IFOPT's
+    set).  hessian: "limited-memory" (IFOPT's default, as
     the reference runs), "exact" (the analytic Lagrangian Hessian on Ground / no-environment
     templates, central differences otherwise) or "analytic" (the analytic one for every environment
     kind; batch_ipm_solve's option).  derivative_test:
@@ -84,11 +89,11 @@ def solve(problem, evaluator=None, x0: Optional[np.ndarray] = None, tol: float =
         if derivative_test == "first-order":
             report = problem.derivative_test(X0)
         r = batch_ipm_solve(problem, X0, None, tol=tol, max_iter=max_iter, hessian=hessian,
-                            jacobian_regularization=jacobian_regularization)
+                            jacobian_regularization=jacobian_regularization, **options)
     else:
         r = batch_ipm_solve(problem, torch.as_tensor(x0[None]), None, evaluator=_HostBatchEvaluator(evaluator),
                             tol=tol, max_iter=max_iter, hessian=hessian,
-                            jacobian_regularization=jacobian_regularization)
+                            jacobian_regularization=jacobian_regularization, **options)
     # the NaN Jacobian entries the solve's own start-point evaluation met (cpl_solver_nan_jacobian)
     nan0 = int(r.nan_jacobian[0])
     if nan0:

@@ -6,8 +6,8 @@
 // (CentroidalPlanner.h:232); IPOPT is not part of this build, so the solver is the NlpSolver
 // interface below: any NLP solver that drives a CplTNLP (an Ipopt::TNLP forwarding adapter, see
 // INTEGRATION.md §1), by default the native engine (NativeSolver: IPOPT's interior-point method on
-// the GPU, csrc/cpl_solver.hip, with IFOPT's IpoptSolver defaults — limited-memory Hessian,
-// max_iter 3000, tol 1e-8).  Like IFOPT's solver, a solve that ends unconverged does not throw
+// the GPU, csrc/cpl_solver.hip, with the engine's defaults — limited-memory Hessian, max_iter 3000,
+// tol 1e-8; SolveOptions::Ifopt() is the option set IFOPT's IpoptSolver constructor runs with).  Like IFOPT's solver, a solve that ends unconverged does not throw
 // (LastSolveSucceeded() tells); a HIP failure throws std::runtime_error.
 #pragma once
 
@@ -29,14 +29,21 @@ class NlpSolver {
   virtual bool Solve(CplTNLP& nlp) = 0;
 };
 
-// The native engine's options (cpl_solve_options), IFOPT's IpoptSolver defaults: limited-memory
-// Hessian (src/CentroidalPlanner.cpp:22-29 keeps IFOPT's setting), max_iter 3000, tol 1e-8.
+// The native engine's options (cpl_solve_options) at the engine's defaults: limited-memory Hessian
+// (src/CentroidalPlanner.cpp:22-29 keeps IFOPT's setting), max_iter 3000, tol 1e-8, the scaled
+// optimality error as the only termination test.  Ifopt(): IFOPT's own set (cpl_solve_options_ifopt:
+// tol 1e-3, IPOPT's full termination tests, max_wall_time 40 s).
 // hessian takes every CPL_HESSIAN_* value; CPL_HESSIAN_ANALYTIC is the analytic Hessian for every
 // environment kind (Superquadric and mixed templates included).
 struct SolveOptions : cpl_solve_options {
   SolveOptions() {
     cpl_solve_options_default(this);
     hessian = CPL_HESSIAN_LIMITED_MEMORY;
+  }
+  static SolveOptions Ifopt() {
+    SolveOptions o;
+    cpl_solve_options_ifopt(&o);
+    return o;
   }
   // src/CentroidalPlanner.cpp:26 SetOption("derivative_test", "first-order"): IPOPT's first-order
   // derivative checker at the start point of every solve (cpl_derivative_test); NativeSolver keeps

@@ -473,6 +473,54 @@ int32_t cpl_ipm_optimality(int64_t batch, int32_t nw, int32_t m, int32_t nfilt, 
                            const int64_t* d_fcount, uint8_t* d_active, int64_t* d_status, int64_t* d_acc,
                            double* d_d_inf, double* d_err0, double* d_base, double* d_mu_out, double* d_filt_t_out,
                            double* d_filt_p_out, int64_t* d_fcount_out, void* stream);
+/*
+ * cpl_ipm_optimality_ex: cpl_ipm_optimality with IPOPT's full termination tests [IPOPT-ext: restated from
+ *   the published semantics of OptimalityErrorConvergenceCheck; IPOPT's source is not part of this
+ *   repository].  term == NULL or term->termination == CPL_TERM_SCALED: exactly cpl_ipm_optimality (the
+ *   same kernel, the same outputs bit for bit; of term only d_skip is read).  CPL_TERM_IPOPT: in the same pass, per instance
+ *     dual_inf    = max_k |dual_k| / df over the free variables (k < nf), |dual_k| dc_r / df over the slack of
+ *                   inequality row r = d_slack_row[k - nf] (IPOPT's unscaled_curr_dual_infeasibility);
+ *     constr_viol = max_r max(0, gl_r - g_r / dc_r, g_r / dc_r - gu_r) — on d(x), not d(x) - s; a NaN row
+ *                   counts as +inf;
+ *     compl_inf   = max(comp_L, comp_U) / df;
+ *     obj_change  = |f - f_prev| / max(1, |f|) on the scaled f (f_prev starts at -1e50, the caller's fill);
+ *   optimal: err0 <= tol and the three measures within dual_inf_tol / constr_viol_tol / compl_inf_tol;
+ *   acceptable (CurrentIsAcceptable: the consecutive count, the backup point, d_acceptable): err0 <= acc_tol,
+ *   the three within the acceptable_* limits and obj_change <= acceptable_obj_change_tol; then, for an
+ *   instance that stopped on neither, max_{k < nf} |w_k| > diverging_iterates_tol -> status
+ *   CPL_SOLVE_DIVERGING.  The barrier floor is min(tol, compl_inf_tol) / 11.  d_f_prev and the three
+ *   measures are written for the instances active at entry; d_acceptable for every instance.
+ */
+typedef struct cpl_term_args {
+  int32_t termination; /* CPL_TERM_* */
+  int32_t nf;          /* w[0 .. nf) are the free variables, w[nf .. nw) the slacks */
+  double dual_inf_tol, constr_viol_tol, compl_inf_tol;
+  double acceptable_dual_inf_tol, acceptable_constr_viol_tol, acceptable_compl_inf_tol, acceptable_obj_change_tol;
+  double diverging_iterates_tol;
+  const double* d_g;          /* [batch, m] the scaled constraint values of the iterate */
+  const double* d_dc;         /* [batch, m] constraint scaling factors, NULL = 1 */
+  const double* d_df;         /* [batch] objective scaling factor, NULL = 1 */
+  const double* d_gl;         /* [m] */
+  const double* d_gu;         /* [m] */
+  const int32_t* d_slack_row; /* [nw - nf] the inequality row of each slack */
+  const double* d_f;          /* [batch] the scaled objective */
+  double* d_f_prev;           /* [batch] in / out */
+  uint8_t* d_acceptable;      /* [batch] out: CurrentIsAcceptable */
+  double* d_dual_inf;         /* [batch] out */
+  double* d_constr_viol;      /* [batch] out */
+  double* d_compl_inf;        /* [batch] out */
+  const uint8_t* d_skip;      /* [batch] or NULL: instances passed through untouched (the solve engine's rows
+                                 in the restoration phase: mu, filter and count are copied, nothing else is
+                                 written); honoured under either termination value */
+} cpl_term_args;
+int32_t cpl_ipm_optimality_ex(int64_t batch, int32_t nw, int32_t m, int32_t nfilt, int32_t nbounds, double tol,
+                              double acc_tol, int32_t acc_iter, const double* d_A, const double* d_gw,
+                              const double* d_c, const double* d_w, const double* d_y, const double* d_zL,
+                              const double* d_zU, const uint8_t* d_hasL, const uint8_t* d_hasU, const double* d_wl0,
+                              const double* d_wu0, const double* d_mu, const double* d_filt_t, const double* d_filt_p,
+                              const int64_t* d_fcount, uint8_t* d_active, int64_t* d_status, int64_t* d_acc,
+                              double* d_d_inf, double* d_err0, double* d_base, double* d_mu_out, double* d_filt_t_out,
+                              double* d_filt_p_out, int64_t* d_fcount_out, const cpl_term_args* term, void* stream);
 int32_t cpl_ipm_max_step(int64_t batch, int32_t nw, const double* d_v, const double* d_dir, const double* d_v2,
                          const double* d_dir2, const uint8_t* d_hasL, const uint8_t* d_hasU, const double* d_lo,
                          const double* d_up, const double* d_tau, double* d_out, void* stream);
@@ -562,6 +610,12 @@ int32_t cpl_ipm_dense_a(int64_t batch, int32_t m, int32_t nw, int32_t nf, int32_
                                     the acceptable level, that point is restored and the status is
                                     CPL_SOLVE_ACCEPTABLE instead (IPOPT's backup acceptable point) */
 
+#define CPL_SOLVE_DIVERGING 5    /* CPL_TERM_IPOPT: max |x| exceeded diverging_iterates_tol */
+#define CPL_SOLVE_TIME_LIMIT 6   /* max_wall_time passed: the instance's current iterate is returned */
+
+#define CPL_TERM_SCALED 0 /* the scaled optimality error alone (the default) */
+#define CPL_TERM_IPOPT 1  /* IPOPT's full termination tests, unscaled measures included */
+
 typedef struct cpl_solve_options {
   int32_t max_iter;        /* 3000 (IPOPT's default) */
   int32_t hessian;         /* CPL_HESSIAN_*, default CPL_HESSIAN_EXACT */
@@ -607,14 +661,43 @@ typedef struct cpl_solve_options {
                               in (dw, s) with A~ = [A, -sqrt(delta_c) I] on the workgroup KKT kernel;
                               needs nw + m <= 128.  The restatements carry the same option
                               (oracle cplo_set_jac_reg, batch_ipm_solve(jacobian_regularization="ipopt")). */
+  int32_t termination;     /* CPL_TERM_SCALED (0, default): the scaled optimality error alone decides (err0 <=
+                              tol, or <= acceptable_tol for acceptable_iter iterations); the seven tolerances
+                              below and diverging_iterates_tol are ignored and the barrier floor is
+                              min(tol, 1e-4) / 11.  CPL_TERM_IPOPT (1): IPOPT's OptimalityErrorConvergenceCheck
+                              [IPOPT-ext] — "optimal" also needs the unscaled dual infeasibility, constraint
+                              violation and complementarity within dual_inf_tol / constr_viol_tol /
+                              compl_inf_tol; "acceptable" needs their acceptable_* counterparts and the
+                              objective change; an instance with max |x| > diverging_iterates_tol stops as
+                              CPL_SOLVE_DIVERGING; the barrier floor is min(tol, compl_inf_tol) / 11. */
+  int32_t reserved_term;   /* 0 */
+  double dual_inf_tol;                /* 1 */
+  double constr_viol_tol;             /* 1e-4 */
+  double compl_inf_tol;               /* 1e-4 */
+  double acceptable_dual_inf_tol;     /* 1e10 */
+  double acceptable_constr_viol_tol;  /* 1e-2 */
+  double acceptable_compl_inf_tol;    /* 1e-2 */
+  double acceptable_obj_change_tol;   /* 1e20 */
+  double diverging_iterates_tol;      /* 1e20 */
+  double max_wall_time;    /* seconds, 0 (default) = none; honoured under either termination value.  Checked on
+                              the host once per lock-step iteration: when it has passed, every still-active
+                              instance stops as CPL_SOLVE_TIME_LIMIT with its current iterate.  (IPOPT's
+                              max_cpu_time is per solve; this bounds the batch's solve call.) */
 } cpl_solve_options;
 
 typedef struct cpl_solver cpl_solver;
 
 void cpl_solve_options_default(cpl_solve_options* o);
+/* The option set IFOPT's IpoptSolver constructor runs with [IFOPT-ext: ifopt_ipopt/src/ipopt_solver.cc, as cited
+ * in VERDICT.md; IFOPT's source is not part of this repository]: the defaults plus hessian =
+ * CPL_HESSIAN_LIMITED_MEMORY, tol = 1e-3, termination = CPL_TERM_IPOPT, max_wall_time = 40 (its max_cpu_time). */
+void cpl_solve_options_ifopt(cpl_solve_options* o);
+/* sizeof(cpl_solve_options), for mirrors of the struct in other languages */
+int64_t cpl_solve_options_sizeof(void);
 /* A solver for `batch` instances of the template `d` (copied): plans the problem (free / fixed
  * variables, slacks, the Jacobian maps) and allocates every device buffer on the current device.
- * nw = free variables + inequality rows must be <= 128. */
+ * nw = free variables + inequality rows must be <= 128.  A negative or NaN tolerance, or a
+ * termination outside CPL_TERM_*, is CPL_ERR_INVALID_ARGUMENT before anything is allocated. */
 int32_t cpl_solver_create(const cpl_problem_desc* d, int64_t batch, const cpl_solve_options* o, cpl_solver** out);
 int32_t cpl_solver_destroy(cpl_solver* s);
 /* Solve every instance from d_x0 [batch, n] (device; masses d_mass [batch] or NULL, tags
@@ -623,7 +706,8 @@ int32_t cpl_solver_destroy(cpl_solver* s);
  * honor_original_bounds), d_y [batch, m] constraint multipliers, d_status (CPL_SOLVE_*), d_iters
  * (iterations per instance), d_obj (f at d_x), d_primal_inf (max violation at d_x), d_dual_inf (the
  * last iterate's dual infeasibility OF THE SCALED PROBLEM when nlp_scaling is on — IPOPT's scaled
- * quantity; d_y is returned unscaled, dc y / df).
+ * quantity; d_y is returned unscaled, dc y / df.  The unscaled dual infeasibility, constraint violation and
+ * complementarity: cpl_solver_unscaled_errors after a CPL_TERM_IPOPT solve).
  * *iterations_run (host, may be NULL): lock-step iterations of the batch; *evaluations: eval launches. */
 int32_t cpl_solver_solve(cpl_solver* s, const double* d_x0, const double* d_mass, const uint8_t* d_env_tag,
                          double* d_x, double* d_y, int32_t* d_status, int32_t* d_iters, double* d_obj,
@@ -659,6 +743,17 @@ int32_t cpl_solver_restorations(const cpl_solver* s, int64_t* d_out, void* strea
  * variables at their values; the cone's 0/0 at F_t = 0, src/Constraints/FrictionCone.cpp:85-87), which
  * the iteration takes as 0 where IPOPT would receive NaN, into d_out [batch] (device int32) */
 int32_t cpl_solver_nan_jacobian(const cpl_solver* s, int32_t* d_out, void* stream);
+/* the unscaled measures of each instance's last regular convergence test under CPL_TERM_IPOPT (dual
+ * infeasibility, constraint violation of d(x), complementarity: see cpl_term_args), into device arrays
+ * [batch] in the instances' own order (any may be NULL); CPL_ERR_UNSUPPORTED after a solve with
+ * CPL_TERM_SCALED */
+int32_t cpl_solver_unscaled_errors(const cpl_solver* s, double* d_dual_inf, double* d_constr_viol, double* d_compl_inf,
+                                   void* stream);
+/* each instance's last iterate w [batch, nw] (the free variables in index order, then the slacks of the
+ * inequality rows in row order — before the projection onto the original bounds that d_x carries) and its
+ * bound multipliers z_L, z_U [batch, nw] (of the scaled problem), with which the measures above can be
+ * recomputed from the callbacks (any may be NULL); CPL_ERR_UNSUPPORTED after a CPL_TERM_SCALED solve */
+int32_t cpl_solver_final_iterate(const cpl_solver* s, double* d_w, double* d_zL, double* d_zU, void* stream);
 
 #ifdef __cplusplus
 }

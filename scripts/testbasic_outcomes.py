@@ -5,8 +5,13 @@ callbacks) the outcome, the iteration count, whether the best-feasible fallback 
 Jacobian entries at the start, the returned point's TestBasic quantities (force / torque balance
 errors, worst cone value) and the wall time.  One JSON line per run.
 
-usage: python scripts/testbasic_outcomes.py [gpu|oracle|both] [pivot|ipopt] > out.jsonl
+usage: python scripts/testbasic_outcomes.py [gpu|oracle|both] [pivot|ipopt] [--options ifopt] > out.jsonl
 (the second argument: the facade's solver_jacobian_regularization; default: the facade's own, pivot)
+--options ifopt: SetSolverOptions(**IFOPT_OPTIONS) — the option set IFOPT's IpoptSolver runs with (tol 1e-3,
+IPOPT's full termination tests, a 40 s limit).  Each line then also says which test decided: the scenario is
+solved a second time from the same start with termination="scaled" (the same iterates until the scaled
+error passes); "unscaled" when the full test stopped at a later iteration or with another status than the
+scaled one, "scaled" otherwise.
 """
 import json
 import os
@@ -79,9 +84,11 @@ class _Oracle:
         return self.po.eval_batch(self.prob.desc(), np.atleast_2d(X), outputs=("g", "jac", "f", "grad"), nthreads=1)
 
 
-def run(name, make, backend, jac_reg=None):
+def run(name, make, backend, jac_reg=None, options=None):
     cpl, wrench, mu = make()
     inner = getattr(cpl, "_cp", cpl)  # (CoMPlanner wraps a CentroidalPlanner)
+    if options:
+        cpl.SetSolverOptions(**options)
     if jac_reg is not None:
         inner.solver_jacobian_regularization = jac_reg
     jac_reg = inner.solver_jacobian_regularization
@@ -99,20 +106,47 @@ def run(name, make, backend, jac_reg=None):
         T_sum += np.cross(v.position_value - sol.com_sol, F)
         cone = max(cone, float(-F.dot(n)), float(np.linalg.norm(F - n.dot(F) * n) - mu * F.dot(n)))
     fb = F_sum - np.array([wrench[0], wrench[1], -MASS * G + wrench[2]])
-    return {"scenario": name, "backend": backend, "jacobian_regularization": jac_reg, "status": sol.message, "iterations": sol.iterations,
-            "fallback": bool(sol.fallback), "nan_jacobian_at_start": int(sol.nan_jacobian_at_start),
-            "force_balance_err": float(np.abs(fb).max()), "torque_balance_err": float(np.abs(T_sum - wrench[3:]).max()),
-            "worst_cone_value": cone, "seconds": dt}
+    out = {"scenario": name, "backend": backend, "jacobian_regularization": jac_reg, "status": sol.message, "iterations": sol.iterations,
+           "fallback": bool(sol.fallback), "nan_jacobian_at_start": int(sol.nan_jacobian_at_start),
+           "force_balance_err": float(np.abs(fb).max()), "torque_balance_err": float(np.abs(T_sum - wrench[3:]).max()),
+           "worst_cone_value": cone, "seconds": dt}
+    if options:
+        out["options"] = {k: v for k, v in options.items()}
+        out["objective"] = _objective(cpl)
+    return out
+
+
+def _objective(cpl):
+    import pyoracle
+
+    prob = cpl.GetCplProblem()
+    return float(pyoracle.eval_batch(prob.desc(), np.asarray(prob.get_starting_point(), dtype=np.float64)[None], outputs=("f",), nthreads=1)["f"][0])
 
 
 def main():
-    which = sys.argv[1] if len(sys.argv) > 1 else "gpu"
+    argv = sys.argv[1:]
+    options = None
+    if "--options" in argv:
+        i = argv.index("--options")
+        if argv[i + 1:i + 2] != ["ifopt"]:
+            sys.exit("--options takes: ifopt")
+        from centroidalplanner_amd.batch_ipm import IFOPT_OPTIONS
+
+        options = dict(IFOPT_OPTIONS)
+        del argv[i:i + 2]
+    which = argv[0] if argv else "gpu"
     backends = ["gpu", "oracle"] if which == "both" else [which]
-    jac_reg = sys.argv[2] if len(sys.argv) > 2 else None
+    jac_reg = argv[1] if len(argv) > 1 else None
     for backend in backends:
         for name, make in (("testSimpleProblem", simple), ("testGroundEnv", ground),
                            ("testSuperquadricEnv", superquadric), ("testCoMPlanner", com_planner)):
-            print(json.dumps(run(name, make, backend, jac_reg)), flush=True)
+            r = run(name, make, backend, jac_reg, options)
+            if options:  # which test decided: against the scaled test alone, everything else the same
+                s = run(name, make, backend, jac_reg, dict(options, termination="scaled"))
+                r["scaled_status"], r["scaled_iterations"] = s["status"], s["iterations"]
+                r["decided_by"] = ("unscaled" if (r["iterations"], r["status"]) != (s["iterations"], s["status"])
+                                   else "scaled")
+            print(json.dumps(r), flush=True)
 
 
 if __name__ == "__main__":
