@@ -1,0 +1,125 @@
+// cpl_engine.hpp — the solve engine's internal interface: every namespace-cpl function that one
+// translation unit defines and another calls (the defining file and the calling file both include
+// this header; default arguments are here and nowhere else), and the argument blocks of cpl_ipm.hip's
+// wide kernels, which cpl_solver.hip fills from its buffers.  As in cpl_solver.hip's groups, no member
+// is __restrict__ and every member has a default.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "cpl_accept.hpp"
+#include "cpl_status.hpp"
+
+namespace cpl {
+
+// ---- cpl_ipm.hip ----
+
+// The optimality test and the monotone barrier update (cpl_ipm_optimality_kernel and its TERM variant):
+// at most mu_rounds barrier decreases down to the floor mu_min; tiny_flag: a forced first decrease after
+// two tiny steps (or NULL); skip: instances in the restoration phase, left untouched (or NULL: none).
+// Writes status / acc / active in place; the barrier parameter and the filter go to the *_out buffers.
+struct IpmOptArgs {
+  int64_t batch = 0;
+  int nw = 0, m = 0, nfilt = 0, nbounds = 0;
+  double tol = 0.0, acc_tol = 0.0;
+  int acc_iter = 0, mu_rounds = 0;
+  double mu_min = 0.0;
+  const double *A = nullptr, *gw = nullptr, *c = nullptr, *w = nullptr, *y = nullptr, *zL = nullptr, *zU = nullptr;
+  const uint8_t *hasL = nullptr, *hasU = nullptr;
+  const double *wl0 = nullptr, *wu0 = nullptr, *mu_in = nullptr, *filt_t = nullptr, *filt_p = nullptr;
+  const int64_t* fcount = nullptr;
+  uint8_t* active = nullptr;
+  int64_t *status = nullptr, *acc = nullptr;
+  double *d_inf_out = nullptr, *err0_out = nullptr, *base_out = nullptr, *mu_out = nullptr;
+  double *filt_t_out = nullptr, *filt_p_out = nullptr;
+  int64_t* fcount_out = nullptr;
+  const uint8_t *tiny_flag = nullptr, *skip = nullptr;
+};
+// unpack: the solve loop's unpack fused into the kernel's tail (or NULL); term: cpl_term_args with
+// CPL_TERM_IPOPT runs the TERM variant (or NULL / CPL_TERM_SCALED: the scaled test alone)
+int32_t ipm_optimality(const IpmOptArgs& a, const IpmUnpack* unpack, const cpl_term_args* term, void* stream);
+// the barrier parameter's floor at tolerance tol
+double ipm_mu_min(double tol);
+
+// The Newton system's matrix and right-hand sides (cpl_ipm_newton_setup_kernel).  The Hessian block is
+// either dense (H [batch, nf, nf] or NULL; h_sym: symmetrised in the kernel) or the engine's compact
+// limited-memory model (Hc != NULL, lm_pairs > 0).
+struct NewtonSetupArgs {
+  int64_t batch = 0;
+  int nw = 0, m = 0, nf = 0;
+  const double *w = nullptr, *zL = nullptr, *zU = nullptr, *gw = nullptr, *A = nullptr, *y = nullptr, *c = nullptr;
+  const double *f = nullptr, *mu = nullptr;
+  const uint8_t *hasL = nullptr, *hasU = nullptr;
+  const double *wl0 = nullptr, *wu0 = nullptr;
+  const double* H = nullptr;
+  int h_sym = 0;
+  const double* Hc = nullptr;
+  int lm_pairs = 0;
+  double *M = nullptr, *r1 = nullptr, *r2 = nullptr, *gphi = nullptr, *mr_diag = nullptr, *theta = nullptr, *phi = nullptr;
+  const uint8_t* active = nullptr;
+};
+int32_t ipm_newton_setup(const NewtonSetupArgs& a, void* stream);
+
+// IPOPT's acceptance test of one trial point per instance and the take (cpl_ipm_judge_take_kernel)
+struct JudgeTakeArgs {
+  int64_t batch = 0;
+  int nw = 0, m = 0, nf = 0, nfilt = 0;
+  const int32_t* row_slack = nullptr;
+  const double* gl = nullptr;
+  const uint8_t *hasL = nullptr, *hasU = nullptr;
+  const double *wl0 = nullptr, *wu0 = nullptr;
+  const double *wt = nullptr, *f_t = nullptr, *g_t = nullptr, *alpha = nullptr;  // the trial
+  const double *mu = nullptr, *theta_k = nullptr, *phi_k = nullptr, *gd = nullptr;
+  const uint8_t* switch_ok = nullptr;
+  const double *theta_max = nullptr, *filt_t = nullptr, *filt_p = nullptr;
+  const uint8_t* extra_mask = nullptr;
+  uint8_t* searching = nullptr;
+  double *st_f = nullptr, *st_g = nullptr, *st_w = nullptr, *st_alpha = nullptr;
+  uint8_t* st_aug = nullptr;
+  double* th_out = nullptr;
+  uint8_t* ok_out = nullptr;
+};
+int32_t ipm_judge_take(const JudgeTakeArgs& a, void* stream);
+
+// cpl_ipm_post_step with the solve loop's line-search setup as its tail (ls != NULL)
+int32_t ipm_post_step_ex(int64_t batch, const PostStepArgs& P, const LsSetupArgs* ls, void* stream);
+// cpl_ipm_accept on the argument block the restoration entry also takes
+int32_t ipm_accept_ex(int64_t batch, const IpmAcceptArgs& a, void* stream);
+
+// ---- cpl_kernels.hip ----
+
+// the backtracking line search, one wave per instance (inst: the solve's instance data in the rows'
+// current order, or null — then the template's search)
+int32_t ls_backtrack(const cpl_problem_desc* d, const LsBacktrackArgs& a, hipStream_t stream,
+                     const cpl_instance_data* inst = nullptr);
+// the fused search kernel takes the post-step prologue (LsBacktrackArgs::with_post) at this batch size
+bool ls_post_prologue(int64_t batch);
+// the instance overlay — g[0:6], f, grad of every row from its instance data
+int32_t eval_overlay(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
+                     const cpl_instance_data* inst, double* d_g, double* d_f, double* d_grad, void* stream,
+                     const uint8_t* gate);
+// the NLP-scaled evaluation (pipelined kernel; CPL_ERR_UNSUPPORTED: not that path)
+int32_t eval_batch_scaled(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
+                          const uint8_t* d_env_tag, double* d_g, double* d_jac, double* d_f, double* d_grad,
+                          int32_t flags, const double* df, const double* dc, const int32_t* row, void* stream,
+                          const uint8_t* gate = nullptr);
+// cpl_eval_batch_ex whose pipelined-kernel launch is a no-op while *gate == 0
+int32_t eval_batch_gated(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
+                         const uint8_t* d_env_tag, double* d_g, double* d_jac, double* d_f, double* d_grad,
+                         int32_t flags, void* stream, const uint8_t* gate);
+
+// ---- cpl_kkt.hip ----
+
+// the system size runs the one-wave kernel (whose factors the fused line-search kernel re-solves with)
+bool kkt_wave_size(int nw, int m);
+// IPOPT's Jacobian regularisation: its workspace doubles per system, or -1 (system too large)
+int64_t kkt_aug_workspace_doubles(int nw, int m);
+// the marked (delta_c != 0) systems of the cpl_kkt_solve call just issued with the same arguments
+int32_t kkt_aug_solve(int mode, int64_t batch, int nw, int m, const double* d_M, const double* d_A, const double* d_r1,
+                      const double* d_r2, const double* d_mu, const double* d_dwl, const uint8_t* d_active, double* d_dw,
+                      double* d_dy, double* d_delta_w, double* d_delta_c, int32_t* d_info, double* d_wsa,
+                      hipStream_t st);
+
+}  // namespace cpl

@@ -15,6 +15,7 @@
 
 #include "cpl_status.hpp"
 #include "cpl_accept.hpp"
+#include "cpl_engine.hpp"
 #include "cpl_wave.hpp"
 
 namespace cpl {
@@ -48,52 +49,44 @@ __global__ __launch_bounds__(256) void cpl_ipm_trial_point_kernel(
 //   ok = finite & theta <= theta_max & filter-acceptable & (f-type ? Armijo : sufficient decrease)
 // for instances with searching & (extra_mask or 1); accepted ones copy (f, g, w_t, alpha, aug) into
 // the line-search state and stop searching.  th_out / ok_out: theta and ok of every instance.
-__global__ __launch_bounds__(256) void cpl_ipm_judge_take_kernel(
-    int64_t batch, int nw, int m, int nf, int nfilt, const int32_t* __restrict__ row_slack,
-    const double* __restrict__ gl, const uint8_t* __restrict__ hasL, const uint8_t* __restrict__ hasU,
-    const double* __restrict__ wl0, const double* __restrict__ wu0, const double* __restrict__ wt,
-    const double* __restrict__ f_t, const double* __restrict__ g_t, const double* __restrict__ alpha,
-    const double* __restrict__ mu, const double* __restrict__ theta_k, const double* __restrict__ phi_k,
-    const double* __restrict__ gd, const uint8_t* __restrict__ switch_ok, const double* __restrict__ theta_max,
-    const double* __restrict__ filt_t, const double* __restrict__ filt_p, const uint8_t* __restrict__ extra_mask,
-    uint8_t* __restrict__ searching, double* __restrict__ st_f, double* __restrict__ st_g, double* __restrict__ st_w,
-    double* __restrict__ st_alpha, uint8_t* __restrict__ st_aug, double* __restrict__ th_out,
-    uint8_t* __restrict__ ok_out, int mode) {
+__global__ __launch_bounds__(256) void cpl_ipm_judge_take_kernel(const JudgeTakeArgs a) {
   const int64_t b = (int64_t)blockIdx.x * IPM_WAVES + (threadIdx.x >> 6);
-  if (b >= batch) return;
+  if (b >= a.batch) return;
   const int lane = threadIdx.x & 63;
-  const double* wb = wt + b * nw;
-  const double* gb = g_t + b * m;
+  const int nw = a.nw, m = a.m, nf = a.nf, nfilt = a.nfilt;
+  const double* wb = a.wt + b * nw;
+  const double* gb = a.g_t + b * m;
   double th = 0.0;
   for (int r = lane; r < m; r += 64) {
-    const int s = row_slack[r];
-    th += fabs(s < 0 ? gb[r] - gl[r] : gb[r] - wb[nf + s]);
+    const int s = a.row_slack[r];
+    th += fabs(s < 0 ? gb[r] - a.gl[r] : gb[r] - wb[nf + s]);
   }
   double lg = 0.0;
   for (int k = lane; k < nw; k += 64) {
-    if (hasL[k]) lg += log(wb[k] - wl0[k]);
-    if (hasU[k]) lg += log(wu0[k] - wb[k]);
+    if (a.hasL[k]) lg += log(wb[k] - a.wl0[k]);
+    if (a.hasU[k]) lg += log(a.wu0[k] - wb[k]);
   }
   th = ipm_wave_sum(th);
   lg = ipm_wave_sum(lg);
-  const double ph = f_t[b] - mu[b] * lg;
-  const double al = alpha[b];
+  const double ft = a.f_t[b];
+  const double ph = ft - a.mu[b] * lg;
+  const double al = a.alpha[b];
   bool aug = false;
-  const bool ok = ls_acceptable_wave(th, ph, theta_k[b], phi_k[b], gd[b], al, switch_ok[b], theta_max[b],
-                                     filt_t + b * nfilt, filt_p + b * nfilt, nfilt, &aug);
-  const bool take = ok && searching[b] && (extra_mask == nullptr || extra_mask[b]);
+  const bool ok = ls_acceptable_wave(th, ph, a.theta_k[b], a.phi_k[b], a.gd[b], al, a.switch_ok[b], a.theta_max[b],
+                                     a.filt_t + b * nfilt, a.filt_p + b * nfilt, nfilt, &aug);
+  const bool take = ok && a.searching[b] && (a.extra_mask == nullptr || a.extra_mask[b]);
   if (take) {
-    for (int r = lane; r < m; r += 64) st_g[b * m + r] = gb[r];
-    for (int k = lane; k < nw; k += 64) st_w[b * nw + k] = wb[k];
+    for (int r = lane; r < m; r += 64) a.st_g[b * m + r] = gb[r];
+    for (int k = lane; k < nw; k += 64) a.st_w[b * nw + k] = wb[k];
   }
   if (lane == 0) {
-    th_out[b] = th;
-    ok_out[b] = ok ? 1 : 0;
+    a.th_out[b] = th;
+    a.ok_out[b] = ok ? 1 : 0;
     if (take) {
-      st_f[b] = f_t[b];
-      st_alpha[b] = al;
-      st_aug[b] = aug ? 1 : 0;
-      searching[b] = 0;
+      a.st_f[b] = ft;
+      a.st_alpha[b] = al;
+      a.st_aug[b] = aug ? 1 : 0;
+      a.searching[b] = 0;
     }
   }
 }
@@ -126,21 +119,13 @@ struct IpmTerm {
 struct IpmNoTerm {};
 
 template <bool TERM, typename TermT>
-__device__ __forceinline__ void ipm_optimality_body(
-    int64_t batch, int nw, int m, int nfilt, int nbounds, double tol, double acc_tol, int acc_iter,
-    const double* __restrict__ A, const double* __restrict__ gw, const double* __restrict__ c,
-    const double* __restrict__ w, const double* __restrict__ y, const double* __restrict__ zL,
-    const double* __restrict__ zU, const uint8_t* __restrict__ hasL, const uint8_t* __restrict__ hasU,
-    const double* __restrict__ wl0, const double* __restrict__ wu0, const double* __restrict__ mu_in,
-    const double* __restrict__ filt_t, const double* __restrict__ filt_p, const int64_t* __restrict__ fcount,
-    uint8_t* __restrict__ active, int64_t* __restrict__ status, int64_t* __restrict__ acc,
-    double* __restrict__ d_inf_out, double* __restrict__ err0_out, double* __restrict__ base_out,
-    double* __restrict__ mu_out, double* __restrict__ filt_t_out, double* __restrict__ filt_p_out,
-    int64_t* __restrict__ fcount_out, int mu_rounds, double mu_min, const uint8_t* __restrict__ tiny_flag,
-    const uint8_t* __restrict__ skip, const IpmUnpack& up, const TermT& T) {
+__device__ __forceinline__ void ipm_optimality_body(const IpmOptArgs& a, const IpmUnpack& up, const TermT& T) {
   const int64_t b = (int64_t)blockIdx.x * IPM_WAVES + (threadIdx.x >> 6);
-  if (b >= batch) return;
+  if (b >= a.batch) return;
   const int lane = threadIdx.x & 63;
+  const int nw = a.nw, m = a.m, nfilt = a.nfilt;
+  const double *w = a.w, *zL = a.zL, *zU = a.zU, *filt_t = a.filt_t, *filt_p = a.filt_p;
+  const uint8_t *hasL = a.hasL, *hasU = a.hasU;
   // (the fused line search's flags cleared here, one launch before the search sets them)
   if (b == 0 && lane == 0 && up.any_reset) up.any_reset[0] = up.any_reset[1] = 0;
   // the solve loop's unpack (IpmUnpack) at the iteration's barrier parameter and active flag
@@ -155,20 +140,20 @@ __device__ __forceinline__ void ipm_optimality_body(
       up.act[b] = act_v && !up.in_resto[b];
     }
   };
-  if (skip && skip[b]) {  // (an instance in the restoration phase: its own test and barrier update)
+  if (a.skip && a.skip[b]) {  // (an instance in the restoration phase: its own test and barrier update)
     for (int k = lane; k < nfilt; k += 64) {
-      filt_t_out[b * nfilt + k] = filt_t[b * nfilt + k];
-      filt_p_out[b * nfilt + k] = filt_p[b * nfilt + k];
+      a.filt_t_out[b * nfilt + k] = filt_t[b * nfilt + k];
+      a.filt_p_out[b * nfilt + k] = filt_p[b * nfilt + k];
     }
     if (lane == 0) {
-      mu_out[b] = mu_in[b];
-      fcount_out[b] = fcount[b];
+      a.mu_out[b] = a.mu_in[b];
+      a.fcount_out[b] = a.fcount[b];
     }
-    unpack(mu_in[b], active[b] != 0);
+    unpack(a.mu_in[b], a.active[b] != 0);
     return;
   }
-  const double* Ab = A + b * (int64_t)m * nw;
-  const double* yb = y + b * m;
+  const double* Ab = a.A + b * (int64_t)m * nw;
+  const double* yb = a.y + b * m;
   // lanes own w entries k = lane, lane + 64 (nw <= 128)
   double cl[2] = {0.0, 0.0}, cu[2] = {0.0, 0.0};
   double dmax = 0.0, zs = 0.0, clmax = 0.0, cumax = 0.0;
@@ -178,20 +163,20 @@ __device__ __forceinline__ void ipm_optimality_body(
   for (int h = 0; h < 2; ++h) {
     const int k = lane + 64 * h;
     if (k < nw) {
-      double dual = gw[b * nw + k];
+      double dual = a.gw[b * nw + k];
       dual = seq_dot_acc(dual, Ab + k, nw, yb, m);
       const double zl = zL[b * nw + k], zu = zU[b * nw + k], wk = w[b * nw + k];
       dual = dual - zl + zu;
       dmax = fmax(dmax, fabs(dual));
       if constexpr (TERM) {  // x part: / df; the slack of row r: dc_r / df
-        double a = fabs(dual);
-        if (k >= T.nf) a = a * (T.dc ? T.dc[b * m + T.slack_row[k - T.nf]] : 1.0);
+        double ad = fabs(dual);
+        if (k >= T.nf) ad = ad * (T.dc ? T.dc[b * m + T.slack_row[k - T.nf]] : 1.0);
         else xmax = fmax(xmax, fabs(wk));
-        du = fmax(du, a / dfv);
+        du = fmax(du, ad / dfv);
       }
       zs += fabs(zl) + fabs(zu);
-      cl[h] = hasL[k] ? (wk - wl0[k]) * zl : 0.0;
-      cu[h] = hasU[k] ? (wu0[k] - wk) * zu : 0.0;
+      cl[h] = hasL[k] ? (wk - a.wl0[k]) * zl : 0.0;
+      cu[h] = hasU[k] ? (a.wu0[k] - wk) * zu : 0.0;
       clmax = fmax(clmax, cl[h]);
       cumax = fmax(cumax, cu[h]);
     }
@@ -199,7 +184,7 @@ __device__ __forceinline__ void ipm_optimality_body(
   double ys = 0.0, cmax = 0.0;
   for (int r = lane; r < m; r += 64) {
     ys += fabs(yb[r]);
-    cmax = fmax(cmax, fabs(c[b * m + r]));
+    cmax = fmax(cmax, fabs(a.c[b * m + r]));
   }
   if constexpr (TERM) {  // the violation of d(x) = g / dc against the original bounds (a NaN row: +inf)
     for (int r = lane; r < m; r += 64) {
@@ -219,14 +204,14 @@ __device__ __forceinline__ void ipm_optimality_body(
   zs = ipm_wave_sum(zs);
   ys = ipm_wave_sum(ys);
   const double s_max = 100.0;
-  const double sd = fmax((ys + zs) / (double)max(m + nbounds, 1), s_max) / s_max;
-  const double sc = fmax(zs / (double)max(nbounds, 1), s_max) / s_max;
+  const double sd = fmax((ys + zs) / (double)max(m + a.nbounds, 1), s_max) / s_max;
+  const double sc = fmax(zs / (double)max(a.nbounds, 1), s_max) / s_max;
   const double base = fmax(dmax / sd, cmax);
   const double err0 = fmax(base, fmax(clmax, cumax) / sc);
   // convergence test
-  bool act = active[b] != 0;
+  bool act = a.active[b] != 0;
   const bool act_in = act;
-  bool opt_lvl = err0 <= tol, acc_lvl = err0 <= acc_tol;  // (CurrentIsAcceptable: acc_lvl)
+  bool opt_lvl = err0 <= a.tol, acc_lvl = err0 <= a.acc_tol;  // (CurrentIsAcceptable: acc_lvl)
   double cp = 0.0, fv = 0.0;
   if constexpr (TERM) {
     cp = fmax(clmax, cumax) / dfv;
@@ -237,8 +222,8 @@ __device__ __forceinline__ void ipm_optimality_body(
               oc <= T.acc_obj_change_tol;
   }
   const bool done_now = act && opt_lvl;
-  const int64_t acc_new = (act && acc_lvl) ? acc[b] + 1 : 0;
-  const bool acc_now = act && !done_now && acc_new >= acc_iter;
+  const int64_t acc_new = (act && acc_lvl) ? a.acc[b] + 1 : 0;
+  const bool acc_now = act && !done_now && acc_new >= a.acc_iter;
   act = act && !done_now && !acc_now;
   bool div_now = false;
   if constexpr (TERM) {
@@ -256,10 +241,10 @@ __device__ __forceinline__ void ipm_optimality_body(
   }
   // barrier update (IPOPT MonotoneMuUpdate, mu_allow_fast_monotone_decrease): while the barrier
   // problem is solved to kappa_eps mu (or once after two tiny steps), at most mu_rounds times
-  double mu = mu_in[b];
+  double mu = a.mu_in[b];
   bool reset = false;
-  const bool force = tiny_flag && tiny_flag[b];
-  for (int round = 0; round < mu_rounds; ++round) {
+  const bool force = a.tiny_flag && a.tiny_flag[b];
+  for (int round = 0; round < a.mu_rounds; ++round) {
     double em = 0.0;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -271,21 +256,21 @@ __device__ __forceinline__ void ipm_optimality_body(
     }
     em = wave_max(em);
     const double err_mu = fmax(base, em / sc);
-    if (act && (err_mu <= 10.0 * mu || (force && round == 0)) && mu > mu_min) {
-      mu = fmax(fmin(0.2 * mu, pow(mu, 1.5)), mu_min);
+    if (act && (err_mu <= 10.0 * mu || (force && round == 0)) && mu > a.mu_min) {
+      mu = fmax(fmin(0.2 * mu, pow(mu, 1.5)), a.mu_min);
       reset = true;
     }
   }
   for (int k = lane; k < nfilt; k += 64) {
-    filt_t_out[b * nfilt + k] = reset ? INFINITY : filt_t[b * nfilt + k];
-    filt_p_out[b * nfilt + k] = reset ? INFINITY : filt_p[b * nfilt + k];
+    a.filt_t_out[b * nfilt + k] = reset ? INFINITY : filt_t[b * nfilt + k];
+    a.filt_p_out[b * nfilt + k] = reset ? INFINITY : filt_p[b * nfilt + k];
   }
   if (lane == 0) {
-    acc[b] = acc_new;
-    if (done_now) status[b] = 0;
-    else if (acc_now) status[b] = 1;
+    a.acc[b] = acc_new;
+    if (done_now) a.status[b] = 0;
+    else if (acc_now) a.status[b] = 1;
     if constexpr (TERM) {
-      if (div_now) status[b] = CPL_SOLVE_DIVERGING;
+      if (div_now) a.status[b] = CPL_SOLVE_DIVERGING;
       T.acceptable[b] = acc_lvl ? 1 : 0;
       if (act_in) {
         T.f_prev[b] = fv;
@@ -294,39 +279,23 @@ __device__ __forceinline__ void ipm_optimality_body(
         T.compl_inf[b] = cp;
       }
     }
-    active[b] = act ? 1 : 0;
-    d_inf_out[b] = dmax;
-    err0_out[b] = err0;
-    base_out[b] = base;
-    mu_out[b] = mu;
-    fcount_out[b] = reset ? 0 : fcount[b];
+    a.active[b] = act ? 1 : 0;
+    a.d_inf_out[b] = dmax;
+    a.err0_out[b] = err0;
+    a.base_out[b] = base;
+    a.mu_out[b] = mu;
+    a.fcount_out[b] = reset ? 0 : a.fcount[b];
     if (reset && up.in_soft) up.in_soft[b] = 0;  // (the line search's Reset: the soft restoration phase ends)
   }
   unpack(mu, act);
 }
 
-#define IPM_OPT_PARAMS                                                                                          \
-  int64_t batch, int nw, int m, int nfilt, int nbounds, double tol, double acc_tol, int acc_iter,               \
-      const double *__restrict__ A, const double *__restrict__ gw, const double *__restrict__ c,                \
-      const double *__restrict__ w, const double *__restrict__ y, const double *__restrict__ zL,                \
-      const double *__restrict__ zU, const uint8_t *__restrict__ hasL, const uint8_t *__restrict__ hasU,        \
-      const double *__restrict__ wl0, const double *__restrict__ wu0, const double *__restrict__ mu_in,         \
-      const double *__restrict__ filt_t, const double *__restrict__ filt_p, const int64_t *__restrict__ fcount, \
-      uint8_t *__restrict__ active, int64_t *__restrict__ status, int64_t *__restrict__ acc,                    \
-      double *__restrict__ d_inf_out, double *__restrict__ err0_out, double *__restrict__ base_out,             \
-      double *__restrict__ mu_out, double *__restrict__ filt_t_out, double *__restrict__ filt_p_out,            \
-      int64_t *__restrict__ fcount_out, int mu_rounds, double mu_min, const uint8_t *__restrict__ tiny_flag,    \
-      const uint8_t *__restrict__ skip, const IpmUnpack up
-#define IPM_OPT_ARGS                                                                                             \
-  batch, nw, m, nfilt, nbounds, tol, acc_tol, acc_iter, A, gw, c, w, y, zL, zU, hasL, hasU, wl0, wu0, mu_in,     \
-      filt_t, filt_p, fcount, active, status, acc, d_inf_out, err0_out, base_out, mu_out, filt_t_out, filt_p_out, \
-      fcount_out, mu_rounds, mu_min, tiny_flag, skip, up
-
-__global__ __launch_bounds__(256) void cpl_ipm_optimality_kernel(IPM_OPT_PARAMS) {
-  ipm_optimality_body<false>(IPM_OPT_ARGS, IpmNoTerm{});
+__global__ __launch_bounds__(256) void cpl_ipm_optimality_kernel(const IpmOptArgs a, const IpmUnpack up) {
+  ipm_optimality_body<false>(a, up, IpmNoTerm{});
 }
-__global__ __launch_bounds__(256) void cpl_ipm_optimality_term_kernel(IPM_OPT_PARAMS, const IpmTerm T) {
-  ipm_optimality_body<true>(IPM_OPT_ARGS, T);
+__global__ __launch_bounds__(256) void cpl_ipm_optimality_term_kernel(const IpmOptArgs a, const IpmUnpack up,
+                                                                      const IpmTerm T) {
+  ipm_optimality_body<true>(a, up, T);
 }
 
 // Fraction-to-the-boundary step (batch_ipm.py max_step, both sides): the largest alpha <= 1 with
@@ -646,68 +615,93 @@ __global__ __launch_bounds__(256) void cpl_ipm_fd_hessian_raw_kernel(int64_t tot
 // (barrier_tol_factor + 1)
 double ipm_mu_min(double tol) { return fmin(tol, 1e-4) / 11.0; }
 
-#define IPM_LAUNCH(kernel, name, ...)                                                                   \
-  do {                                                                                                 \
-    const int64_t blocks_ = (batch + IPM_WAVES - 1) / IPM_WAVES;                                       \
-    if (blocks_ > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, name ": batch too large");       \
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks_), dim3(64 * IPM_WAVES), 0, (hipStream_t)stream,   \
-                       __VA_ARGS__);                                                                   \
-    hipError_t e_ = hipGetLastError();                                                                 \
-    if (e_ != hipSuccess) return fail(CPL_ERR_HIP, std::string(name " launch: ") + hipGetErrorString(e_)); \
-    return CPL_OK;                                                                                     \
-  } while (0)
-
+// ---- the file's launches: `blocks` workgroups of 256 threads under the C entry point's name — the grid
+// limit, the launch and its error.  launch_waves: one wave per instance (IPM_WAVES to a workgroup);
+// launch_elems: one thread per element.
+template <typename... P, typename... A>
+int32_t ipm_launch(const char* name, void (*kernel)(P...), int64_t blocks, size_t lds, void* stream, const A&... args) {
+  if (blocks <= 0) return CPL_OK;
+  if (blocks > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, std::string(name) + ": batch too large");
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * IPM_WAVES), lds, (hipStream_t)stream, (P)args...);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(CPL_ERR_HIP, std::string(name) + " launch: " + hipGetErrorString(e));
+  return CPL_OK;
+}
+template <typename... P, typename... A>
+int32_t launch_waves(const char* name, void (*kernel)(P...), int64_t batch, void* stream, const A&... args) {
+  return ipm_launch(name, kernel, (batch + IPM_WAVES - 1) / IPM_WAVES, 0, stream, args...);
+}
+template <typename... P, typename... A>
+int32_t launch_elems(const char* name, void (*kernel)(P...), int64_t total, void* stream, const A&... args) {
+  return ipm_launch(name, kernel, (total + 255) / 256, 0, stream, args...);
+}
 
 // cpl_ipm_post_step with the solve loop's line-search setup fused in (ls != NULL: LsSetupArgs)
 int32_t ipm_post_step_ex(int64_t batch, const PostStepArgs& P, const LsSetupArgs* ls, void* stream) {
-  const LsSetupArgs L = ls ? *ls : LsSetupArgs{};
-  IPM_LAUNCH(cpl_ipm_post_step_kernel, "cpl_ipm_post_step", batch, P, L);
+  return launch_waves("cpl_ipm_post_step", cpl_ipm_post_step_kernel, batch, stream, batch, P,
+                      ls ? *ls : LsSetupArgs{});
 }
 
 // cpl_ipm_accept on the engine's argument block
 int32_t ipm_accept_ex(int64_t batch, const IpmAcceptArgs& a, void* stream) {
-  IPM_LAUNCH(cpl_ipm_accept_kernel, "cpl_ipm_accept", a, batch);
+  return launch_waves("cpl_ipm_accept", cpl_ipm_accept_kernel, batch, stream, a, batch);
 }
 
-// cpl_ipm_optimality with the engine's extras: mu_rounds barrier decreases at most, the floor
-// mu_min, tiny_flag (a forced first decrease after two tiny steps) and skip (instances in the
-// restoration phase, left untouched: their own test and barrier update run in its kernels)
-int32_t ipm_optimality_ex(int64_t batch, int32_t nw, int32_t m, int32_t nfilt, int32_t nbounds, double tol,
-                          double acc_tol, int32_t acc_iter, const double* d_A, const double* d_gw, const double* d_c,
-                          const double* d_w, const double* d_y, const double* d_zL, const double* d_zU,
-                          const uint8_t* d_hasL, const uint8_t* d_hasU, const double* d_wl0, const double* d_wu0,
-                          const double* d_mu, const double* d_filt_t, const double* d_filt_p, const int64_t* d_fcount,
-                          uint8_t* d_active, int64_t* d_status, int64_t* d_acc, double* d_d_inf, double* d_err0,
-                          double* d_base, double* d_mu_out, double* d_filt_t_out, double* d_filt_p_out,
-                          int64_t* d_fcount_out, int32_t mu_rounds, double mu_min, const uint8_t* d_tiny_flag,
-                          const uint8_t* d_skip, const IpmUnpack* unpack, void* stream, const cpl_term_args* term) {
-  const int64_t blocks = (batch + IPM_WAVES - 1) / IPM_WAVES;
-  IpmUnpack up{};
-  if (unpack) up = *unpack;
-  if (batch == 0) return CPL_OK;
+int32_t ipm_judge_take(const JudgeTakeArgs& a, void* stream) {
+  return launch_waves("cpl_ipm_judge_take", cpl_ipm_judge_take_kernel, a.batch, stream, a);
+}
+
+// batches up to NEWTON_WIDE_MAX run one instance per workgroup (WIDE); the limited-memory model (Hc)
+// takes the LM instances, whose U | W staging is the launch's dynamic LDS
+int32_t ipm_newton_setup(const NewtonSetupArgs& a, void* stream) {
+  const bool lm = a.Hc != nullptr;
+  // (Sigma is staged per wave in sig_s[IPM_WAVES][128]: nw <= 128)
+  if (a.batch < 0 || a.nw <= 0 || a.nw > 128 || a.m < 0 || a.nf < 0 || a.nf > a.nw || (lm && a.lm_pairs <= 0))
+    return fail(CPL_ERR_INVALID_ARGUMENT, "ipm_newton_setup: bad arguments");
+  const bool wide = a.batch <= NEWTON_WIDE_MAX;
+  const int64_t blocks = wide ? a.batch : (a.batch + IPM_WAVES - 1) / IPM_WAVES;
+  const size_t lds = lm ? sizeof(double) * (wide ? 1 : IPM_WAVES) * 2 * (size_t)a.lm_pairs * a.nf : 0;
+  const auto kernel =
+      lm ? (wide ? cpl_ipm_newton_setup_kernel<true, true> : cpl_ipm_newton_setup_kernel<true, false>)
+         : (wide ? cpl_ipm_newton_setup_kernel<false, true> : cpl_ipm_newton_setup_kernel<false, false>);
+  // (the kernel keeps its positional __restrict__ list: as a block its one-workgroup LM form lost a wave per SIMD)
+  return ipm_launch("cpl_ipm_newton_setup", kernel, blocks, lds, stream, a.batch, a.nw, a.m, a.nf, a.w, a.zL, a.zU,
+                    a.gw, a.A, a.y, a.c, a.f, a.mu, a.hasL, a.hasU, a.wl0, a.wu0, a.H, a.h_sym, a.M, a.r1, a.r2, a.gphi,
+                    a.mr_diag, a.theta, a.phi, a.active, a.Hc, a.lm_pairs);
+}
+
+// the optimality test and barrier update on its argument block (IpmOptArgs, cpl_engine.hpp)
+int32_t ipm_optimality(const IpmOptArgs& a, const IpmUnpack* unpack, const cpl_term_args* term, void* stream) {
+  const IpmUnpack up = unpack ? *unpack : IpmUnpack{};
   if (term && term->termination == CPL_TERM_IPOPT) {  // the compile-time variant with IPOPT's full tests
     const IpmTerm T{(int)term->nf, term->dual_inf_tol, term->constr_viol_tol, term->compl_inf_tol,
                     term->acceptable_dual_inf_tol, term->acceptable_constr_viol_tol, term->acceptable_compl_inf_tol,
                     term->acceptable_obj_change_tol, term->diverging_iterates_tol, term->d_g, term->d_dc, term->d_df,
                     term->d_gl, term->d_gu, term->d_slack_row, term->d_f, term->d_f_prev, term->d_acceptable,
                     term->d_dual_inf, term->d_constr_viol, term->d_compl_inf};
-    hipLaunchKernelGGL(cpl_ipm_optimality_term_kernel, dim3((unsigned)blocks), dim3(64 * IPM_WAVES), 0,
-                       (hipStream_t)stream, batch, (int)nw, (int)m, (int)nfilt, (int)nbounds, tol, acc_tol,
-                       (int)acc_iter, d_A, d_gw, d_c, d_w, d_y, d_zL, d_zU, d_hasL, d_hasU, d_wl0, d_wu0, d_mu, d_filt_t,
-                       d_filt_p, d_fcount, d_active, d_status, d_acc, d_d_inf, d_err0, d_base, d_mu_out, d_filt_t_out,
-                       d_filt_p_out, d_fcount_out, (int)mu_rounds, mu_min, d_tiny_flag, d_skip, up, T);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(CPL_ERR_HIP, std::string("cpl_ipm_optimality_ex launch: ") + hipGetErrorString(e));
-    return CPL_OK;
+    return launch_waves("cpl_ipm_optimality_ex", cpl_ipm_optimality_term_kernel, a.batch, stream, a, up, T);
   }
-  hipLaunchKernelGGL(cpl_ipm_optimality_kernel, dim3((unsigned)blocks), dim3(64 * IPM_WAVES), 0, (hipStream_t)stream,
-                     batch, (int)nw, (int)m, (int)nfilt, (int)nbounds, tol, acc_tol, (int)acc_iter, d_A, d_gw, d_c, d_w,
-                     d_y, d_zL, d_zU, d_hasL, d_hasU, d_wl0, d_wu0, d_mu, d_filt_t, d_filt_p, d_fcount, d_active,
-                     d_status, d_acc, d_d_inf, d_err0, d_base, d_mu_out, d_filt_t_out, d_filt_p_out, d_fcount_out,
-                     (int)mu_rounds, mu_min, d_tiny_flag, d_skip, up);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CPL_ERR_HIP, std::string("cpl_ipm_optimality launch: ") + hipGetErrorString(e));
-  return CPL_OK;
+  return launch_waves("cpl_ipm_optimality", cpl_ipm_optimality_kernel, a.batch, stream, a, up);
+}
+
+// the block from the argument list the two C entry points share (mu_rounds and the floor: IPOPT's)
+static IpmOptArgs opt_args_abi(int64_t batch, int32_t nw, int32_t m, int32_t nfilt, int32_t nbounds, double tol,
+                               double acc_tol, int32_t acc_iter, const double* d_A, const double* d_gw,
+                               const double* d_c, const double* d_w, const double* d_y, const double* d_zL,
+                               const double* d_zU, const uint8_t* d_hasL, const uint8_t* d_hasU, const double* d_wl0,
+                               const double* d_wu0, const double* d_mu, const double* d_filt_t, const double* d_filt_p,
+                               const int64_t* d_fcount, uint8_t* d_active, int64_t* d_status, int64_t* d_acc,
+                               double* d_d_inf, double* d_err0, double* d_base, double* d_mu_out, double* d_filt_t_out,
+                               double* d_filt_p_out, int64_t* d_fcount_out) {
+  IpmOptArgs a;
+  a.batch = batch; a.nw = nw; a.m = m; a.nfilt = nfilt; a.nbounds = nbounds; a.tol = tol; a.acc_tol = acc_tol;
+  a.acc_iter = acc_iter; a.mu_rounds = IPM_MU_ROUNDS; a.mu_min = ipm_mu_min(tol);
+  a.A = d_A; a.gw = d_gw; a.c = d_c; a.w = d_w; a.y = d_y; a.zL = d_zL; a.zU = d_zU; a.hasL = d_hasL; a.hasU = d_hasU;
+  a.wl0 = d_wl0; a.wu0 = d_wu0; a.mu_in = d_mu; a.filt_t = d_filt_t; a.filt_p = d_filt_p; a.fcount = d_fcount;
+  a.active = d_active; a.status = d_status; a.acc = d_acc; a.d_inf_out = d_d_inf; a.err0_out = d_err0;
+  a.base_out = d_base; a.mu_out = d_mu_out; a.filt_t_out = d_filt_t_out; a.filt_p_out = d_filt_p_out;
+  a.fcount_out = d_fcount_out;
+  return a;
 }
 
 }  // namespace cpl
@@ -726,14 +720,8 @@ int32_t cpl_ipm_trial_point(int64_t batch, int32_t n, int32_t nf, int32_t nw, co
   if (!d_free_idx || (n > nf && !d_fixed_idx) || !d_Xbase || !d_w || !d_dir || !d_alpha || !d_mask || !d_w_keep ||
       !d_wt || !d_X)
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_trial_point: missing buffer");
-  const int64_t blocks = (batch + IPM_WAVES - 1) / IPM_WAVES;
-  if (blocks > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_trial_point: batch too large");
-  hipLaunchKernelGGL(cpl_ipm_trial_point_kernel, dim3((unsigned)blocks), dim3(64 * IPM_WAVES), 0, (hipStream_t)stream,
-                     batch, (int)n, (int)nf, (int)nw, d_free_idx, d_fixed_idx, d_Xbase, d_w, d_dir, d_alpha, d_mask,
-                     d_w_keep, d_wt, d_X);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CPL_ERR_HIP, std::string("cpl_ipm_trial_point launch: ") + hipGetErrorString(e));
-  return CPL_OK;
+  return launch_waves("cpl_ipm_trial_point", cpl_ipm_trial_point_kernel, batch, stream, batch, n, nf, nw, d_free_idx,
+                      d_fixed_idx, d_Xbase, d_w, d_dir, d_alpha, d_mask, d_w_keep, d_wt, d_X);
 }
 
 int32_t cpl_ipm_judge_take(int64_t batch, int32_t nw, int32_t m, int32_t nf, int32_t nfilt, const int32_t* d_row_slack,
@@ -752,16 +740,14 @@ int32_t cpl_ipm_judge_take(int64_t batch, int32_t nw, int32_t m, int32_t nf, int
       (nfilt > 0 && (!d_filt_t || !d_filt_p)) || !d_searching || !d_st_f || !d_st_w || !d_st_alpha || !d_st_aug ||
       !d_th_out || !d_ok_out)
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_judge_take: missing buffer");
-  const int64_t blocks = (batch + IPM_WAVES - 1) / IPM_WAVES;
-  if (blocks > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_judge_take: batch too large");
-  hipLaunchKernelGGL(cpl_ipm_judge_take_kernel, dim3((unsigned)blocks), dim3(64 * IPM_WAVES), 0, (hipStream_t)stream,
-                     batch, (int)nw, (int)m, (int)nf, (int)nfilt, d_row_slack, d_gl, d_hasL, d_hasU, d_wl0, d_wu0, d_wt,
-                     d_f_t, d_g_t, d_alpha, d_mu, d_theta_k, d_phi_k, d_gd, d_switch_ok, d_theta_max, d_filt_t,
-                     d_filt_p, d_extra_mask, d_searching, d_st_f, d_st_g, d_st_w, d_st_alpha, d_st_aug, d_th_out,
-                     d_ok_out, (int)mode);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CPL_ERR_HIP, std::string("cpl_ipm_judge_take launch: ") + hipGetErrorString(e));
-  return CPL_OK;
+  JudgeTakeArgs a;
+  a.batch = batch; a.nw = nw; a.m = m; a.nf = nf; a.nfilt = nfilt; a.row_slack = d_row_slack; a.gl = d_gl;
+  a.hasL = d_hasL; a.hasU = d_hasU; a.wl0 = d_wl0; a.wu0 = d_wu0; a.wt = d_wt; a.f_t = d_f_t; a.g_t = d_g_t;
+  a.alpha = d_alpha; a.mu = d_mu; a.theta_k = d_theta_k; a.phi_k = d_phi_k; a.gd = d_gd; a.switch_ok = d_switch_ok;
+  a.theta_max = d_theta_max; a.filt_t = d_filt_t; a.filt_p = d_filt_p; a.extra_mask = d_extra_mask;
+  a.searching = d_searching; a.st_f = d_st_f; a.st_g = d_st_g; a.st_w = d_st_w; a.st_alpha = d_st_alpha;
+  a.st_aug = d_st_aug; a.th_out = d_th_out; a.ok_out = d_ok_out;
+  return ipm_judge_take(a, stream);
 }
 
 int32_t cpl_ipm_optimality(int64_t batch, int32_t nw, int32_t m, int32_t nfilt, int32_t nbounds, double tol,
@@ -779,12 +765,11 @@ int32_t cpl_ipm_optimality(int64_t batch, int32_t nw, int32_t m, int32_t nfilt, 
       !d_wu0 || !d_mu || (nfilt > 0 && (!d_filt_t || !d_filt_p || !d_filt_t_out || !d_filt_p_out)) || !d_fcount ||
       !d_active || !d_status || !d_acc || !d_d_inf || !d_err0 || !d_base || !d_mu_out || !d_fcount_out)
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_optimality: missing buffer");
-  const int64_t blocks = (batch + IPM_WAVES - 1) / IPM_WAVES;
-  if (blocks > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_optimality: batch too large");
-  return ipm_optimality_ex(batch, nw, m, nfilt, nbounds, tol, acc_tol, acc_iter, d_A, d_gw, d_c, d_w, d_y, d_zL, d_zU,
-                           d_hasL, d_hasU, d_wl0, d_wu0, d_mu, d_filt_t, d_filt_p, d_fcount, d_active, d_status, d_acc,
-                           d_d_inf, d_err0, d_base, d_mu_out, d_filt_t_out, d_filt_p_out, d_fcount_out, IPM_MU_ROUNDS,
-                           ipm_mu_min(tol), nullptr, nullptr, nullptr, stream, nullptr);
+  const IpmOptArgs a = opt_args_abi(batch, nw, m, nfilt, nbounds, tol, acc_tol, acc_iter, d_A, d_gw, d_c, d_w, d_y, d_zL,
+                                    d_zU, d_hasL, d_hasU, d_wl0, d_wu0, d_mu, d_filt_t, d_filt_p, d_fcount, d_active,
+                                    d_status, d_acc, d_d_inf, d_err0, d_base, d_mu_out, d_filt_t_out, d_filt_p_out,
+                                    d_fcount_out);
+  return ipm_optimality(a, nullptr, nullptr, stream);
 }
 
 int32_t cpl_ipm_optimality_ex(int64_t batch, int32_t nw, int32_t m, int32_t nfilt, int32_t nbounds, double tol,
@@ -821,13 +806,12 @@ int32_t cpl_ipm_optimality_ex(int64_t batch, int32_t nw, int32_t m, int32_t nfil
       !d_wu0 || !d_mu || (nfilt > 0 && (!d_filt_t || !d_filt_p || !d_filt_t_out || !d_filt_p_out)) || !d_fcount ||
       !d_active || !d_status || !d_acc || !d_d_inf || !d_err0 || !d_base || !d_mu_out || !d_fcount_out)
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_optimality_ex: missing buffer");
-  const int64_t blocks = (batch + IPM_WAVES - 1) / IPM_WAVES;
-  if (blocks > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_optimality_ex: batch too large");
-  return ipm_optimality_ex(batch, nw, m, nfilt, nbounds, tol, acc_tol, acc_iter, d_A, d_gw, d_c, d_w, d_y, d_zL, d_zU,
-                           d_hasL, d_hasU, d_wl0, d_wu0, d_mu, d_filt_t, d_filt_p, d_fcount, d_active, d_status, d_acc,
-                           d_d_inf, d_err0, d_base, d_mu_out, d_filt_t_out, d_filt_p_out, d_fcount_out, IPM_MU_ROUNDS,
-                           scaled_only ? ipm_mu_min(tol) : fmin(tol, term->compl_inf_tol) / 11.0, nullptr, term->d_skip,
-                           nullptr, stream, term);
+  IpmOptArgs a = opt_args_abi(batch, nw, m, nfilt, nbounds, tol, acc_tol, acc_iter, d_A, d_gw, d_c, d_w, d_y, d_zL, d_zU,
+                              d_hasL, d_hasU, d_wl0, d_wu0, d_mu, d_filt_t, d_filt_p, d_fcount, d_active, d_status,
+                              d_acc, d_d_inf, d_err0, d_base, d_mu_out, d_filt_t_out, d_filt_p_out, d_fcount_out);
+  if (!scaled_only) a.mu_min = fmin(tol, term->compl_inf_tol) / 11.0;
+  a.skip = term->d_skip;
+  return ipm_optimality(a, nullptr, term, stream);
 }
 
 int32_t cpl_ipm_max_step(int64_t batch, int32_t nw, const double* d_v, const double* d_dir, const double* d_v2,
@@ -837,13 +821,8 @@ int32_t cpl_ipm_max_step(int64_t batch, int32_t nw, const double* d_v, const dou
   if (batch == 0) return CPL_OK;
   if (!d_v || !d_dir || !d_hasL || !d_hasU || (d_v2 ? !d_dir2 : (!d_lo || !d_up)) || !d_tau || !d_out)
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_max_step: missing buffer");
-  const int64_t blocks = (batch + IPM_WAVES - 1) / IPM_WAVES;
-  if (blocks > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_max_step: batch too large");
-  hipLaunchKernelGGL(cpl_ipm_max_step_kernel, dim3((unsigned)blocks), dim3(64 * IPM_WAVES), 0, (hipStream_t)stream,
-                     batch, (int)nw, d_v, d_dir, d_v2, d_dir2, d_hasL, d_hasU, d_lo, d_up, d_tau, d_out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CPL_ERR_HIP, std::string("cpl_ipm_max_step launch: ") + hipGetErrorString(e));
-  return CPL_OK;
+  return launch_waves("cpl_ipm_max_step", cpl_ipm_max_step_kernel, batch, stream, batch, nw, d_v, d_dir, d_v2, d_dir2,
+                      d_hasL, d_hasU, d_lo, d_up, d_tau, d_out);
 }
 
 
@@ -860,18 +839,12 @@ int32_t cpl_ipm_newton_setup(int64_t batch, int32_t nw, int32_t m, int32_t nf, c
   if (!d_w || !d_zL || !d_zU || !d_gw || (m > 0 && (!d_A || !d_y || !d_c || !d_r2)) || !d_f || !d_mu || !d_hasL ||
       !d_hasU || !d_wl0 || !d_wu0 || !d_M || !d_r1 || !d_gphi || !d_mr_diag || !d_theta || !d_phi)
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_newton_setup: missing buffer");
-  if (batch <= NEWTON_WIDE_MAX) {  // one instance per workgroup
-    hipLaunchKernelGGL((cpl_ipm_newton_setup_kernel<false, true>), dim3((unsigned)batch), dim3(64 * IPM_WAVES), 0,
-                       (hipStream_t)stream, batch, (int)nw, (int)m, (int)nf, d_w, d_zL,
-             d_zU, d_gw, d_A, d_y, d_c, d_f, d_mu, d_hasL, d_hasU, d_wl0, d_wu0, d_H, (int)h_sym, d_M, d_r1, d_r2,
-             d_gphi, d_mr_diag, d_theta, d_phi, d_active, nullptr, 0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(CPL_ERR_HIP, std::string("cpl_ipm_newton_setup launch: ") + hipGetErrorString(e));
-    return CPL_OK;
-  }
-  IPM_LAUNCH(cpl_ipm_newton_setup_kernel<false>, "cpl_ipm_newton_setup", batch, (int)nw, (int)m, (int)nf, d_w, d_zL,
-             d_zU, d_gw, d_A, d_y, d_c, d_f, d_mu, d_hasL, d_hasU, d_wl0, d_wu0, d_H, (int)h_sym, d_M, d_r1, d_r2,
-             d_gphi, d_mr_diag, d_theta, d_phi, d_active, nullptr, 0);
+  NewtonSetupArgs a;
+  a.batch = batch; a.nw = nw; a.m = m; a.nf = nf; a.w = d_w; a.zL = d_zL; a.zU = d_zU; a.gw = d_gw; a.A = d_A;
+  a.y = d_y; a.c = d_c; a.f = d_f; a.mu = d_mu; a.hasL = d_hasL; a.hasU = d_hasU; a.wl0 = d_wl0; a.wu0 = d_wu0;
+  a.H = d_H; a.h_sym = h_sym; a.M = d_M; a.r1 = d_r1; a.r2 = d_r2; a.gphi = d_gphi; a.mr_diag = d_mr_diag;
+  a.theta = d_theta; a.phi = d_phi; a.active = d_active;
+  return ipm_newton_setup(a, stream);
 }
 
 
@@ -921,13 +894,8 @@ int32_t cpl_ipm_masked_rows(int64_t batch, int64_t row_len, const uint8_t* d_mas
   if (batch == 0 || row_len == 0) return CPL_OK;
   if (!d_mask || !d_src || !d_dst) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_masked_rows: missing buffer");
   const int64_t total = batch * row_len;
-  const int64_t blocks = (total + 255) / 256;
-  if (blocks > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_masked_rows: batch too large");
-  hipLaunchKernelGGL(cpl_ipm_masked_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, total,
-                     row_len, d_mask, d_src, d_dst);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CPL_ERR_HIP, std::string("cpl_ipm_masked_rows launch: ") + hipGetErrorString(e));
-  return CPL_OK;
+  return launch_elems("cpl_ipm_masked_rows", cpl_ipm_masked_rows_kernel, total, stream, total, row_len, d_mask, d_src,
+                      d_dst);
 }
 
 int32_t cpl_ipm_dense_a(int64_t batch, int32_t m, int32_t nw, int32_t nf, int32_t nnz, const int32_t* d_amap,
@@ -939,13 +907,8 @@ int32_t cpl_ipm_dense_a(int64_t batch, int32_t m, int32_t nw, int32_t nf, int32_
   if (!d_amap || !d_row_slack || (nnz > 0 && !d_jac) || !d_A)
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_dense_a: missing buffer");
   const int64_t total = batch * (int64_t)m * nw;
-  const int64_t blocks = (total + 255) / 256;
-  if (blocks > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_dense_a: batch too large");
-  hipLaunchKernelGGL(cpl_ipm_dense_a_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, total, (int)m,
-                     (int)nw, (int)nf, (int)nnz, d_amap, d_row_slack, d_jac, d_A, d_active);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CPL_ERR_HIP, std::string("cpl_ipm_dense_a launch: ") + hipGetErrorString(e));
-  return CPL_OK;
+  return launch_elems("cpl_ipm_dense_a", cpl_ipm_dense_a_kernel, total, stream, total, m, nw, nf, nnz, d_amap,
+                      d_row_slack, d_jac, d_A, d_active);
 }
 
 int32_t cpl_ipm_fd_points(int64_t batch, int32_t n, int32_t nf, double fd_step, const int32_t* d_freepos,
@@ -954,13 +917,8 @@ int32_t cpl_ipm_fd_points(int64_t batch, int32_t n, int32_t nf, double fd_step, 
   if (batch == 0 || nf == 0) return CPL_OK;
   if (!d_freepos || !d_X || !d_Xp || !d_h) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_fd_points: missing buffer");
   const int64_t total = batch * 2 * (int64_t)nf * n;
-  const int64_t blocks = (total + 255) / 256;
-  if (blocks > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_fd_points: batch too large");
-  hipLaunchKernelGGL(cpl_ipm_fd_points_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, total,
-                     (int)n, (int)nf, fd_step, d_freepos, d_X, d_Xp, d_h, d_active);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CPL_ERR_HIP, std::string("cpl_ipm_fd_points launch: ") + hipGetErrorString(e));
-  return CPL_OK;
+  return launch_elems("cpl_ipm_fd_points", cpl_ipm_fd_points_kernel, total, stream, total, n, nf, fd_step, d_freepos,
+                      d_X, d_Xp, d_h, d_active);
 }
 
 int32_t cpl_ipm_fd_hessian_raw(int64_t batch, int32_t n, int32_t nf, const int64_t* d_free_idx, const double* d_gL,
@@ -969,39 +927,8 @@ int32_t cpl_ipm_fd_hessian_raw(int64_t batch, int32_t n, int32_t nf, const int64
   if (batch == 0 || nf == 0) return CPL_OK;
   if (!d_free_idx || !d_gL || !d_h || !d_H) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_fd_hessian_raw: missing buffer");
   const int64_t total = batch * (int64_t)nf * nf;
-  const int64_t blocks = (total + 255) / 256;
-  if (blocks > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_fd_hessian_raw: batch too large");
-  hipLaunchKernelGGL(cpl_ipm_fd_hessian_raw_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, total,
-                     (int)n, (int)nf, d_free_idx, d_gL, d_h, d_H, d_active);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CPL_ERR_HIP, std::string("cpl_ipm_fd_hessian_raw launch: ") + hipGetErrorString(e));
-  return CPL_OK;
+  return launch_elems("cpl_ipm_fd_hessian_raw", cpl_ipm_fd_hessian_raw_kernel, total, stream, total, n, nf, d_free_idx,
+                      d_gL, d_h, d_H, d_active);
 }
 
 }  // extern "C"
-
-namespace cpl {
-// The native engine's Newton setup over its compact limited-memory model (see the LM kernel above);
-// the arguments otherwise as cpl_ipm_newton_setup.
-int32_t ipm_newton_setup_lm(int64_t batch, int32_t nw, int32_t m, int32_t nf, const double* d_w, const double* d_zL,
-                            const double* d_zU, const double* d_gw, const double* d_A, const double* d_y,
-                            const double* d_c, const double* d_f, const double* d_mu, const uint8_t* d_hasL,
-                            const uint8_t* d_hasU, const double* d_wl0, const double* d_wu0, const double* d_Hc,
-                            int32_t lm_pairs, double* d_M, double* d_r1, double* d_r2, double* d_gphi,
-                            double* d_mr_diag, double* d_theta, double* d_phi, const uint8_t* d_active, void* stream) {
-  if (batch < 0 || nw <= 0 || nw > 128 || m < 0 || nf < 0 || nf > nw || lm_pairs <= 0 || !d_Hc)
-    return fail(CPL_ERR_INVALID_ARGUMENT, "ipm_newton_setup_lm: bad arguments");
-  if (batch == 0) return CPL_OK;
-  const int64_t blocks = (batch + IPM_WAVES - 1) / IPM_WAVES;
-  if (blocks > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "ipm_newton_setup_lm: batch too large");
-  const bool wide = batch <= NEWTON_WIDE_MAX;  // one instance per workgroup
-  const size_t lds = sizeof(double) * (wide ? 1 : IPM_WAVES) * 2 * (size_t)lm_pairs * nf;
-  hipLaunchKernelGGL((wide ? cpl_ipm_newton_setup_kernel<true, true> : cpl_ipm_newton_setup_kernel<true, false>),
-                     dim3((unsigned)(wide ? batch : blocks)), dim3(64 * IPM_WAVES), lds, (hipStream_t)stream, batch, (int)nw, (int)m, (int)nf, d_w, d_zL, d_zU, d_gw, d_A, d_y, d_c, d_f,
-                     d_mu, d_hasL, d_hasU, d_wl0, d_wu0, nullptr, 0, d_M, d_r1, d_r2, d_gphi, d_mr_diag, d_theta, d_phi,
-                     d_active, d_Hc, (int)lm_pairs);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(CPL_ERR_HIP, std::string("ipm_newton_setup_lm launch: ") + hipGetErrorString(e));
-  return CPL_OK;
-}
-}  // namespace cpl

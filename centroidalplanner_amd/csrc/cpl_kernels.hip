@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "cpl_accept.hpp"
+#include "cpl_engine.hpp"
 #include "cpl_kkt_block.hpp"
 #include "cpl_kkt_wave.hpp"
 #include "cpl_layout.hpp"

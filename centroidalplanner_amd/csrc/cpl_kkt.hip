@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "cpl_status.hpp"
+#include "cpl_engine.hpp"
 #include "cpl_wave.hpp"
 #include "cpl_kkt_wave.hpp"
 #include "cpl_kkt_qd.hpp"

@@ -28,58 +28,12 @@
 #include <vector>
 
 #include "cpl_accept.hpp"
+#include "cpl_engine.hpp"
 #include "cpl_kkt_qd.hpp"
 #include "cpl_layout.hpp"
 #include "cpl_status.hpp"
 
 namespace cpl {
-// cpl_ipm.hip: cpl_ipm_newton_setup over the engine's compact limited-memory model
-int32_t ipm_newton_setup_lm(int64_t batch, int32_t nw, int32_t m, int32_t nf, const double* d_w, const double* d_zL,
-                            const double* d_zU, const double* d_gw, const double* d_A, const double* d_y,
-                            const double* d_c, const double* d_f, const double* d_mu, const uint8_t* d_hasL,
-                            const uint8_t* d_hasU, const double* d_wl0, const double* d_wu0, const double* d_Hc,
-                            int32_t lm_pairs, double* d_M, double* d_r1, double* d_r2, double* d_gphi,
-                            double* d_mr_diag, double* d_theta, double* d_phi, const uint8_t* d_active, void* stream);
-// cpl_kernels.hip: the backtracking line search after the first trial, one wave per instance
-// (inst: the solve's instance data in the rows' current order, or null — then the template's search)
-int32_t ls_backtrack(const cpl_problem_desc* d, const LsBacktrackArgs& a, hipStream_t stream,
-                     const cpl_instance_data* inst = nullptr);
-// cpl_kernels.hip: the instance overlay — g[0:6], f, grad of every row from its instance data
-int32_t eval_overlay(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
-                     const cpl_instance_data* inst, double* d_g, double* d_f, double* d_grad, void* stream,
-                     const uint8_t* gate);
-// cpl_kernels.hip: the NLP-scaled evaluation (pipelined kernel; CPL_ERR_UNSUPPORTED: not that path)
-int32_t eval_batch_scaled(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
-                          const uint8_t* d_env_tag, double* d_g, double* d_jac, double* d_f, double* d_grad,
-                          int32_t flags, const double* df, const double* dc, const int32_t* row, void* stream,
-                          const uint8_t* gate = nullptr);
-// cpl_kernels.hip: cpl_eval_batch_ex whose pipelined-kernel launch is a no-op while *gate == 0
-int32_t eval_batch_gated(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
-                         const uint8_t* d_env_tag, double* d_g, double* d_jac, double* d_f, double* d_grad,
-                         int32_t flags, void* stream, const uint8_t* gate);
-bool kkt_wave_size(int nw, int m);
-int64_t kkt_aug_workspace_doubles(int nw, int m);
-int32_t kkt_aug_solve(int mode, int64_t batch, int nw, int m, const double* d_M, const double* d_A, const double* d_r1,
-                      const double* d_r2, const double* d_mu, const double* d_dwl, const uint8_t* d_active, double* d_dw,
-                      double* d_dy, double* d_delta_w, double* d_delta_c, int32_t* d_info, double* d_wsa,
-                      hipStream_t st);
-bool ls_post_prologue(int64_t batch);
-// cpl_ipm.hip: the post-step kernel with the line-search setup (LsSetupArgs) as its tail
-int32_t ipm_post_step_ex(int64_t batch, const PostStepArgs& P, const LsSetupArgs* ls, void* stream);
-// cpl_ipm.hip: cpl_ipm_accept on the argument block the restoration entry also takes
-int32_t ipm_accept_ex(int64_t batch, const IpmAcceptArgs& a, void* stream);
-// cpl_ipm.hip: the optimality test + monotone barrier update with IPOPT's per-iteration rounds
-double ipm_mu_min(double tol);
-int32_t ipm_optimality_ex(int64_t batch, int32_t nw, int32_t m, int32_t fmax, int32_t nbounds, double tol,
-                          double acceptable_tol, int32_t acceptable_iter, const double* d_A, const double* d_gw,
-                          const double* d_c, const double* d_w, const double* d_y, const double* d_zL,
-                          const double* d_zU, const uint8_t* d_hasL, const uint8_t* d_hasU, const double* d_wl0,
-                          const double* d_wu0, const double* d_mu, const double* d_filt_t, const double* d_filt_p,
-                          const int64_t* d_fcount,
-                          uint8_t* d_active, int64_t* d_status, int64_t* d_acc, double* d_dinf, double* d_err0,
-                          double* d_base, double* d_mu_o, double* d_ft, double* d_fp, int64_t* d_fc,
-                          int32_t mu_rounds, double mu_min, const uint8_t* d_tiny_flag, const uint8_t* d_skip,
-                          const IpmUnpack* unpack, void* stream, const cpl_term_args* term);
 namespace {
 
 constexpr int FMAX = 64;          // filter entries kept per instance (a ring), as batch_ipm.FMAX
@@ -964,7 +918,7 @@ __global__ __launch_bounds__(256) void k_lbfgs(int64_t B, const LbfgsArgs L) {
   }
   __syncthreads();
   // the taken pairs (s_i'a_i > 0: always, for a positive definite model) in order, as the compact
-  // model the Newton setup expands entry by entry (ipm_newton_setup_lm)
+  // model the Newton setup expands entry by entry (ipm_newton_setup, Hc)
   for (int e = tid; e < nc * nf; e += blockDim.x) {
     const int i = e / nf, k = e - i * nf;
     if (!(s_sa[i] > 0.0)) continue;
@@ -1994,24 +1948,13 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_tail_small(int64_t B, const Re
 }
 // the accepted point's f, grad, g and Jacobian records into the iterate's, active instances only:
 // one launch over the concatenated row [f | grad (n) | g (m) | J (nnz_rec)]
-__global__ __launch_bounds__(256) void k_accept_rows(int64_t B, int n, int m, int nnz, const uint8_t* __restrict__ act,
-                                                     const double* __restrict__ f_n, const double* __restrict__ grad_n,
-                                                     const double* __restrict__ g_n, const double* __restrict__ J_n,
-                                                     double* __restrict__ f, double* __restrict__ grad,
-                                                     double* __restrict__ g, double* __restrict__ J) {
-  const int64_t L = 1 + n + m + nnz;
+__global__ __launch_bounds__(256) void k_accept_rows(int64_t B, const AcceptRows a) {
+  const int64_t L = 1 + a.n + a.m + a.nnz;
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= B * L) return;
   const int64_t b = e / L;
-  if (!act[b]) return;
-  int q = (int)(e - b * L);
-  if (q == 0) { f[b] = f_n[b]; return; }
-  q -= 1;
-  if (q < n) { grad[b * n + q] = grad_n[b * n + q]; return; }
-  q -= n;
-  if (q < m) { g[b * m + q] = g_n[b * m + q]; return; }
-  q -= m;
-  J[b * nnz + q] = J_n[b * nnz + q];
+  if (!a.moved[b]) return;
+  accept_row_entry(a, b, e - b * L);
 }
 __global__ void k_count_zero(int32_t* __restrict__ count) {
   if (threadIdx.x == 0 && blockIdx.x == 0) count[0] = count[1] = 0;
@@ -2359,9 +2302,6 @@ struct cpl_solver {
   double *fin_f, *fin_g;
   // compaction: original instance of each row, compacted masses / tags, full-batch results
   int32_t *orig, *pos, *d_count, *h_count = nullptr;
-  bool tail_fused = false;  // P_FUSED: the soft judge launch also ends the search (k_soft_judge_fail)
-  bool soft_fused = false;  // P_FUSED(_R): the search kernel starts the soft step (no k_soft_begin)
-  bool soft_begun = false;  // ... and the Newton phase's search kernel did (P_SOFT skips k_soft_begin)
   double *mass_c, *fw, *fy, *fX, *fdinf;
   uint8_t* tag_c;
   // this solve's instance data (cpl_solver_solve_inst): the solver's own copies, by batch row (moved by
@@ -2472,6 +2412,11 @@ int32_t eval_full(cpl_solver* S, const double* X, double* fo, double* grado, dou
 // whether or not an instance needs them, and the host reads only the counts.
 constexpr int64_t FUSE_ROWS = 256;  // (see the phase list above)
 enum Phase { P_NEWTON = 1, P_SOFT, P_ACCEPT, P_RNEWTON, P_RACCEPT, P_ACCEPT_NR, P_FUSED, P_FUSED_R };
+// How P_FUSED(_R) runs the phases it is made of (a phase launched on its own: neither)
+struct StepMode {
+  bool soft_fused = false;  // the fused search kernel also starts the soft step (no k_soft_begin in P_SOFT)
+  bool tail_fused = false;  // P_FUSED: the soft judge's launch also ends the search (k_soft_judge_fail)
+};
 
 int32_t hessian_into(cpl_solver* S, const cpl_problem_desc* d, const uint8_t* mask, const double** Hblk, int* h_sym) {
   const int64_t B = S->Bcur;
@@ -2643,6 +2588,58 @@ TrackBest track_best(const cpl_solver* S) {
   return TrackBest{S->nw, S->opt.fallback_viol_tol, S->w, S->f, S->g, S->gl, S->gu, S->best_w, S->best_f,
                    S->scaled ? S->dc : nullptr};
 }
+// cpl_ipm.hip's blocks (cpl_engine.hpp, cpl_accept.hpp).  The optimality test's serves the iteration's
+// test (which adds tiny_flag) and the final one: the barrier update's outputs are mu_o, ft, fp, fc.
+IpmOptArgs opt_args_of(const cpl_solver* S) {
+  const cpl_solve_options& o = S->opt;
+  IpmOptArgs a;
+  a.batch = S->Bcur; a.nw = S->nw; a.m = S->m; a.nfilt = FMAX; a.nbounds = S->nbounds;
+  a.tol = o.tol; a.acc_tol = o.acceptable_tol; a.acc_iter = o.acceptable_iter;
+  a.mu_rounds = MU_ROUNDS; a.mu_min = S->mu_min;
+  a.A = S->A; a.gw = S->gradw; a.c = S->c; a.w = S->w; a.y = S->y; a.zL = S->zL; a.zU = S->zU;
+  a.hasL = S->hasL; a.hasU = S->hasU; a.wl0 = S->wl0; a.wu0 = S->wu0;
+  a.mu_in = S->mu; a.filt_t = S->filt_t; a.filt_p = S->filt_p; a.fcount = S->fcount;
+  a.active = S->active; a.status = S->status; a.acc = S->acc; a.d_inf_out = S->d_inf; a.err0_out = S->err0;
+  a.base_out = S->base; a.mu_out = S->mu_o; a.filt_t_out = S->ft; a.filt_p_out = S->fp; a.fcount_out = S->fc;
+  a.skip = S->in_resto;
+  return a;
+}
+// The Newton setup of the regular phase or of the restoration phase (resto), which has its own bound
+// multipliers, gradient, barrier parameter and mask, and whose r2, theta and phi k_resto_prep2 replaces
+// (they land in scratch); a caller adds the dense Hessian block.  The limited-memory model is the same.
+NewtonSetupArgs newton_args_of(const cpl_solver* S, bool resto) {
+  NewtonSetupArgs a;
+  a.batch = S->Bcur; a.nw = S->nw; a.m = S->m; a.nf = S->nf;
+  a.w = S->w; a.A = S->A; a.y = S->y; a.c = S->c; a.f = S->f;
+  a.hasL = S->hasL; a.hasU = S->hasU; a.wl0 = S->wl0; a.wu0 = S->wu0;
+  a.M = S->M; a.r1 = S->r1; a.gphi = S->gphi; a.mr_diag = S->mr_diag;
+  a.zL = resto ? S->zLR : S->zL; a.zU = resto ? S->zUR : S->zU;
+  a.gw = resto ? S->gfR : S->gradw;
+  a.mu = resto ? S->muR : S->mu_o;
+  a.r2 = resto ? S->scr2 : S->r2;
+  a.theta = resto ? S->scr1 : S->theta_k; a.phi = resto ? S->scr1 + S->B : S->phi_k;
+  a.active = resto ? S->actR : S->act;
+  if (S->bfgs) { a.Hc = S->Hq; a.lm_pairs = LM_HIST; }
+  return a;
+}
+PostStepArgs post_step_args_of(const cpl_solver* S) {
+  PostStepArgs p;
+  p.nw = S->nw; p.w = S->w; p.dw = S->dw; p.zL = S->zL; p.zU = S->zU; p.gphi = S->gphi;
+  p.mu = S->mu_o; p.tau = S->tau; p.hasL = S->hasL; p.hasU = S->hasU; p.wl0 = S->wl0;
+  p.wu0 = S->wu0; p.theta = S->theta_k; p.theta_min = S->theta_min; p.active = S->act;
+  p.delta_w = S->delta_w; p.dwl = S->dwl; p.dzL = S->dzL; p.dzU = S->dzU; p.a_max = S->a_max;
+  p.a_z = S->a_z; p.gd_out = S->gd; p.switch_ok = S->switch_ok;
+  return p;
+}
+LsSetupArgs ls_setup_args_of(const cpl_solver* S) {
+  LsSetupArgs ls;
+  ls.m = S->m; ls.act = S->act; ls.w = S->w; ls.dw = S->dw; ls.dy = S->dy; ls.c = S->c; ls.f = S->f; ls.g = S->g;
+  ls.theta_k = S->theta_k; ls.theta_min = S->theta_min; ls.in_soft = S->in_soft; ls.soft_cnt = S->soft_cnt;
+  ls.tiny_last = S->tiny_last; ls.tiny_flag = S->tiny_flag; ls.tiny_now = S->tiny_now; ls.soft_now = S->soft_now;
+  ls.a_min = S->a_min; ls.searching = S->searching; ls.st_f = S->st_f; ls.st_g = S->st_g; ls.st_w = S->st_w;
+  ls.st_alpha = S->st_alpha; ls.st_aug = S->st_aug; ls.alpha = S->alpha; ls.any = S->d_any;
+  return ls;
+}
 static_assert(sizeof(RestoArgs) <= 1024 && sizeof(SoftStepArgs) + sizeof(FailTail) <= 1024,
               "the widest kernel arguments stay far below the 4 KiB kernarg limit");
 
@@ -2685,18 +2682,37 @@ LsBacktrackArgs ls_backtrack_args(const cpl_solver* S, const Search& q) {
   return la;
 }
 
-int32_t step_phase(cpl_solver* S, int phase) {
+int32_t step_phase(cpl_solver* S, int phase, const StepMode mode = {}) {
   const int64_t B = S->Bcur;
   const int n = S->n, m = S->m, nf = S->nf, nw = S->nw;
   hipStream_t st = S->stream;
   const cpl_solve_options& o = S->opt;
   const int64_t lmc = S->bfgs ? LMC(nf) : 0;
   const RestoArgs ra = resto_args(S);
+  // the whole search in one launch (first trial, its corrections, the backtracking): ls_kernel 2 (the
+  // default) or a small batch, at a system size whose factors the search kernel can re-solve with
+  const bool fused_ls = (o.ls_kernel == 2 || (o.ls_kernel == 1 && B <= FUSE_ROWS)) && S->ls_fusable;
+  const bool soft_begun = mode.soft_fused && fused_ls;  // that kernel also started the soft step
+  const AcceptRows ar{S->moved, n, m, S->nnz_rec, S->f_n, S->grad_n, S->g_n, S->J_n, S->f, S->grad, S->g, S->J};
+  auto accept_rows = [&](const AcceptRows& rows, const char* what) -> int32_t {
+    hipLaunchKernelGGL(k_accept_rows, dim3(blocks_elems(B * (1 + n + m + S->nnz_rec))), dim3(256), 0, st, B, rows);
+    LAUNCHED(what);
+    return CPL_OK;
+  };
+  // a trial (wt, f, g there, its step al) against the regular search's state; the take into the staged point
   auto judge = [&](const double* wt, const double* ft_, const double* gt_, const double* al, const uint8_t* extra,
                    double* th, uint8_t* ok) {
-    return cpl_ipm_judge_take(B, nw, m, nf, FMAX, S->row_slack, S->gl, S->hasL, S->hasU, S->wl0, S->wu0, wt, ft_, gt_,
-                              al, S->mu_o, S->theta_k, S->phi_k, S->gd, S->switch_ok, S->theta_max, S->ft, S->fp,
-                              extra, S->searching, S->st_f, S->st_g, S->st_w, S->st_alpha, S->st_aug, th, ok, 0, st);
+    const Search q = search_of(S);
+    const Staged t = staged_of(S);
+    const Bounds bd = bounds_of(S);
+    JudgeTakeArgs j;
+    j.batch = B; j.nw = nw; j.m = m; j.nf = nf; j.nfilt = FMAX; j.row_slack = S->row_slack; j.gl = S->gl;
+    j.hasL = bd.hasL; j.hasU = bd.hasU; j.wl0 = bd.wl0; j.wu0 = bd.wu0;
+    j.wt = wt; j.f_t = ft_; j.g_t = gt_; j.alpha = al; j.extra_mask = extra; j.th_out = th; j.ok_out = ok;
+    j.mu = q.mu; j.theta_k = q.theta; j.phi_k = q.phi; j.gd = q.gd; j.switch_ok = q.switch_ok;
+    j.theta_max = q.theta_max; j.filt_t = q.filt_t; j.filt_p = q.filt_p; j.searching = q.searching;
+    j.st_f = t.f; j.st_g = t.g; j.st_w = t.w; j.st_alpha = t.alpha; j.st_aug = t.aug;
+    return ipm_judge_take(j, st);
   };
   auto halve = [&](uint8_t* searching, double* alpha, const double* a_min, int fi, bool soft) -> int32_t {
     hipLaunchKernelGGL(k_halve2, dim3(blocks_elems(B)), dim3(256), 0, st, B, searching, alpha, a_min, S->act,
@@ -2768,29 +2784,17 @@ int32_t step_phase(cpl_solver* S, int phase) {
       // the whole search in one launch (first trial, its corrections, the backtracking), the post-step
       // quantities and the search's setup in that launch's prologue; or the first trial step by step
       // and the remaining trials in one launch
-      const bool fused = o.ls_kernel == 2 || (o.ls_kernel == 1 && B <= FUSE_ROWS);  // (2: the default)
-      const bool fused_ls = fused && S->ls_fusable;
       const bool post_in_ls = fused_ls && ls_post_prologue(B);  // (the search kernel's prologue)
       const IpmUnpack unp{n, S->freepos, S->Xbase, S->in_resto, S->X, S->tau, S->act,
                           S->acc_w, S->acc_y, S->acc_zL, S->acc_zU, S->has_acc, post_in_ls ? S->d_any : nullptr,
                           S->in_soft};
       const cpl_term_args term = S->term ? term_args(S, true) : cpl_term_args{};
-      CK(ipm_optimality_ex(B, nw, m, FMAX, S->nbounds, o.tol, o.acceptable_tol, o.acceptable_iter, S->A, S->gradw,
-                           S->c, S->w, S->y, S->zL, S->zU, S->hasL, S->hasU, S->wl0, S->wu0, S->mu, S->filt_t,
-                           S->filt_p, S->fcount, S->active, S->status, S->acc, S->d_inf, S->err0, S->base, S->mu_o,
-                           S->ft, S->fp, S->fc, MU_ROUNDS, S->mu_min, S->tiny_flag, S->in_resto, &unp, st,
-                           S->term ? &term : nullptr));
-      const double* Hblk = nullptr;
-      int h_sym = 0;
-      CK(hessian_into(S, &S->desc, S->act, &Hblk, &h_sym));
-      if (S->bfgs)
-        CK(ipm_newton_setup_lm(B, nw, m, nf, S->w, S->zL, S->zU, S->gradw, S->A, S->y, S->c, S->f, S->mu_o, S->hasL,
-                               S->hasU, S->wl0, S->wu0, S->Hq, LM_HIST, S->M, S->r1, S->r2, S->gphi, S->mr_diag,
-                               S->theta_k, S->phi_k, S->act, st));
-      else
-        CK(cpl_ipm_newton_setup(B, nw, m, nf, S->w, S->zL, S->zU, S->gradw, S->A, S->y, S->c, S->f, S->mu_o, S->hasL,
-                                S->hasU, S->wl0, S->wu0, Hblk, h_sym, S->M, S->r1, S->r2, S->gphi, S->mr_diag,
-                                S->theta_k, S->phi_k, S->act, st));
+      IpmOptArgs opt = opt_args_of(S);
+      opt.tiny_flag = S->tiny_flag;
+      CK(ipm_optimality(opt, &unp, S->term ? &term : nullptr, st));
+      NewtonSetupArgs ns = newton_args_of(S, false);
+      CK(hessian_into(S, &S->desc, S->act, &ns.H, &ns.h_sym));
+      CK(ipm_newton_setup(ns, st));
       CK(cpl_kkt_solve(0, B, nw, m, S->M, S->A, S->r1, S->r2, S->mu_o, S->dwl, S->act, S->dw, S->dy, S->delta_w,
                        S->delta_c, S->info, S->ws, st));
       if (S->jreg)
@@ -2798,18 +2802,8 @@ int32_t step_phase(cpl_solver* S, int phase) {
                          S->delta_c, S->info, S->ws_aug, st));
       // the step's multipliers / fraction-to-the-boundary, then the search's setup: a launch of their
       // own, or the fused search kernel's prologue
-      LsSetupArgs ls;
-      ls.m = m; ls.act = S->act; ls.w = S->w; ls.dw = S->dw; ls.dy = S->dy; ls.c = S->c; ls.f = S->f; ls.g = S->g;
-      ls.theta_k = S->theta_k; ls.theta_min = S->theta_min; ls.in_soft = S->in_soft; ls.soft_cnt = S->soft_cnt;
-      ls.tiny_last = S->tiny_last; ls.tiny_flag = S->tiny_flag; ls.tiny_now = S->tiny_now; ls.soft_now = S->soft_now;
-      ls.a_min = S->a_min; ls.searching = S->searching; ls.st_f = S->st_f; ls.st_g = S->st_g; ls.st_w = S->st_w;
-      ls.st_alpha = S->st_alpha; ls.st_aug = S->st_aug; ls.alpha = S->alpha; ls.any = S->d_any;
-      PostStepArgs post;
-      post.nw = nw; post.w = S->w; post.dw = S->dw; post.zL = S->zL; post.zU = S->zU; post.gphi = S->gphi;
-      post.mu = S->mu_o; post.tau = S->tau; post.hasL = S->hasL; post.hasU = S->hasU; post.wl0 = S->wl0;
-      post.wu0 = S->wu0; post.theta = S->theta_k; post.theta_min = S->theta_min; post.active = S->act;
-      post.delta_w = S->delta_w; post.dwl = S->dwl; post.dzL = S->dzL; post.dzU = S->dzU; post.a_max = S->a_max;
-      post.a_z = S->a_z; post.gd_out = S->gd; post.switch_ok = S->switch_ok;
+      const LsSetupArgs ls = ls_setup_args_of(S);
+      const PostStepArgs post = post_step_args_of(S);
       if (!post_in_ls) CK(ipm_post_step_ex(B, post, &ls, st));
       if (!fused_ls) CK(first_trial());
       if (!fused_ls && o.max_ls <= 1) return CPL_OK;
@@ -2820,9 +2814,8 @@ int32_t step_phase(cpl_solver* S, int phase) {
         la.c = S->c; la.M = S->M; la.r1 = S->r1; la.kkt_ws = S->ws; la.tau = S->tau;
         if (S->jreg) { la.aug_dc = S->delta_c; la.aug_ws = S->ws_aug; }  // (the regularised systems' re-solves)
         la.a_max = S->a_max; la.a_z = S->a_z;
-        if (S->soft_fused) {
+        if (mode.soft_fused) {
           la.soft_ws = S->ws_; la.soft_X = S->Xs; la.soft_try = S->soft_try; la.a_soft = S->a_soft;
-          S->soft_begun = true;
         }
         la.post = post;
         la.setup = ls;
@@ -2835,14 +2828,14 @@ int32_t step_phase(cpl_solver* S, int phase) {
     }
     case P_SOFT: {
       const SoftStepArgs soft = soft_step_args(S);
-      if (!S->soft_begun) {  // (else the Newton phase's search kernel started the soft step)
+      if (!soft_begun) {  // (else the Newton phase's search kernel started the soft step)
         hipLaunchKernelGGL(k_soft_begin, dim3(blocks_for(B)), dim3(256), 0, st, B, soft);
         LAUNCHED("k_soft_begin");
       }
       // (the fused search kernel raised d_any[1] exactly where it set soft_try: with no soft-step candidate
       // this evaluation's outputs are read by nobody, and its launch returns at once)
-      CK(eval_full(S, S->Xs, S->f_n, S->grad_n, S->g_n, S->J_n, S->soft_begun ? S->d_any + 1 : nullptr));
-      if (S->tail_fused)
+      CK(eval_full(S, S->Xs, S->f_n, S->grad_n, S->g_n, S->J_n, soft_begun ? S->d_any + 1 : nullptr));
+      if (mode.tail_fused)
         hipLaunchKernelGGL(k_soft_judge_fail, dim3(blocks_for(B)), dim3(256), 0, st, B, soft, fail_tail(S));
       else
         hipLaunchKernelGGL(k_soft_judge, dim3(blocks_for(B)), dim3(256), 0, st, B, soft);
@@ -2853,7 +2846,7 @@ int32_t step_phase(cpl_solver* S, int phase) {
     case P_ACCEPT_NR: {
       // the failed-search bookkeeping and the accepted points (done by the soft judge's launch in
       // P_FUSED), then one full evaluation there
-      if (!S->tail_fused) {
+      if (!mode.tail_fused) {
         hipLaunchKernelGGL(k_fail_unpack, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, fail_tail(S));
         LAUNCHED("k_fail_unpack");
       }
@@ -2863,12 +2856,9 @@ int32_t step_phase(cpl_solver* S, int phase) {
                               S->phi_k, S->ft, S->fp, S->fc, S->st_w, S->dy, S->dzL, S->dzU, S->mu_o, S->hasL,
                               S->hasU, S->wl0, S->wu0, S->w, S->y, S->zL, S->zU, S->mu, S->iters, S->filt_t,
                               S->filt_p, S->fcount};
-      AcceptRows ar{S->moved, n, m, S->nnz_rec, S->f_n, S->grad_n, S->g_n, S->J_n, S->f, S->grad, S->g, S->J};
       if (phase == P_ACCEPT_NR) {  // no instance can have failed its search: no entry
         CK(ipm_accept_ex(B, acc, st));
-        hipLaunchKernelGGL(k_accept_rows, dim3(blocks_elems(B * (1 + n + m + S->nnz_rec))), dim3(256), 0, st, B, n,
-                           m, S->nnz_rec, S->moved, S->f_n, S->grad_n, S->g_n, S->J_n, S->f, S->grad, S->g, S->J);
-        LAUNCHED("k_accept_rows");
+        CK(accept_rows(ar, "k_accept_rows"));
         goto count;
       }
       {  // the restoration phase starts where the line search failed
@@ -2920,17 +2910,9 @@ int32_t step_phase(cpl_solver* S, int phase) {
       hipLaunchKernelGGL(k_restore_acc, dim3(blocks_for(B)), dim3(256), 0, st, B, m, nw, S->status, S->has_acc,
                          S->acc_w, S->acc_y, S->acc_zL, S->acc_zU, S->w, S->y, S->zL, S->zU);
       LAUNCHED("k_restore_acc");
-      const double* Hblk = nullptr;
-      int h_sym = 0;
-      CK(hessian_into(S, &S->desc_R, S->actR, &Hblk, &h_sym));
-      if (S->bfgs)
-        CK(ipm_newton_setup_lm(B, nw, m, nf, S->w, S->zLR, S->zUR, S->gfR, S->A, S->y, S->c, S->f, S->muR, S->hasL,
-                               S->hasU, S->wl0, S->wu0, S->Hq, LM_HIST, S->M, S->r1, S->scr2, S->gphi, S->mr_diag,
-                               S->scr1, S->scr1 + S->B, S->actR, st));
-      else
-        CK(cpl_ipm_newton_setup(B, nw, m, nf, S->w, S->zLR, S->zUR, S->gfR, S->A, S->y, S->c, S->f, S->muR, S->hasL,
-                                S->hasU, S->wl0, S->wu0, Hblk, h_sym, S->M, S->r1, S->scr2, S->gphi, S->mr_diag,
-                                S->scr1, S->scr1 + S->B, S->actR, st));
+      NewtonSetupArgs ns = newton_args_of(S, true);
+      CK(hessian_into(S, &S->desc_R, S->actR, &ns.H, &ns.h_sym));
+      CK(ipm_newton_setup(ns, st));
       hipLaunchKernelGGL(k_resto_prep2, dim3(blocks_for(B)), dim3(256), 0, st, B, m, nf, nw, S->actR, S->c, S->w, S->y,
                          S->wR, S->pR, S->nR, S->zp, S->zn, S->muR, S->hasL, S->hasU, S->wl0, S->wu0, S->M, S->rp,
                          S->rn, S->Dinv, S->r2, S->thetaR, S->phiR);
@@ -2967,30 +2949,19 @@ int32_t step_phase(cpl_solver* S, int phase) {
       }
       hipLaunchKernelGGL(k_resto_accept, dim3(blocks_for(B)), dim3(256), 0, st, B, ra);
       LAUNCHED("k_resto_accept");
-      hipLaunchKernelGGL(k_accept_rows, dim3(blocks_elems(B * (1 + n + m + S->nnz_rec))), dim3(256), 0, st, B, n, m,
-                         S->nnz_rec, S->movedR, S->f_n, S->grad_n, S->g_n, S->J_n, S->f, S->grad, S->g, S->J);
-      LAUNCHED("k_accept_rows (resto)");
-      return CPL_OK;
+      AcceptRows arR = ar;
+      arR.moved = S->movedR;
+      return accept_rows(arR, "k_accept_rows (resto)");
     }
     case P_FUSED:
     case P_FUSED_R: {
-      S->soft_fused = true;
-      S->soft_begun = false;
-      {
-        const int32_t rc0 = step_phase(S, P_NEWTON);
-        if (rc0 != CPL_OK) {
-          S->soft_fused = S->soft_begun = false;
-          return rc0;
-        }
-      }
-      // P_SOFT and P_ACCEPT adjacent (no restoration iteration between): one launch ends the search
-      S->tail_fused = phase == P_FUSED;
-      int32_t rc = step_phase(S, P_SOFT);
-      S->soft_fused = S->soft_begun = false;
-      if (rc == CPL_OK && phase == P_FUSED_R) rc = step_phase(S, P_RNEWTON);
-      if (rc == CPL_OK) rc = step_phase(S, P_ACCEPT);
-      S->tail_fused = false;
-      return rc;
+      // the search kernel starts the soft step; P_SOFT and P_ACCEPT adjacent (no restoration iteration
+      // between): one launch ends the search
+      const StepMode fm{true, phase == P_FUSED};
+      CK(step_phase(S, P_NEWTON, fm));
+      CK(step_phase(S, P_SOFT, fm));
+      if (phase == P_FUSED_R) CK(step_phase(S, P_RNEWTON));
+      return step_phase(S, P_ACCEPT, fm);
     }
     default:
       return fail(CPL_ERR_INVALID_ARGUMENT, "step_phase: bad phase");
@@ -3690,11 +3661,7 @@ int32_t cpl_solver_solve_inst(cpl_solver* S, const double* d_x0, const double* d
                      S->grad, S->g, S->w, S->gradw, S->c);
   LAUNCHED("k_prep");
   const cpl_term_args term_fin = S->term ? term_args(S, false) : cpl_term_args{};
-  CK(ipm_optimality_ex(Bc, nw, m, FMAX, S->nbounds, S->opt.tol, S->opt.acceptable_tol, S->opt.acceptable_iter, S->A,
-                       S->gradw, S->c, S->w, S->y, S->zL, S->zU, S->hasL, S->hasU, S->wl0, S->wu0, S->mu, S->filt_t,
-                       S->filt_p, S->fcount, S->active, S->status, S->acc, S->d_inf, S->err0, S->base, S->mu_o, S->ft,
-                       S->fp, S->fc, MU_ROUNDS, S->mu_min, nullptr, S->in_resto, nullptr, st,
-                       S->term ? &term_fin : nullptr));
+  CK(ipm_optimality(opt_args_of(S), nullptr, S->term ? &term_fin : nullptr, st));
   if (S->term) {
     hipLaunchKernelGGL(k_scatter_term, dim3(blocks_elems(Bc * nw)), dim3(256), 0, st, Bc * nw, nw, false, S->orig,
                        S->active, S->u_dinf, S->u_cviol, S->u_compl, S->zL, S->zU, S->fu_dinf, S->fu_cviol, S->fu_compl,

@@ -465,6 +465,21 @@ def test_newton_setup_forms_agree_bit_for_bit_and_skip_inactive_rows(nw, m, hcas
 
 
 @pytest.mark.gpu
+def test_newton_setup_form_is_chosen_at_1024_instances_bit_for_bit():
+    """One launcher picks the form from the batch size: 1 024 instances still run one per workgroup,
+    1 025 one per wave.  The 4-contact size (nw 47, m 30, nf 39) with a dense Hessian block taken as it
+    is (h_sym 0): every output of the first 1 024 rows is the same bits in both launches."""
+    nw, m, nf = 47, 30, 39
+    d = _setup_inputs(1025, nw, m, nf, "given", seed=600)
+    assert d["h_sym"] == 0
+    wide = _setup(d, 1024, nw, m, nf)
+    wave = _setup(d, 1025, nw, m, nf)
+    for k in ("M", "r1", "r2", "gphi", "mr_diag", "theta", "phi"):
+        assert np.isfinite(wide[k]).all() and np.isfinite(wave[k]).all(), k
+        assert _bits(wide[k]) == _bits(wave[k][:1024]), k
+
+
+@pytest.mark.gpu
 def test_newton_setup_chained_into_the_kkt_solve():
     """The assembled M, r1, r2 of (47, 30) instances handed to cpl_kkt_solve: the step against the truth
     of the system assembled in longdouble, under the mode-0 bound."""
