@@ -539,7 +539,8 @@ __global__ __launch_bounds__(256) void cpl_ipm_accept_kernel(const IpmAcceptArgs
   ipm_accept_one(a, b, threadIdx.x & 63);
 }
 
-// dst[b] = src[b] for the rows with mask[b] (row length len doubles), 16-byte accesses when aligned.
+// dst[b] = src[b] for the rows with mask[b] (row length len doubles): one thread per double, 8-byte
+// accesses (rows need no more than a double's alignment).
 __global__ __launch_bounds__(256) void cpl_ipm_masked_rows_kernel(int64_t total, int64_t len,
                                                                   const uint8_t* __restrict__ mask,
                                                                   const double* __restrict__ src,
@@ -714,7 +715,7 @@ int32_t cpl_ipm_trial_point(int64_t batch, int32_t n, int32_t nf, int32_t nw, co
                             const int64_t* d_fixed_idx, const double* d_Xbase, const double* d_w, const double* d_dir,
                             const double* d_alpha, const uint8_t* d_mask, const double* d_w_keep, double* d_wt,
                             double* d_X, void* stream) {
-  if (batch < 0 || n <= 0 || nf < 0 || nf > n || nw < nf)
+  if (batch < 0 || n <= 0 || nf < 0 || nf > n || nw <= 0 || nw < nf)
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_trial_point: bad sizes");
   if (batch == 0) return CPL_OK;
   if (!d_free_idx || (n > nf && !d_fixed_idx) || !d_Xbase || !d_w || !d_dir || !d_alpha || !d_mask || !d_w_keep ||

@@ -540,8 +540,13 @@ int32_t cpl_ipm_max_step(int64_t batch, int32_t nw, const double* d_v, const dou
  * cpl_ipm_accept: filter augmentation / reset, y, z (kappa_Sigma safeguard), w, mu and iteration
  *   counters written back in place (d_failed: filter reset rows, d_rest: rows keeping z; both optional).
  * cpl_ipm_masked_rows: dst[b, :] = src[b, :] where mask[b].
- * d_active (optional, where present): instances with active[b] == 0 are skipped — their outputs
- * are left unwritten (converged instances of the solve loop, whose Newton data is never read).
+ * d_active of cpl_ipm_newton_setup, cpl_ipm_fd_points, cpl_ipm_fd_hessian_raw and cpl_ipm_dense_a (optional):
+ * instances with active[b] == 0 are skipped — their outputs are left unwritten (converged instances of
+ * the solve loop, whose Newton data is never read).  cpl_ipm_post_step and cpl_ipm_accept take d_active
+ * (required) as a row mask instead, as the host path of batch_ipm.py does: cpl_ipm_post_step writes every output of every instance and
+ * gates only delta_w_last; cpl_ipm_accept keeps w, y, zL, zU and iters of an inactive instance and does
+ * not augment its filter, but still writes its mu_state (<- d_mu), copies its filter to d_filt_t /
+ * d_filt_p (reset where d_failed) and writes its d_fcount.
  */
 int32_t cpl_ipm_newton_setup(int64_t batch, int32_t nw, int32_t m, int32_t nf, const double* d_w, const double* d_zL,
                              const double* d_zU, const double* d_gw, const double* d_A, const double* d_y,
