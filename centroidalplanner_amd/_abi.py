@@ -272,6 +272,11 @@ SIGNATURES = {
     "cpl_ipm_max_step": (c_int32, [c_int64, c_int32] + [c_void_p] * 11),
     "cpl_ipm_newton_setup": (c_int32, [c_int64, c_int32, c_int32, c_int32] + [c_void_p] * 14 + [c_int32]
                              + [c_void_p] * 9),
+    "cpl_ipm_lm_model_doubles": (c_int64, [c_int32, c_int32]),
+    "cpl_ipm_newton_setup_ex": (c_int32, [c_int64, c_int32, c_int32, c_int32] + [c_void_p] * 14 + [c_int32]
+                                + [c_void_p] * 8 + [c_int32, c_void_p, c_void_p]),
+    "cpl_ipm_lbfgs_update": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 18
+                             + [c_int32, c_void_p]),
     "cpl_ipm_fd_hessian_raw": (c_int32, [c_int64, c_int32, c_int32] + [c_void_p] * 6),
     "cpl_ipm_fd_points": (c_int32, [c_int64, c_int32, c_int32, c_double] + [c_void_p] * 6),
     "cpl_ipm_post_step": (c_int32, [c_int64, c_int32] + [c_void_p] * 23),

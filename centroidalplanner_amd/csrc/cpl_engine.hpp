@@ -110,6 +110,26 @@ int32_t eval_batch_gated(const cpl_problem_desc* d, int64_t batch, const double*
                          const uint8_t* d_env_tag, double* d_g, double* d_jac, double* d_f, double* d_grad,
                          int32_t flags, void* stream, const uint8_t* gate);
 
+// ---- cpl_solver.hip ----
+
+// The limited-memory update (k_lbfgs / k_lbfgs_wave) of the instances of `act`, from the old point to the
+// new one.  The memory holds LM_HIST pairs; the compact model Hq is [sigma, nv, U, W] with LM_HIST rows
+// of nf in U and in W (what NewtonSetupArgs::Hc takes with lm_pairs = LM_HIST).
+constexpr int LM_HIST = 6;
+struct LbfgsArgs {
+  int n = 0, m = 0, nf = 0, nw = 0, nnz_rec = 0;
+  const int32_t *amap = nullptr, *free_idx = nullptr;
+  const uint8_t *act = nullptr, *failed = nullptr;
+  const double *w_old = nullptr, *w_new = nullptr, *y = nullptr, *dy = nullptr, *alpha = nullptr;
+  const double *gw_old = nullptr, *J_old = nullptr, *grad_new = nullptr, *J_new = nullptr;
+  double *lm_s = nullptr, *lm_y = nullptr;
+  uint8_t *lm_cnt = nullptr, *lm_skip = nullptr;
+  double* Hq = nullptr;
+};
+// form 0: the one-wave kernel for nf <= 64, else the workgroup kernel; 1: the workgroup kernel (nf <= 128);
+// 2: the one-wave kernel (nf <= 64).  The sizes are the caller's to check (cpl_ipm_lbfgs_update does).
+int32_t lbfgs_launch(int64_t batch, const LbfgsArgs& L, int form, hipStream_t stream);
+
 // ---- cpl_kkt.hip ----
 
 // the system size runs the one-wave kernel (whose factors the fused line-search kernel re-solves with)

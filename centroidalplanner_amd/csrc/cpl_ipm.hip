@@ -827,15 +827,42 @@ int32_t cpl_ipm_max_step(int64_t batch, int32_t nw, const double* d_v, const dou
 }
 
 
+int64_t cpl_ipm_lm_model_doubles(int32_t nf, int32_t lm_pairs) {
+  if (nf < 0 || lm_pairs <= 0) return -1;
+  return 2 + 2 * (int64_t)lm_pairs * nf;
+}
+
 int32_t cpl_ipm_newton_setup(int64_t batch, int32_t nw, int32_t m, int32_t nf, const double* d_w, const double* d_zL,
                              const double* d_zU, const double* d_gw, const double* d_A, const double* d_y,
                              const double* d_c, const double* d_f, const double* d_mu, const uint8_t* d_hasL,
                              const uint8_t* d_hasU, const double* d_wl0, const double* d_wu0, const double* d_H,
                              int32_t h_sym, double* d_M, double* d_r1, double* d_r2, double* d_gphi, double* d_mr_diag,
                              double* d_theta, double* d_phi, const uint8_t* d_active, void* stream) {
+  return cpl_ipm_newton_setup_ex(batch, nw, m, nf, d_w, d_zL, d_zU, d_gw, d_A, d_y, d_c, d_f, d_mu, d_hasL, d_hasU, d_wl0,
+                                 d_wu0, d_H, h_sym, d_M, d_r1, d_r2, d_gphi, d_mr_diag, d_theta, d_phi, nullptr, 0,
+                                 d_active, stream);
+}
+
+int32_t cpl_ipm_newton_setup_ex(int64_t batch, int32_t nw, int32_t m, int32_t nf, const double* d_w,
+                                const double* d_zL, const double* d_zU, const double* d_gw, const double* d_A,
+                                const double* d_y, const double* d_c, const double* d_f, const double* d_mu,
+                                const uint8_t* d_hasL, const uint8_t* d_hasU, const double* d_wl0,
+                                const double* d_wu0, const double* d_H, int32_t h_sym, double* d_M, double* d_r1,
+                                double* d_r2, double* d_gphi, double* d_mr_diag, double* d_theta, double* d_phi,
+                                const double* d_Hc, int32_t lm_pairs, const uint8_t* d_active, void* stream) {
   if (batch < 0 || nw <= 0 || m < 0 || nf < 0 || nf > nw) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_newton_setup: bad sizes");
   // Sigma is staged per wave in sig_s[IPM_WAVES][128] (same limit as cpl_ipm_optimality / cpl_kkt_solve)
   if (nw > 128) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_newton_setup: nw > 128 is not supported");
+  if (d_Hc) {
+    if (d_H) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_newton_setup: a dense Hessian and a compact model");
+    if (lm_pairs <= 0) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_newton_setup: a compact model needs lm_pairs > 0");
+    // (with nf = 0 the model has no rows and the launch no LDS to stage them in, yet the column build
+    // reads row entry 0 of each of the nv pairs)
+    if (nf == 0) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_newton_setup: a compact model needs nf > 0");
+    // the U | W staging of the one-instance-per-wave form, four waves a workgroup, in 64 KiB of LDS less Sigma's rows
+    if (sizeof(double) * IPM_WAVES * 2 * (size_t)lm_pairs * nf > 60 * 1024)
+      return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_newton_setup: lm_pairs * nf too large for the LDS staging");
+  }
   if (batch == 0) return CPL_OK;
   if (!d_w || !d_zL || !d_zU || !d_gw || (m > 0 && (!d_A || !d_y || !d_c || !d_r2)) || !d_f || !d_mu || !d_hasL ||
       !d_hasU || !d_wl0 || !d_wu0 || !d_M || !d_r1 || !d_gphi || !d_mr_diag || !d_theta || !d_phi)
@@ -844,7 +871,7 @@ int32_t cpl_ipm_newton_setup(int64_t batch, int32_t nw, int32_t m, int32_t nf, c
   a.batch = batch; a.nw = nw; a.m = m; a.nf = nf; a.w = d_w; a.zL = d_zL; a.zU = d_zU; a.gw = d_gw; a.A = d_A;
   a.y = d_y; a.c = d_c; a.f = d_f; a.mu = d_mu; a.hasL = d_hasL; a.hasU = d_hasU; a.wl0 = d_wl0; a.wu0 = d_wu0;
   a.H = d_H; a.h_sym = h_sym; a.M = d_M; a.r1 = d_r1; a.r2 = d_r2; a.gphi = d_gphi; a.mr_diag = d_mr_diag;
-  a.theta = d_theta; a.phi = d_phi; a.active = d_active;
+  a.theta = d_theta; a.phi = d_phi; a.active = d_active; a.Hc = d_Hc; a.lm_pairs = d_Hc ? lm_pairs : 0;
   return ipm_newton_setup(a, stream);
 }
 

@@ -740,19 +740,9 @@ __global__ __launch_bounds__(256) void k_soft_judge_fail(int64_t B, const SoftSt
 //   pair clamped to [1e-8, 1e8], and the dense model is rebuilt from sigma I by the BFGS recursion
 //   over the stored pairs, oldest first: B <- B - (Bs)(Bs)' / s'Bs + y y' / s'y  (mathematically the
 //   compact representation IPOPT applies; B stays bitwise symmetric: every update is an outer product).
-constexpr int LM_HIST = 6, LM_MAX_SKIP = 2;
+constexpr int LM_MAX_SKIP = 2;  // (LM_HIST and the update's argument block LbfgsArgs: cpl_engine.hpp)
 // doubles per instance of the compact model: sigma, the number of pairs nv, U [LM_HIST][nf], W [LM_HIST][nf]
 __host__ __device__ constexpr int64_t LMC(int nf) { return 2 + 2 * (int64_t)LM_HIST * nf; }
-struct LbfgsArgs {  // the update for the instances of `act`, from the old point to the new one
-  int n = 0, m = 0, nf = 0, nw = 0, nnz_rec = 0;
-  const int32_t *amap = nullptr, *free_idx = nullptr;
-  const uint8_t *act = nullptr, *failed = nullptr;
-  const double *w_old = nullptr, *w_new = nullptr, *y = nullptr, *dy = nullptr, *alpha = nullptr;
-  const double *gw_old = nullptr, *J_old = nullptr, *grad_new = nullptr, *J_new = nullptr;
-  double *lm_s = nullptr, *lm_y = nullptr;
-  uint8_t *lm_cnt = nullptr, *lm_skip = nullptr;
-  double* Hq = nullptr;
-};
 // Column k of J_free^T yn at both points over the rows part, part + parts, ..., straight from the
 // values-only Jacobian records (the entries of A = [J_free | -P] as cpl_ipm_dense_a forms them: amap
 // -1 = 0, -2 = constant 1, NaN = 0).  Rows in order, eight at a time: the eight amap indices, then
@@ -2643,23 +2633,29 @@ LsSetupArgs ls_setup_args_of(const cpl_solver* S) {
 static_assert(sizeof(RestoArgs) <= 1024 && sizeof(SoftStepArgs) + sizeof(FailTail) <= 1024,
               "the widest kernel arguments stay far below the 4 KiB kernarg limit");
 
+}  // namespace
+// The one launch of both L-BFGS kernels (cpl_engine.hpp): the engine's update below and the C-ABI's
+// cpl_ipm_lbfgs_update.  The one-wave form stages yn per wave in dynamic LDS.
+int32_t lbfgs_launch(int64_t B, const LbfgsArgs& L, int form, hipStream_t stream) {
+  if (form == 2 || (form == 0 && L.nf <= 64))
+    hipLaunchKernelGGL(k_lbfgs_wave, dim3((unsigned)((B + LBW_WAVES - 1) / LBW_WAVES)), dim3(64 * LBW_WAVES),
+                       sizeof(double) * LBW_WAVES * (size_t)L.m, stream, B, L);
+  else
+    hipLaunchKernelGGL(k_lbfgs, dim3((unsigned)B), dim3(256), 0, stream, B, L);
+  LAUNCHED("k_lbfgs");
+  return CPL_OK;
+}
+namespace {
 // The L-BFGS update of the instances of `mask` from (w, gw_old, J) to the accepted point (st_w, grad_new,
 // J_n); grad_new == nullptr: no cost term (the restoration phase's model: the constraint curvature
-// alone).  nf <= 64 takes the one-wave form, larger problems the workgroup form.
+// alone).  nf <= 64 takes the one-wave form, larger problems the workgroup form (lbfgs_launch, form 0).
 int32_t lbfgs_update(cpl_solver* S, const uint8_t* mask, const double* gw_old, const double* grad_new) {
   LbfgsArgs L;
   L.n = S->n; L.m = S->m; L.nf = S->nf; L.nw = S->nw; L.nnz_rec = S->nnz_rec; L.amap = S->amap; L.free_idx = S->free32;
   L.act = mask; L.failed = S->zeros_u8; L.w_old = S->w; L.w_new = S->st_w; L.y = S->y; L.dy = S->dy;
   L.alpha = S->st_alpha; L.gw_old = gw_old; L.J_old = S->J; L.grad_new = grad_new; L.J_new = S->J_n;
   L.lm_s = S->lm_s; L.lm_y = S->lm_y; L.lm_cnt = S->lm_cnt; L.lm_skip = S->lm_skip; L.Hq = S->Hq;
-  const int64_t B = S->Bcur;
-  if (S->nf <= 64)
-    hipLaunchKernelGGL(k_lbfgs_wave, dim3((unsigned)((B + LBW_WAVES - 1) / LBW_WAVES)), dim3(64 * LBW_WAVES),
-                       sizeof(double) * LBW_WAVES * (size_t)S->m, S->stream, B, L);
-  else
-    hipLaunchKernelGGL(k_lbfgs, dim3((unsigned)B), dim3(256), 0, S->stream, B, L);
-  LAUNCHED("k_lbfgs");
-  return CPL_OK;
+  return lbfgs_launch(S->Bcur, L, 0, S->stream);
 }
 
 // The backtracking kernel's arguments common to its three uses, for the search `q` (the regular one or
@@ -3698,6 +3694,33 @@ int32_t cpl_solver_solve_inst(cpl_solver* S, const double* d_x0, const double* d
   if (iterations_run) *iterations_run = it;
   if (evaluations) *evaluations = evals;
   return CPL_OK;
+}
+
+// One limited-memory update outside a solve: the engine's launch (lbfgs_launch) on the caller's buffers.
+int32_t cpl_ipm_lbfgs_update(int64_t batch, int32_t n, int32_t m, int32_t nf, int32_t nw, int32_t nnz_rec,
+                             const int32_t* d_amap, const int32_t* d_free_idx, const uint8_t* d_act,
+                             const uint8_t* d_failed, const double* d_w_old, const double* d_w_new, const double* d_y,
+                             const double* d_dy, const double* d_alpha, const double* d_gw_old, const double* d_J_old,
+                             const double* d_grad_new, const double* d_J_new, double* d_lm_s, double* d_lm_y,
+                             uint8_t* d_lm_cnt, uint8_t* d_lm_skip, double* d_Hc, int32_t form, void* stream) {
+  if (batch < 0 || n <= 0 || m < 0 || nf <= 0 || nf > n || nf > nw || nnz_rec < 0)
+    return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_lbfgs_update: bad sizes");
+  // the workgroup form's pair rows hold NFX entries; both forms stage yn in LDS (the workgroup form's yn[256])
+  if (nw > NFX) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_lbfgs_update: nw > 128 is not supported");
+  if (m > 256) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_lbfgs_update: m > 256 is not supported");
+  if (form < 0 || form > 2) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_lbfgs_update: unknown form");
+  if (form == 2 && nf > 64) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_lbfgs_update: the one-wave form needs nf <= 64");
+  if (batch == 0) return CPL_OK;
+  if (!d_free_idx || !d_act || !d_failed || !d_w_old || !d_w_new || !d_alpha || !d_gw_old || !d_lm_s || !d_lm_y ||
+      !d_lm_cnt || !d_lm_skip || !d_Hc || (m > 0 && (!d_amap || !d_y || !d_dy || !d_J_old || !d_J_new)))
+    return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_lbfgs_update: missing buffer");
+  if (batch > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_lbfgs_update: batch too large");
+  LbfgsArgs L;
+  L.n = n; L.m = m; L.nf = nf; L.nw = nw; L.nnz_rec = nnz_rec; L.amap = d_amap; L.free_idx = d_free_idx;
+  L.act = d_act; L.failed = d_failed; L.w_old = d_w_old; L.w_new = d_w_new; L.y = d_y; L.dy = d_dy;
+  L.alpha = d_alpha; L.gw_old = d_gw_old; L.J_old = d_J_old; L.grad_new = d_grad_new; L.J_new = d_J_new;
+  L.lm_s = d_lm_s; L.lm_y = d_lm_y; L.lm_cnt = d_lm_cnt; L.lm_skip = d_lm_skip; L.Hq = d_Hc;
+  return lbfgs_launch(batch, L, form, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -554,6 +554,57 @@ int32_t cpl_ipm_newton_setup(int64_t batch, int32_t nw, int32_t m, int32_t nf, c
                              const uint8_t* d_hasU, const double* d_wl0, const double* d_wu0, const double* d_H,
                              int32_t h_sym, double* d_M, double* d_r1, double* d_r2, double* d_gphi, double* d_mr_diag,
                              double* d_theta, double* d_phi, const uint8_t* d_active, void* stream);
+/*
+ * The limited-memory quasi-Newton model (hessian = CPL_HESSIAN_LIMITED_MEMORY) outside a solve.
+ *
+ * The compact model of one instance is cpl_ipm_lm_model_doubles(nf, lm_pairs) = 2 + 2 lm_pairs nf doubles:
+ *   [sigma, nv, U (lm_pairs rows of nf), W (lm_pairs rows of nf)], of which the first nv rows of U and of W
+ *   count (0 <= nv <= lm_pairs, stored as a double), and stands for the nf x nf matrix
+ *   sigma I - sum_{i < nv} u_i u_i' + sum_{i < nv} w_i w_i'.  The engine's lm_pairs is 6.  (-1: nf < 0 or
+ *   lm_pairs <= 0.)
+ *
+ * cpl_ipm_newton_setup_ex: cpl_ipm_newton_setup whose Hessian block may instead be that model, expanded entry
+ *   by entry into M: d_Hc [batch, cpl_ipm_lm_model_doubles(nf, lm_pairs)] (or NULL, then lm_pairs is ignored and
+ *   the call is cpl_ipm_newton_setup).  Refused: d_Hc together with d_H, lm_pairs <= 0, nf = 0 (a model
+ *   without rows), 64 lm_pairs nf bytes beyond the 60 KiB staged per workgroup.  The rows' nv is the caller's
+ *   to keep within lm_pairs.
+ *
+ * cpl_ipm_lbfgs_update: one update of the memory and the model of every instance with d_act[b] != 0, from
+ *   the point w_old to the accepted point w_new (IPOPT's LimMemQuasiNewtonUpdater: history 6, scalar1
+ *   initialisation clamped to [1e-8, 1e8], max_skipping 2).
+ *     d_amap [m, nf], d_J_old / d_J_new [batch, nnz_rec]: A = [J_free | -P]'s free columns as cpl_ipm_dense_a
+ *       reads them from the Jacobian records at both points (every d_amap entry -1, -2 or in [0, nnz_rec));
+ *     d_free_idx [nf]: the position in x (of n) of each free variable; d_grad_new [batch, n]: the cost
+ *       gradient at the new point, or NULL (no cost term: the restoration phase's model);
+ *     d_gw_old [batch, nw]: the cost gradient over w at the old point (its first nf entries are read);
+ *     d_w_old, d_w_new [batch, nw]; d_y, d_dy [batch, m], d_alpha [batch]: the multipliers yn = y + alpha dy;
+ *     d_failed [batch]: != 0 resets the instance's model whatever the pair;
+ *     d_lm_s, d_lm_y [batch, 6, nf]: the stored pairs, oldest first; d_lm_cnt, d_lm_skip [batch]: how many
+ *       are stored and the consecutive skipped updates; d_Hc [batch, cpl_ipm_lm_model_doubles(nf, 6)].
+ *   The pair is s = (w_new - w_old)[0:nf], yk = (grad_new[free] + J_new_free' yn) - (gw_old + J_old_free' yn).
+ *   s'yk <= sqrt(eps) |s| |yk| skips it: lm_skip + 1, nothing else written, and past two skips in a row (or
+ *   d_failed) the reset: sigma 1, nv 0, lm_cnt 0, lm_skip 0, the pair rows left as they are.  A taken pair
+ *   is appended (a full memory first drops its oldest), lm_skip 0, lm_cnt min(lm_cnt + 1, 6), and the
+ *   model rebuilt from the stored pairs.  An instance with d_act[b] = 0 keeps all five outputs.
+ *   form 0: the one-wave kernel for nf <= 64 and the workgroup kernel above, as the engine chooses; 1: the
+ *   workgroup kernel; 2: the one-wave kernel (refused for nf > 64).  The forms give the same bits.
+ *   Refused: nf <= 0, nf > n, nf > nw, nw > 128, m > 256, an unknown form, a missing buffer (with m = 0 the
+ *   row buffers d_amap, d_y, d_dy, d_J_old, d_J_new are optional; d_grad_new always is).
+ */
+int64_t cpl_ipm_lm_model_doubles(int32_t nf, int32_t lm_pairs);
+int32_t cpl_ipm_newton_setup_ex(int64_t batch, int32_t nw, int32_t m, int32_t nf, const double* d_w,
+                                const double* d_zL, const double* d_zU, const double* d_gw, const double* d_A,
+                                const double* d_y, const double* d_c, const double* d_f, const double* d_mu,
+                                const uint8_t* d_hasL, const uint8_t* d_hasU, const double* d_wl0,
+                                const double* d_wu0, const double* d_H, int32_t h_sym, double* d_M, double* d_r1,
+                                double* d_r2, double* d_gphi, double* d_mr_diag, double* d_theta, double* d_phi,
+                                const double* d_Hc, int32_t lm_pairs, const uint8_t* d_active, void* stream);
+int32_t cpl_ipm_lbfgs_update(int64_t batch, int32_t n, int32_t m, int32_t nf, int32_t nw, int32_t nnz_rec,
+                             const int32_t* d_amap, const int32_t* d_free_idx, const uint8_t* d_act,
+                             const uint8_t* d_failed, const double* d_w_old, const double* d_w_new, const double* d_y,
+                             const double* d_dy, const double* d_alpha, const double* d_gw_old, const double* d_J_old,
+                             const double* d_grad_new, const double* d_J_new, double* d_lm_s, double* d_lm_y,
+                             uint8_t* d_lm_cnt, uint8_t* d_lm_skip, double* d_Hc, int32_t form, void* stream);
 int32_t cpl_ipm_fd_hessian_raw(int64_t batch, int32_t n, int32_t nf, const int64_t* d_free_idx, const double* d_gL,
                                const double* d_h, double* d_H, const uint8_t* d_active, void* stream);
 int32_t cpl_ipm_fd_points(int64_t batch, int32_t n, int32_t nf, double fd_step, const int32_t* d_freepos,
