@@ -148,6 +148,23 @@ class InstanceDataC(ctypes.Structure):
     ]
 
 
+class WarmStart(ctypes.Structure):
+    """cpl_warm_start (include/cpl_mi355x.h): device pointers (d_mask may be NULL) and the warm_start_* constants."""
+
+    _fields_ = [
+        ("d_y", c_void_p),
+        ("d_zL", c_void_p),
+        ("d_zU", c_void_p),
+        ("d_mask", c_void_p),
+        ("mu_init", c_double),
+        ("bound_push", c_double),
+        ("bound_frac", c_double),
+        ("slack_bound_push", c_double),
+        ("slack_bound_frac", c_double),
+        ("mult_bound_push", c_double),
+    ]
+
+
 class DerivativeReport(ctypes.Structure):
     """cpl_derivative_report (include/cpl_mi355x.h)."""
 
@@ -298,6 +315,11 @@ SIGNATURES = {
     "cpl_solver_nan_jacobian": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "cpl_solver_unscaled_errors": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "cpl_solver_final_iterate": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cpl_warm_start_default": (None, [POINTER(WarmStart)]),
+    "cpl_warm_start_sizeof": (c_int64, []),
+    "cpl_solver_solve_warm": (c_int32, [c_void_p] * 4 + [POINTER(InstanceDataC), c_int32, POINTER(WarmStart)]
+                              + [c_void_p] * 7 + [POINTER(c_int32), POINTER(c_int64), c_void_p]),
+    "cpl_solver_warm_state": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 
@@ -377,3 +399,5 @@ if lib.cpl_desc_sizeof() != ctypes.sizeof(ProblemDesc):  # pragma: no cover - la
     raise ImportError("cpl_problem_desc layout mismatch between header and ctypes mirror")
 if lib.cpl_solve_options_sizeof() != ctypes.sizeof(SolveOptions):  # pragma: no cover - layout guard
     raise ImportError("cpl_solve_options layout mismatch between header and ctypes mirror")
+if lib.cpl_warm_start_sizeof() != ctypes.sizeof(WarmStart):  # pragma: no cover - layout guard
+    raise ImportError("cpl_warm_start layout mismatch between header and ctypes mirror")

@@ -181,6 +181,74 @@ class KernelEvaluator:
         return H
 
 
+class WarmStart:
+    """A previous solve's multipliers to start the next one from [IPOPT-ext: warm_start_init_point with
+    warm_start_bound_push / _frac, warm_start_slack_bound_push / _frac, warm_start_mult_bound_push;
+    cpl_warm_start, include/cpl_mi355x.h]: y [B, m], z_L and z_U [B, n] of the UNSCALED problem
+    (BatchSolveResult.y / mult_x_L / mult_x_U), float64, all three or none.  x [B, n] (optional) is the
+    solution they belong to: the planners take their start point from it; the solvers read X0.
+    mask [B] (bool / uint8, optional): False = that instance starts cold.  An instance whose y, or whose
+    z at a free variable with that bound, is not finite starts cold as well.  mu_init: the barrier
+    parameter of the warm instances (0: the solver's mu_init) — a small value such as 1e-4, never a
+    converged solve's final mu: the monotone update cannot raise it again (DESIGN.md §5 "Warm start")."""
+
+    PUSHES = ("mu_init", "bound_push", "bound_frac", "slack_bound_push", "slack_bound_frac", "mult_bound_push")
+
+    def __init__(self, y, z_L, z_U, x=None, mask=None, mu_init=0.0, bound_push=1e-3, bound_frac=1e-3,
+                 slack_bound_push=1e-3, slack_bound_frac=1e-3, mult_bound_push=1e-3):
+        import torch
+
+        if y is None or z_L is None or z_U is None:
+            raise ValueError("WarmStart needs y, z_L and z_U together")
+        for k, t in (("y", y), ("z_L", z_L), ("z_U", z_U), ("x", x)):
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or t.dtype != torch.float64:
+                raise ValueError(f"WarmStart.{k} must be a float64 tensor")
+            if t.dim() != 2 or t.shape[0] != y.shape[0]:
+                raise ValueError(f"WarmStart.{k} must have shape [B, .] with y's B = {y.shape[0]}, not {tuple(t.shape)}")
+            if t.device != y.device:
+                raise ValueError(f"WarmStart.{k} must be on y's device {y.device}, not {t.device}")
+        if z_L.shape != z_U.shape or (x is not None and x.shape != z_L.shape):
+            raise ValueError("WarmStart: z_L, z_U (and x) must have the same shape [B, n]")
+        if mask is not None:
+            if not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8):
+                raise ValueError("WarmStart.mask must be a bool or uint8 tensor")
+            if tuple(mask.shape) != (y.shape[0],) or mask.device != y.device:
+                raise ValueError(f"WarmStart.mask must have shape ({y.shape[0]},) on {y.device}")
+        self.y, self.z_L, self.z_U, self.x, self.mask = y, z_L, z_U, x, mask
+        self.mu_init, self.bound_push, self.bound_frac = float(mu_init), float(bound_push), float(bound_frac)
+        self.slack_bound_push, self.slack_bound_frac = float(slack_bound_push), float(slack_bound_frac)
+        self.mult_bound_push = float(mult_bound_push)
+        for k in self.PUSHES:
+            if not (getattr(self, k) >= 0.0):
+                raise ValueError(f"WarmStart.{k} must be >= 0")
+
+    def validated(self, batch: int, n: int, m: int, device) -> "WarmStart":
+        """Checked against the solve (ValueError naming the field), tensors contiguous, the mask uint8."""
+        import torch
+
+        for k, cols in (("y", m), ("z_L", n), ("z_U", n), ("x", n)):
+            t = getattr(self, k)
+            if t is None:
+                continue
+            if tuple(t.shape) != (batch, cols):
+                raise ValueError(f"WarmStart.{k} must have shape {(batch, cols)}, not {tuple(t.shape)}")
+            if t.device != device:
+                raise ValueError(f"WarmStart.{k} must be on the solve's device {device}, not {t.device}")
+        out = WarmStart(self.y.contiguous(), self.z_L.contiguous(), self.z_U.contiguous(),
+                        None if self.x is None else self.x.contiguous(),
+                        None if self.mask is None else self.mask.to(torch.uint8).contiguous(),
+                        **{k: getattr(self, k) for k in self.PUSHES})
+        return out
+
+    def c_struct(self) -> "_abi.WarmStart":
+        """The C record over these tensors (which must stay alive while it is in use)."""
+        return _abi.WarmStart(self.y.data_ptr(), self.z_L.data_ptr(), self.z_U.data_ptr(),
+                              None if self.mask is None else self.mask.data_ptr(),
+                              *(getattr(self, k) for k in self.PUSHES))
+
+
 @dataclass
 class BatchSolveResult:
     x: object            # [B, n] final iterates
@@ -208,10 +276,22 @@ class BatchSolveResult:
     w: object = None
     z_L: object = None
     z_U: object = None
+    # the state a later solve warm-starts from (either termination; IPOPT's names): the bound multipliers
+    # over x of the UNSCALED problem [B, n], 0 at fixed / unbounded entries, and the final barrier parameter [B]
+    mult_x_L: object = None
+    mult_x_U: object = None
+    mu: object = None
 
     @property
     def success(self):
         return self.status <= STATUS_ACCEPTABLE
+
+    def warm_start(self, **overrides) -> "WarmStart":
+        """This result as the next solve's WarmStart: its x, y, mult_x_L, mult_x_U, the instances that
+        succeeded (mask = success); overrides: WarmStart's other arguments, e.g. mu_init=1e-4."""
+        kw = dict(x=self.x, mask=self.success)
+        kw.update(overrides)
+        return WarmStart(self.y, self.mult_x_L, self.mult_x_U, **kw)
 
 
 _PIVOT_REL = 2.220446049250313e-16  # DBL_EPSILON: the KKT inertia test's zero-pivot level
@@ -258,10 +338,12 @@ class NativeSolver:
             _abi.lib.cpl_solver_destroy(h)
             self.handle = None
 
-    def solve(self, X0, mass=None, env_tag=None, instance=None, fixed_from_x0=False) -> "BatchSolveResult":
+    def solve(self, X0, mass=None, env_tag=None, instance=None, fixed_from_x0=False,
+              warm_start=None) -> "BatchSolveResult":
         """instance: per-instance wrench / cost references (InstanceData); fixed_from_x0: every variable
         the template fixes (lb == ub) takes instance b's value from X0[b] instead of the template's
-        bound (cpl_solver_solve_inst)."""
+        bound (cpl_solver_solve_inst).  warm_start: a WarmStart (cpl_solver_solve_warm); the start point
+        is still X0."""
         import torch
 
         n, m, _ = self.problem.get_nlp_info()
@@ -286,7 +368,19 @@ class NativeSolver:
         obj, pinf, dinf = (torch.empty(B, dtype=torch.float64, device=dev) for _ in range(3))
         it = ctypes.c_int32()
         ev = ctypes.c_int64()
-        if (instance is not None and instance) or fixed_from_x0:
+        if warm_start is not None:
+            if not isinstance(warm_start, WarmStart):
+                raise ValueError("warm_start must be a WarmStart")
+            ws = warm_start.validated(B, n, m, dev)
+            wcs = ws.c_struct()
+            inst = (instance if instance is not None else InstanceData()).validated(B, len(self.problem.contact_names), dev)
+            cs = inst.c_struct()
+            _abi.check(_abi.lib.cpl_solver_solve_warm(
+                self.handle, _ptr(X0), None if mass is None else _ptr(mass), None if env_tag is None else _ptr(env_tag),
+                ctypes.byref(cs), 1 if fixed_from_x0 else 0, ctypes.byref(wcs), _ptr(x), _ptr(y), _ptr(status),
+                _ptr(iters), _ptr(obj), _ptr(pinf), _ptr(dinf), ctypes.byref(it), ctypes.byref(ev),
+                ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        elif (instance is not None and instance) or fixed_from_x0:
             inst = (instance if instance is not None else InstanceData()).validated(B, len(self.problem.contact_names), dev)
             cs = inst.c_struct()
             _abi.check(_abi.lib.cpl_solver_solve_inst(
@@ -317,6 +411,10 @@ class NativeSolver:
                                objective=obj, primal_inf=pinf, dual_inf=dinf, evaluations=int(ev.value),
                                iterations_run=int(it.value), graph=bool(g.value), compactions=int(nc.value),
                                final_rows=int(rows.value), restorations=resto, fallback=fb.bool(), nan_jacobian=nanj.to(torch.int64))
+        res.mult_x_L, res.mult_x_U = (torch.empty(B, n, dtype=torch.float64, device=dev) for _ in range(2))
+        res.mu = torch.empty(B, dtype=torch.float64, device=dev)
+        _abi.check(_abi.lib.cpl_solver_warm_state(self.handle, _ptr(res.mult_x_L), _ptr(res.mult_x_U), _ptr(res.mu),
+                                                  ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         if self.termination == "ipopt":
             u = [torch.empty(B, dtype=torch.float64, device=dev) for _ in range(3)]
             _abi.check(_abi.lib.cpl_solver_unscaled_errors(self.handle, _ptr(u[0]), _ptr(u[1]), _ptr(u[2]),
@@ -364,7 +462,7 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
                     compl_inf_tol: float = 1e-4, acceptable_dual_inf_tol: float = 1e10,
                     acceptable_constr_viol_tol: float = 1e-2, acceptable_compl_inf_tol: float = 1e-2,
                     acceptable_obj_change_tol: float = 1e20, diverging_iterates_tol: float = 1e20,
-                    max_wall_time: float = 0.0) -> BatchSolveResult:
+                    max_wall_time: float = 0.0, warm_start: Optional[WarmStart] = None) -> BatchSolveResult:
     """Solve B instances of `problem`'s template from the starting points X0 [B, n] (torch float64,
     device tensor), per-instance robot masses `mass` [B] (None: the template's).
 
@@ -424,6 +522,12 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
     floor is min(tol, compl_inf_tol) / 11.  The result's unscaled_* carry the last regular test's measures.
     max_wall_time (seconds, 0: none; either termination): checked once per lock-step iteration; when it
     has passed every still-active instance ends STATUS_TIME_LIMIT with its current iterate.
+    warm_start: a WarmStart (a previous result's warm_start()) — [IPOPT-ext] IPOPT's warm_start_init_point:
+    the warm instances start from X0 pushed into the bounds by warm_start_bound_push / _frac, slacks g_I
+    pushed by the slack constants, y = df y_in / dc, bound multipliers max(mult_bound_push, df z_in) over x
+    and max(mult_bound_push, -/+ y_r) on row r's slack, mu = warm_start.mu_init; no least-squares
+    multipliers.  The other instances (mask False, a non-finite warm value) start cold, bit for bit.
+    The result's mult_x_L / mult_x_U / mu are what the next warm start takes.
     IFOPT_OPTIONS is the set IFOPT's IpoptSolver runs with."""
     if termination not in ("scaled", "ipopt"):
         raise ValueError("termination must be 'scaled' or 'ipopt'")
@@ -463,7 +567,7 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
         if instance is None and evaluator is not None:
             instance = evaluator.instance
         r = ns.solve(X0, mass, None if evaluator is None else evaluator.env_tag, instance=instance,
-                     fixed_from_x0=fixed_from_x0)
+                     fixed_from_x0=fixed_from_x0, warm_start=warm_start)
         if evaluator is not None:
             evaluator.calls += r.evaluations
         return r
@@ -526,11 +630,12 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
     mu_min = min(tol, compl_inf_tol if ipopt_term else COMPL_INF_TOL) / (BARRIER_TOL_FACTOR + 1.0)
     xmask = torch.cat([torch.ones(nf, dtype=torch.bool, device=dev), torch.zeros(nI, dtype=torch.bool, device=dev)])
 
-    def push(v):  # IPOPT bound_push = bound_frac = 1e-2 (absolute and relative to the range)
-        k = 1e-2
+    def push(v, kp=1e-2, kf=1e-2):
+        # IPOPT bound_push = bound_frac = 1e-2 (absolute and relative to the range); a warm start: each
+        # instance's own constants [B, nw] (push_into2)
         rng = torch.where(hasL & hasU, wu0 - wl0, torch.full_like(wl0, float("inf")))
-        pl = torch.minimum(k * torch.clamp(wl0.abs(), min=1.0), k * rng)
-        pu = torch.minimum(k * torch.clamp(wu0.abs(), min=1.0), k * rng)
+        pl = torch.minimum(kp * torch.clamp(wl0.abs(), min=1.0), kf * rng)
+        pu = torch.minimum(kp * torch.clamp(wu0.abs(), min=1.0), kf * rng)
         v = torch.where(hasL, torch.maximum(v, wl0 + pl), v)
         return torch.where(hasU, torch.minimum(v, wu0 - pu), v)
 
@@ -910,11 +1015,43 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
         return ok, ~(is_ftype & armijo)
 
     # ---- starting point: x pushed into its bounds, slacks = g_I(x) pushed into theirs
-    Xs = unpack(push(torch.cat([Xbase[:, free], zeros_I], 1)))
+    # [IPOPT-ext] warm start (k_warm_flag / k_start_x_warm / k_init_state_warm): the instances that start
+    # warm — the mask says so and every warm value the start reads is finite — and their push constants
+    ws = None
+    warm = torch.zeros(B, dtype=torch.bool, device=dev)
+    kp, kf = 1e-2, 1e-2
+    if warm_start is not None:
+        if not isinstance(warm_start, WarmStart):
+            raise ValueError("warm_start must be a WarmStart")
+        ws = warm_start.validated(B, n, m, dev)
+        hLx, hUx = hasL[:nf], hasU[:nf]
+        warm = torch.isfinite(ws.y).all(1) & (torch.isfinite(ws.z_L[:, free]) | ~hLx).all(1) & \
+            (torch.isfinite(ws.z_U[:, free]) | ~hUx).all(1)
+        if ws.mask is not None:
+            warm = warm & (ws.mask != 0)
+        xcol = torch.cat([torch.ones(nf, dtype=torch.bool, device=dev), torch.zeros(nI, dtype=torch.bool, device=dev)])
+
+        def consts(vx, vs):
+            c = torch.where(xcol, torch.full_like(wl0, vx), torch.full_like(wl0, vs))
+            return torch.where(warm[:, None], c, torch.full_like(wl0, 1e-2))
+
+        kp, kf = consts(ws.bound_push, ws.slack_bound_push), consts(ws.bound_frac, ws.slack_bound_frac)
+    Xs = unpack(push(torch.cat([Xbase[:, free], zeros_I], 1), kp, kf))
     cur0 = evaluate(Xs)
-    w0 = push(torch.cat([Xs[:, free], cur0["g"][:, I]], 1))
+    w0 = push(torch.cat([Xs[:, free], cur0["g"][:, I]], 1), kp, kf)
     zL0 = torch.where(hasL, torch.ones_like(w0), torch.zeros_like(w0))
     zU0 = torch.where(hasU, torch.ones_like(w0), torch.zeros_like(w0))
+    mu0 = torch.full((B,), mu_init, dtype=dt, device=dev)
+    if ws is not None:
+        # y = df y_in / dc; z over x = max(mult_bound_push, df z_in); row r's slack, whose stationarity row
+        # is -y_r - zL + zU = 0 (A's slack column is -1): zL = max(push, -y_r), zU = max(push, y_r)
+        yw = (df[:, None] * ws.y) / dc
+        mp = torch.full_like(w0, ws.mult_bound_push)
+        zLw = torch.maximum(mp, torch.cat([df[:, None] * ws.z_L[:, free], -yw[:, I]], 1))
+        zUw = torch.maximum(mp, torch.cat([df[:, None] * ws.z_U[:, free], yw[:, I]], 1))
+        zL0 = torch.where(warm[:, None], torch.where(hasL, zLw, torch.zeros_like(w0)), zL0)
+        zU0 = torch.where(warm[:, None], torch.where(hasU, zUw, torch.zeros_like(w0)), zU0)
+        mu0 = torch.where(warm, torch.full_like(mu0, ws.mu_init if ws.mu_init > 0.0 else mu_init), mu0)
     theta0 = cons(cur0["g"], w0[:, nf:]).abs().sum(1)
     theta_max = 1e4 * theta0.clamp(min=1.0)
     theta_min = 1e-4 * theta0.clamp(min=1.0)
@@ -924,6 +1061,8 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
     L0, info0 = torch.linalg.cholesky_ex(A0 @ A0.transpose(1, 2) + 1e-12 * eye_m)
     y0 = -torch.cholesky_solve(A0 @ (gw0 - zL0 + zU0).unsqueeze(2), L0).squeeze(2)
     y0 = torch.where(((y0.abs().amax(1) <= 1e3) & (info0 == 0)).unsqueeze(1), y0, torch.zeros_like(y0))
+    if ws is not None:  # (the engine launches the least-squares solve only when an instance starts cold)
+        y0 = torch.where(warm[:, None], yw, y0)
 
     zB = lambda: zeros_B.clone()  # noqa: E731
     zBm = lambda: torch.zeros(B, m, dtype=dt, device=dev)  # noqa: E731
@@ -932,7 +1071,7 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
     # persistent state: the iteration reads these and writes them back in place
     S = {
         "w": w0.contiguous(), "y": y0.contiguous(), "zL": zL0, "zU": zU0,
-        "mu": torch.full((B,), mu_init, dtype=dt, device=dev),
+        "mu": mu0,
         "active": torch.ones(B, dtype=torch.bool, device=dev),
         "status": torch.full((B,), STATUS_MAX_ITER, dtype=torch.int64, device=dev),
         "iters": torch.zeros(B, dtype=torch.int64, device=dev),
@@ -1691,6 +1830,11 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
                            objective=fin["f"].clone(), primal_inf=viol, dual_inf=S["d_inf"], evaluations=n_eval,
                            iterations_run=it_run, graph=False)
     res.restorations = S["n_resto"]
+    # the state to warm-start from: the unscaled problem's bound multipliers over x (z / df), the final mu
+    res.mult_x_L, res.mult_x_U = (torch.zeros(B, n, dtype=dt, device=dev) for _ in range(2))
+    res.mult_x_L[:, free] = S["zL"][:, :nf] / df[:, None] if scaled else S["zL"][:, :nf]
+    res.mult_x_U[:, free] = S["zU"][:, :nf] / df[:, None] if scaled else S["zU"][:, :nf]
+    res.mu = S["mu"].clone()
     res.nan_jacobian = nan_jacobian
     res.fallback = fallback
     if ipopt_term:

@@ -99,6 +99,17 @@ __device__ __forceinline__ double push_into(double v, bool hl, bool hu, double l
   return v;
 }
 
+// push_into with its two constants apart (kp absolute, kf relative to the range): a warm start's
+// warm_start_bound_push / _frac; kp = kf = 1e-2 is push_into, operation for operation
+__device__ __forceinline__ double push_into2(double v, bool hl, bool hu, double lo, double up, double kp, double kf) {
+  const double rng = (hl && hu) ? up - lo : INFINITY;
+  const double pl = fmin(kp * fmax(fabs(lo), 1.0), kf * rng);
+  const double pu = fmin(kp * fmax(fabs(up), 1.0), kf * rng);
+  if (hl) v = fmax(v, lo + pl);
+  if (hu) v = fmin(v, up - pu);
+  return v;
+}
+
 // constraint residual of row r: g - g_l (equality), g - s (inequality, slack s)
 __device__ __forceinline__ double cons_row(const double* g, const double* w, int nf, int r, const int32_t* row_slack,
                                            const double* gl) {
@@ -293,6 +304,172 @@ __global__ __launch_bounds__(256) void k_y0(int64_t B, int m, const double* __re
   mx = wave_max(mx);
   const bool keep = mx <= 1e3 && info[b] == 0;
   for (int r = lane; r < m; r += 64) y[b * m + r] = keep ? dy[b * m + r] : 0.0;
+}
+
+// ---- warm start [IPOPT-ext: warm_start_init_point, WarmStartIterateInitializer restated in this
+// engine's sign convention; include/cpl_mi355x.h cpl_warm_start, batch_ipm.py WarmStart] ----
+struct WarmArgs {
+  const double *y_in = nullptr, *zL_in = nullptr, *zU_in = nullptr;  // the caller's [B, m], [B, n], [B, n] (unscaled)
+  const uint8_t* mask = nullptr;                                     // the caller's [B] or nullptr
+  uint8_t *flag = nullptr, *any_cold = nullptr;                      // [B]: 1 = starts warm; [0]: a cold instance exists
+  const double *df = nullptr, *dc = nullptr;                         // nlp_scaling's factors (nullptr: the option is off)
+  double mu = 0.0, bound_push = 0.0, bound_frac = 0.0, slack_push = 0.0, slack_frac = 0.0, mult_push = 0.0;
+};
+
+// which instances start warm (one wave each): the mask says so and every warm value the start reads
+// is finite — y, and z_L / z_U at the free variables that have the bound
+__global__ __launch_bounds__(256) void k_warm_flag(int64_t B, int n, int m, int nf, const int32_t* __restrict__ free_idx,
+                                                   const uint8_t* __restrict__ hasL, const uint8_t* __restrict__ hasU,
+                                                   const WarmArgs wa) {
+  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const int lane = threadIdx.x & 63;
+  bool bad = false;
+  for (int r = lane; r < m; r += 64) bad |= !(fabs(wa.y_in[b * m + r]) < INFINITY);
+  for (int k = lane; k < nf; k += 64) {
+    const int64_t e = b * n + free_idx[k];
+    if (hasL[k]) bad |= !(fabs(wa.zL_in[e]) < INFINITY);
+    if (hasU[k]) bad |= !(fabs(wa.zU_in[e]) < INFINITY);
+  }
+  const bool warm = __ballot(bad) == 0 && (!wa.mask || wa.mask[b] != 0);
+  if (lane == 0) {
+    wa.flag[b] = warm ? 1 : 0;
+    if (!warm) wa.any_cold[0] = 1;
+  }
+}
+
+// k_start_x with each instance's own constants: a warm instance's warm_start_bound_push / _frac
+__global__ void k_start_x_warm(int64_t total, int n, const int32_t* __restrict__ freepos, const double* __restrict__ Xbase,
+                               const uint8_t* __restrict__ hasL, const uint8_t* __restrict__ hasU,
+                               const double* __restrict__ wl0, const double* __restrict__ wu0,
+                               const uint8_t* __restrict__ flag, double kp, double kf, double* __restrict__ X) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const int j = (int)(e % n);
+  const int k = freepos[j];
+  const bool warm = flag[e / n];
+  X[e] = k >= 0 ? push_into2(Xbase[e], hasL[k], hasU[k], wl0[k], wu0[k], warm ? kp : 1e-2, warm ? kf : 1e-2) : Xbase[e];
+}
+
+// k_init_state for a batch of warm and cold instances (one wave each).  A cold one (flag 0) gets
+// k_init_state's start, operation for operation; its y follows from the least-squares solve (k_y0_warm).
+// A warm one: w pushed by its own constants, y = df y_in / dc, z over x = max(mult_push, df z_in) where
+// the bound exists, z of row r's slack from that slack's stationarity row -y_r - zL + zU = 0
+// (zL = max(mult_push, -y_r), zU = max(mult_push, y_r)), mu = wa.mu.
+__global__ __launch_bounds__(256) void k_init_state_warm(int64_t B, const InitStateArgs a, const WarmArgs wa) {
+  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const int lane = threadIdx.x & 63;
+  const int n = a.n, m = a.m, nf = a.nf, nw = a.nw;
+  const auto [hasL, hasU, wl0, wu0] = a.bd;
+  const auto [w, y, zL, zU] = a.it;
+  const bool warm = wa.flag[b];
+  const double kpx = warm ? wa.bound_push : 1e-2, kfx = warm ? wa.bound_frac : 1e-2;
+  const double kps = warm ? wa.slack_push : 1e-2, kfs = warm ? wa.slack_frac : 1e-2;
+  const double d = wa.df ? wa.df[b] : 1.0;
+  // the scaled problem's multiplier of row r
+  auto y_of = [&](int r) {
+    const double yi = wa.y_in[b * m + r];
+    return wa.df ? (d * yi) / wa.dc[b * m + r] : yi;
+  };
+  double* wb = w + b * nw;
+  for (int k = lane; k < nw; k += 64) {
+    const double v = k < nf ? a.X[b * n + a.free_idx[k]] : a.g[b * m + a.ineq_row[k - nf]];
+    const bool hl = hasL[k], hu = hasU[k];
+    wb[k] = push_into2(v, hl, hu, wl0[k], wu0[k], k < nf ? kpx : kps, k < nf ? kfx : kfs);
+    double zl = hl ? 1.0 : 0.0, zu = hu ? 1.0 : 0.0;
+    if (warm) {
+      if (k < nf) {
+        const int64_t e = b * n + a.free_idx[k];
+        zl = hl ? fmax(wa.mult_push, d * wa.zL_in[e]) : 0.0;
+        zu = hu ? fmax(wa.mult_push, d * wa.zU_in[e]) : 0.0;
+      } else {
+        const double yr = y_of(a.ineq_row[k - nf]);
+        zl = hl ? fmax(wa.mult_push, -yr) : 0.0;
+        zu = hu ? fmax(wa.mult_push, yr) : 0.0;
+      }
+    }
+    zL[b * nw + k] = zl;
+    zU[b * nw + k] = zu;
+    const double gw = k < nf ? a.grad[b * n + a.free_idx[k]] : 0.0;
+    a.r1[b * nw + k] = -((gw - zl) + zu);
+    for (int j = 0; j < nw; ++j) a.M[(b * nw + k) * nw + j] = j == k ? 1.0 : 0.0;
+  }
+  double th = 0.0;
+  for (int r = lane; r < m; r += 64) {  // (the slack recomputed: this lane did not write it)
+    const int sl = a.row_slack[r];
+    const double gv = a.g[b * m + r];
+    const double c =
+        sl >= 0 ? gv - push_into2(gv, hasL[nf + sl], hasU[nf + sl], wl0[nf + sl], wu0[nf + sl], kps, kfs) : gv - a.gl[r];
+    th += fabs(c);
+    a.r2[b * m + r] = 0.0;
+    if (warm) y[b * m + r] = y_of(r);
+  }
+  th = wave_sum(th);
+  for (int k = lane; k < FMAX; k += 64) {
+    a.filt_t[b * FMAX + k] = INFINITY;
+    a.filt_p[b * FMAX + k] = INFINITY;
+  }
+  if (lane == 0) {
+    a.theta_max[b] = 1e4 * fmax(th, 1.0);
+    a.theta_min[b] = 1e-4 * fmax(th, 1.0);
+    a.mu[b] = warm ? wa.mu : a.mu_init;
+    a.active[b] = 1;
+    a.status[b] = CPL_SOLVE_MAX_ITER;
+    a.iters[b] = 0;
+    a.acc[b] = 0;
+    a.fcount[b] = 0;
+    a.dwl[b] = 0.0;
+    a.d_inf[b] = 0.0;
+    a.lm_cnt[b] = 0;
+    a.lm_skip[b] = 0;
+  }
+}
+
+// k_y0 for the cold instances of a warm batch (a warm one keeps the y k_init_state_warm gave it)
+__global__ __launch_bounds__(256) void k_y0_warm(int64_t B, int m, const double* __restrict__ dy,
+                                                 const int32_t* __restrict__ info, const uint8_t* __restrict__ flag,
+                                                 double* __restrict__ y) {
+  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
+  if (b >= B || flag[b]) return;
+  const int lane = threadIdx.x & 63;
+  double mx = 0.0;
+  for (int r = lane; r < m; r += 64) mx = fmax(mx, fabs(dy[b * m + r]));
+  mx = wave_max(mx);
+  const bool keep = mx <= 1e3 && info[b] == 0;
+  for (int r = lane; r < m; r += 64) y[b * m + r] = keep ? dy[b * m + r] : 0.0;
+}
+
+// the state a later solve warm-starts from, of every row that leaves the batch (finished, or at the
+// end: all rows; one wave each), at the instance's own position: the bound multipliers over x of the
+// unscaled problem, z / df (df = nullptr: unscaled), 0 at fixed entries (and where there is no bound: z
+// is 0 there), and the barrier parameter
+__global__ __launch_bounds__(256) void k_scatter_warm(int64_t rows, int n, int nw, bool finished_only,
+                                                      const int32_t* __restrict__ orig, const uint8_t* __restrict__ active,
+                                                      const int32_t* __restrict__ freepos, const double* __restrict__ zL,
+                                                      const double* __restrict__ zU, const double* __restrict__ df,
+                                                      const double* __restrict__ mu, double* __restrict__ fzLx,
+                                                      double* __restrict__ fzUx, double* __restrict__ fmu) {
+  const int64_t r = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const int32_t o = orig[r];
+  if (o < 0 || (finished_only && active[r])) return;
+  const int lane = threadIdx.x & 63;
+  for (int j = lane; j < n; j += 64) {
+    const int k = freepos[j];
+    double zl = 0.0, zu = 0.0;
+    if (k >= 0) {
+      zl = zL[r * nw + k];
+      zu = zU[r * nw + k];
+      if (df) {
+        zl = zl / df[r];
+        zu = zu / df[r];
+      }
+    }
+    fzLx[(int64_t)o * n + j] = zl;
+    fzUx[(int64_t)o * n + j] = zu;
+  }
+  if (lane == 0) fmu[o] = mu[r];
 }
 
 // gradient over w (gw = [grad f over the free variables, 0]) and the constraint residual c
@@ -2320,6 +2497,11 @@ struct cpl_solver {
   uint8_t* sc_any;
   bool scaled = false;
   bool sc_fused = true;  // the evaluations apply the scaling themselves (until a path says unsupported)
+  // warm start (cpl_solver_solve_warm): which instances start warm [B] (read before the first iteration
+  // only), the "a cold instance exists" byte; and, after every solve, the state to warm-start from by
+  // original instance (cpl_solver_warm_state): unscaled bound multipliers over x [B, n], final mu [B]
+  uint8_t *warm_flag, *warm_any;
+  double *wzL, *wzU, *wmu;
 };
 
 namespace cpl {
@@ -3029,6 +3211,15 @@ int32_t read_flags(cpl_solver* S) {
 // rows move to the front (every buffer carved as `state` gathered: cpl::Carver), the batch shrinks to
 // Bn rows (the rows past `count` padded inactive), so later iterations cost what their active
 // instances do.
+// the warm-start state of the rows leaving the batch (finished ones at a compaction, every row at the end)
+int32_t scatter_warm(cpl_solver* S, bool finished_only) {
+  hipLaunchKernelGGL(k_scatter_warm, dim3(blocks_for(S->Bcur)), dim3(256), 0, S->stream, S->Bcur, S->n, S->nw,
+                     finished_only, S->orig, S->active, S->freepos, S->zL, S->zU, S->scaled ? S->df : nullptr, S->mu,
+                     S->wzL, S->wzU, S->wmu);
+  LAUNCHED("k_scatter_warm");
+  return CPL_OK;
+}
+
 int32_t compact(cpl_solver* S, int64_t count, int64_t Bn) {
   hipStream_t st = S->stream;
   const int64_t Bc = S->Bcur;
@@ -3046,6 +3237,7 @@ int32_t compact(cpl_solver* S, int64_t count, int64_t Bn) {
                        S->fu_compl, S->fzL, S->fzU);
     LAUNCHED("k_scatter_term");
   }
+  CK(scatter_warm(S, true));
   hipLaunchKernelGGL(k_positions, dim3(1), dim3(1024), 0, st, Bc, S->active, S->pos);
   LAUNCHED("k_positions");
   // every state buffer whose condition holds, gathered through the scratch and copied back
@@ -3449,6 +3641,8 @@ int32_t cpl_solver_create(const cpl_problem_desc* d, int64_t batch, const cpl_so
   S->u_dinf = c.state<double>(tw, ALWAYS); S->u_cviol = c.state<double>(tw, ALWAYS); S->u_compl = c.state<double>(tw, ALWAYS);
   S->fu_dinf = c.full<double>(tw); S->fu_cviol = c.full<double>(tw); S->fu_compl = c.full<double>(tw);
   S->fzL = c.full<double>(tw * nw); S->fzU = c.full<double>(tw * nw);
+  S->warm_flag = c.temp<uint8_t>(1); S->warm_any = c.fixed<uint8_t>(4);
+  S->wzL = c.full<double>(n); S->wzU = c.full<double>(n); S->wmu = c.full<double>(1);
   // last: the gather scratch holds the widest state row of every instance, in 8-byte words
   S->scratch_words = (int64_t)((c.row_bytes + 7) / 8);
   S->scratch = c.temp<uint64_t>((size_t)S->scratch_words);
@@ -3497,6 +3691,37 @@ int32_t cpl_solver_solve_inst(cpl_solver* S, const double* d_x0, const double* d
                               const cpl_instance_data* inst, int32_t fixed_from_x0, double* d_x, double* d_y,
                               int32_t* d_status, int32_t* d_iters, double* d_obj, double* d_primal_inf,
                               double* d_dual_inf, int32_t* iterations_run, int64_t* evaluations, void* stream) {
+  return cpl_solver_solve_warm(S, d_x0, d_mass, d_env_tag, inst, fixed_from_x0, nullptr, d_x, d_y, d_status, d_iters,
+                               d_obj, d_primal_inf, d_dual_inf, iterations_run, evaluations, stream);
+}
+
+void cpl_warm_start_default(cpl_warm_start* w) {
+  if (!w) return;
+  std::memset(w, 0, sizeof(*w));
+  w->mu_init = 0.0;  // the solver's opt.mu_init
+  w->bound_push = w->bound_frac = 1e-3;              // IPOPT warm_start_bound_push / _frac
+  w->slack_bound_push = w->slack_bound_frac = 1e-3;  // warm_start_slack_bound_push / _frac
+  w->mult_bound_push = 1e-3;                         // warm_start_mult_bound_push
+}
+
+int64_t cpl_warm_start_sizeof(void) { return (int64_t)sizeof(cpl_warm_start); }
+
+int32_t cpl_solver_warm_state(const cpl_solver* S, double* d_zL, double* d_zU, double* d_mu, void* stream) {
+  if (!S) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_warm_state: null solver");
+  const struct { double* dst; const double* src; size_t width; } outs[] = {
+      {d_zL, S->wzL, (size_t)S->n}, {d_zU, S->wzU, (size_t)S->n}, {d_mu, S->wmu, 1}};
+  for (const auto& o : outs)
+    if (o.dst)
+      HK(hipMemcpyAsync(o.dst, o.src, 8 * (size_t)S->B * o.width, hipMemcpyDeviceToDevice, (hipStream_t)stream),
+         "hipMemcpyAsync warm state");
+  return CPL_OK;
+}
+
+int32_t cpl_solver_solve_warm(cpl_solver* S, const double* d_x0, const double* d_mass, const uint8_t* d_env_tag,
+                              const cpl_instance_data* inst, int32_t fixed_from_x0, const cpl_warm_start* warm,
+                              double* d_x, double* d_y, int32_t* d_status, int32_t* d_iters, double* d_obj,
+                              double* d_primal_inf, double* d_dual_inf, int32_t* iterations_run, int64_t* evaluations,
+                              void* stream) {
   if (!S || !d_x0) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_solve: missing solver or x0");
   if (S->desc.env_kind == CPL_ENV_MIXED && !d_env_tag)
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_solve: mixed batches need the env tags");
@@ -3505,6 +3730,15 @@ int32_t cpl_solver_solve_inst(cpl_solver* S, const double* d_x0, const double* d
     return fail(CPL_ERR_UNSUPPORTED,
                 "cpl_solver_solve_inst: instance data needs a Hessian that is not central differences: create the "
                 "solver with CPL_HESSIAN_ANALYTIC or CPL_HESSIAN_LIMITED_MEMORY");
+  // a warm start: all three multiplier arrays, or none (then this is cpl_solver_solve_inst)
+  const bool is_warm = warm && (warm->d_y || warm->d_zL || warm->d_zU);
+  if (is_warm) {
+    if (!warm->d_y || !warm->d_zL || !warm->d_zU)
+      return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_solve_warm: a warm start needs d_y, d_zL and d_zU together");
+    for (double v : {warm->mu_init, warm->bound_push, warm->bound_frac, warm->slack_bound_push, warm->slack_bound_frac,
+                     warm->mult_bound_push})
+      if (!(v >= 0.0)) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_solve_warm: a push or mu_init is negative or NaN");
+  }
   const int64_t B = S->B;
   const int n = S->n, m = S->m, nf = S->nf, nw = S->nw;
   hipStream_t st = S->stream;
@@ -3576,21 +3810,54 @@ int32_t cpl_solver_solve_inst(cpl_solver* S, const double* d_x0, const double* d
     HK(hipStreamSynchronize(st), "hipStreamSynchronize");
     S->scaled = S->h_flag[0] != 0;
   }
-  hipLaunchKernelGGL(k_start_x, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, n, S->freepos, S->Xbase, S->hasL,
-                     S->hasU, S->wl0, S->wu0, S->X);
-  LAUNCHED("k_start_x");
+  WarmArgs wa;
+  bool any_cold = true;  // the batch holds an instance that needs the least-squares multipliers
+  if (is_warm) {
+    wa.y_in = warm->d_y; wa.zL_in = warm->d_zL; wa.zU_in = warm->d_zU; wa.mask = warm->d_mask;
+    wa.flag = S->warm_flag; wa.any_cold = S->warm_any;
+    wa.df = S->opt.nlp_scaling ? S->df : nullptr; wa.dc = S->opt.nlp_scaling ? S->dc : nullptr;
+    wa.mu = warm->mu_init > 0.0 ? warm->mu_init : S->opt.mu_init;
+    wa.bound_push = warm->bound_push; wa.bound_frac = warm->bound_frac;
+    wa.slack_push = warm->slack_bound_push; wa.slack_frac = warm->slack_bound_frac; wa.mult_push = warm->mult_bound_push;
+    // which instances start warm, and whether any starts cold (read on the host: it decides the launches below)
+    HK(hipMemsetAsync(S->warm_any, 0, 4, st), "hipMemsetAsync");
+    hipLaunchKernelGGL(k_warm_flag, dim3(blocks_for(B)), dim3(256), 0, st, B, n, m, nf, S->free32, S->hasL, S->hasU, wa);
+    LAUNCHED("k_warm_flag");
+    HK(hipMemcpyAsync(S->h_flag, S->warm_any, 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+    HK(hipStreamSynchronize(st), "hipStreamSynchronize");
+    any_cold = S->h_flag[0] != 0;
+    hipLaunchKernelGGL(k_start_x_warm, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, n, S->freepos, S->Xbase,
+                       S->hasL, S->hasU, S->wl0, S->wu0, S->warm_flag, wa.bound_push, wa.bound_frac, S->X);
+    LAUNCHED("k_start_x_warm");
+  } else {
+    hipLaunchKernelGGL(k_start_x, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, n, S->freepos, S->Xbase, S->hasL,
+                       S->hasU, S->wl0, S->wu0, S->X);
+    LAUNCHED("k_start_x");
+  }
   CK(eval_full(S, S->X, S->f, S->grad, S->g, S->J));
   ++evals;
-  hipLaunchKernelGGL(k_init_state, dim3(blocks_for(B)), dim3(256), 0, st, B, init_state_args(S));
-  LAUNCHED("k_init_state");
-  CK(cpl_ipm_dense_a(B, m, nw, nf, S->nnz_rec, S->amap, S->row_slack, S->J, S->A, nullptr, st));
-  CK(cpl_kkt_solve(0, B, nw, m, S->M, S->A, S->r1, S->r2, S->mu, S->zeros_B, nullptr, S->dw, S->dy, S->delta_w,
-                   S->delta_c, S->info, S->ws, st));
-  if (S->jreg)
-    CK(kkt_aug_solve(0, B, nw, m, S->M, S->A, S->r1, S->r2, S->mu, S->zeros_B, nullptr, S->dw, S->dy, S->delta_w,
-                     S->delta_c, S->info, S->ws_aug, st));
-  hipLaunchKernelGGL(k_y0, dim3(blocks_for(B)), dim3(256), 0, st, B, m, S->dy, S->info, S->y);
-  LAUNCHED("k_y0");
+  if (is_warm) {
+    hipLaunchKernelGGL(k_init_state_warm, dim3(blocks_for(B)), dim3(256), 0, st, B, init_state_args(S), wa);
+    LAUNCHED("k_init_state_warm");
+  } else {
+    hipLaunchKernelGGL(k_init_state, dim3(blocks_for(B)), dim3(256), 0, st, B, init_state_args(S));
+    LAUNCHED("k_init_state");
+  }
+  if (any_cold) {  // (a batch of warm instances only: no least-squares solve)
+    CK(cpl_ipm_dense_a(B, m, nw, nf, S->nnz_rec, S->amap, S->row_slack, S->J, S->A, nullptr, st));
+    CK(cpl_kkt_solve(0, B, nw, m, S->M, S->A, S->r1, S->r2, S->mu, S->zeros_B, nullptr, S->dw, S->dy, S->delta_w,
+                     S->delta_c, S->info, S->ws, st));
+    if (S->jreg)
+      CK(kkt_aug_solve(0, B, nw, m, S->M, S->A, S->r1, S->r2, S->mu, S->zeros_B, nullptr, S->dw, S->dy, S->delta_w,
+                       S->delta_c, S->info, S->ws_aug, st));
+    if (is_warm) {
+      hipLaunchKernelGGL(k_y0_warm, dim3(blocks_for(B)), dim3(256), 0, st, B, m, S->dy, S->info, S->warm_flag, S->y);
+      LAUNCHED("k_y0_warm");
+    } else {
+      hipLaunchKernelGGL(k_y0, dim3(blocks_for(B)), dim3(256), 0, st, B, m, S->dy, S->info, S->y);
+      LAUNCHED("k_y0");
+    }
+  }
   if (S->bfgs) {  // model initialised to init_val I (IPOPT's limited_memory_init_val = 1)
     hipLaunchKernelGGL(k_lm_init, dim3(blocks_elems(B)), dim3(256), 0, st, B, nf, S->Hq);
     LAUNCHED("k_lm_init");
@@ -3672,6 +3939,7 @@ int32_t cpl_solver_solve_inst(cpl_solver* S, const double* d_x0, const double* d
   // every row still in the batch to its instance's place in the full-batch results
   hipLaunchKernelGGL(k_scatter_final, dim3(blocks_for(Bc)), dim3(256), 0, st, Bc, leave);
   LAUNCHED("k_scatter_final");
+  CK(scatter_warm(S, false));
   // IPOPT honor_original_bounds: the final point projected into the original bounds, re-evaluated
   double* Xf = d_x ? d_x : S->Xn;
   // (fixed_from_x0: the projection skips the fixed entries — the template's bound is not the instance's value)

@@ -811,6 +811,49 @@ int32_t cpl_solver_unscaled_errors(const cpl_solver* s, double* d_dual_inf, doub
  * recomputed from the callbacks (any may be NULL); CPL_ERR_UNSUPPORTED after a CPL_TERM_SCALED solve */
 int32_t cpl_solver_final_iterate(const cpl_solver* s, double* d_w, double* d_zL, double* d_zU, void* stream);
 
+/*
+ * Warm start [IPOPT-ext: warm_start_init_point and its warm_start_* options, restated from IPOPT's
+ * published semantics (WarmStartIterateInitializer) in this engine's sign convention]: a solve that starts
+ * from a previous solve's multipliers instead of bound multipliers 1 and the least-squares y.
+ * Per warm instance (w = [x_free, s], A = [J_free | -P]):
+ *   - the scaling factors df, dc and the NaN-Jacobian count come from the evaluation at x0, as always;
+ *   - the free variables are pushed into their bounds by min(bound_push max(|bound|, 1), bound_frac range)
+ *     (a cold start: both 1e-2), the slacks are g_I there, pushed by the two slack constants;
+ *   - y = df d_y / dc (nlp_scaling off: d_y); no least-squares solve;
+ *   - a free variable's z_L = max(mult_bound_push, df d_zL) where it has a lower bound, else 0 (z_U likewise);
+ *   - the slack of inequality row r (its stationarity row is -y_r - z_L + z_U = 0):
+ *     z_L = max(mult_bound_push, -y_r), z_U = max(mult_bound_push, y_r), 0 without that bound;
+ *   - mu = mu_init here, or cpl_solve_options.mu_init when 0.  Do not pass a converged solve's final mu:
+ *     the monotone barrier update cannot raise mu again (DESIGN.md §5 "Warm start").
+ * An instance starts cold — the start of cpl_solver_solve_inst, bit for bit — when d_mask[b] == 0 or when
+ * any of its d_y, or of its d_zL / d_zU at a free variable with that bound, is not finite.  The
+ * least-squares multiplier solve is launched only when the batch holds a cold instance.
+ */
+typedef struct cpl_warm_start {
+  const double* d_y;     /* [batch, m]  constraint multipliers of the UNSCALED problem, as cpl_solver_solve returns d_y */
+  const double* d_zL;    /* [batch, n]  lower-bound multipliers over x, unscaled; entries of fixed / unbounded variables are ignored */
+  const double* d_zU;    /* [batch, n]  upper-bound multipliers */
+  const uint8_t* d_mask; /* [batch] or NULL (all): 0 = this instance starts cold */
+  double mu_init;        /* barrier parameter of the warm instances; 0 = the solver's opt.mu_init (IPOPT's behaviour) */
+  double bound_push, bound_frac;             /* 1e-3, 1e-3  (warm_start_bound_push / _frac) */
+  double slack_bound_push, slack_bound_frac; /* 1e-3, 1e-3 */
+  double mult_bound_push;                    /* 1e-3 */
+} cpl_warm_start;
+void cpl_warm_start_default(cpl_warm_start* w); /* pointers NULL, mu_init 0, the five pushes 1e-3 */
+int64_t cpl_warm_start_sizeof(void);
+/* cpl_solver_solve_inst from a warm start.  warm == NULL, or d_y, d_zL and d_zU all NULL: exactly
+ * cpl_solver_solve_inst (the same launches, the same bits).  Some but not all of the three given, or a
+ * negative or NaN push or mu_init: CPL_ERR_INVALID_ARGUMENT before any launch. */
+int32_t cpl_solver_solve_warm(cpl_solver* s, const double* d_x0, const double* d_mass, const uint8_t* d_env_tag,
+                              const cpl_instance_data* inst, int32_t fixed_from_x0, const cpl_warm_start* warm,
+                              double* d_x, double* d_y, int32_t* d_status, int32_t* d_iters, double* d_obj,
+                              double* d_primal_inf, double* d_dual_inf, int32_t* iterations_run, int64_t* evaluations,
+                              void* stream);
+/* the last solve's state to warm-start from, in the instances' own order, after ANY solve (either
+ * termination): the bound multipliers over x of the UNSCALED problem (z / df) [batch, n], 0 at fixed /
+ * unbounded entries, and the final barrier parameter [batch] (any may be NULL) */
+int32_t cpl_solver_warm_state(const cpl_solver* s, double* d_zL, double* d_zU, double* d_mu, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
