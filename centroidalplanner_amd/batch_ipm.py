@@ -632,7 +632,7 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
 
     def push(v, kp=1e-2, kf=1e-2):
         # IPOPT bound_push = bound_frac = 1e-2 (absolute and relative to the range); a warm start: each
-        # instance's own constants [B, nw] (push_into2)
+        # instance's own constants [B, nw] (push_into's kp, kf)
         rng = torch.where(hasL & hasU, wu0 - wl0, torch.full_like(wl0, float("inf")))
         pl = torch.minimum(kp * torch.clamp(wl0.abs(), min=1.0), kf * rng)
         pu = torch.minimum(kp * torch.clamp(wu0.abs(), min=1.0), kf * rng)
@@ -1015,7 +1015,7 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
         return ok, ~(is_ftype & armijo)
 
     # ---- starting point: x pushed into its bounds, slacks = g_I(x) pushed into theirs
-    # [IPOPT-ext] warm start (k_warm_flag / k_start_x_warm / k_init_state_warm): the instances that start
+    # [IPOPT-ext] warm start (k_warm_flag / k_start_x<true> / k_init_state<true>): the instances that start
     # warm — the mask says so and every warm value the start reads is finite — and their push constants
     ws = None
     warm = torch.zeros(B, dtype=torch.bool, device=dev)

@@ -19,7 +19,9 @@ LIB = os.path.join(HERE, "libcpl_mi355x.so")
 
 SOURCES = ["cpl_host.cpp", "cpl_kernels.hip", "cpl_kkt.hip", "cpl_ipm.hip", "cpl_solver.hip", "cpl_check.hip"]
 HEADERS = ["cpl_layout.hpp", "cpl_status.hpp", "cpl_wave.hpp", "cpl_accept.hpp", "cpl_engine.hpp", "cpl_kkt_block.hpp",
-           "cpl_kkt_qd.hpp", "cpl_kkt_wave.hpp"]
+           "cpl_kkt_qd.hpp", "cpl_kkt_wave.hpp", "cpl_solver_common.hpp", "cpl_solver_start.hpp",
+           "cpl_solver_search.hpp", "cpl_solver_lbfgs.hpp", "cpl_solver_resto.hpp", "cpl_solver_batch.hpp",
+           "cpl_solver_state.hpp"]
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950",

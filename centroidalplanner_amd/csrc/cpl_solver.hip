@@ -1,20 +1,42 @@
-// cpl_solver.hip — the native batched solve engine (C-ABI cpl_solver_*, include/cpl_mi355x.h).
+// cpl_solver.hip — the host side of the native batched solve engine (C-ABI cpl_solver_*,
+// include/cpl_mi355x.h) and the one translation unit its kernels are compiled in.
 //
-// Many concurrent CentroidalPlanner solves in lock-step on one GPU: IPOPT's primal-dual
-// interior-point method (Waechter & Biegler 2006) as restated in centroidalplanner_amd/batch_ipm.py
-// — whose host path (CPU tensors, the oracle's callbacks) is the checker of this engine — with every
-// per-instance quantity a row of a device buffer:
-//   * callbacks: cpl_eval_batch(_ex) (values-only Jacobian records), the analytic Lagrangian Hessian
-//     (cpl_lagrangian_hessian; cpl_lagrangian_hessian_ex under CPL_HESSIAN_ANALYTIC, every
-//     environment kind) or central differences (cpl_ipm_fd_points + cpl_eval_lagrangian_grad
-//     + cpl_ipm_fd_hessian_raw), or IPOPT's limited-memory BFGS model (6 pairs, scalar1; IFOPT's
-//     IpoptSolver default, the reference's configuration, src/CentroidalPlanner.cpp:22-29);
-//   * per-instance iteration work: cpl_ipm_optimality / newton_setup / post_step / trial_point /
-//     judge_take / accept / max_step / dense_a / masked_rows, the Newton step cpl_kkt_solve;
-//   * the glue between them (the line-search state, second-order corrections, the feasibility step
-//     standing in for the restoration phase, L-BFGS) in the small kernels below — no framework ops.
-// One iteration (fixed trip counts, masked updates, no host synchronisation) is captured once as a
-// HIP graph and replayed; the host reads an "any instance active" byte one iteration behind.
+// Many concurrent CentroidalPlanner solves in lock-step on one GPU: IPOPT's primal-dual interior-point
+// method (Waechter & Biegler 2006) as restated in centroidalplanner_amd/batch_ipm.py — whose host path
+// (CPU tensors, the oracle's callbacks) is the checker of this engine — with every per-instance quantity
+// a row of a device buffer, and no framework ops.
+//
+// A solve (cpl_solver_solve_warm; _solve and _solve_inst are the same call with less given) is three
+// functions on the solver's own stream: solve_start (inputs, scaling, the cold or warm starting iterate),
+// solve_iterate (the loop below), solve_finish (the final test, the rows' results, the outputs).
+//
+// An iteration is a sequence of phases (the list at `enum Phase`): the convergence test, Newton step and
+// regular line search; IPOPT's soft restoration step where a search found no trial; one iteration of
+// the restoration phase (MinC_1NrmRestorationPhase) for the instances inside it; the accept, with the
+// restoration phase's entry.  step_phase launches a phase's kernels — fixed trip counts, masked updates,
+// no host synchronisation inside — and run_phase captures them once per (batch size, inputs given, phase)
+// as a HIP graph and replays it.  Batches of at most FUSE_ROWS rows run the whole iteration as one graph.
+//
+// What the host reads per iteration: after the Newton phase the d_any flag bytes (a copy and a stream
+// synchronisation; not in the one-graph iteration), and after the accept the counts of active and
+// restoration-phase instances.  Up to COUNT1_MAX rows the counts arrive in a mailbox — pinned host memory
+// that the counting kernel writes [count, resto, seq] to behind a system-scope fence, and wait_mail polls
+// for the iteration's sequence number — otherwise by a copy.  When half the rows have finished, compact()
+// scatters their results and gathers the active rows to the front.
+//
+// Where the kernels are (each header belongs to this translation unit alone):
+//   cpl_solver_common.hpp  sizes, launch geometry, the buffer groups, the wave reductions (bfly_*), push_into
+//   cpl_solver_start.hpp   starting point, NLP scaling, the cold / warm starting state and multipliers
+//   cpl_solver_search.hpp  gradient / residual / unpack glue, second-order corrections, the soft step,
+//                          the failed-search bookkeeping
+//   cpl_solver_lbfgs.hpp   IPOPT's limited-memory quasi-Newton model
+//   cpl_solver_resto.hpp   the restoration phase: entry, Newton-step glue, judge, accept and return
+//   cpl_solver_batch.hpp   per batch, not per phase: counts and mailbox, the small-batch tail, compaction,
+//                          best-iterate tracking, the results of rows leaving the batch
+//   cpl_solver_state.hpp   host only: the arena, the buffer records, struct cpl_solver
+// The callbacks (cpl_eval_batch and the Hessians: cpl_kernels.hip), the per-instance iteration kernels
+// (optimality, Newton setup, post-step, trial, judge, accept: cpl_ipm.hip) and the Newton step
+// (cpl_kkt.hip) are other translation units, reached through cpl_engine.hpp and the C ABI.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -33,2476 +55,13 @@
 #include "cpl_layout.hpp"
 #include "cpl_status.hpp"
 
-namespace cpl {
-namespace {
-
-constexpr int FMAX = 64;          // filter entries kept per instance (a ring), as batch_ipm.FMAX
-constexpr double BIG = 1.0e19;    // |bound| >= 1e19 is infinite (IPOPT nlp_lower/upper_bound_inf)
-constexpr int WPB = 4;            // instances per 256-thread workgroup (one wave each)
-
-#define CK(expr)                      \
-  do {                                \
-    const int32_t st_ = (expr);       \
-    if (st_ != CPL_OK) return st_;    \
-  } while (0)
-
-inline unsigned blocks_for(int64_t batch) { return (unsigned)((batch + WPB - 1) / WPB); }
-inline unsigned blocks_elems(int64_t total) { return (unsigned)((total + 255) / 256); }
-
-// ---- the solver's buffers grouped by meaning: the wide kernels below take these groups inside one
-// by-value argument struct (built from the solver by the functions after `struct cpl_solver`), and
-// unpack a group with a structured binding — every buffer is named once per group, not once per
-// position of a 50-pointer list.  No member is __restrict__: several kernels store to the iterate or
-// the staged trial through one group and read it through another.
-struct Bounds {  // of w = [x_free, s]: which are finite, and their (relaxed) values
-  const uint8_t *hasL = nullptr, *hasU = nullptr;
-  const double *wl0 = nullptr, *wu0 = nullptr;
-};
-struct Iterate {  // the primal-dual iterate (the restoration phase's: its own bound multipliers)
-  double *w = nullptr, *y = nullptr, *zL = nullptr, *zU = nullptr;
-};
-struct Step {  // the Newton step
-  double *dw = nullptr, *dy = nullptr, *dzL = nullptr, *dzU = nullptr;
-};
-struct Staged {  // the accepted trial of the current search (p, n: the restoration phase's)
-  double *f = nullptr, *g = nullptr, *w = nullptr, *alpha = nullptr;
-  uint8_t* aug = nullptr;
-  double *p = nullptr, *n = nullptr;
-};
-struct Search {  // a line search's state: the regular one, and the restoration phase's own
-  uint8_t *act = nullptr, *searching = nullptr;
-  double *alpha = nullptr, *a_min = nullptr, *mu = nullptr, *theta = nullptr, *phi = nullptr, *gd = nullptr;
-  uint8_t* switch_ok = nullptr;
-  double *theta_max = nullptr, *filt_t = nullptr, *filt_p = nullptr;
-};
-struct RestoVars {  // the restoration problem's own variables and their multipliers
-  double *wR = nullptr, *pR = nullptr, *nR = nullptr, *zp = nullptr, *zn = nullptr;
-};
-
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
-}
-
-// IPOPT bound_push = bound_frac = 1e-2 (absolute and relative to the range), batch_ipm.push
-__device__ __forceinline__ double push_into(double v, bool hl, bool hu, double lo, double up) {
-  const double k = 1e-2;
-  const double rng = (hl && hu) ? up - lo : INFINITY;
-  const double pl = fmin(k * fmax(fabs(lo), 1.0), k * rng);
-  const double pu = fmin(k * fmax(fabs(up), 1.0), k * rng);
-  if (hl) v = fmax(v, lo + pl);
-  if (hu) v = fmin(v, up - pu);
-  return v;
-}
-
-// push_into with its two constants apart (kp absolute, kf relative to the range): a warm start's
-// warm_start_bound_push / _frac; kp = kf = 1e-2 is push_into, operation for operation
-__device__ __forceinline__ double push_into2(double v, bool hl, bool hu, double lo, double up, double kp, double kf) {
-  const double rng = (hl && hu) ? up - lo : INFINITY;
-  const double pl = fmin(kp * fmax(fabs(lo), 1.0), kf * rng);
-  const double pu = fmin(kp * fmax(fabs(up), 1.0), kf * rng);
-  if (hl) v = fmax(v, lo + pl);
-  if (hu) v = fmin(v, up - pu);
-  return v;
-}
-
-// constraint residual of row r: g - g_l (equality), g - s (inequality, slack s)
-__device__ __forceinline__ double cons_row(const double* g, const double* w, int nf, int r, const int32_t* row_slack,
-                                           const double* gl) {
-  const int s = row_slack[r];
-  return s >= 0 ? g[r] - w[nf + s] : g[r] - gl[r];
-}
-
-// Xbase = x0 with the fixed variables at their (equal) bounds
-__global__ void k_xbase(int64_t total, int n, const double* __restrict__ x0, const uint8_t* __restrict__ is_fixed,
-                        const double* __restrict__ xl, double* __restrict__ Xbase) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= total) return;
-  const int j = (int)(e % n);
-  Xbase[e] = is_fixed[j] ? xl[j] : x0[e];
-}
-
-// the starting point's x: the free variables pushed into their bounds (batch_ipm: Xs)
-__global__ void k_start_x(int64_t total, int n, const int32_t* __restrict__ freepos, const double* __restrict__ Xbase,
-                          const uint8_t* __restrict__ hasL, const uint8_t* __restrict__ hasU,
-                          const double* __restrict__ wl0, const double* __restrict__ wu0, double* __restrict__ X) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= total) return;
-  const int j = (int)(e % n);
-  const int k = freepos[j];
-  X[e] = k >= 0 ? push_into(Xbase[e], hasL[k], hasU[k], wl0[k], wu0[k]) : Xbase[e];
-}
-
-// the starting state of every instance (one wave each): w0 = push([x_free, g_I]), bound multipliers
-// 1, theta_0 and the filter's theta_max / theta_min, mu, flags; gw0 and the least-squares system's
-// right-hand side r1 = -(gw0 - zL0 + zU0) (the multiplier estimate is one KKT solve with M = I)
-struct InitStateArgs {
-  int n = 0, m = 0, nf = 0, nw = 0;
-  double mu_init = 0.0;
-  const int32_t *free_idx = nullptr, *ineq_row = nullptr, *row_slack = nullptr;
-  const double *gl = nullptr, *X = nullptr, *g = nullptr, *grad = nullptr;
-  Bounds bd;
-  Iterate it;
-  double *theta_max = nullptr, *theta_min = nullptr, *mu = nullptr, *filt_t = nullptr, *filt_p = nullptr;
-  double *dwl = nullptr, *d_inf = nullptr, *r1 = nullptr, *r2 = nullptr, *M = nullptr;
-  uint8_t *active = nullptr, *lm_cnt = nullptr, *lm_skip = nullptr;
-  int64_t *status = nullptr, *iters = nullptr, *acc = nullptr, *fcount = nullptr;
-};
-__global__ __launch_bounds__(256) void k_init_state(int64_t B, const InitStateArgs a) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
-  const int n = a.n, m = a.m, nf = a.nf, nw = a.nw;
-  const auto [hasL, hasU, wl0, wu0] = a.bd;
-  const auto [w, y, zL, zU] = a.it;
-  double* wb = w + b * nw;
-  for (int k = lane; k < nw; k += 64) {
-    const double v = k < nf ? a.X[b * n + a.free_idx[k]] : a.g[b * m + a.ineq_row[k - nf]];
-    const bool hl = hasL[k], hu = hasU[k];
-    wb[k] = push_into(v, hl, hu, wl0[k], wu0[k]);
-    const double zl = hl ? 1.0 : 0.0, zu = hu ? 1.0 : 0.0;
-    zL[b * nw + k] = zl;
-    zU[b * nw + k] = zu;
-    const double gw = k < nf ? a.grad[b * n + a.free_idx[k]] : 0.0;
-    a.r1[b * nw + k] = -((gw - zl) + zu);
-    for (int j = 0; j < nw; ++j) a.M[(b * nw + k) * nw + j] = j == k ? 1.0 : 0.0;
-  }
-  double th = 0.0;
-  for (int r = lane; r < m; r += 64) {  // (the slack recomputed: this lane did not write it)
-    const int sl = a.row_slack[r];
-    const double gv = a.g[b * m + r];
-    const double c =
-        sl >= 0 ? gv - push_into(gv, hasL[nf + sl], hasU[nf + sl], wl0[nf + sl], wu0[nf + sl]) : gv - a.gl[r];
-    th += fabs(c);
-    a.r2[b * m + r] = 0.0;
-  }
-  th = wave_sum(th);
-  for (int k = lane; k < FMAX; k += 64) {
-    a.filt_t[b * FMAX + k] = INFINITY;
-    a.filt_p[b * FMAX + k] = INFINITY;
-  }
-  if (lane == 0) {
-    a.theta_max[b] = 1e4 * fmax(th, 1.0);
-    a.theta_min[b] = 1e-4 * fmax(th, 1.0);
-    a.mu[b] = a.mu_init;
-    a.active[b] = 1;
-    a.status[b] = CPL_SOLVE_MAX_ITER;
-    a.iters[b] = 0;
-    a.acc[b] = 0;
-    a.fcount[b] = 0;
-    a.dwl[b] = 0.0;
-    a.d_inf[b] = 0.0;
-    a.lm_cnt[b] = 0;
-    a.lm_skip[b] = 0;
-  }
-}
-
-// least-squares multipliers: kept when |y|max <= 1e3 (IPOPT constr_mult_init_max) and the solve succeeded
-// IPOPT's gradient-based NLP scaling (GradientScaling::DetermineScalingParametersImpl, with
-// nlp_scaling_max_gradient 100 and nlp_scaling_min_value 1e-8; batch_ipm.py nlp_scaling,
-// oracle/cpl_solve_host.c nlp_scaling), from the callbacks at the starting point: one wave per
-// instance.  df = max(1e-8, 100 / max|grad f|) when that maximum exceeds 100; per block of rows (the
-// equalities, the inequalities) whose largest row gradient exceeds 100, dc_r = max(1e-8,
-// 100 * (1 / max(100, max_j |J_rj|))) on each row of the block.  Gradients over the free variables
-// (srp / srq: the free-column records of each row), a NaN entry counting as 0.  any[0] = 1 when an
-// instance has a factor != 1.  Also (always) the NaN entries of the instance's Jacobian there — the
-// 0/0 of a cone at F_t = 0, which the iteration takes as 0 — into nan_cnt[b] (scale = 0: that only).
-__global__ __launch_bounds__(256) void k_nlp_scaling(int64_t B, int n, int m, int nnz_rec, int scale,
-                                                     const uint8_t* __restrict__ is_fixed,
-                                                     const int32_t* __restrict__ row_slack, const int32_t* __restrict__ srp,
-                                                     const int32_t* __restrict__ srq, const double* __restrict__ grad,
-                                                     const double* __restrict__ J, double* __restrict__ df,
-                                                     double* __restrict__ dc, uint8_t* __restrict__ any,
-                                                     int32_t* __restrict__ nan_cnt) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
-  int nans = 0;
-  for (int q = lane; q < nnz_rec; q += 64) nans += J[b * nnz_rec + q] != J[b * nnz_rec + q];
-  nans = (int)wave_sum((double)nans);
-  if (lane == 0) nan_cnt[b] = nans;
-  if (!scale) return;
-  double gm = 0.0;
-  for (int j = lane; j < n; j += 64)
-    if (!is_fixed[j]) {
-      const double v = grad[b * n + j];
-      gm = fmax(gm, v == v ? fabs(v) : 0.0);
-    }
-  gm = wave_max(gm);
-  const double d = gm > 100.0 ? fmax(100.0 / gm, 1e-8) : 1.0;
-  double rm[2] = {0.0, 0.0}, emax = 0.0, imax = 0.0;  // m <= 128: two rows per lane at most
-  for (int h = 0; h < 2; ++h) {
-    const int r = lane + 64 * h;
-    if (r >= m) break;
-    double v = 0.0;
-    for (int t = srp[r]; t < srp[r + 1]; ++t) {
-      const double a = J[b * nnz_rec + srq[t]];
-      v = fmax(v, a == a ? fabs(a) : 0.0);
-    }
-    rm[h] = v;
-    if (row_slack[r] < 0) emax = fmax(emax, v);
-    else imax = fmax(imax, v);
-  }
-  emax = wave_max(emax);
-  imax = wave_max(imax);
-  bool scaled = d != 1.0;
-  for (int h = 0; h < 2; ++h) {
-    const int r = lane + 64 * h;
-    if (r >= m) break;
-    const double bm = row_slack[r] < 0 ? emax : imax;
-    const double s = bm > 100.0 ? fmax(100.0 * (1.0 / fmax(rm[h], 100.0)), 1e-8) : 1.0;
-    dc[b * m + r] = s;
-    scaled |= s != 1.0;
-  }
-  if (lane == 0) df[b] = d;
-  if (__ballot(scaled) != 0 && lane == 0) any[0] = 1;
-}
-
-// the scaled problem's callback values in place: f, grad f times df; g, J (records, row rrow[q])
-// times dc (any output may be nullptr)
-__global__ __launch_bounds__(256) void k_apply_scaling(int64_t B, int n, int m, int nnz_rec, const int32_t* __restrict__ rrow,
-                                                       const double* __restrict__ df, const double* __restrict__ dc,
-                                                       double* __restrict__ f, double* __restrict__ grad,
-                                                       double* __restrict__ g, double* __restrict__ J) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
-  const double d = df[b];
-  if (f && lane == 0) f[b] = f[b] * d;
-  if (grad)
-    for (int j = lane; j < n; j += 64) grad[b * n + j] = grad[b * n + j] * d;
-  if (g)
-    for (int r = lane; r < m; r += 64) g[b * m + r] = g[b * m + r] * dc[b * m + r];
-  if (J)
-    for (int q = lane; q < nnz_rec; q += 64) J[b * nnz_rec + q] = J[b * nnz_rec + q] * dc[b * m + rrow[q]];
-}
-
-// the Hessian callbacks' multipliers (dc y) / df [B, m]
-__global__ void k_scale_y(int64_t total, int m, const double* __restrict__ dc, const double* __restrict__ df,
-                          const double* __restrict__ y, double* __restrict__ yt) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < total) yt[e] = (dc[e] * y[e]) / df[e / m];
-}
-
-// v [B, per] times df[b] row by row
-__global__ void k_scale_rows(int64_t total, int64_t per, const double* __restrict__ df, double* __restrict__ v) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < total) v[e] = v[e] * df[e / per];
-}
-
-__global__ __launch_bounds__(256) void k_y0(int64_t B, int m, const double* __restrict__ dy, const int32_t* __restrict__ info,
-                                            double* __restrict__ y) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
-  double mx = 0.0;
-  for (int r = lane; r < m; r += 64) mx = fmax(mx, fabs(dy[b * m + r]));
-  mx = wave_max(mx);
-  const bool keep = mx <= 1e3 && info[b] == 0;
-  for (int r = lane; r < m; r += 64) y[b * m + r] = keep ? dy[b * m + r] : 0.0;
-}
-
-// ---- warm start [IPOPT-ext: warm_start_init_point, WarmStartIterateInitializer restated in this
-// engine's sign convention; include/cpl_mi355x.h cpl_warm_start, batch_ipm.py WarmStart] ----
-struct WarmArgs {
-  const double *y_in = nullptr, *zL_in = nullptr, *zU_in = nullptr;  // the caller's [B, m], [B, n], [B, n] (unscaled)
-  const uint8_t* mask = nullptr;                                     // the caller's [B] or nullptr
-  uint8_t *flag = nullptr, *any_cold = nullptr;                      // [B]: 1 = starts warm; [0]: a cold instance exists
-  const double *df = nullptr, *dc = nullptr;                         // nlp_scaling's factors (nullptr: the option is off)
-  double mu = 0.0, bound_push = 0.0, bound_frac = 0.0, slack_push = 0.0, slack_frac = 0.0, mult_push = 0.0;
-};
-
-// which instances start warm (one wave each): the mask says so and every warm value the start reads
-// is finite — y, and z_L / z_U at the free variables that have the bound
-__global__ __launch_bounds__(256) void k_warm_flag(int64_t B, int n, int m, int nf, const int32_t* __restrict__ free_idx,
-                                                   const uint8_t* __restrict__ hasL, const uint8_t* __restrict__ hasU,
-                                                   const WarmArgs wa) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
-  bool bad = false;
-  for (int r = lane; r < m; r += 64) bad |= !(fabs(wa.y_in[b * m + r]) < INFINITY);
-  for (int k = lane; k < nf; k += 64) {
-    const int64_t e = b * n + free_idx[k];
-    if (hasL[k]) bad |= !(fabs(wa.zL_in[e]) < INFINITY);
-    if (hasU[k]) bad |= !(fabs(wa.zU_in[e]) < INFINITY);
-  }
-  const bool warm = __ballot(bad) == 0 && (!wa.mask || wa.mask[b] != 0);
-  if (lane == 0) {
-    wa.flag[b] = warm ? 1 : 0;
-    if (!warm) wa.any_cold[0] = 1;
-  }
-}
-
-// k_start_x with each instance's own constants: a warm instance's warm_start_bound_push / _frac
-__global__ void k_start_x_warm(int64_t total, int n, const int32_t* __restrict__ freepos, const double* __restrict__ Xbase,
-                               const uint8_t* __restrict__ hasL, const uint8_t* __restrict__ hasU,
-                               const double* __restrict__ wl0, const double* __restrict__ wu0,
-                               const uint8_t* __restrict__ flag, double kp, double kf, double* __restrict__ X) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= total) return;
-  const int j = (int)(e % n);
-  const int k = freepos[j];
-  const bool warm = flag[e / n];
-  X[e] = k >= 0 ? push_into2(Xbase[e], hasL[k], hasU[k], wl0[k], wu0[k], warm ? kp : 1e-2, warm ? kf : 1e-2) : Xbase[e];
-}
-
-// k_init_state for a batch of warm and cold instances (one wave each).  A cold one (flag 0) gets
-// k_init_state's start, operation for operation; its y follows from the least-squares solve (k_y0_warm).
-// A warm one: w pushed by its own constants, y = df y_in / dc, z over x = max(mult_push, df z_in) where
-// the bound exists, z of row r's slack from that slack's stationarity row -y_r - zL + zU = 0
-// (zL = max(mult_push, -y_r), zU = max(mult_push, y_r)), mu = wa.mu.
-__global__ __launch_bounds__(256) void k_init_state_warm(int64_t B, const InitStateArgs a, const WarmArgs wa) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
-  const int n = a.n, m = a.m, nf = a.nf, nw = a.nw;
-  const auto [hasL, hasU, wl0, wu0] = a.bd;
-  const auto [w, y, zL, zU] = a.it;
-  const bool warm = wa.flag[b];
-  const double kpx = warm ? wa.bound_push : 1e-2, kfx = warm ? wa.bound_frac : 1e-2;
-  const double kps = warm ? wa.slack_push : 1e-2, kfs = warm ? wa.slack_frac : 1e-2;
-  const double d = wa.df ? wa.df[b] : 1.0;
-  // the scaled problem's multiplier of row r
-  auto y_of = [&](int r) {
-    const double yi = wa.y_in[b * m + r];
-    return wa.df ? (d * yi) / wa.dc[b * m + r] : yi;
-  };
-  double* wb = w + b * nw;
-  for (int k = lane; k < nw; k += 64) {
-    const double v = k < nf ? a.X[b * n + a.free_idx[k]] : a.g[b * m + a.ineq_row[k - nf]];
-    const bool hl = hasL[k], hu = hasU[k];
-    wb[k] = push_into2(v, hl, hu, wl0[k], wu0[k], k < nf ? kpx : kps, k < nf ? kfx : kfs);
-    double zl = hl ? 1.0 : 0.0, zu = hu ? 1.0 : 0.0;
-    if (warm) {
-      if (k < nf) {
-        const int64_t e = b * n + a.free_idx[k];
-        zl = hl ? fmax(wa.mult_push, d * wa.zL_in[e]) : 0.0;
-        zu = hu ? fmax(wa.mult_push, d * wa.zU_in[e]) : 0.0;
-      } else {
-        const double yr = y_of(a.ineq_row[k - nf]);
-        zl = hl ? fmax(wa.mult_push, -yr) : 0.0;
-        zu = hu ? fmax(wa.mult_push, yr) : 0.0;
-      }
-    }
-    zL[b * nw + k] = zl;
-    zU[b * nw + k] = zu;
-    const double gw = k < nf ? a.grad[b * n + a.free_idx[k]] : 0.0;
-    a.r1[b * nw + k] = -((gw - zl) + zu);
-    for (int j = 0; j < nw; ++j) a.M[(b * nw + k) * nw + j] = j == k ? 1.0 : 0.0;
-  }
-  double th = 0.0;
-  for (int r = lane; r < m; r += 64) {  // (the slack recomputed: this lane did not write it)
-    const int sl = a.row_slack[r];
-    const double gv = a.g[b * m + r];
-    const double c =
-        sl >= 0 ? gv - push_into2(gv, hasL[nf + sl], hasU[nf + sl], wl0[nf + sl], wu0[nf + sl], kps, kfs) : gv - a.gl[r];
-    th += fabs(c);
-    a.r2[b * m + r] = 0.0;
-    if (warm) y[b * m + r] = y_of(r);
-  }
-  th = wave_sum(th);
-  for (int k = lane; k < FMAX; k += 64) {
-    a.filt_t[b * FMAX + k] = INFINITY;
-    a.filt_p[b * FMAX + k] = INFINITY;
-  }
-  if (lane == 0) {
-    a.theta_max[b] = 1e4 * fmax(th, 1.0);
-    a.theta_min[b] = 1e-4 * fmax(th, 1.0);
-    a.mu[b] = warm ? wa.mu : a.mu_init;
-    a.active[b] = 1;
-    a.status[b] = CPL_SOLVE_MAX_ITER;
-    a.iters[b] = 0;
-    a.acc[b] = 0;
-    a.fcount[b] = 0;
-    a.dwl[b] = 0.0;
-    a.d_inf[b] = 0.0;
-    a.lm_cnt[b] = 0;
-    a.lm_skip[b] = 0;
-  }
-}
-
-// k_y0 for the cold instances of a warm batch (a warm one keeps the y k_init_state_warm gave it)
-__global__ __launch_bounds__(256) void k_y0_warm(int64_t B, int m, const double* __restrict__ dy,
-                                                 const int32_t* __restrict__ info, const uint8_t* __restrict__ flag,
-                                                 double* __restrict__ y) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B || flag[b]) return;
-  const int lane = threadIdx.x & 63;
-  double mx = 0.0;
-  for (int r = lane; r < m; r += 64) mx = fmax(mx, fabs(dy[b * m + r]));
-  mx = wave_max(mx);
-  const bool keep = mx <= 1e3 && info[b] == 0;
-  for (int r = lane; r < m; r += 64) y[b * m + r] = keep ? dy[b * m + r] : 0.0;
-}
-
-// the state a later solve warm-starts from, of every row that leaves the batch (finished, or at the
-// end: all rows; one wave each), at the instance's own position: the bound multipliers over x of the
-// unscaled problem, z / df (df = nullptr: unscaled), 0 at fixed entries (and where there is no bound: z
-// is 0 there), and the barrier parameter
-__global__ __launch_bounds__(256) void k_scatter_warm(int64_t rows, int n, int nw, bool finished_only,
-                                                      const int32_t* __restrict__ orig, const uint8_t* __restrict__ active,
-                                                      const int32_t* __restrict__ freepos, const double* __restrict__ zL,
-                                                      const double* __restrict__ zU, const double* __restrict__ df,
-                                                      const double* __restrict__ mu, double* __restrict__ fzLx,
-                                                      double* __restrict__ fzUx, double* __restrict__ fmu) {
-  const int64_t r = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (r >= rows) return;
-  const int32_t o = orig[r];
-  if (o < 0 || (finished_only && active[r])) return;
-  const int lane = threadIdx.x & 63;
-  for (int j = lane; j < n; j += 64) {
-    const int k = freepos[j];
-    double zl = 0.0, zu = 0.0;
-    if (k >= 0) {
-      zl = zL[r * nw + k];
-      zu = zU[r * nw + k];
-      if (df) {
-        zl = zl / df[r];
-        zu = zu / df[r];
-      }
-    }
-    fzLx[(int64_t)o * n + j] = zl;
-    fzUx[(int64_t)o * n + j] = zu;
-  }
-  if (lane == 0) fmu[o] = mu[r];
-}
-
-// gradient over w (gw = [grad f over the free variables, 0]) and the constraint residual c
-__global__ __launch_bounds__(256) void k_prep(int64_t B, int n, int m, int nf, int nw, const int32_t* __restrict__ free_idx,
-                                              const int32_t* __restrict__ row_slack, const double* __restrict__ gl,
-                                              const double* __restrict__ grad, const double* __restrict__ g,
-                                              const double* __restrict__ w, double* __restrict__ gradw,
-                                              double* __restrict__ c) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
-  for (int k = lane; k < nw; k += 64) gradw[b * nw + k] = k < nf ? grad[b * n + free_idx[k]] : 0.0;
-  if (c)
-    for (int r = lane; r < m; r += 64) c[b * m + r] = cons_row(g + b * m, w + b * nw, nf, r, row_slack, gl);
-}
-
-// A = [J_free | -P] (cpl_ipm_dense_a's entries) and k_prep in one launch: the first nblk_a
-// workgroups take A's entries, the rest k_prep's instances (independent outputs, no ordering)
-__global__ __launch_bounds__(256) void k_dense_a_prep(int64_t totalA, unsigned nblk_a, int m, int nw, int nf, int nnz,
-                                                      const int32_t* __restrict__ amap,
-                                                      const int32_t* __restrict__ row_slack,
-                                                      const double* __restrict__ jac, double* __restrict__ A,
-                                                      const uint8_t* __restrict__ active, int64_t B, int n, const int32_t* __restrict__ free_idx,
-                                                      const double* __restrict__ gl, const double* __restrict__ grad,
-                                                      const double* __restrict__ g, const double* __restrict__ w,
-                                                      double* __restrict__ gradw, double* __restrict__ c) {
-  if (blockIdx.x < nblk_a) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < totalA) dense_a_entry(e, m, nw, nf, nnz, amap, row_slack, jac, A, active);
-    return;
-  }
-  const int64_t b = (int64_t)(blockIdx.x - nblk_a) * WPB + (threadIdx.x >> 6);
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
-  for (int k = lane; k < nw; k += 64) gradw[b * nw + k] = k < nf ? grad[b * n + free_idx[k]] : 0.0;
-  for (int r = lane; r < m; r += 64) c[b * m + r] = cons_row(g + b * m, w + b * nw, nf, r, row_slack, gl);
-}
-
-// after the optimality kernel: tau = max(0.99, 1 - mu), the iteration's active snapshot, and the
-// evaluation point X = unpack(w) for the Hessian (the solve loop has it fused into the optimality
-// kernel: IpmUnpack)
-__global__ void k_unpack_tau(int64_t total, int n, int nw, const int32_t* __restrict__ freepos,
-                             const double* __restrict__ Xbase, const double* __restrict__ w,
-                             const double* __restrict__ mu, const uint8_t* __restrict__ active,
-                             const uint8_t* __restrict__ in_resto, double* __restrict__ X, double* __restrict__ tau,
-                             uint8_t* __restrict__ act) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= total) return;
-  const int64_t b = e / n;
-  const int j = (int)(e - b * n);
-  const int k = freepos[j];
-  X[e] = k >= 0 ? w[b * nw + k] : Xbase[e];
-  if (j == 0) {
-    tau[b] = fmax(1.0 - mu[b], 0.99);
-    act[b] = active[b] && !in_resto[b];  // the restoration phase's instances take their own step
-  }
-}
-
-// X = unpack(w), the free variables clamped into [xl, xu]; the fixed ones keep Xbase's value (the
-// instance's own under fixed_from_x0, where the template's bound is not theirs)
-__global__ void k_unpack_free(int64_t total, int n, int nw, const int32_t* __restrict__ freepos,
-                              const double* __restrict__ Xbase, const double* __restrict__ w,
-                              const double* __restrict__ xl, const double* __restrict__ xu, double* __restrict__ X) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= total) return;
-  const int64_t b = e / n;
-  const int j = (int)(e - b * n);
-  const int k = freepos[j];
-  X[e] = k >= 0 ? fmin(fmax(w[b * nw + k], xl[j]), xu[j]) : Xbase[e];
-}
-
-// X = unpack(w) (optionally clamped into [xl, xu]: IPOPT honor_original_bounds)
-__global__ void k_unpack(int64_t total, int n, int nw, const int32_t* __restrict__ freepos,
-                         const double* __restrict__ Xbase, const double* __restrict__ w, const double* __restrict__ xl,
-                         const double* __restrict__ xu, double* __restrict__ X) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= total) return;
-  const int64_t b = e / n;
-  const int j = (int)(e - b * n);
-  const int k = freepos[j];
-  double v = k >= 0 ? w[b * nw + k] : Xbase[e];
-  if (xl) v = fmin(fmax(v, xl[j]), xu[j]);
-  X[e] = v;
-}
-
-// ---- IPOPT constants of the line search / restoration phase (batch_ipm.py restates them) ------
-// (the acceptance test itself: cpl_accept.hpp)
-constexpr double GAMMA_TH = LS_GAMMA_TH, GAMMA_PHI = LS_GAMMA_PHI, DELTA_SW = LS_DELTA, S_TH = LS_S_TH, S_PHI = LS_S_PHI;
-constexpr double KAPPA_SOC = 0.99, KAPPA_SIGMA = 1e10;
-constexpr double RHO_R = 1000.0, KAPPA_RESTO = 0.9, BOUND_MULT_RESET = 1000.0, SOFT_RESTO_FACTOR = 0.9999;
-constexpr int MAX_SOFT_RESTO = LS_MAX_SOFT_RESTO, MU_ROUNDS = 6;
-
-__device__ __forceinline__ double wave_min_d(double v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
-  return v;
-}
-
-// IPOPT FilterLSAcceptor::CalculateAlphaMin (cpl_accept.hpp)
-__device__ __forceinline__ double alpha_min_of(double theta, double gd, double theta_min) {
-  return ls_alpha_min_of(theta, gd, theta_min);
-}
-
-// IPOPT FilterLSAcceptor::CheckAcceptabilityOfTrialPoint on one wave: theta_max, the filter (entries
-// stored with their margins), switching condition / Armijo / sufficient decrease against the
-// reference point with the obj_max_inc guard.  Returns ok; *h_type = the step augments the filter.
-__device__ __forceinline__ bool acceptable_wave(double th, double ph, double tk, double pk, double g, double al,
-                                                uint8_t switch_ok, double theta_max, const double* ft, const double* fp,
-                                                bool* h_type) {
-  return ls_acceptable_wave(th, ph, tk, pk, g, al, switch_ok, theta_max, ft, fp, FMAX, h_type);
-}
-
-// (the line-search setup after the Newton step: cpl_accept.hpp ls_setup_wave, run by the post-step
-// kernel)
-
-// c_soc = a_soc c_soc + c(trial point); the correction's right-hand side r2 = -c_soc
-__global__ __launch_bounds__(256) void k_soc_rhs(int64_t B, int m, int nf, int nw, const int32_t* __restrict__ row_slack,
-                                                 const double* __restrict__ gl, const double* __restrict__ g_t,
-                                                 const double* __restrict__ w_t, const double* __restrict__ a_soc,
-                                                 double* __restrict__ c_soc, double* __restrict__ r2) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
-  const double a = a_soc[b];
-  for (int r = lane; r < m; r += 64) {
-    const double ct = cons_row(g_t + b * m, w_t + b * nw, nf, r, row_slack, gl);
-    const double v = a * c_soc[b * m + r] + ct;
-    c_soc[b * m + r] = v;
-    r2[b * m + r] = -v;
-  }
-}
-
-// second-order correction bookkeeping (batch_ipm.py: soc, c_soc, a_soc, th_old = theta of the first
-// trial point as IPOPT's TrySecondOrderCorrection) and the first correction's right-hand side
-__global__ __launch_bounds__(256) void k_soc_begin_rhs(int64_t B, int m, int nf, int nw, const uint8_t* __restrict__ searching,
-                                                       const double* __restrict__ th, const double* __restrict__ theta_k,
-                                                       const double* __restrict__ c, const double* __restrict__ alpha,
-                                                       const int32_t* __restrict__ row_slack, const double* __restrict__ gl,
-                                                       const double* __restrict__ g_t, const double* __restrict__ w_t,
-                                                       uint8_t* __restrict__ soc, double* __restrict__ c_soc,
-                                                       double* __restrict__ a_soc, double* __restrict__ th_old,
-                                                       double* __restrict__ r2) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
-  const double a = alpha[b];
-  for (int r = lane; r < m; r += 64) {
-    const double ct = cons_row(g_t + b * m, w_t + b * nw, nf, r, row_slack, gl);
-    const double v = a * c[b * m + r] + ct;
-    c_soc[b * m + r] = v;
-    r2[b * m + r] = -v;
-  }
-  if (lane == 0) {
-    soc[b] = searching[b] && th[b] >= theta_k[b];
-    a_soc[b] = a;
-    th_old[b] = th[b];
-  }
-}
-
-__global__ void k_soc_after(int64_t B, uint8_t* __restrict__ soc, const uint8_t* __restrict__ ok,
-                            const double* __restrict__ th, double* __restrict__ th_old) {
-  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  soc[b] = soc[b] && !ok[b] && th[b] <= KAPPA_SOC * th_old[b];
-  th_old[b] = th[b];
-}
-
-// after a trial: alpha halved where still searching, the search given up below alpha_min (IPOPT
-// tries the next point only while alpha > alpha_min); flags (zeroed by ls_setup_wave / k_resto_post):
-// any[fi] = an instance is still searching; with soft_now, any[1] = an instance has no accepted
-// point yet and will try the soft restoration step
-__global__ void k_halve2(int64_t B, uint8_t* __restrict__ searching, double* __restrict__ alpha,
-                         const double* __restrict__ a_min, const uint8_t* __restrict__ act,
-                         const uint8_t* __restrict__ tiny, const uint8_t* __restrict__ soft_now,
-                         const int32_t* __restrict__ soft_cnt, const double* __restrict__ st_alpha,
-                         uint8_t* __restrict__ any, int fi) {
-  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  bool s = searching[b] != 0;
-  if (s) {
-    const double a = 0.5 * alpha[b];
-    alpha[b] = a;
-    if (!(a > a_min[b])) s = false;
-    searching[b] = s ? 1 : 0;
-  }
-  if (s) any[fi] = 1;
-  if (soft_now && act[b] && !tiny[b] &&
-      ((soft_now[b] && soft_cnt[b] <= MAX_SOFT_RESTO) || (!soft_now[b] && !(st_alpha[b] > 0.0))))
-    any[1] = 1;
-}
-
-// IPOPT's soft restoration step, part 1 (BacktrackingLineSearch::TrySoftRestoStep): the instances
-// without an accepted trial (or in the soft phase, at most max_soft_resto_iters times) try the full
-// primal-dual step alpha = min(alpha_primal_max, alpha_dual_max): its point w + alpha dw and X
-struct SoftStepArgs {  // the soft step's buffers: k_soft_begin starts it, k_soft_judge(_fail) judge it
-  int n = 0, m = 0, nf = 0, nw = 0, nnz_rec = 0;
-  const int32_t *amap = nullptr, *row_slack = nullptr, *free32 = nullptr, *freepos = nullptr;
-  const double *gl = nullptr, *Xbase = nullptr;
-  Bounds bd;
-  Iterate it;
-  Step sp;
-  Search ls;
-  Staged st;
-  const uint8_t *tiny = nullptr, *soft_now = nullptr;
-  uint8_t *soft_try = nullptr, *in_soft = nullptr;
-  int32_t* soft_cnt = nullptr;
-  double *a_soft = nullptr, *ws = nullptr, *Xs = nullptr;  // the step's length, its point, X = unpack(ws)
-  const double *f_s = nullptr, *grad_s = nullptr, *g_s = nullptr, *J_s = nullptr;  // the callbacks there
-  const double *A = nullptr, *gradw = nullptr, *c = nullptr;                       // ... and at the iterate
-  const double* a_max = nullptr;
-  double *a_z = nullptr, *cs_tmp = nullptr;
-};
-__global__ __launch_bounds__(256) void k_soft_begin(int64_t B, const SoftStepArgs a) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
-  const int n = a.n, nw = a.nw;
-  const double *w = a.it.w, *dw = a.sp.dw;
-  const bool t = a.ls.act[b] && !a.tiny[b] &&
-                 ((a.soft_now[b] && a.soft_cnt[b] <= MAX_SOFT_RESTO) || (!a.soft_now[b] && !(a.st.alpha[b] > 0.0)));
-  const double as = fmin(a.a_max[b], a.a_z[b]);
-  for (int k = lane; k < nw; k += 64) a.ws[b * nw + k] = w[b * nw + k] + (t ? as : 0.0) * dw[b * nw + k];
-  for (int j = lane; j < n; j += 64) {
-    const int k = a.freepos[j];
-    a.Xs[b * n + j] = k >= 0 ? w[b * nw + k] + (t ? as : 0.0) * dw[b * nw + k] : a.Xbase[b * n + j];
-  }
-  if (lane == 0) {
-    a.soft_try[b] = t ? 1 : 0;
-    a.a_soft[b] = as;
-  }
-}
-
-// IPOPT's primal-dual error of the barrier problem (1-norms of the dual residual, the constraint
-// residual and the mu-complementarity) of one instance on one wave.  A row r, column k: from the
-// dense A (Ad != NULL) or from the values-only Jacobian records through amap (as cpl_ipm_dense_a).
-__device__ __forceinline__ double pd_error_wave(int m, int nf, int nw, const double* Ad, const double* Jrec,
-                                                const int32_t* amap, const int32_t* row_slack, const double* gw_free,
-                                                int gw_stride_n, const int32_t* free32, const double* c,
-                                                const double* w, const double* y, const double* zL, const double* zU,
-                                                const double* alpha_dy, const double* dy, const double* dzL,
-                                                const double* dzU, double a, const uint8_t* hasL, const uint8_t* hasU,
-                                                const double* wl0, const double* wu0, double mu) {
-  const int lane = threadIdx.x & 63;
-  double s = 0.0;
-  for (int k = lane; k < nw; k += 64) {
-    double dual = k < nf ? (gw_stride_n ? gw_free[free32[k]] : gw_free[k]) : 0.0;
-    for (int r = 0; r < m; ++r) {
-      double akr;
-      if (Ad) {
-        akr = Ad[r * nw + k];
-      } else if (k < nf) {
-        const int q = amap[r * nf + k];
-        akr = q == -1 ? 0.0 : (q == -2 ? 1.0 : Jrec[q]);
-        akr = akr == akr ? akr : 0.0;
-      } else {
-        akr = row_slack[r] == k - nf ? -1.0 : 0.0;
-      }
-      const double yr = dy ? y[r] + a * dy[r] : y[r];
-      dual += akr * yr;
-    }
-    const double zl = hasL[k] ? (dzL ? zL[k] + a * dzL[k] : zL[k]) : 0.0;
-    const double zu = hasU[k] ? (dzU ? zU[k] + a * dzU[k] : zU[k]) : 0.0;
-    dual = dual - zl + zu;
-    s += fabs(dual);
-    if (hasL[k]) s += fabs((w[k] - wl0[k]) * zl - mu);
-    if (hasU[k]) s += fabs((wu0[k] - w[k]) * zu - mu);
-  }
-  for (int r = lane; r < m; r += 64) s += fabs(c[r]);
-  (void)alpha_dy;
-  return wave_sum(s);
-}
-
-// part 2: the soft step is taken when the original filter / current iterate accept it (the soft
-// phase ends) or when it cuts the primal-dual error by soft_resto_pderror_reduction_factor (the
-// soft phase starts or continues); the step's alpha then also moves the bound multipliers
-__device__ __forceinline__ void soft_judge_wave(int64_t b, const SoftStepArgs& a) {
-  const int n = a.n, m = a.m, nf = a.nf, nw = a.nw, nnz_rec = a.nnz_rec;
-  const auto [hasL, hasU, wl0, wu0] = a.bd;
-  const auto [w, y, zL, zU] = a.it;
-  const auto [dw, dy, dzL, dzU] = a.sp;
-  const auto [act, searching, alpha, a_min, mu, theta_k, phi_k, gd, switch_ok, theta_max, ft, fp] = a.ls;
-  const auto [st_f, st_g, st_w, st_alpha, st_aug, st_p, st_n] = a.st;
-  const int32_t *amap = a.amap, *row_slack = a.row_slack, *free32 = a.free32;
-  const double *gl = a.gl, *ws = a.ws, *f_s = a.f_s, *grad_s = a.grad_s, *g_s = a.g_s, *J_s = a.J_s;
-  double* cs_tmp = a.cs_tmp;
-  const int lane = threadIdx.x & 63;
-  const double* wb = ws + b * nw;
-  const double mub = mu[b], as = a.a_soft[b];
-  double th = 0.0, lg = 0.0;
-  for (int r = lane; r < m; r += 64) {
-    const double cr = cons_row(g_s + b * m, wb, nf, r, row_slack, gl);
-    cs_tmp[b * m + r] = cr;
-    th += fabs(cr);
-  }
-  for (int k = lane; k < nw; k += 64) {
-    if (hasL[k]) lg += log(wb[k] - wl0[k]);
-    if (hasU[k]) lg += log(wu0[k] - wb[k]);
-  }
-  th = wave_sum(th);
-  lg = wave_sum(lg);
-  const double ph = f_s[b] - mub * lg;
-  const bool orig_ok = acceptable_wave(th, ph, theta_k[b], phi_k[b], gd[b], 0.0, switch_ok[b], theta_max[b],
-                                       ft + b * FMAX, fp + b * FMAX, nullptr);
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  __builtin_amdgcn_wave_barrier();
-  const double pd_t = pd_error_wave(m, nf, nw, nullptr, J_s + b * (int64_t)nnz_rec, amap, row_slack, grad_s + b * n, 1,
-                                    free32, cs_tmp + b * m, wb, y + b * m, zL + b * nw, zU + b * nw, nullptr,
-                                    dy + b * m, dzL + b * nw, dzU + b * nw, as, hasL, hasU, wl0, wu0, mub);
-  const double pd_c = pd_error_wave(m, nf, nw, a.A + b * (int64_t)m * nw, nullptr, amap, row_slack, a.gradw + b * nw, 0,
-                                    free32, a.c + b * m, w + b * nw, y + b * m, zL + b * nw, zU + b * nw, nullptr,
-                                    nullptr, nullptr, nullptr, 0.0, hasL, hasU, wl0, wu0, mub);
-  const bool ok = isfinite(th) && isfinite(ph) && (orig_ok || pd_t <= SOFT_RESTO_FACTOR * pd_c);
-  if (ok) {
-    for (int r = lane; r < m; r += 64) st_g[b * m + r] = g_s[b * m + r];
-    for (int k = lane; k < nw; k += 64) st_w[b * nw + k] = wb[k];
-  }
-  if (lane == 0) {
-    if (ok) {
-      st_f[b] = f_s[b];
-      st_alpha[b] = as;
-      st_aug[b] = 0;
-      a.a_z[b] = as;
-    }
-    const bool left = ok && orig_ok;
-    if (left) a.in_soft[b] = 0;
-    else if (ok) a.in_soft[b] = 1;
-    if (left || (ok && !a.soft_now[b])) a.soft_cnt[b] = 0;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_soft_judge(int64_t B, const SoftStepArgs a) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B || !a.soft_try[b]) return;
-  soft_judge_wave(b, a);
-}
-
-// the end of the regular line search: failed = no accepted point (-> the restoration phase),
-// moved = an accepted one; a failed search leaves the soft phase.  IPOPT calls no restoration phase
-// at an acceptable point (BacktrackingLineSearch: "Restoration phase called at acceptable point" ->
-// STOP_AT_ACCEPTABLE_POINT): an instance whose search failed there ends with status acceptable.
-// Nor at an almost feasible point (theta <= 1e-2 tol): the backup acceptable point is restored and
-// the solve stops there as acceptable (RestoreAcceptablePoint), or without one it ends as a
-// restoration failure ("Restoration phase called, but point is almost feasible").
-struct NearFeasible {
-  const double* theta_k;
-  double near_tol;  // 1e-2 tol
-  int nw, m;
-  uint8_t* has_acc;
-  const double *acc_w, *acc_y, *acc_zL, *acc_zU;
-  double *w, *y, *zL, *zU;
-};
-// ... together with the accepted point's X = unpack(st_w): the end of the search
-struct FailTail {
-  int n = 0, nw = 0;
-  const int32_t* freepos = nullptr;
-  const double* Xbase = nullptr;
-  double* X = nullptr;
-  const uint8_t* act = nullptr;
-  Staged st;
-  const double* err0 = nullptr;
-  double acc_tol = 0.0;
-  const uint8_t* acc_ok = nullptr;  // CPL_TERM_IPOPT: the optimality kernel's CurrentIsAcceptable byte (else err0 <= acc_tol)
-  uint8_t *failed = nullptr, *moved = nullptr, *in_soft = nullptr;
-  int32_t* soft_cnt = nullptr;
-  int64_t* status = nullptr;
-  uint8_t* active = nullptr;
-  NearFeasible nf;
-};
-// The bookkeeping of instance b:
-__device__ __forceinline__ void fail_book(int64_t b, const FailTail& t) {
-  const NearFeasible& nf = t.nf;
-  const bool a = t.act[b] != 0;
-  bool f = a && !(t.st.alpha[b] > 0.0);
-  const bool at_acc = f && (t.acc_ok ? t.acc_ok[b] != 0 : t.err0[b] <= t.acc_tol);
-  const bool near = f && !at_acc && nf.theta_k[b] <= nf.near_tol;
-  if (at_acc || near) {
-    const bool back = near && nf.has_acc[b] != 0;
-    if (back) {  // (a rare branch: one thread copies the instance's backup point)
-      const int nw = nf.nw, m = nf.m;
-      for (int k = 0; k < nw; ++k) {
-        nf.w[b * nw + k] = nf.acc_w[b * nw + k];
-        nf.zL[b * nw + k] = nf.acc_zL[b * nw + k];
-        nf.zU[b * nw + k] = nf.acc_zU[b * nw + k];
-      }
-      for (int r = 0; r < m; ++r) nf.y[b * m + r] = nf.acc_y[b * m + r];
-      nf.has_acc[b] = 0;
-    }
-    t.status[b] = (at_acc || back) ? CPL_SOLVE_ACCEPTABLE : CPL_SOLVE_RESTO_FAILED;
-    t.active[b] = 0;
-    t.failed[b] = 0;
-    t.moved[b] = 0;
-    return;
-  }
-  t.failed[b] = f ? 1 : 0;
-  t.moved[b] = (a && !f) ? 1 : 0;
-  if (f) {
-    t.in_soft[b] = 0;
-    t.soft_cnt[b] = 0;
-  }
-}
-
-// ... in one launch (an element per thread; the first element of each instance also does that
-// instance's bookkeeping — which does not touch st_w)
-__global__ void k_fail_unpack(int64_t total, const FailTail t) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= total) return;
-  const int64_t b = e / t.n;
-  const int j = (int)(e - b * t.n);
-  const int k = t.freepos[j];
-  t.X[e] = k >= 0 ? t.st.w[b * t.nw + k] : t.Xbase[e];
-  if (j != 0) return;
-  fail_book(b, t);
-}
-
-// The small-batch iteration (P_FUSED) runs the soft step's judge and the end of the search as one
-// wave per instance: the judge (soft_try instances), then — its st_w / st_alpha / soft counters
-// written by the same wave, made visible to the wave's other lanes by a workgroup fence — the
-// accepted point's X = unpack(st_w) and the bookkeeping.  The same operations on the same values
-// as k_soft_judge + k_fail_unpack.
-__global__ __launch_bounds__(256) void k_soft_judge_fail(int64_t B, const SoftStepArgs a, const FailTail t) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B) return;
-  if (a.soft_try[b]) soft_judge_wave(b, a);
-  __threadfence_block();
-  __builtin_amdgcn_wave_barrier();
-  const int lane = threadIdx.x & 63, n = t.n, nw = t.nw;
-  for (int j = lane; j < n; j += 64) {
-    const int k = t.freepos[j];
-    t.X[b * n + j] = k >= 0 ? t.st.w[b * nw + k] : t.Xbase[b * n + j];
-  }
-  if (lane == 0) fail_book(b, t);
-}
-
-// IPOPT's limited-memory quasi-Newton model (LimMemQuasiNewtonUpdater [IPOPT] with the defaults
-// IFOPT's IpoptSolver leaves in place behind src/CentroidalPlanner.cpp:22-29: update type bfgs,
-// limited_memory_max_history 6, initialization scalar1, init_val 1 (bounds 1e-8 / 1e8),
-// max_skipping 2; every variable is nonlinear since IFOPT declares no linear ones), over x_free,
-// one workgroup per active instance (batch_ipm step(), use_bfgs):
-//   s = dw_free, y = grad_x L(w_new, y_new) - grad_x L(w, y_new)  (the Jacobian parts from A = [J_free | -P]);
-//   the pair is skipped when s'y <= sqrt(eps) |s| |y|; more than max_skipping consecutive skips
-//   reset the memory (model back to init_val I), and so does a failed line search (the step came
-//   from the feasibility step standing in for IPOPT's restoration phase, whose return restarts the
-//   quasi-Newton model; without it the degenerate TestBasic ground problem — force weight 0 —
-//   stalls on a model whose scalar1 sigma collapsed along a flat direction);
-//   otherwise the pair enters the memory (the oldest of 6 dropped), sigma = s'y / s's of the newest
-//   pair clamped to [1e-8, 1e8], and the dense model is rebuilt from sigma I by the BFGS recursion
-//   over the stored pairs, oldest first: B <- B - (Bs)(Bs)' / s'Bs + y y' / s'y  (mathematically the
-//   compact representation IPOPT applies; B stays bitwise symmetric: every update is an outer product).
-constexpr int LM_MAX_SKIP = 2;  // (LM_HIST and the update's argument block LbfgsArgs: cpl_engine.hpp)
-// doubles per instance of the compact model: sigma, the number of pairs nv, U [LM_HIST][nf], W [LM_HIST][nf]
-__host__ __device__ constexpr int64_t LMC(int nf) { return 2 + 2 * (int64_t)LM_HIST * nf; }
-// Column k of J_free^T yn at both points over the rows part, part + parts, ..., straight from the
-// values-only Jacobian records (the entries of A = [J_free | -P] as cpl_ipm_dense_a forms them: amap
-// -1 = 0, -2 = constant 1, NaN = 0).  Rows in order, eight at a time: the eight amap indices, then
-// the eight record entries they name, are loads in flight together (one row at a time waited two
-// dependent L2 round trips per row); the accumulation is the plain loop's.  Both L-BFGS forms call
-// it, so their partial sums are the same bit for bit.
-__device__ __forceinline__ void lbfgs_jty_part(const int32_t* amap, const double* jnb, const double* job,
-                                               const double* yn, int m, int nf, int k, int part, int parts,
-                                               double& jn, double& jo) {
-  const int R = m > part ? (m - part + parts - 1) / parts : 0;
-  for (int t0 = 0; t0 < R; t0 += 8) {
-    int qv[8];
-    double anv[8], aov[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) qv[u] = t0 + u < R ? amap[(part + (t0 + u) * parts) * nf + k] : -1;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      anv[u] = qv[u] >= 0 ? jnb[qv[u]] : 1.0;
-      aov[u] = qv[u] >= 0 ? job[qv[u]] : 1.0;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      if (qv[u] == -1) continue;  // structural zero (or past the last row): A's entry is 0
-      double an = anv[u], ao = aov[u];
-      if (qv[u] >= 0) {
-        an = an == an ? an : 0.0;
-        ao = ao == ao ? ao : 0.0;
-      }
-      const int r = part + (t0 + u) * parts;
-      jn += an * yn[r];
-      jo += ao * yn[r];
-    }
-  }
-}
-// The workgroup form, for nf > 64 (nf <= 64 — the 4-contact problem's 39 — takes k_lbfgs_wave below):
-// the pair vectors in LDS rows of NFX = 128 doubles, 28.5 KiB per workgroup
-constexpr int NFX = 128;
-__global__ __launch_bounds__(256) void k_lbfgs(int64_t B, const LbfgsArgs L) {
-  const int n = L.n, m = L.m, nf = L.nf, nw = L.nw, nnz_rec = L.nnz_rec;
-  const int64_t b = blockIdx.x;
-  if (b >= B || !L.act[b]) return;
-  __shared__ double Ps[LM_HIST][NFX], Py[LM_HIST][NFX], yn[256], red[8];
-  const int tid = threadIdx.x;
-  const double al = L.alpha[b];
-  for (int r = tid; r < m; r += blockDim.x) yn[r] = L.y[b * m + r] + al * L.dy[b * m + r];
-  // both counters read before any barrier: thread 0 rewrites them below
-  const int cnt = L.lm_cnt[b], skipped = L.lm_skip[b] + 1;
-  __syncthreads();
-  // the new pair goes to slot `last`; a full memory shifts down by one (the oldest dropped)
-  const int shift = cnt == LM_HIST ? 1 : 0, last = cnt - shift;
-  double* gs = L.lm_s + b * (int64_t)LM_HIST * nf;
-  double* gy = L.lm_y + b * (int64_t)LM_HIST * nf;
-  {  // J_free^T y at both points: the rows split over `parts` thread groups, partials summed in fixed order
-    __shared__ double pjn[4][NFX], pjo[4][NFX];
-    const int kp = nf <= 64 ? 64 : 128, parts = (int)blockDim.x / kp;
-    const int k = tid % kp, part = tid / kp;
-    if (k < nf && part < parts) {
-      double jn = 0.0, jo = 0.0;
-      lbfgs_jty_part(L.amap, L.J_new + b * (int64_t)nnz_rec, L.J_old + b * (int64_t)nnz_rec, yn, m, nf, k, part, parts,
-                     jn, jo);
-      pjn[part][k] = jn;
-      pjo[part][k] = jo;
-    }
-    __syncthreads();
-    for (int k2 = tid; k2 < nf; k2 += blockDim.x) {
-      double jn = pjn[0][k2], jo = pjo[0][k2];
-      for (int q = 1; q < parts; ++q) {
-        jn += pjn[q][k2];
-        jo += pjo[q][k2];
-      }
-      Ps[last][k2] = L.w_new[b * nw + k2] - L.w_old[b * nw + k2];
-      // grad_w f at the new point: its free components (k_prep's gather), 0 without a cost (grad_new NULL)
-      const double gn = L.grad_new ? L.grad_new[b * n + L.free_idx[k2]] : 0.0;
-      Py[last][k2] = (gn + jn) - (L.gw_old[b * nw + k2] + jo);
-      for (int j = 0; j < last; ++j) {
-        Ps[j][k2] = gs[(j + shift) * nf + k2];
-        Py[j][k2] = gy[(j + shift) * nf + k2];
-      }
-    }
-  }
-  __syncthreads();
-  auto block_dot = [&](const double* a, const double* c) {
-    double v = 0.0;
-    for (int k = tid; k < nf; k += blockDim.x) v += a[k] * c[k];
-    v = wave_sum(v);
-    __syncthreads();
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int q = 0; q < (int)(blockDim.x >> 6); ++q) t += red[q];
-    return t;
-  };
-  const double sy = block_dot(Ps[last], Py[last]);
-  const double ss = block_dot(Ps[last], Ps[last]);
-  const double yy = block_dot(Py[last], Py[last]);
-  double* hc = L.Hq + b * (int64_t)LMC(nf);  // the compact model: [sigma, nv, U, W]
-  const bool skip = !(sy > sqrt(DBL_EPSILON) * sqrt(ss) * sqrt(yy));
-  if (skip || L.failed[b]) {  // (uniform branch)
-    if (!L.failed[b] && skipped <= LM_MAX_SKIP) {
-      if (tid == 0) L.lm_skip[b] = (uint8_t)skipped;
-      return;
-    }
-    if (tid == 0) {  // the model back to init_val I
-      hc[0] = 1.0;
-      hc[1] = 0.0;
-      L.lm_skip[b] = 0;
-      L.lm_cnt[b] = 0;
-    }
-    return;
-  }
-  const int nc = last + 1;
-  for (int k = tid; k < nf; k += blockDim.x)
-    for (int j = 0; j < nc; ++j) {
-      gs[j * nf + k] = Ps[j][k];
-      gy[j * nf + k] = Py[j][k];
-    }
-  if (tid == 0) {
-    L.lm_skip[b] = 0;
-    L.lm_cnt[b] = (uint8_t)nc;
-  }
-  const double sigma = fmin(fmax(sy / ss, 1e-8), 1e8);
-  // The recursion unrolled onto vectors: a_j = B_j s_j = sigma s_j + sum_{i<j} [y_i (y_i's_j) / s_i'y_i
-  // - a_i (a_i's_j) / s_i'a_i] (pair i taken when s_i'a_i > 0), on wave 0 with lanes over x_free
-  // (two entries per lane, wave sums: no barriers); then every entry of
-  // B = sigma I + sum_i [-(a_i a_i') / s_i'a_i + (y_i y_i') / s_i'y_i] once (as products of the scaled
-  // vectors a_i / sqrt(s_i'a_i), y_i / sqrt(s_i'y_i)), straight to global
-  // memory.  Same model as the dense rank-2 recursion (which re-read and re-wrote B six times).
-  __shared__ double Pa[LM_HIST][NFX], s_sa[LM_HIST], s_sy[LM_HIST];
-  if (tid < 64) {
-    const int k0 = tid, k1 = tid + 64;
-    const bool h0 = k0 < nf, h1 = k1 < nf;
-    for (int j = 0; j < nc; ++j) {
-      const double s0 = h0 ? Ps[j][k0] : 0.0, s1 = h1 ? Ps[j][k1] : 0.0;
-      double v0 = sigma * s0, v1 = sigma * s1;
-      for (int i = 0; i < j; ++i) {
-        if (!(s_sa[i] > 0.0)) continue;  // (uniform)
-        const double a0 = h0 ? Pa[i][k0] : 0.0, a1 = h1 ? Pa[i][k1] : 0.0;
-        const double y0 = h0 ? Py[i][k0] : 0.0, y1 = h1 ? Py[i][k1] : 0.0;
-        const double as = wave_sum(a0 * s0 + a1 * s1) / s_sa[i];
-        const double ys = wave_sum(y0 * s0 + y1 * s1) / s_sy[i];
-        v0 = (v0 - a0 * as) + y0 * ys;
-        v1 = (v1 - a1 * as) + y1 * ys;
-      }
-      if (h0) Pa[j][k0] = v0;
-      if (h1) Pa[j][k1] = v1;
-      const double y0 = h0 ? Py[j][k0] : 0.0, y1 = h1 ? Py[j][k1] : 0.0;
-      const double sa = wave_sum(s0 * v0 + s1 * v1);
-      const double sjy = wave_sum(s0 * y0 + s1 * y1);
-      if (tid == 0) {
-        s_sa[j] = sa;
-        s_sy[j] = sjy;
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // lane 0's s_sa / s_sy visible to the next j
-    }
-    // scaled in place, u_i = a_i / sqrt(s_i'a_i) and v_i = y_i / sqrt(s_i'y_i) (both > 0 for a taken
-    // pair), so that every model entry is a sum of products u_r u_c, v_r v_c: symmetric bit for bit
-    for (int i = 0; i < nc; ++i) {
-      if (!(s_sa[i] > 0.0)) continue;
-      const double qa = sqrt(s_sa[i]), qy = sqrt(s_sy[i]);
-      if (h0) { Pa[i][k0] /= qa; Py[i][k0] /= qy; }
-      if (h1) { Pa[i][k1] /= qa; Py[i][k1] /= qy; }
-    }
-  }
-  __syncthreads();
-  // the taken pairs (s_i'a_i > 0: always, for a positive definite model) in order, as the compact
-  // model the Newton setup expands entry by entry (ipm_newton_setup, Hc)
-  for (int e = tid; e < nc * nf; e += blockDim.x) {
-    const int i = e / nf, k = e - i * nf;
-    if (!(s_sa[i] > 0.0)) continue;
-    int pos = 0;
-    for (int q = 0; q < i; ++q) pos += s_sa[q] > 0.0;
-    hc[2 + pos * nf + k] = Pa[i][k];
-    hc[2 + LM_HIST * nf + pos * nf + k] = Py[i][k];
-  }
-  if (tid == 0) {
-    int nv = 0;
-    for (int q = 0; q < nc; ++q) nv += s_sa[q] > 0.0;
-    hc[0] = sigma;
-    hc[1] = (double)nv;
-  }
-}
-
-// k_lbfgs for nf <= 64 with one wave per instance (four instances per workgroup) and the pair vectors
-// in registers (lane k holds entry k of every stored pair): the same operations in the same order as
-// k_lbfgs runs for such a problem (its kp = 64 split) — the J^T y row partials in its four row groups
-// summed in its order, its block dots as 0 + the wave sum, its recursion — so bitwise the same model,
-// without its barriers and idle waves (that form runs its recursion on one wave of four).
-constexpr int LBW_WAVES = 4;
-__global__ __launch_bounds__(64 * LBW_WAVES) void k_lbfgs_wave(int64_t B, const LbfgsArgs L) {
-  const int n = L.n, m = L.m, nf = L.nf, nw = L.nw, nnz_rec = L.nnz_rec;
-  extern __shared__ double ynw[];  // [LBW_WAVES][m]
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t b = (int64_t)blockIdx.x * LBW_WAVES + wv;
-  if (b >= B || !L.act[b]) return;
-  double* yn = ynw + (size_t)wv * m;
-  const double al = L.alpha[b];
-  for (int r = lane; r < m; r += 64) yn[r] = L.y[b * m + r] + al * L.dy[b * m + r];
-  const int cnt = L.lm_cnt[b], skipped = L.lm_skip[b] + 1;
-  __builtin_amdgcn_wave_barrier();
-  const int shift = cnt == LM_HIST ? 1 : 0, last = cnt - shift;
-  double* gs = L.lm_s + b * (int64_t)LM_HIST * nf;
-  double* gy = L.lm_y + b * (int64_t)LM_HIST * nf;
-  const int k = lane;
-  const bool hk = k < nf;
-  double Ps[LM_HIST], Py[LM_HIST];
-  {  // J_free^T y at both points: the workgroup form's four row groups (rows part, part + 4, ...), each in its
-     // eight-row batches, the group partials summed in order
-    constexpr int PARTS = 4;
-    const double* jnb = L.J_new + b * (int64_t)nnz_rec;
-    const double* job = L.J_old + b * (int64_t)nnz_rec;
-    double pn[PARTS], po[PARTS];
-#pragma unroll
-    for (int part = 0; part < PARTS; ++part) {
-      double jn = 0.0, jo = 0.0;
-      if (hk) lbfgs_jty_part(L.amap, jnb, job, yn, m, nf, k, part, PARTS, jn, jo);
-      pn[part] = jn;
-      po[part] = jo;
-    }
-    double jn = pn[0], jo = po[0];
-#pragma unroll
-    for (int q = 1; q < PARTS; ++q) {
-      jn += pn[q];
-      jo += po[q];
-    }
-#pragma unroll
-    for (int j = 0; j < LM_HIST; ++j) {
-      Ps[j] = 0.0;
-      Py[j] = 0.0;
-      if (hk && j < last) {
-        Ps[j] = gs[(j + shift) * nf + k];
-        Py[j] = gy[(j + shift) * nf + k];
-      }
-    }
-    if (hk) {
-      const double sl = L.w_new[b * nw + k] - L.w_old[b * nw + k];
-      const double gn = L.grad_new ? L.grad_new[b * n + L.free_idx[k]] : 0.0;
-      const double yl = (gn + jn) - (L.gw_old[b * nw + k] + jo);
-#pragma unroll
-      for (int j = 0; j < LM_HIST; ++j)
-        if (j == last) {
-          Ps[j] = sl;
-          Py[j] = yl;
-        }
-    }
-  }
-  // the newest pair (slot `last`, wave-uniform) and the three dots as the workgroup form's block_dot: 0 + the
-  // wave sum of the lanes' products (lanes >= nf contribute 0)
-  double sL = 0.0, yL = 0.0;
-#pragma unroll
-  for (int j = 0; j < LM_HIST; ++j)
-    if (j == last) {
-      sL = Ps[j];
-      yL = Py[j];
-    }
-  auto wdot = [&](double a, double c) {
-    double v = 0.0;
-    if (hk) v += a * c;
-    return 0.0 + wave_sum(v);
-  };
-  const double sy = wdot(sL, yL);
-  const double ss = wdot(sL, sL);
-  const double yy = wdot(yL, yL);
-  double* hc = L.Hq + b * (int64_t)LMC(nf);
-  const bool skip = !(sy > sqrt(DBL_EPSILON) * sqrt(ss) * sqrt(yy));
-  if (skip || L.failed[b]) {
-    if (!L.failed[b] && skipped <= LM_MAX_SKIP) {
-      if (lane == 0) L.lm_skip[b] = (uint8_t)skipped;
-      return;
-    }
-    if (lane == 0) {
-      hc[0] = 1.0;
-      hc[1] = 0.0;
-      L.lm_skip[b] = 0;
-      L.lm_cnt[b] = 0;
-    }
-    return;
-  }
-  const int nc = last + 1;
-  if (hk) {
-#pragma unroll
-    for (int j = 0; j < LM_HIST; ++j)
-      if (j < nc) {
-        gs[j * nf + k] = Ps[j];
-        gy[j * nf + k] = Py[j];
-      }
-  }
-  if (lane == 0) {
-    L.lm_skip[b] = 0;
-    L.lm_cnt[b] = (uint8_t)nc;
-  }
-  const double sigma = fmin(fmax(sy / ss, 1e-8), 1e8);
-  // the recursion (the workgroup form's, lane k0 = k; its second entry k1 = k + 64 >= nf contributes zeros)
-  double Pa[LM_HIST], s_sa[LM_HIST], s_sy[LM_HIST];
-#pragma unroll
-  for (int j = 0; j < LM_HIST; ++j) {
-    Pa[j] = 0.0;
-    s_sa[j] = 0.0;
-    s_sy[j] = 0.0;
-  }
-#pragma unroll
-  for (int j = 0; j < LM_HIST; ++j) {
-    if (j >= nc) break;
-    const double s0 = hk ? Ps[j] : 0.0, s1 = 0.0;
-    double v0 = sigma * s0, v1 = sigma * s1;
-#pragma unroll
-    for (int i = 0; i < j; ++i) {
-      if (!(s_sa[i] > 0.0)) continue;
-      const double a0 = hk ? Pa[i] : 0.0, a1 = 0.0;
-      const double y0 = hk ? Py[i] : 0.0, y1 = 0.0;
-      const double as = wave_sum(a0 * s0 + a1 * s1) / s_sa[i];
-      const double ys = wave_sum(y0 * s0 + y1 * s1) / s_sy[i];
-      v0 = (v0 - a0 * as) + y0 * ys;
-      v1 = (v1 - a1 * as) + y1 * ys;
-    }
-    if (hk) Pa[j] = v0;
-    const double y0 = hk ? Py[j] : 0.0, y1 = 0.0;
-    s_sa[j] = wave_sum(s0 * v0 + s1 * v1);
-    s_sy[j] = wave_sum(s0 * y0 + s1 * y1);
-  }
-#pragma unroll
-  for (int i = 0; i < LM_HIST; ++i) {
-    if (i >= nc) break;
-    if (!(s_sa[i] > 0.0)) continue;
-    const double qa = sqrt(s_sa[i]), qy = sqrt(s_sy[i]);
-    if (hk) {
-      Pa[i] /= qa;
-      Py[i] /= qy;
-    }
-  }
-  int pos = 0;
-#pragma unroll
-  for (int i = 0; i < LM_HIST; ++i) {
-    if (i >= nc) break;
-    if (!(s_sa[i] > 0.0)) continue;
-    if (hk) {
-      hc[2 + pos * nf + k] = Pa[i];
-      hc[2 + LM_HIST * nf + pos * nf + k] = Py[i];
-    }
-    ++pos;
-  }
-  if (lane == 0) {
-    hc[0] = sigma;
-    hc[1] = (double)pos;
-  }
-}
-
-// ---- the restoration phase (IPOPT MinC_1NrmRestorationPhase; batch_ipm.py enter_resto /
-// resto_step / leave_resto restate these kernels) -------------------------------------------
-// The restoration problem of an instance whose line search failed at w_R:
-//   min rho sum(p + n) + eta/2 |D_R (x - x_R)|^2  s.t.  c(w) - p + n = 0,  w in its bounds, p, n >= 0,
-// eta = sqrt(mu_R), D_R = diag(1 / max(1, |x_R|)) over x_free; solved by the same interior-point
-// method (its own barrier parameter, filter and line search; p and n eliminated from the Newton
-// system) until the original infeasibility falls to kappa_resto of its value at the start and the
-// point is acceptable to the original filter and to the iterate where the phase began.
-
-// The accepted point's rows [f | grad (n) | g (m) | J (nnz_rec)] into the iterate's (k_accept_rows),
-// entry q of instance b; k_resto_enter does it for the instances that moved (moved != NULL) in its
-// launch — one launch fewer per iteration.
-struct AcceptRows {
-  const uint8_t* moved;
-  int n, m, nnz;
-  const double *f_n, *grad_n, *g_n, *J_n;
-  double *f, *grad, *g, *J;
-};
-__device__ __forceinline__ void accept_row_entry(const AcceptRows& a, int64_t b, int64_t q) {
-  if (q == 0) { a.f[b] = a.f_n[b]; return; }
-  q -= 1;
-  if (q < a.n) { a.grad[b * a.n + q] = a.grad_n[b * a.n + q]; return; }
-  q -= a.n;
-  if (q < a.m) { a.g[b * a.m + q] = a.g_n[b * a.m + q]; return; }
-  q -= a.m;
-  a.J[b * a.nnz + q] = a.J_n[b * a.nnz + q];
-}
-
-// Entry (RestoIterateInitializer): x_R = w; mu_R = max(mu, |c|inf); p, n from the closed form of the
-// barrier subproblem at fixed x (p - n = c, both positive); their bound multipliers mu_R / p,
-// mu_R / n; the x-bound multipliers min(rho, z); the original filter augmented with the current
-// point (PrepareRestoPhaseStart); an empty restoration filter; a fresh quasi-Newton model; and the
-// least-squares system of the constraint multipliers (W = I, Sigma_p = Sigma_n = 1) for
-// cpl_kkt_qd_solve: r1 = zLR - zUR, r2 = zp - zn, D^-1 = 1/2.
-struct RestoEnterArgs {
-  int m, nw;
-  const uint8_t* failed;
-  const double *c, *w, *zL, *zU, *mu, *theta_k, *phi_k;
-  const uint8_t *hasL, *hasU;
-  double *filt_t, *filt_p;
-  int64_t *fcount, *iters;
-  uint8_t* in_resto;
-  int64_t* n_resto;
-  double *wR, *pR, *nR, *zp, *zn, *zLR, *zUR, *muR, *ftR, *fpR;
-  int64_t* fcR;
-  double *thmaxR, *thminR, *th_o0, *ph_o0, *dwlR;
-  uint8_t *lm_cnt, *lm_skip;
-  double* Hq;
-  int64_t lmc;
-  double *Mw, *r1, *r2, *Dinv;
-  AcceptRows ar;
-  IpmAcceptArgs acc;
-  bool with_accept;
-};
-// instance b's entry by one wave (lane = its lane)
-__device__ __forceinline__ void resto_enter_one(const RestoEnterArgs& E, int64_t b, int lane) {
-  const int m = E.m, nw = E.nw;
-  const uint8_t* __restrict__ failed = E.failed;
-  const double* __restrict__ c = E.c;
-  const double* w = E.w;  // (w, zL, zU, the filter and the counts: stored to by ipm_accept_one below)
-  const double* zL = E.zL;
-  const double* zU = E.zU;
-  const double* __restrict__ mu = E.mu;
-  const double* __restrict__ theta_k = E.theta_k;
-  const double* __restrict__ phi_k = E.phi_k;
-  const uint8_t* __restrict__ hasL = E.hasL;
-  const uint8_t* __restrict__ hasU = E.hasU;
-  double* filt_t = E.filt_t;
-  double* filt_p = E.filt_p;
-  int64_t* fcount = E.fcount;
-  int64_t* iters = E.iters;
-  uint8_t* __restrict__ in_resto = E.in_resto;
-  int64_t* __restrict__ n_resto = E.n_resto;
-  double* __restrict__ wR = E.wR;
-  double* __restrict__ pR = E.pR;
-  double* __restrict__ nR = E.nR;
-  double* __restrict__ zp = E.zp;
-  double* __restrict__ zn = E.zn;
-  double* __restrict__ zLR = E.zLR;
-  double* __restrict__ zUR = E.zUR;
-  double* __restrict__ muR = E.muR;
-  double* __restrict__ ftR = E.ftR;
-  double* __restrict__ fpR = E.fpR;
-  int64_t* __restrict__ fcR = E.fcR;
-  double* __restrict__ thmaxR = E.thmaxR;
-  double* __restrict__ thminR = E.thminR;
-  double* __restrict__ th_o0 = E.th_o0;
-  double* __restrict__ ph_o0 = E.ph_o0;
-  double* __restrict__ dwlR = E.dwlR;
-  uint8_t* __restrict__ lm_cnt = E.lm_cnt;
-  uint8_t* __restrict__ lm_skip = E.lm_skip;
-  double* __restrict__ Hq = E.Hq;
-  const int64_t lmc = E.lmc;
-  double* __restrict__ Mw = E.Mw;
-  double* __restrict__ r1 = E.r1;
-  double* __restrict__ r2 = E.r2;
-  double* __restrict__ Dinv = E.Dinv;
-  const AcceptRows& ar = E.ar;
-  if (E.with_accept) {  // (cpl_ipm_accept for this instance first, in the same launch)
-    ipm_accept_one(E.acc, b, lane);
-    __threadfence_block();  // its filter / count stores before the entry's loads of them
-  }
-  if (ar.moved && ar.moved[b]) {  // (k_accept_rows for the instances that moved, in the same launch)
-    const int64_t L = 1 + ar.n + ar.m + ar.nnz;
-    for (int64_t q = lane; q < L; q += 64) accept_row_entry(ar, b, q);
-    return;
-  }
-  if (!failed[b]) return;
-  const double mub = mu[b];
-  double cinf = 0.0;
-  for (int r = lane; r < m; r += 64) cinf = fmax(cinf, fabs(c[b * m + r]));
-  cinf = wave_max(cinf);
-  const double mr = fmax(mub, cinf);
-  double th = 0.0;
-  for (int r = lane; r < m; r += 64) {
-    const double cr = c[b * m + r];
-    const double a = (mr - RHO_R * cr) / (2.0 * RHO_R);
-    const double nv = a + sqrt(a * a + mr * cr / (2.0 * RHO_R));
-    const double pv = cr + nv;
-    pR[b * m + r] = pv;
-    nR[b * m + r] = nv;
-    zp[b * m + r] = mr / pv;
-    zn[b * m + r] = mr / nv;
-    th += fabs(cr - pv + nv);
-    r2[b * m + r] = mr / pv - mr / nv;
-    Dinv[b * m + r] = 0.5;
-  }
-  th = wave_sum(th);
-  for (int k = lane; k < nw; k += 64) {
-    wR[b * nw + k] = w[b * nw + k];
-    const double zl = hasL[k] ? fmin(zL[b * nw + k], RHO_R) : 0.0;
-    const double zu = hasU[k] ? fmin(zU[b * nw + k], RHO_R) : 0.0;
-    zLR[b * nw + k] = zl;
-    zUR[b * nw + k] = zu;
-    r1[b * nw + k] = zl - zu;
-    for (int j = 0; j < nw; ++j) Mw[(b * nw + k) * nw + j] = j == k ? 1.0 : 0.0;
-  }
-  for (int k = lane; k < FMAX; k += 64) {
-    ftR[b * FMAX + k] = INFINITY;
-    fpR[b * FMAX + k] = INFINITY;
-  }
-  // the original filter augmented with the point where the phase begins
-  const int64_t fc = fcount[b];
-  const int slot = (int)(fc % FMAX);
-  const double tk = theta_k[b], pk = phi_k[b];
-  if (lane == 0) {
-    filt_t[b * FMAX + slot] = (1.0 - GAMMA_TH) * tk;
-    filt_p[b * FMAX + slot] = pk - GAMMA_PHI * tk;
-    fcount[b] = fc + 1;
-    iters[b] += 1;
-    in_resto[b] = 1;
-    n_resto[b] += 1;
-    muR[b] = mr;
-    fcR[b] = 0;
-    thmaxR[b] = 1e4 * fmax(th, 1.0);
-    thminR[b] = 1e-4 * fmax(th, 1.0);
-    th_o0[b] = tk;
-    ph_o0[b] = pk;
-    dwlR[b] = 0.0;
-    lm_cnt[b] = 0;
-    lm_skip[b] = 0;
-    if (Hq) {  // (limited-memory mode only)
-      Hq[b * lmc] = 1.0;
-      Hq[b * lmc + 1] = 0.0;
-    }
-  }
-}
-__global__ __launch_bounds__(256) void k_resto_enter(int64_t B, const RestoEnterArgs E) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B) return;
-  resto_enter_one(E, b, threadIdx.x & 63);
-}
-
-// the restoration problem's optimality error, its monotone barrier update (resetting its filter) and
-// the proximity term's gradient over w.  The restoration problem converged (IPOPT's
-// RestoConvergenceCheck): a point of local infeasibility when the original problem's max |c| exceeds
-// 1e2 tol; otherwise the point is feasible but unacceptable to the original filter — the first time the
-// restoration tolerance is tightened to 1e-2 tol and the phase goes on (resto_tight), the second time
-// the solve ends as a restoration failure (IPOPT's RESTORATION_CONVERGED_TO_FEASIBLE_POINT)
-// The restoration phase's buffers, for k_resto_prep1, k_resto_judge and k_resto_accept below (resto_args()
-// builds it once per phase).  k_resto_prep2 and k_resto_post keep positional __restrict__ parameters: as
-// struct members without the no-alias promise both compiled to more registers and lost occupancy.
-struct RestoArgs {
-  int m = 0, nf = 0, nw = 0, nbounds = 0;
-  double tol = 0.0, mu_min = 0.0;
-  int64_t lmc = 0;
-  const int32_t* row_slack = nullptr;
-  const double* gl = nullptr;
-  Bounds bd;
-  Iterate it;    // w, y and the restoration problem's bound multipliers zLR, zUR
-  RestoVars rv;
-  Step sp;
-  Search ls;     // the restoration problem's own search: mu_R, theta_R, phi_R, its filter
-  Staged st;
-  double *dp = nullptr, *dn = nullptr, *dzp = nullptr, *dzn = nullptr, *tauR = nullptr, *gfR = nullptr;
-  double* a_z = nullptr;                                        // the restoration step's dual step length
-  const double *A = nullptr, *c = nullptr;                      // at the iterate
-  const double *wt = nullptr, *f_t = nullptr, *g_t = nullptr;   // the first trial
-  const double *f_n = nullptr, *g_n = nullptr;                  // the accepted point
-  uint8_t *active = nullptr, *in_resto = nullptr, *resto_tight = nullptr, *movedR = nullptr;
-  int64_t *status = nullptr, *iters = nullptr, *fcR = nullptr, *acc = nullptr;
-  // the original problem's state the return test reads and the return resets
-  const double *mu = nullptr, *filt_t = nullptr, *filt_p = nullptr, *th_o0 = nullptr, *ph_o0 = nullptr;
-  double *zL = nullptr, *zU = nullptr;
-  uint8_t *lm_cnt = nullptr, *lm_skip = nullptr;
-  double* Hq = nullptr;
-};
-__global__ __launch_bounds__(256) void k_resto_prep1(int64_t B, const RestoArgs R) {
-  const int m = R.m, nf = R.nf, nw = R.nw;
-  const auto [hasL, hasU, wl0, wu0] = R.bd;
-  const auto [w, y, zLR, zUR] = R.it;
-  const auto [wR, pR, nR, zp, zn] = R.rv;
-  const auto [actR, searching, alpha, a_min, muR, thetaR, phiR, gdR, switchR, thmaxR, ftR, fpR] = R.ls;
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
-  const bool a = R.active[b] && R.in_resto[b];
-  if (!a) {
-    if (lane == 0) actR[b] = 0;
-    return;
-  }
-  const double* Ab = R.A + b * (int64_t)m * nw;
-  double mu = muR[b];
-  double eta = sqrt(mu);
-  double dmax = 0.0, zs = 0.0, cmax = 0.0, ys = 0.0, crmax = 0.0;
-  double clv[2] = {0, 0}, cuv[2] = {0, 0};
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int k = lane + 64 * h;
-    if (k < nw) {
-      const double wk = w[b * nw + k];
-      const double dr = k < nf ? 1.0 / fmax(fabs(wR[b * nw + k]), 1.0) : 0.0;
-      double dual = k < nf ? eta * (dr * dr) * (wk - wR[b * nw + k]) : 0.0;
-      dual = seq_dot_acc(dual, Ab + k, nw, y + b * m, m);
-      const double zl = zLR[b * nw + k], zu = zUR[b * nw + k];
-      dual = dual - zl + zu;
-      dmax = fmax(dmax, fabs(dual));
-      zs += fabs(zl) + fabs(zu);
-      clv[h] = hasL[k] ? (wk - wl0[k]) * zl : 0.0;
-      cuv[h] = hasU[k] ? (wu0[k] - wk) * zu : 0.0;
-      cmax = fmax(cmax, fmax(clv[h], cuv[h]));
-    }
-  }
-  double cp[2] = {0, 0}, cn[2] = {0, 0}, cinf = 0.0;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int r = lane + 64 * h;
-    if (r < m) {
-      const double yr = y[b * m + r], pv = pR[b * m + r], nv = nR[b * m + r], zpv = zp[b * m + r], znv = zn[b * m + r];
-      dmax = fmax(dmax, fmax(fabs(RHO_R - yr - zpv), fabs(RHO_R + yr - znv)));
-      zs += fabs(zpv) + fabs(znv);
-      ys += fabs(yr);
-      crmax = fmax(crmax, fabs(R.c[b * m + r] - pv + nv));
-      cinf = fmax(cinf, fabs(R.c[b * m + r]));
-      cp[h] = pv * zpv;
-      cn[h] = nv * znv;
-      cmax = fmax(cmax, fmax(cp[h], cn[h]));
-    }
-  }
-  dmax = wave_max(dmax);
-  cmax = wave_max(cmax);
-  crmax = wave_max(crmax);
-  zs = wave_sum(zs);
-  ys = wave_sum(ys);
-  const int nbR = R.nbounds + 2 * m;
-  const double sd = fmax((ys + zs) / (double)max(m + nbR, 1), 100.0) / 100.0;
-  const double sc = fmax(zs / (double)max(nbR, 1), 100.0) / 100.0;
-  const double base = fmax(dmax / sd, crmax);
-  const double err0 = fmax(base, cmax / sc);
-  const bool tight = R.resto_tight[b] != 0;
-  if (err0 <= (tight ? 1e-2 * R.tol : R.tol)) {  // the restoration problem converged
-    cinf = wave_max(cinf);
-    const bool feasible = cinf <= 1e2 * R.tol;
-    if (!feasible || tight) {
-      if (lane == 0) {
-        R.status[b] = feasible ? CPL_SOLVE_RESTO_FAILED : CPL_SOLVE_INFEASIBLE;
-        R.active[b] = 0;
-        actR[b] = 0;
-      }
-      return;
-    }
-    if (lane == 0) R.resto_tight[b] = 1;  // once: the restoration tolerance 1e-2 tol, and on
-  }
-  bool reset = false;
-  for (int round = 0; round < MU_ROUNDS; ++round) {
-    double em = 0.0;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int k = lane + 64 * h;
-      if (k < nw) {
-        if (hasL[k]) em = fmax(em, fabs(clv[h] - mu));
-        if (hasU[k]) em = fmax(em, fabs(cuv[h] - mu));
-      }
-      if (lane + 64 * h < m) em = fmax(em, fmax(fabs(cp[h] - mu), fabs(cn[h] - mu)));
-    }
-    em = wave_max(em);
-    if (fmax(base, em / sc) <= 10.0 * mu && mu > R.mu_min) {
-      mu = fmax(fmin(0.2 * mu, pow(mu, 1.5)), R.mu_min);
-      reset = true;
-    }
-  }
-  if (reset) {
-    for (int k = lane; k < FMAX; k += 64) {
-      ftR[b * FMAX + k] = INFINITY;
-      fpR[b * FMAX + k] = INFINITY;
-    }
-  }
-  eta = sqrt(mu);
-  for (int k = lane; k < nw; k += 64) {
-    const double dr = k < nf ? 1.0 / fmax(fabs(wR[b * nw + k]), 1.0) : 0.0;
-    R.gfR[b * nw + k] = k < nf ? eta * (dr * dr) * (w[b * nw + k] - wR[b * nw + k]) : 0.0;
-  }
-  if (lane == 0) {
-    actR[b] = 1;
-    muR[b] = mu;
-    R.tauR[b] = fmax(1.0 - mu, 0.99);
-    if (reset) R.fcR[b] = 0;
-  }
-}
-
-// a restoration phase that failed (k_resto_prep1: RESTO_FAILED) with a backup acceptable point: IPOPT
-// restores that point and stops there as acceptable (BacktrackingLineSearch: RestoreAcceptablePoint,
-// STOP_AT_ACCEPTABLE_POINT); batch_ipm.py resto_step restates it
-__global__ __launch_bounds__(256) void k_restore_acc(int64_t B, int m, int nw, int64_t* __restrict__ status,
-                                                     uint8_t* __restrict__ has_acc, const double* __restrict__ acc_w,
-                                                     const double* __restrict__ acc_y, const double* __restrict__ acc_zL,
-                                                     const double* __restrict__ acc_zU, double* __restrict__ w,
-                                                     double* __restrict__ y, double* __restrict__ zL,
-                                                     double* __restrict__ zU) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B || status[b] != CPL_SOLVE_RESTO_FAILED || !has_acc[b]) return;
-  const int lane = threadIdx.x & 63;
-  for (int k = lane; k < nw; k += 64) {
-    w[b * nw + k] = acc_w[b * nw + k];
-    zL[b * nw + k] = acc_zL[b * nw + k];
-    zU[b * nw + k] = acc_zU[b * nw + k];
-  }
-  for (int r = lane; r < m; r += 64) y[b * m + r] = acc_y[b * m + r];
-  __builtin_amdgcn_wave_barrier();  // (one wave per instance: its lanes read status / has_acc above)
-  if (lane == 0) {
-    status[b] = CPL_SOLVE_ACCEPTABLE;
-    has_acc[b] = 0;
-  }
-}
-
-// after the Newton setup (M = diag(Sigma_R) + H_c, r1 = -(grad phi_R,w + A^T y)): the proximity
-// term's Hessian eta D_R^2 on M's diagonal, the eliminated p / n blocks (Sigma_p = zp / p,
-// Sigma_n = zn / n, D^-1 = 1 / (1/Sigma_p + 1/Sigma_n), r2 = -(c - p + n) + r_p / Sigma_p - r_n / Sigma_n)
-// and the restoration problem's theta and barrier objective phi_R
-__global__ __launch_bounds__(256) void k_resto_prep2(
-    int64_t B, int m, int nf, int nw, const uint8_t* __restrict__ actR, const double* __restrict__ c,
-    const double* __restrict__ w, const double* __restrict__ y, const double* __restrict__ wR,
-    const double* __restrict__ pR, const double* __restrict__ nR, const double* __restrict__ zp,
-    const double* __restrict__ zn, const double* __restrict__ muR, const uint8_t* __restrict__ hasL,
-    const uint8_t* __restrict__ hasU, const double* __restrict__ wl0, const double* __restrict__ wu0,
-    double* __restrict__ M, double* __restrict__ rp, double* __restrict__ rn, double* __restrict__ Dinv,
-    double* __restrict__ r2, double* __restrict__ thetaR, double* __restrict__ phiR) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B || !actR[b]) return;
-  const int lane = threadIdx.x & 63;
-  const double mu = muR[b], eta = sqrt(mu);
-  double prox = 0.0, lg = 0.0, th = 0.0, pn = 0.0, lpn = 0.0;
-  for (int k = lane; k < nw; k += 64) {
-    const double wk = w[b * nw + k];
-    if (k < nf) {
-      const double dr = 1.0 / fmax(fabs(wR[b * nw + k]), 1.0);
-      const double d2 = dr * dr;
-      M[(b * nw + k) * nw + k] += eta * d2;
-      const double dx = wk - wR[b * nw + k];
-      prox += d2 * (dx * dx);
-    }
-    if (hasL[k]) lg += log(wk - wl0[k]);
-    if (hasU[k]) lg += log(wu0[k] - wk);
-  }
-  for (int r = lane; r < m; r += 64) {
-    const double pv = pR[b * m + r], nv = nR[b * m + r], yr = y[b * m + r];
-    const double sp = zp[b * m + r] / pv, sn = zn[b * m + r] / nv;
-    const double a = -((RHO_R - mu / pv) - yr), q = -((RHO_R - mu / nv) + yr);
-    const double cr = c[b * m + r] - pv + nv;
-    rp[b * m + r] = a;
-    rn[b * m + r] = q;
-    Dinv[b * m + r] = 1.0 / (1.0 / sp + 1.0 / sn);
-    r2[b * m + r] = -cr + a / sp - q / sn;
-    th += fabs(cr);
-    pn += pv + nv;
-    lpn += log(pv) + log(nv);
-  }
-  prox = wave_sum(prox);
-  lg = wave_sum(lg);
-  th = wave_sum(th);
-  pn = wave_sum(pn);
-  lpn = wave_sum(lpn);
-  if (lane == 0) {
-    thetaR[b] = th;
-    phiR[b] = RHO_R * pn + 0.5 * eta * prox - mu * lg - mu * lpn;
-  }
-}
-
-// after the restoration Newton step: dp, dn, the bound-multiplier steps, the fraction-to-the-boundary
-// steps (primal over w, p, n; dual over zLR, zUR, zp, zn), gd = grad phi_R . (dw, dp, dn), the
-// switching condition, alpha_min and the line search's state
-__global__ __launch_bounds__(256) void k_resto_post(
-    int64_t B, int m, int nw, const uint8_t* __restrict__ actR, const double* __restrict__ w,
-    const double* __restrict__ dw, const double* __restrict__ dy, const double* __restrict__ gphi,
-    const double* __restrict__ pR, const double* __restrict__ nR, const double* __restrict__ zp,
-    const double* __restrict__ zn, const double* __restrict__ zLR, const double* __restrict__ zUR,
-    const double* __restrict__ rp, const double* __restrict__ rn, const double* __restrict__ muR,
-    const double* __restrict__ tauR, const uint8_t* __restrict__ hasL, const uint8_t* __restrict__ hasU,
-    const double* __restrict__ wl0, const double* __restrict__ wu0, const double* __restrict__ thetaR,
-    const double* __restrict__ thminR, const double* __restrict__ f, const double* __restrict__ g,
-    double* __restrict__ dp, double* __restrict__ dn, double* __restrict__ dzL, double* __restrict__ dzU,
-    double* __restrict__ dzp, double* __restrict__ dzn, double* __restrict__ a_max, double* __restrict__ a_z,
-    double* __restrict__ gdR, uint8_t* __restrict__ switchR, double* __restrict__ a_min,
-    uint8_t* __restrict__ searching, double* __restrict__ st_f, double* __restrict__ st_g, double* __restrict__ st_w,
-    double* __restrict__ st_p, double* __restrict__ st_n, double* __restrict__ st_alpha, uint8_t* __restrict__ st_aug,
-    double* __restrict__ alpha, uint8_t* __restrict__ any) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
-  if (b == 0 && lane == 0 && any) any[2] = 0;
-  if (!actR[b]) return;
-  const double mu = muR[b], t = tauR[b];
-  double rpmax = INFINITY, rz = INFINITY, gd = 0.0;
-  for (int k = lane; k < nw; k += 64) {
-    const double wk = w[b * nw + k], dk = dw[b * nw + k];
-    gd += gphi[b * nw + k] * dk;
-    double dzl = 0.0, dzu = 0.0;
-    if (hasL[k]) {
-      const double dl = wk - wl0[k], zl = zLR[b * nw + k];
-      dzl = mu / dl - zl - zl / dl * dk;
-      if (dk < 0.0) rpmax = fmin(rpmax, -t * dl / dk);
-      if (dzl < 0.0) rz = fmin(rz, -t * zl / dzl);
-    }
-    if (hasU[k]) {
-      const double du = wu0[k] - wk, zu = zUR[b * nw + k];
-      dzu = mu / du - zu + zu / du * dk;
-      if (dk > 0.0) rpmax = fmin(rpmax, -t * du / -dk);
-      if (dzu < 0.0) rz = fmin(rz, -t * zu / dzu);
-    }
-    dzL[b * nw + k] = dzl;
-    dzU[b * nw + k] = dzu;
-    st_w[b * nw + k] = wk;
-  }
-  for (int r = lane; r < m; r += 64) {
-    const double pv = pR[b * m + r], nv = nR[b * m + r], zpv = zp[b * m + r], znv = zn[b * m + r];
-    const double dyr = dy[b * m + r];
-    const double sp = zpv / pv, sn = znv / nv;
-    const double dpv = (rp[b * m + r] + dyr) / sp, dnv = (rn[b * m + r] - dyr) / sn;
-    const double dzpv = mu / pv - zpv - zpv / pv * dpv, dznv = mu / nv - znv - znv / nv * dnv;
-    dp[b * m + r] = dpv;
-    dn[b * m + r] = dnv;
-    dzp[b * m + r] = dzpv;
-    dzn[b * m + r] = dznv;
-    gd += (RHO_R - mu / pv) * dpv + (RHO_R - mu / nv) * dnv;
-    if (dpv < 0.0) rpmax = fmin(rpmax, -t * pv / dpv);
-    if (dnv < 0.0) rpmax = fmin(rpmax, -t * nv / dnv);
-    if (dzpv < 0.0) rz = fmin(rz, -t * zpv / dzpv);
-    if (dznv < 0.0) rz = fmin(rz, -t * znv / dznv);
-    st_g[b * m + r] = g[b * m + r];
-    st_p[b * m + r] = pv;
-    st_n[b * m + r] = nv;
-  }
-  rpmax = wave_min_d(rpmax);
-  rz = wave_min_d(rz);
-  gd = wave_sum(gd);
-  if (lane == 0) {
-    const double am = fmin(rpmax, 1.0);
-    a_max[b] = am;
-    a_z[b] = fmin(rz, 1.0);
-    gdR[b] = gd;
-    const double th = thetaR[b];
-    switchR[b] = ls_switch_flags(th, thminR[b], gd);
-    a_min[b] = alpha_min_of(th, gd, thminR[b]);
-    searching[b] = 1;
-    st_f[b] = f[b];
-    st_alpha[b] = 0.0;
-    st_aug[b] = 0;
-    alpha[b] = am;
-  }
-}
-
-// the restoration line search's acceptance test at one trial point (p, n along with w) and the take
-__global__ __launch_bounds__(256) void k_resto_judge(int64_t B, const RestoArgs R) {
-  const int m = R.m, nf = R.nf, nw = R.nw;
-  const auto [hasL, hasU, wl0, wu0] = R.bd;
-  const auto [wR, pR, nR, zp, zn] = R.rv;
-  const auto [actR, searching, alpha, a_min, muR, thetaR, phiR, gdR, switchR, thmaxR, ftR, fpR] = R.ls;
-  const auto [st_f, st_g, st_w, st_alpha, st_aug, st_p, st_n] = R.st;
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B || !searching[b]) return;
-  const int lane = threadIdx.x & 63;
-  const double al = alpha[b], mu = muR[b], eta = sqrt(mu);
-  const double* wb = R.wt + b * nw;
-  double th = 0.0, pn = 0.0, lpn = 0.0, prox = 0.0, lg = 0.0;
-  for (int r = lane; r < m; r += 64) {
-    const double pt = pR[b * m + r] + al * R.dp[b * m + r], nt = nR[b * m + r] + al * R.dn[b * m + r];
-    th += fabs(cons_row(R.g_t + b * m, wb, nf, r, R.row_slack, R.gl) - pt + nt);
-    pn += pt + nt;
-    lpn += log(pt) + log(nt);
-  }
-  for (int k = lane; k < nw; k += 64) {
-    if (k < nf) {
-      const double dr = 1.0 / fmax(fabs(wR[b * nw + k]), 1.0);
-      const double dx = wb[k] - wR[b * nw + k];
-      prox += (dr * dr) * (dx * dx);
-    }
-    if (hasL[k]) lg += log(wb[k] - wl0[k]);
-    if (hasU[k]) lg += log(wu0[k] - wb[k]);
-  }
-  th = wave_sum(th);
-  pn = wave_sum(pn);
-  lpn = wave_sum(lpn);
-  prox = wave_sum(prox);
-  lg = wave_sum(lg);
-  const double ph = RHO_R * pn + 0.5 * eta * prox - mu * lg - mu * lpn;
-  bool h = false;
-  const bool ok = acceptable_wave(th, ph, thetaR[b], phiR[b], gdR[b], al, switchR[b], thmaxR[b], ftR + b * FMAX,
-                                  fpR + b * FMAX, &h);
-  if (!ok) return;
-  for (int r = lane; r < m; r += 64) {
-    st_g[b * m + r] = R.g_t[b * m + r];
-    st_p[b * m + r] = pR[b * m + r] + al * R.dp[b * m + r];
-    st_n[b * m + r] = nR[b * m + r] + al * R.dn[b * m + r];
-  }
-  for (int k = lane; k < nw; k += 64) st_w[b * nw + k] = wb[k];
-  if (lane == 0) {
-    st_f[b] = R.f_t[b];
-    st_alpha[b] = al;
-    st_aug[b] = h ? 1 : 0;
-    searching[b] = 0;
-  }
-}
-
-// the restoration iteration's acceptance: a failed line search ends the instance (restoration
-// failed); otherwise y, the bound multipliers (kappa_Sigma safeguard at mu_R), p, n, w, the
-// restoration filter; then the return test (RestoConvergenceCheck: the original theta at most
-// kappa_resto of its value where the phase began, the point acceptable to the original filter and
-// to that iterate) and the return (ComputeBoundMultiplierStep for the original bound multipliers, a
-// reset to 1 when any exceeds 1000, y = 0, a fresh quasi-Newton model)
-__global__ __launch_bounds__(256) void k_resto_accept(int64_t B, const RestoArgs R) {
-  const int m = R.m, nf = R.nf, nw = R.nw;
-  const auto [hasL, hasU, wl0, wu0] = R.bd;
-  const auto [w, y, zLR, zUR] = R.it;
-  const auto [wR, pR, nR, zp, zn] = R.rv;
-  const auto [dw, dy, dzL, dzU] = R.sp;
-  const auto [actR, searching, alpha, a_min, muR, thetaR, phiR, gdR, switchR, thmaxR, ftR, fpR] = R.ls;
-  const auto [st_f, st_g, st_w, st_alpha, st_aug, st_p, st_n] = R.st;
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
-  if (!actR[b]) {
-    if (lane == 0) R.movedR[b] = 0;
-    return;
-  }
-  const double al = st_alpha[b];
-  if (!(al > 0.0)) {
-    // the restoration phase's line search failed: IPOPT's restoration phase for the restoration problem
-    // (RestoRestorationPhase::PerformRestoration) — x (here w) and every multiplier stay, p and n take
-    // the closed-form minimisers of the barrier subproblem at the current c(w) and mu_R (the
-    // restoration phase's start, RestoIterateInitializer), and that is the next iterate.  (g_n = g(w):
-    // the search state's point is the iterate when no trial was taken.)
-    const double mur = muR[b];
-    for (int r = lane; r < m; r += 64) {
-      const double c = cons_row(R.g_n + b * m, st_w + b * nw, nf, r, R.row_slack, R.gl);
-      const double a = (mur - RHO_R * c) / (2.0 * RHO_R);
-      const double nn = a + sqrt(a * a + mur * c / (2.0 * RHO_R));
-      nR[b * m + r] = nn;
-      pR[b * m + r] = c + nn;
-    }
-    if (lane == 0) {
-      R.movedR[b] = 0;
-      R.iters[b] += 1;
-    }
-    return;
-  }
-  const double mur = muR[b], az = R.a_z[b];
-  for (int r = lane; r < m; r += 64) {
-    y[b * m + r] += al * dy[b * m + r];
-    const double pn = st_p[b * m + r], nn = st_n[b * m + r];
-    zp[b * m + r] = fmin(fmax(zp[b * m + r] + az * R.dzp[b * m + r], mur / (KAPPA_SIGMA * pn)), KAPPA_SIGMA * mur / pn);
-    zn[b * m + r] = fmin(fmax(zn[b * m + r] + az * R.dzn[b * m + r], mur / (KAPPA_SIGMA * nn)), KAPPA_SIGMA * mur / nn);
-    pR[b * m + r] = pn;
-    nR[b * m + r] = nn;
-  }
-  for (int k = lane; k < nw; k += 64) {
-    const double wn = st_w[b * nw + k];
-    if (hasL[k]) {
-      const double dl = wn - wl0[k];
-      zLR[b * nw + k] = fmin(fmax(zLR[b * nw + k] + az * dzL[b * nw + k], mur / (KAPPA_SIGMA * dl)), KAPPA_SIGMA * mur / dl);
-    }
-    if (hasU[k]) {
-      const double du = wu0[k] - wn;
-      zUR[b * nw + k] = fmin(fmax(zUR[b * nw + k] + az * dzU[b * nw + k], mur / (KAPPA_SIGMA * du)), KAPPA_SIGMA * mur / du);
-    }
-    w[b * nw + k] = wn;
-  }
-  if (lane == 0) {
-    R.movedR[b] = 1;
-    R.iters[b] += 1;
-    if (st_aug[b]) {
-      const int64_t fc = R.fcR[b];
-      const int slot = (int)(fc % FMAX);
-      const double tk = thetaR[b], pk = phiR[b];
-      ftR[b * FMAX + slot] = (1.0 - GAMMA_TH) * tk;
-      fpR[b * FMAX + slot] = pk - GAMMA_PHI * tk;
-      R.fcR[b] = fc + 1;
-    }
-  }
-  // ---- back to the regular iteration?
-  const double mub = R.mu[b];
-  double th = 0.0, lg = 0.0;
-  for (int r = lane; r < m; r += 64) th += fabs(cons_row(R.g_n + b * m, st_w + b * nw, nf, r, R.row_slack, R.gl));
-  for (int k = lane; k < nw; k += 64) {
-    const double wn = st_w[b * nw + k];
-    if (hasL[k]) lg += log(wn - wl0[k]);
-    if (hasU[k]) lg += log(wu0[k] - wn);
-  }
-  th = wave_sum(th);
-  lg = wave_sum(lg);
-  const double ph = R.f_n[b] - mub * lg;
-  bool rejected = false;
-  for (int k = lane; k < FMAX; k += 64) rejected |= !((th <= R.filt_t[b * FMAX + k]) || (ph <= R.filt_p[b * FMAX + k]));
-  const bool in_filter = __ballot(rejected) == 0;
-  const double t0 = R.th_o0[b];
-  const double p0 = R.ph_o0[b];
-  const bool vs_start = (th - (1.0 - GAMMA_TH) * t0 <= 10.0 * DBL_EPSILON * fabs(t0)) ||
-                        ((ph - p0) - (-GAMMA_PHI * t0) <= 10.0 * DBL_EPSILON * fabs(p0));
-  const bool back = isfinite(th) && isfinite(ph) && th <= KAPPA_RESTO * t0 && in_filter && vs_start;
-  if (!back) return;
-  const double tau = fmax(1.0 - mub, 0.99);
-  double ad = INFINITY;
-  double dzl[2] = {0, 0}, dzu[2] = {0, 0};
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int k = lane + 64 * h;
-    if (k < nw) {
-      const double wr = wR[b * nw + k], wn = st_w[b * nw + k];
-      if (hasL[k]) {
-        const double s0 = wr - wl0[k], s1 = wn - wl0[k], z = R.zL[b * nw + k];
-        dzl[h] = (z * (s0 - s1) + mub) / s0 - z;
-        if (dzl[h] < 0.0) ad = fmin(ad, -tau * z / dzl[h]);
-      }
-      if (hasU[k]) {
-        const double s0 = wu0[k] - wr, s1 = wu0[k] - wn, z = R.zU[b * nw + k];
-        dzu[h] = (z * (s0 - s1) + mub) / s0 - z;
-        if (dzu[h] < 0.0) ad = fmin(ad, -tau * z / dzu[h]);
-      }
-    }
-  }
-  ad = fmin(wave_min_d(ad), 1.0);
-  double zmax = -INFINITY, zl_n[2] = {0, 0}, zu_n[2] = {0, 0};
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int k = lane + 64 * h;
-    if (k < nw) {
-      zl_n[h] = hasL[k] ? R.zL[b * nw + k] + ad * dzl[h] : R.zL[b * nw + k];
-      zu_n[h] = hasU[k] ? R.zU[b * nw + k] + ad * dzu[h] : R.zU[b * nw + k];
-      zmax = fmax(zmax, fmax(zl_n[h], zu_n[h]));
-    }
-  }
-  zmax = wave_max(zmax);
-  const bool big = zmax > BOUND_MULT_RESET;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int k = lane + 64 * h;
-    if (k < nw) {
-      R.zL[b * nw + k] = (big && hasL[k]) ? 1.0 : zl_n[h];
-      R.zU[b * nw + k] = (big && hasU[k]) ? 1.0 : zu_n[h];
-    }
-  }
-  for (int r = lane; r < m; r += 64) y[b * m + r] = 0.0;
-  if (lane == 0) {
-    R.in_resto[b] = 0;
-    R.acc[b] = 0;
-    R.lm_cnt[b] = 0;
-    R.lm_skip[b] = 0;
-    if (R.Hq) {  // (limited-memory mode only)
-      R.Hq[b * R.lmc] = 1.0;
-      R.Hq[b * R.lmc + 1] = 0.0;
-    }
-  }
-}
-
-// the number of instances still active, and of those in the restoration phase, into two ints
-// (read by the host after each iteration): up to COUNT1_MAX instances one workgroup counts them.
-// With a mailbox (coherent pinned host memory: [count, resto, seq]) the two counts also go straight
-// to the host, then the iteration's sequence number (count[2], incremented here) behind a
-// system-scope fence: the host polls seq instead of a D2H copy + stream synchronisation (a blit
-// kernel and two host wake-ups per iteration, ~35 us of a single solve's ~200 us iteration).
-constexpr int64_t COUNT1_MAX = 65536;
-constexpr int64_t TRACK_FUSE_ROWS = 64;  // batches up to this size track the best iterate inside k_count1
-struct TrackBest {  // (small batches) k_track_best's work inside k_count1; best_w == NULL: none
-  int nw;
-  double vtol;
-  const double *w, *f, *g, *gl, *gu;
-  double *best_w, *best_f;
-  const double* dc;  // (scaled solves) the row factors: the violation is the unscaled g's; else NULL
-};
-// max violation of the constraint values g_b [m] against their original bounds (NaN: infinite), on
-// one wave.  dcb (scaled solves: the instance's row factors, else NULL): g_b holds the scaled problem's
-// values dc g, so the original constraint's value is g_b / dc (the bounds, 0 or infinite, are the
-// original ones either way) — fallback_viol_tol applies to the original constraints
-__device__ __forceinline__ double orig_violation_wave(int m, const double* __restrict__ gb,
-                                                      const double* __restrict__ gl, const double* __restrict__ gu,
-                                                      const double* __restrict__ dcb) {
-  double v = 0.0;
-  for (int r = threadIdx.x & 63; r < m; r += 64) {
-    const double gv = dcb ? gb[r] / dcb[r] : gb[r];
-    v = fmax(v, fmax(fmax(gl[r] - gv, gv - gu[r]), 0.0));
-    if (gv != gv) v = INFINITY;
-  }
-  return wave_max(v);
-}
-// k_track_best's work for instance b (one wave)
-__device__ __forceinline__ void track_best_one(const TrackBest& tb, const uint8_t* __restrict__ active, int m,
-                                               int64_t b, int lane) {
-  if (!active[b]) return;
-  const double v = orig_violation_wave(m, tb.g + b * m, tb.gl, tb.gu, tb.dc ? tb.dc + b * m : nullptr);
-  const double fb = tb.f[b];
-  if (!(v <= tb.vtol) || !(fb < tb.best_f[b])) return;
-  for (int k = lane; k < tb.nw; k += 64) tb.best_w[b * tb.nw + k] = tb.w[b * tb.nw + k];
-  if (lane == 0) tb.best_f[b] = fb;
-}
-// the entry's least-squares estimate of a failed instance b, kept when |y|max <= constr_mult_init_max = 1e3
-// (one wave)
-__device__ __forceinline__ void resto_y0_one(int m, const double* __restrict__ dy, double* __restrict__ y, int64_t b,
-                                             int lane) {
-  double mx = 0.0;
-  for (int r = lane; r < m; r += 64) mx = fmax(mx, fabs(dy[b * m + r]));
-  mx = wave_max(mx);
-  for (int r = lane; r < m; r += 64) y[b * m + r] = mx <= 1e3 ? dy[b * m + r] : 0.0;
-}
-__global__ __launch_bounds__(256) void k_resto_y0(int64_t B, int m, const uint8_t* __restrict__ failed,
-                                                  const double* __restrict__ dy, double* __restrict__ y) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b < B && failed[b]) resto_y0_one(m, dy, y, b, threadIdx.x & 63);
-}
-// the two counts into count[0..1] and, with a mailbox, to the host behind the sequence number
-__device__ __forceinline__ void post_counts(int t, int tr, int32_t* __restrict__ count, int32_t* __restrict__ mail) {
-  count[0] = t;
-  count[1] = tr;
-  if (mail) {
-    const int32_t seq = count[2] + 1;
-    count[2] = seq;
-    volatile int32_t* mb = mail;
-    mb[0] = t;
-    mb[1] = tr;
-    __threadfence_system();
-    mb[2] = seq;
-  }
-}
-// the counts by the NT threads of one workgroup into count[0..1], and the mailbox post
-template <int NT>
-__device__ __forceinline__ void count_post(int64_t B, const uint8_t* __restrict__ active,
-                                           const uint8_t* __restrict__ in_resto, int32_t* __restrict__ count,
-                                           int32_t* __restrict__ mail) {
-  __shared__ int s_w[NT / 64], s_r[NT / 64];
-  int c = 0, cr = 0;
-  for (int64_t b = threadIdx.x; b < B; b += NT) {
-    c += active[b] ? 1 : 0;
-    cr += (active[b] && in_resto[b]) ? 1 : 0;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    c += __shfl_xor(c, o);
-    cr += __shfl_xor(cr, o);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    s_w[threadIdx.x >> 6] = c;
-    s_r[threadIdx.x >> 6] = cr;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int t = 0, tr = 0;
-    for (int q = 0; q < NT / 64; ++q) {
-      t += s_w[q];
-      tr += s_r[q];
-    }
-    post_counts(t, tr, count, mail);
-  }
-}
-__global__ __launch_bounds__(1024) void k_count1(int64_t B, const uint8_t* __restrict__ active,
-                                                 const uint8_t* __restrict__ in_resto, int32_t* __restrict__ count,
-                                                 int32_t* __restrict__ mail, int m, const uint8_t* __restrict__ failed,
-                                                 const double* __restrict__ dy, double* __restrict__ y,
-                                                 const TrackBest tb) {
-  const int lane = threadIdx.x & 63;
-  if (tb.best_w)  // k_track_best's work, a wave per instance (the same operations)
-    for (int64_t b = threadIdx.x >> 6; b < B; b += 16) track_best_one(tb, active, m, b, lane);
-  if (failed)  // k_resto_y0's work, a wave per instance (no dependence on the counts below)
-    for (int64_t b = threadIdx.x >> 6; b < B; b += 16)
-      if (failed[b]) resto_y0_one(m, dy, y, b, lane);
-  count_post<1024>(B, active, in_resto, count, mail);
-}
-
-// The small-batch iteration's tail (B <= FUSE_ROWS: a single-instance Solve(), every solve's
-// compacted tail) in ONE launch instead of three (k_resto_enter, cpl_kkt_qd_kernel, k_count1: ~4.5
-// us each at B = 1, latency only), one workgroup per instance: k_resto_enter's work (the accept,
-// the accepted rows, the restoration entry) by its first wave; for an instance whose search failed
-// the entry's least-squares multipliers by the workgroup (qd_solve_block, cpl_kkt_qd_kernel's
-// solve) and k_resto_y0's estimate; k_count1's best-iterate tracking.  Per instance these are the
-// three launches' operations in their order (bitwise the same state).  The last workgroup to arrive
-// (a 64-bit arrival word at count + 4 that also carries the counts, reset by that workgroup for the
-// next replay) posts the active / restoration counts: k_count1's counting.
-constexpr int TAIL_THREADS = 256;
-struct QdSolveArgs {
-  int nw, m;
-  const double *W, *A, *Dinv, *r1, *r2;
-  double *dwl, *dw, *dy, *delta_w, *Kws;
-};
-__global__ __launch_bounds__(TAIL_THREADS) void k_tail_small(int64_t B, const RestoEnterArgs E, const QdSolveArgs Q,
-                                                             const uint8_t* __restrict__ active,
-                                                             const uint8_t* in_resto, int32_t* __restrict__ count,
-                                                             int32_t* __restrict__ mail, double* y,
-                                                             const TrackBest tb) {
-  // (in_resto and y without __restrict__: the entry stores to both through E)
-  extern __shared__ __align__(16) double qd_lds[];
-  const int64_t b = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63;
-  if (tid < 64) resto_enter_one(E, b, lane);
-  __syncthreads();  // (its global stores before the solve's and the tracking's loads of them)
-  const bool fl = E.failed[b] != 0;
-  if (fl) {
-    qd_solve_block<TAIL_THREADS>(b, Q.nw, Q.m, Q.W, Q.A, Q.Dinv, Q.r1, Q.r2, Q.dwl, Q.dw, Q.dy, Q.delta_w, Q.Kws,
-                                 qd_lds);
-    __syncthreads();  // (dy)
-  }
-  if (tid < 64) {
-    if (tb.best_w) track_best_one(tb, active, E.m, b, lane);
-    if (fl) resto_y0_one(E.m, Q.dy, y, b, lane);
-  }
-  // the arrival: ONE 64-bit atomic carries the instance's counts and the arrival itself (bits 0-20
-  // active, 21-41 in the restoration phase, 42- arrivals; B <= FUSE_ROWS), so the last workgroup
-  // reads the totals from its return value — nothing else crosses workgroups, so no device-scope
-  // fences (each an L2 write-back: with them this launch cost as much as the three it replaces)
-  if (tid == 0) {
-    const unsigned long long a = active[b] ? 1ull : 0ull;
-    const unsigned long long r = (a && in_resto[b]) ? 1ull : 0ull;  // (in_resto[b]: this thread's own store)
-    const unsigned long long mine = (1ull << 42) | (r << 21) | a;
-    unsigned long long* acc = reinterpret_cast<unsigned long long*>(count + 4);
-    const unsigned long long tot = atomicAdd(acc, mine) + mine;
-    if ((tot >> 42) == (unsigned long long)B) {
-      atomicExch(acc, 0ull);  // (every workgroup has arrived: reset for the next launch)
-      post_counts((int)(tot & 0x1fffffull), (int)((tot >> 21) & 0x1fffffull), count, mail);
-    }
-  }
-}
-// the accepted point's f, grad, g and Jacobian records into the iterate's, active instances only:
-// one launch over the concatenated row [f | grad (n) | g (m) | J (nnz_rec)]
-__global__ __launch_bounds__(256) void k_accept_rows(int64_t B, const AcceptRows a) {
-  const int64_t L = 1 + a.n + a.m + a.nnz;
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= B * L) return;
-  const int64_t b = e / L;
-  if (!a.moved[b]) return;
-  accept_row_entry(a, b, e - b * L);
-}
-__global__ void k_count_zero(int32_t* __restrict__ count) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) count[0] = count[1] = 0;
-}
-__global__ __launch_bounds__(256) void k_count(int64_t B, const uint8_t* __restrict__ active,
-                                               const uint8_t* __restrict__ in_resto, int32_t* __restrict__ count) {
-  __shared__ int s_cnt[2];
-  if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
-  __syncthreads();
-  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int a = (b < B && active[b]) ? 1 : 0;
-  const int r = (a && in_resto[b]) ? 1 : 0;
-  const unsigned long long bal = __ballot(a), balr = __ballot(r);
-  if ((threadIdx.x & 63) == 0) {
-    if (bal) atomicAdd(&s_cnt[0], __popcll(bal));
-    if (balr) atomicAdd(&s_cnt[1], __popcll(balr));
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (s_cnt[0]) atomicAdd(count, s_cnt[0]);
-    if (s_cnt[1]) atomicAdd(count + 1, s_cnt[1]);
-  }
-}
-
-// ---- active-set compaction (the lock-step batch shrinks to its active instances) ----------
-// pos[j] = the row of the j-th active instance (j < count), one workgroup scanning the flags
-__global__ __launch_bounds__(1024) void k_positions(int64_t B, const uint8_t* __restrict__ active,
-                                                    int32_t* __restrict__ pos) {
-  __shared__ int s_base;
-  __shared__ int s_wave[16];
-  if (threadIdx.x == 0) s_base = 0;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int64_t c0 = 0; c0 < B; c0 += blockDim.x) {
-    const int64_t b = c0 + threadIdx.x;
-    const int a = (b < B && active[b]) ? 1 : 0;
-    const unsigned long long bal = __ballot(a);
-    if (lane == 0) s_wave[wave] = __popcll(bal);
-    __syncthreads();
-    int off = s_base;
-    for (int w = 0; w < wave; ++w) off += s_wave[w];
-    if (a) pos[off + __popcll(bal & ((1ull << lane) - 1ull))] = (int32_t)b;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int t = 0;
-      for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += s_wave[w];
-      s_base += t;
-    }
-    __syncthreads();
-  }
-}
-
-// dst[j] = src[pos[j]] for rows of `len` 8-byte words (j < k); rows j in [k, rows) untouched
-__global__ void k_gather_rows(int64_t k, int64_t len, const int32_t* __restrict__ pos, const uint64_t* __restrict__ src,
-                              uint64_t* __restrict__ dst) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= k * len) return;
-  const int64_t j = e / len;
-  dst[e] = src[(int64_t)pos[j] * len + (e - j * len)];
-}
-__global__ void k_gather_bytes(int64_t k, const int32_t* __restrict__ pos, const uint8_t* __restrict__ src,
-                               uint8_t* __restrict__ dst) {
-  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < k) dst[j] = src[pos[j]];
-}
-
-// the final state of every row that leaves the batch (finished, or at the end: all rows), written
-// to the instance's own position orig[r] of the full-batch result arrays
-struct LeaveArgs {  // rows leaving the batch: k_fallback, then k_scatter_final
-  int n = 0, m = 0, nw = 0;
-  double vtol = 0.0;
-  bool finished_only = false;
-  const int32_t* orig = nullptr;
-  const uint8_t* active = nullptr;
-  Iterate it;
-  const double *dc = nullptr, *df = nullptr, *Xbase = nullptr, *d_inf = nullptr;
-  const double *g = nullptr, *gl = nullptr, *gu = nullptr, *best_w = nullptr, *best_f = nullptr;
-  const int64_t *status = nullptr, *iters = nullptr, *n_resto = nullptr;
-  double *fw = nullptr, *fy = nullptr, *fX = nullptr, *fdinf = nullptr;
-  int64_t *fstatus = nullptr, *fiters = nullptr, *fresto = nullptr;
-  uint8_t* fbest = nullptr;
-};
-__global__ __launch_bounds__(256) void k_scatter_final(int64_t rows, const LeaveArgs a) {
-  const int n = a.n, m = a.m, nw = a.nw;
-  const auto [w, y, zL, zU] = a.it;
-  const int64_t r = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (r >= rows) return;
-  const int32_t o = a.orig[r];
-  if (o < 0 || (a.finished_only && a.active[r])) return;
-  const int lane = threadIdx.x & 63;
-  for (int k = lane; k < nw; k += 64) a.fw[(int64_t)o * nw + k] = w[r * nw + k];
-  // the multipliers of the unscaled problem: (dc y) / df (nlp_scaling; dc = nullptr: unscaled)
-  for (int k = lane; k < m; k += 64)
-    a.fy[(int64_t)o * m + k] = a.dc ? (a.dc[r * m + k] * y[r * m + k]) / a.df[r] : y[r * m + k];
-  for (int k = lane; k < n; k += 64) a.fX[(int64_t)o * n + k] = a.Xbase[r * n + k];
-  if (lane == 0) {
-    a.fdinf[o] = a.d_inf[r];
-    a.fstatus[o] = a.status[r];
-    a.fiters[o] = a.iters[r];
-    a.fresto[o] = a.n_resto[r];
-  }
-}
-
-// the restoration-phase instances whose trial was accepted in the current search
-__global__ void k_moved_r(int64_t B, const uint8_t* __restrict__ actR, const double* __restrict__ st_alpha,
-                          uint8_t* __restrict__ movedR) {
-  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < B) movedR[b] = actR[b] && st_alpha[b] > 0.0;
-}
-
-__global__ void k_gather_i32(int64_t k, const int32_t* __restrict__ pos, const int32_t* __restrict__ src,
-                             int32_t* __restrict__ dst) {
-  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < k) dst[j] = src[pos[j]];
-}
-__global__ void k_pad(int64_t k, int64_t rows, uint8_t* __restrict__ active, int32_t* __restrict__ orig) {
-  const int64_t j = k + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= rows) return;
-  active[j] = 0;
-  orig[j] = -1;
-}
-
-__global__ void k_iota(int64_t B, int32_t* __restrict__ orig) {
-  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < B) orig[b] = (int32_t)b;
-}
-
-// The best iterate of every active instance: after each iteration's acceptance, the current point
-// (w, f, g in sync) replaces the kept one when its original constraints hold to `vtol` and its
-// objective is lower.  (Not IPOPT: a solve that ends without convergence at an infeasible iterate
-// returns this one instead, k_fallback.)
-__global__ __launch_bounds__(256) void k_track_best(int64_t B, int m, const uint8_t* __restrict__ active,
-                                                    const TrackBest tb) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b < B) track_best_one(tb, active, m, b, threadIdx.x & 63);
-}
-
-// Rows leaving the batch (finished ones, or every row at the end): an instance that stopped without
-// converging (max_iter, local infeasibility, restoration failure) at an iterate violating its
-// constraints by more than `vtol` returns its best feasible iterate (k_track_best) when it met one;
-// fbest[orig] records it
-__global__ __launch_bounds__(256) void k_fallback(int64_t rows, const LeaveArgs a) {
-  const int m = a.m, nw = a.nw;
-  const auto [w, y, zL, zU] = a.it;
-  const int64_t r = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (r >= rows) return;
-  const int32_t o = a.orig[r];
-  if (o < 0 || (a.finished_only && a.active[r]) || a.status[r] <= CPL_SOLVE_ACCEPTABLE) return;
-  const double v = orig_violation_wave(m, a.g + r * m, a.gl, a.gu, a.dc ? a.dc + r * m : nullptr);
-  if (v <= a.vtol || !(a.best_f[r] < INFINITY)) return;
-  const int lane = threadIdx.x & 63;
-  for (int k = lane; k < nw; k += 64) w[r * nw + k] = a.best_w[r * nw + k];
-  if (lane == 0) a.fbest[o] = 1;
-}
-
-__global__ void k_fill(int64_t B, double v, double* __restrict__ out) {
-  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b < B) out[b] = v;
-}
-
-// max_wall_time: every still-active row stops with its current iterate
-__global__ void k_time_limit(int64_t B, uint8_t* __restrict__ active, int64_t* __restrict__ status) {
-  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B || !active[b]) return;
-  status[b] = CPL_SOLVE_TIME_LIMIT;
-  active[b] = 0;
-}
-
-// CPL_TERM_IPOPT: the unscaled measures and the bound multipliers of the rows leaving the batch, beside
-// k_scatter_final's results (an element of z per thread; the row's first also copies the measures)
-__global__ void k_scatter_term(int64_t total, int nw, bool finished_only, const int32_t* __restrict__ orig,
-                               const uint8_t* __restrict__ active, const double* __restrict__ du,
-                               const double* __restrict__ cv, const double* __restrict__ cp,
-                               const double* __restrict__ zL, const double* __restrict__ zU, double* __restrict__ fdu,
-                               double* __restrict__ fcv, double* __restrict__ fcp, double* __restrict__ fzL,
-                               double* __restrict__ fzU) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= total) return;
-  const int64_t r = e / nw;
-  const int k = (int)(e - r * nw);
-  const int32_t o = orig[r];
-  if (o < 0 || (finished_only && active[r])) return;
-  fzL[(int64_t)o * nw + k] = zL[e];
-  fzU[(int64_t)o * nw + k] = zU[e];
-  if (k != 0) return;
-  fdu[o] = du[r];
-  fcv[o] = cv[r];
-  fcp[o] = cp[r];
-}
-
-// results: max violation of g against its bounds, int32 copies of status / iterations
-__global__ __launch_bounds__(256) void k_final(int64_t B, int m, const double* __restrict__ g, const double* __restrict__ gl,
-                                               const double* __restrict__ gu, const int64_t* __restrict__ status,
-                                               const int64_t* __restrict__ iters, double* __restrict__ pinf,
-                                               int32_t* __restrict__ st32, int32_t* __restrict__ it32) {
-  const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-  if (b >= B) return;
-  const int lane = threadIdx.x & 63;
-  double v = 0.0;
-  for (int r = lane; r < m; r += 64) {
-    const double gv = g[b * m + r];
-    v = fmax(v, fmax(fmax(gl[r] - gv, gv - gu[r]), 0.0));
-    if (gv != gv) v = INFINITY;
-  }
-  v = wave_max(v);
-  if (lane == 0) {
-    if (pinf) pinf[b] = v;
-    if (st32) st32[b] = (int32_t)status[b];
-    if (it32) it32[b] = (int32_t)iters[b];
-  }
-}
-
-// the compact limited-memory model of every instance at init_val I: sigma = 1, no pairs
-__global__ void k_lm_init(int64_t B, int nf, double* __restrict__ Hq) {
-  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  Hq[b * LMC(nf)] = 1.0;
-  Hq[b * LMC(nf) + 1] = 0.0;
-}
-
-__global__ void k_repeat(int64_t B, int rep, const double* __restrict__ src, double* __restrict__ dst,
-                         const uint8_t* __restrict__ tsrc, uint8_t* __restrict__ tdst) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= B * rep) return;
-  if (src) dst[e] = src[e / rep];
-  if (tsrc) tdst[e] = tsrc[e / rep];
-}
-
-// ------------------------------------------------------------------------------------------
-struct Arena {
-  char* base = nullptr;
-  size_t cap = 0, used = 0;
-  template <typename T>
-  T* take(size_t count) {
-    const size_t bytes = ((count ? count : 1) * sizeof(T) + 255) & ~size_t(255);
-    T* p = reinterpret_cast<T*>(base + used);
-    used += bytes;
-    return p;
-  }
-};
-
-// cpl_solver_create carves every device buffer through a call that names its class (DESIGN.md §5,
-// "Where the engine's buffers are declared"); compact(), the reset at the head of cpl_solver_solve and
-// the gather scratch's size know the buffers only by the records these calls leave:
-//   fixed  `count` elements, no batch factor (problem constants, flag and count words)
-//   state  [B, width] by batch row, live across iterations: gathered by the compaction when `when`
-//          holds (never at width 0: the limited-memory rows with the mode off)
-//   temp   [B, width] by batch row, written before it is read within an iteration
-//   full   [B, width] by original instance (results, constant zeros)
-// ZEROED: cleared at the start of every solve.
-// (the solve is scaled / has masses / tags / instance data)
-enum MoveWhen : uint8_t { NEVER, ALWAYS, IF_SCALED, IF_MASS, IF_TAG, IF_INST };
-constexpr bool ZEROED = true;
-struct BufRec { void* ptr; size_t elem; int64_t width; MoveWhen when; bool zeroed; };  // elem: bytes; width: per row
-struct Carver {
-  Arena& a;
-  size_t B;
-  std::vector<BufRec>* recs;  // the state and the zeroed buffers, in carve order (null: the measuring pass)
-  size_t row_bytes = 0;       // the widest state row
-  bool ok = true;             // (the 1- and 4-byte gathers move one element per row)
-  template <typename T> T* fixed(size_t count) { return a.take<T>(count); }
-  template <typename T> T* temp(size_t width) { return a.take<T>(B * width); }
-  template <typename T> T* full(size_t width, bool zeroed = false) { return rows<T>(width, NEVER, zeroed); }
-  template <typename T> T* state(size_t width, MoveWhen when, bool zeroed = false) {
-    row_bytes = std::max(row_bytes, width * sizeof(T));
-    ok = ok && when != NEVER && (sizeof(T) == 8 || width == 1);
-    return rows<T>(width, when, zeroed);
-  }
-  template <typename T> T* rows(size_t width, MoveWhen when, bool zeroed) {
-    T* p = a.take<T>(B * width);
-    if (recs && (when != NEVER || zeroed)) recs->push_back({p, sizeof(T), (int64_t)width, when, zeroed});
-    return p;
-  }
-};
-
-}  // namespace
-}  // namespace cpl
-
-struct cpl_solver {
-  cpl_problem_desc desc;
-  cpl_problem_desc desc_R;  // the template with zero cost weights: y^T g's Hessian for the restoration phase
-  cpl_solve_options opt;
-  int64_t B = 0;
-  int64_t Bcur = 0;  // rows in play: B, shrunk by active-set compaction
-  int n = 0, m = 0, nnz = 0, nnz_rec = 0, nf = 0, nI = 0, nw = 0, nbounds = 0;
-  bool analytic_H = false, bfgs = false, fd = false, fd_fused = true;
-  bool ls_fusable = false;  // the one-wave KKT size: the fused line-search kernel can re-solve with its factors
-  bool jreg = false;        // IPOPT's Jacobian regularisation (cpl_kkt_aug_kernel after every KKT call)
-  double* ws_aug = nullptr; // its workspace
-  double mu_min = 0.0;
-  hipStream_t stream = nullptr;
-  bool captured = false;  // an iteration graph exists
-  std::map<int64_t, std::pair<hipGraph_t, hipGraphExec_t>> graphs;  // (size, inputs given, phase) -> graph
-  uint8_t* h_flag = nullptr;  // pinned: the device's 4 flag bytes
-  cpl::Arena arena;
-  std::vector<cpl::BufRec> bufs;  // the state buffers and the zeroed ones, in carve order (cpl::Carver)
-  const double* mass = nullptr;       // per solve
-  const uint8_t* tag = nullptr;
-  // problem constants (device)
-  int32_t *free32, *ineq_row, *row_slack, *freepos, *amap, *col_ptr, *csc_k, *csc_row;
-  int64_t *free64, *fixed64;
-  uint8_t *is_fixed, *hasL, *hasU, *zeros_u8;
-  double *xl, *xu, *gl, *gu, *wl0, *wu0, *zeros_w, *zeros_B;
-  // state
-  double *Xbase, *w, *y, *zL, *zU, *mu, *filt_t, *filt_p, *dwl, *f, *grad, *g, *J, *d_inf, *Hq, *lm_s, *lm_y, *theta_max,
-      *theta_min;
-  int64_t *status, *iters, *acc, *fcount, *n_resto;
-  // d_any [4]: batch-wide "any instance" flags the host reads once per phase (h_flag):
-  //   [0] an instance is still searching after its trials, [1] an instance needs the soft restoration
-  //   step (both set by the search kernels, cpl_kernels.hip cpl_ls_backtrack_kernel / cpl_ipm_judge_take),
-  //   [2] an instance is searching inside the restoration phase.  Who clears them, per iteration:
-  //   * fused search with the post-step prologue (post_in_ls): block 0 of the OPTIMALITY kernel clears
-  //     [0..1] (IpmUnpack.any) — several launches before the search kernel sets them.  Invariant: no
-  //     launch between the two (Hessian / FD evaluation, Newton setup, KKT factorisation) reads or
-  //     writes d_any; the search kernel's own prologue cannot clear them (its other blocks set them
-  //     concurrently: setup.any = nullptr there);
-  //   * fused search without the prologue: the post-step kernel's tail clears [0..1] (LsSetup.any);
-  //   * step-by-step search: a memset of [0..1] before the first trial;
-  //   * [2]: a memset before the restoration phase's search, or block 0 of k_resto_post.
-  //   tests/test_gpu_solve_engine.py covers the fused paths on both sides of LS_GF_MIN (B 2047 / 2048).
-  uint8_t *active, *lm_cnt, *lm_skip, *d_any, *in_soft, *tiny_last, *tiny_flag, *in_resto, *resto_tight;
-  double *best_w, *best_f;  // the best iterate feasible to fallback_viol_tol (lowest f) and its f
-  double *acc_w, *acc_y, *acc_zL, *acc_zU;  // IPOPT's backup acceptable point
-  uint8_t* has_acc;
-  uint8_t* fbest;           // [B] full-batch: the solve returned that iterate instead of its last one
-  int32_t* soft_cnt;
-  // restoration state
-  double *wR, *pR, *nR, *zp, *zn, *zLR, *zUR, *muR, *ftR, *fpR, *th_o0, *ph_o0, *dwlR, *thmaxR, *thminR;
-  int64_t* fcR;
-  // iteration temporaries
-  double *A, *gradw, *c, *err0, *base, *mu_o, *ft, *fp, *tau, *X, *H, *M, *Kqd, *r1, *r2, *gphi,
-      *mr_diag, *theta_k, *phi_k, *dw, *dy, *delta_w, *delta_c, *dzL, *dzU, *a_max, *a_z, *gd, *ws, *a_min, *a_soft,
-      *cs_tmp, *scr1, *scr2;
-  int64_t* fc;
-  int32_t* info;
-  uint8_t *act, *switch_ok, *searching, *st_aug, *ok, *soc, *ok_s, *failed, *moved, *tiny_now, *soft_now, *soft_try;
-  double *st_f, *st_g, *st_w, *st_alpha, *alpha, *th, *wt, *Xt, *f_t, *g_t;
-  double *c_soc, *a_soc, *th_old, *r2s, *dws, *dys, *ws_, *Xs, *f_s, *g_s, *th_s;
-  double *Xn, *f_n, *grad_n, *g_n, *J_n, *Xp, *hfd, *gL, *mass_fd, *jac_fd, *grad_fd;
-  uint8_t* tag_fd;
-  // restoration temporaries
-  double *gfR, *tauR, *rp, *rn, *Dinv, *dp, *dn, *dzp, *dzn, *st_p, *st_n, *thetaR, *phiR, *gdR, *a_maxR, *a_zR,
-      *a_minR, *alphaR;
-  uint8_t *actR, *movedR, *searchingR, *switchR;
-  double *fin_f, *fin_g;
-  // compaction: original instance of each row, compacted masses / tags, full-batch results
-  int32_t *orig, *pos, *d_count, *h_count = nullptr;
-  double *mass_c, *fw, *fy, *fX, *fdinf;
-  uint8_t* tag_c;
-  // this solve's instance data (cpl_solver_solve_inst): the solver's own copies, by batch row (moved by
-  // the compaction with their rows); inst's pointers name them, null where the caller gave no array
-  // (the kernels then read the template's value)
-  double *inst_w, *inst_c, *inst_p, *inst_F;
-  cpl_instance_data inst = {nullptr, nullptr, nullptr, nullptr};
-  bool has_inst = false;
-  int64_t *fstatus, *fiters, *fresto;
-  uint64_t* scratch;
-  int64_t scratch_words = 0;
-  int32_t compactions = 0;
-  // IPOPT's gradient-based NLP scaling (cpl_solve_options.nlp_scaling): df [B], dc [B, m] (rows
-  // compacted with the batch), the Hessian callbacks' multipliers (dc y) / df [B, m]; the records' row
-  // [nnz_rec]; the free-column records of every row (CSR: srp [m + 1], srq); scaled: this solve has a
-  // factor != 1 (the scaling kernels run; graphs keyed by it)
-  double *df, *dc, *ytil;
-  int32_t *rrow, *srp, *srq;
-  int32_t* nan_cnt;  // [B] full batch: NaN Jacobian entries at each instance's start point
-  // CPL_TERM_IPOPT (cpl_term_args): the previous test's objective, the CurrentIsAcceptable byte, the last
-  // regular test's unscaled measures by batch row and by original instance
-  bool term = false;
-  bool term_done = false;  // the last solve ran with it (cpl_solver_unscaled_errors)
-  double *f_prev, *u_dinf, *u_cviol, *u_compl, *fu_dinf, *fu_cviol, *fu_compl, *fzL, *fzU;
-  uint8_t* acc_ok;
-  uint8_t* sc_any;
-  bool scaled = false;
-  bool sc_fused = true;  // the evaluations apply the scaling themselves (until a path says unsupported)
-  // warm start (cpl_solver_solve_warm): which instances start warm [B] (read before the first iteration
-  // only), the "a cold instance exists" byte; and, after every solve, the state to warm-start from by
-  // original instance (cpl_solver_warm_state): unscaled bound multipliers over x [B, n], final mu [B]
-  uint8_t *warm_flag, *warm_any;
-  double *wzL, *wzU, *wmu;
-};
+#include "cpl_solver_common.hpp"
+#include "cpl_solver_start.hpp"
+#include "cpl_solver_search.hpp"
+#include "cpl_solver_lbfgs.hpp"
+#include "cpl_solver_resto.hpp"
+#include "cpl_solver_batch.hpp"
+#include "cpl_solver_state.hpp"
 
 namespace cpl {
 namespace {
@@ -2877,6 +436,26 @@ int32_t step_phase(cpl_solver* S, int phase, const StepMode mode = {}) {
     LAUNCHED(what);
     return CPL_OK;
   };
+  // the accept's tail: the best iterate's tracking, then the active / restoration counts to the host
+  auto count_rows = [&](int ph) -> int32_t {
+    const bool track_fused = o.fallback_viol_tol > 0.0 && B <= TRACK_FUSE_ROWS;
+    const TrackBest tb = track_fused ? track_best(S) : TrackBest{};
+    if (o.fallback_viol_tol > 0.0 && !track_fused) {
+      hipLaunchKernelGGL(k_track_best, dim3(blocks_for(B)), dim3(256), 0, st, B, m, S->active, track_best(S));
+      LAUNCHED("k_track_best");
+    }
+    if (B > COUNT1_MAX) {
+      hipLaunchKernelGGL(k_count_zero, dim3(1), dim3(64), 0, st, S->d_count);
+      LAUNCHED("k_count_zero");
+      hipLaunchKernelGGL(k_count, dim3(blocks_elems(B)), dim3(256), 0, st, B, S->active, S->in_resto, S->d_count);
+    } else {
+      // (with the restoration entry's multiplier reset fused in: P_ACCEPT)
+      hipLaunchKernelGGL(k_count1, dim3(1), dim3(1024), 0, st, B, S->active, S->in_resto, S->d_count, S->h_count, m,
+                         ph == P_ACCEPT ? S->failed : nullptr, S->dy, S->y, tb);
+    }
+    LAUNCHED("k_count");
+    return CPL_OK;
+  };
   // a trial (wt, f, g there, its step al) against the regular search's state; the take into the staged point
   auto judge = [&](const double* wt, const double* ft_, const double* gt_, const double* al, const uint8_t* extra,
                    double* th, uint8_t* ok) {
@@ -3037,9 +616,9 @@ int32_t step_phase(cpl_solver* S, int phase, const StepMode mode = {}) {
       if (phase == P_ACCEPT_NR) {  // no instance can have failed its search: no entry
         CK(ipm_accept_ex(B, acc, st));
         CK(accept_rows(ar, "k_accept_rows"));
-        goto count;
+        return count_rows(phase);
       }
-      {  // the restoration phase starts where the line search failed
+      // the restoration phase starts where the line search failed
       RestoEnterArgs E{m, nw, S->failed, S->c, S->w, S->zL, S->zU, S->mu_o, S->theta_k, S->phi_k, S->hasL, S->hasU,
                        S->filt_t, S->filt_p, S->fcount, S->iters, S->in_resto, S->n_resto, S->wR, S->pR, S->nR, S->zp,
                        S->zn, S->zLR, S->zUR, S->muR, S->ftR, S->fpR, S->fcR, S->thmaxR, S->thminR, S->th_o0, S->ph_o0,
@@ -3062,25 +641,7 @@ int32_t step_phase(cpl_solver* S, int phase, const StepMode mode = {}) {
         hipLaunchKernelGGL(k_resto_y0, dim3(blocks_for(B)), dim3(256), 0, st, B, m, S->failed, S->dy, S->y);
         LAUNCHED("k_resto_y0");
       }
-      }
-    count:
-      const bool track_fused = o.fallback_viol_tol > 0.0 && B <= TRACK_FUSE_ROWS;
-      const TrackBest tb = track_fused ? track_best(S) : TrackBest{};
-      if (o.fallback_viol_tol > 0.0 && !track_fused) {
-        hipLaunchKernelGGL(k_track_best, dim3(blocks_for(B)), dim3(256), 0, st, B, m, S->active, track_best(S));
-        LAUNCHED("k_track_best");
-      }
-      if (B > COUNT1_MAX) {
-        hipLaunchKernelGGL(k_count_zero, dim3(1), dim3(64), 0, st, S->d_count);
-        LAUNCHED("k_count_zero");
-        hipLaunchKernelGGL(k_count, dim3(blocks_elems(B)), dim3(256), 0, st, B, S->active, S->in_resto, S->d_count);
-      } else {
-        // (with the restoration entry's multiplier reset fused in: P_ACCEPT)
-        hipLaunchKernelGGL(k_count1, dim3(1), dim3(1024), 0, st, B, S->active, S->in_resto, S->d_count, S->h_count, m,
-                           phase == P_ACCEPT ? S->failed : nullptr, S->dy, S->y, tb);
-      }
-      LAUNCHED("k_count");
-      return CPL_OK;
+      return count_rows(phase);
     }
     case P_RNEWTON: {
       hipLaunchKernelGGL(k_resto_prep1, dim3(blocks_for(B)), dim3(256), 0, st, B, ra);
@@ -3180,7 +741,6 @@ int32_t run_phase(cpl_solver* S, int phase) {
   return CPL_OK;
 }
 
-// the device's flags (any still searching / soft candidates / restoration searching) to the host
 // wait for iteration `seq`'s counts in the mailbox (k_count1), polling; the stream is queried
 // every 1024 polls so that a failed launch ends the wait with its error
 int32_t wait_mail(cpl_solver* S, int32_t seq) {
@@ -3201,16 +761,13 @@ int32_t wait_mail(cpl_solver* S, int32_t seq) {
   return CPL_OK;
 }
 
+// the device's flags (any still searching / soft candidates / restoration searching) to the host
 int32_t read_flags(cpl_solver* S) {
   HK(hipMemcpyAsync(S->h_flag, S->d_any, 4, hipMemcpyDeviceToHost, S->stream), "hipMemcpyAsync flags");
   HK(hipStreamSynchronize(S->stream), "hipStreamSynchronize");
   return CPL_OK;
 }
 
-// Active-set compaction: the finished rows' results go to the full-batch arrays, the `count` active
-// rows move to the front (every buffer carved as `state` gathered: cpl::Carver), the batch shrinks to
-// Bn rows (the rows past `count` padded inactive), so later iterations cost what their active
-// instances do.
 // the warm-start state of the rows leaving the batch (finished ones at a compaction, every row at the end)
 int32_t scatter_warm(cpl_solver* S, bool finished_only) {
   hipLaunchKernelGGL(k_scatter_warm, dim3(blocks_for(S->Bcur)), dim3(256), 0, S->stream, S->Bcur, S->n, S->nw,
@@ -3220,6 +777,10 @@ int32_t scatter_warm(cpl_solver* S, bool finished_only) {
   return CPL_OK;
 }
 
+// Active-set compaction: the finished rows' results go to the full-batch arrays, the `count` active
+// rows move to the front (every buffer carved as `state` gathered: cpl::Carver), the batch shrinks to
+// Bn rows (the rows past `count` padded inactive), so later iterations cost what their active
+// instances do.
 int32_t compact(cpl_solver* S, int64_t count, int64_t Bn) {
   hipStream_t st = S->stream;
   const int64_t Bc = S->Bcur;
@@ -3266,6 +827,243 @@ int32_t compact(cpl_solver* S, int64_t count, int64_t Bn) {
     LAUNCHED("k_repeat");
   }
   ++S->compactions;
+  return CPL_OK;
+}
+
+// ---- a solve in three parts (cpl_solver_solve_warm), all on the solver's stream --------------------
+// The start: the solver's own copies of the inputs, the resets, Xbase, IPOPT's NLP scaling, the warm
+// flags, the starting iterate (cold, or per instance warm), the least-squares y, the quasi-Newton model.
+// inst: null without instance data; warm: null for a cold solve.
+int32_t solve_start(cpl_solver* S, const double* d_x0, const double* d_mass, const uint8_t* d_env_tag,
+                    const cpl_instance_data* inst, int32_t fixed_from_x0, const cpl_warm_start* warm, int64_t* evals) {
+  const int64_t B = S->B;
+  const int n = S->n, m = S->m, nf = S->nf, nw = S->nw;
+  hipStream_t st = S->stream;
+  S->Bcur = B;
+  S->compactions = 0;
+  // the iteration reads the solver's own copies of the masses / tags (compaction reorders them), so
+  // a captured graph never holds a caller's pointer
+  S->mass = d_mass ? S->mass_c : nullptr;
+  S->tag = d_env_tag ? S->tag_c : nullptr;
+  if (d_mass) HK(hipMemcpyAsync(S->mass_c, d_mass, 8 * (size_t)B, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync mass");
+  if (d_env_tag) HK(hipMemcpyAsync(S->tag_c, d_env_tag, (size_t)B, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync tag");
+  // ... and of the instance data, array by array (an array not given stays the template's value)
+  S->has_inst = inst != nullptr;
+  S->inst = cpl_instance_data{nullptr, nullptr, nullptr, nullptr};
+  if (inst) {
+    const size_t N3 = 3 * (size_t)S->desc.n_contacts;
+    const struct { const double* src; double* dst; const double** slot; size_t width; } arrays[] = {
+        {inst->d_wrench, S->inst_w, &S->inst.d_wrench, 6}, {inst->d_com_ref, S->inst_c, &S->inst.d_com_ref, 3},
+        {inst->d_p_ref, S->inst_p, &S->inst.d_p_ref, N3}, {inst->d_F_ref, S->inst_F, &S->inst.d_F_ref, N3}};
+    for (const auto& a : arrays) {
+      if (!a.src) continue;
+      HK(hipMemcpyAsync(a.dst, a.src, 8 * (size_t)B * a.width, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync instance data");
+      *a.slot = a.dst;
+    }
+  }
+  hipLaunchKernelGGL(k_iota, dim3(blocks_elems(B)), dim3(256), 0, st, B, S->orig);
+  LAUNCHED("k_iota");
+  // the buffers carved ZEROED (per-instance flags and counts of the line search and the restoration
+  // phase) start cleared; the best iterate's objective starts at +inf
+  for (const BufRec& r : S->bufs)
+    if (r.zeroed) HK(hipMemsetAsync(r.ptr, 0, r.elem * (size_t)(B * r.width), st), "hipMemsetAsync");
+  hipLaunchKernelGGL(k_fill, dim3(blocks_elems(B)), dim3(256), 0, st, B, INFINITY, S->best_f);
+  LAUNCHED("k_fill best_f");
+  S->term_done = S->term;
+  if (S->term) {  // IPOPT's last_obj_val starts at -1e50; the measures of an instance never tested read 0
+    hipLaunchKernelGGL(k_fill, dim3(blocks_elems(B)), dim3(256), 0, st, B, -1e50, S->f_prev);
+    LAUNCHED("k_fill f_prev");
+    for (double* p : {S->u_dinf, S->u_cviol, S->u_compl})
+      HK(hipMemsetAsync(p, 0, 8 * (size_t)B, st), "hipMemsetAsync unscaled errors");
+  }
+  S->t_start = std::chrono::steady_clock::now();
+  if (S->fd && (d_mass || d_env_tag)) {
+    hipLaunchKernelGGL(k_repeat, dim3(blocks_elems(B * 2 * nf)), dim3(256), 0, st, B, 2 * nf, S->mass, S->mass_fd,
+                       S->tag, S->tag_fd);
+    LAUNCHED("k_repeat");
+  }
+  // starting point: x pushed into its bounds, slacks = g_I(x) pushed into theirs, least-squares y
+  if (fixed_from_x0) {  // k_xbase with the fixed entries from x0 as well: the copy
+    HK(hipMemcpyAsync(S->Xbase, d_x0, 8 * (size_t)(B * n), hipMemcpyDeviceToDevice, st), "hipMemcpyAsync x0");
+  } else {
+    hipLaunchKernelGGL(k_xbase, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, n, d_x0, S->is_fixed, S->xl, S->Xbase);
+    LAUNCHED("k_xbase");
+  }
+  // IPOPT's gradient-based NLP scaling from the callbacks at the starting point (fixed variables at
+  // their value); the iteration runs on the scaled problem when any instance has a factor != 1
+  // (and the NaN Jacobian entries there: cpl_solver_nan_jacobian)
+  S->scaled = false;
+  CK(eval_full(S, S->Xbase, S->f, S->grad, S->g, S->J));
+  ++*evals;
+  HK(hipMemsetAsync(S->sc_any, 0, 4, st), "hipMemsetAsync");
+  hipLaunchKernelGGL(k_nlp_scaling, dim3(blocks_for(B)), dim3(256), 0, st, B, n, m, S->nnz_rec, S->opt.nlp_scaling,
+                     S->is_fixed, S->row_slack, S->srp, S->srq, S->grad, S->J, S->df, S->dc, S->sc_any, S->nan_cnt);
+  LAUNCHED("k_nlp_scaling");
+  if (S->opt.nlp_scaling) {
+    HK(hipMemcpyAsync(S->h_flag, S->sc_any, 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+    HK(hipStreamSynchronize(st), "hipStreamSynchronize");
+    S->scaled = S->h_flag[0] != 0;
+  }
+  // The one start path: a solve with a warm start launches the <true> instantiations, which select per
+  // instance by wa.flag; a cold solve the <false> ones, which never read wa.
+  const bool is_warm = warm != nullptr;
+  const auto start_x = is_warm ? k_start_x<true> : k_start_x<false>;
+  const auto init_state = is_warm ? k_init_state<true> : k_init_state<false>;
+  const auto y0 = is_warm ? k_y0<true> : k_y0<false>;
+  WarmArgs wa;
+  bool any_cold = true;  // the batch holds an instance that needs the least-squares multipliers
+  if (is_warm) {
+    wa.y_in = warm->d_y; wa.zL_in = warm->d_zL; wa.zU_in = warm->d_zU; wa.mask = warm->d_mask;
+    wa.flag = S->warm_flag; wa.any_cold = S->warm_any;
+    wa.df = S->opt.nlp_scaling ? S->df : nullptr; wa.dc = S->opt.nlp_scaling ? S->dc : nullptr;
+    wa.mu = warm->mu_init > 0.0 ? warm->mu_init : S->opt.mu_init;
+    wa.bound_push = warm->bound_push; wa.bound_frac = warm->bound_frac;
+    wa.slack_push = warm->slack_bound_push; wa.slack_frac = warm->slack_bound_frac; wa.mult_push = warm->mult_bound_push;
+    // which instances start warm, and whether any starts cold (read on the host: it decides the launches below)
+    HK(hipMemsetAsync(S->warm_any, 0, 4, st), "hipMemsetAsync");
+    hipLaunchKernelGGL(k_warm_flag, dim3(blocks_for(B)), dim3(256), 0, st, B, n, m, nf, S->free32, S->hasL, S->hasU, wa);
+    LAUNCHED("k_warm_flag");
+    HK(hipMemcpyAsync(S->h_flag, S->warm_any, 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+    HK(hipStreamSynchronize(st), "hipStreamSynchronize");
+    any_cold = S->h_flag[0] != 0;
+  }
+  hipLaunchKernelGGL(start_x, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, n, S->freepos, S->Xbase, S->hasL,
+                     S->hasU, S->wl0, S->wu0, S->X, wa);
+  LAUNCHED("k_start_x");
+  CK(eval_full(S, S->X, S->f, S->grad, S->g, S->J));
+  ++*evals;
+  hipLaunchKernelGGL(init_state, dim3(blocks_for(B)), dim3(256), 0, st, B, init_state_args(S), wa);
+  LAUNCHED("k_init_state");
+  if (any_cold) {  // (a batch of warm instances only: no least-squares solve)
+    CK(cpl_ipm_dense_a(B, m, nw, nf, S->nnz_rec, S->amap, S->row_slack, S->J, S->A, nullptr, st));
+    CK(cpl_kkt_solve(0, B, nw, m, S->M, S->A, S->r1, S->r2, S->mu, S->zeros_B, nullptr, S->dw, S->dy, S->delta_w,
+                     S->delta_c, S->info, S->ws, st));
+    if (S->jreg)
+      CK(kkt_aug_solve(0, B, nw, m, S->M, S->A, S->r1, S->r2, S->mu, S->zeros_B, nullptr, S->dw, S->dy, S->delta_w,
+                       S->delta_c, S->info, S->ws_aug, st));
+    hipLaunchKernelGGL(y0, dim3(blocks_for(B)), dim3(256), 0, st, B, m, S->dy, S->info, S->y, wa);
+    LAUNCHED("k_y0");
+  }
+  if (S->bfgs) {  // model initialised to init_val I (IPOPT's limited_memory_init_val = 1)
+    hipLaunchKernelGGL(k_lm_init, dim3(blocks_elems(B)), dim3(256), 0, st, B, nf, S->Hq);
+    LAUNCHED("k_lm_init");
+  }
+  return CPL_OK;
+}
+
+// The iteration loop: the phases, the counts (mailbox or copy), max_wall_time, the compaction.  *it: the
+// lock-step iterations run.
+int32_t solve_iterate(cpl_solver* S, int* it_out, int64_t* evals) {
+  hipStream_t st = S->stream;
+  const int64_t ev_newton = (S->fd ? 1 : 0) + 1 + S->opt.max_soc;
+  int it = 0;
+  const int max_iter = S->opt.max_iter;
+  const bool compacting = S->opt.compact != 0 && S->opt.use_graph;
+  const int64_t min_rows = 256;  // (below it a compaction costs more than its smaller iterations save: profiles/r5/compact_floor)
+  int32_t resto_rows = 0;  // instances in the restoration phase after the previous iteration
+  // the mailbox's sequence: the device counter restarts with this solve (the previous solve ended
+  // with a stream synchronisation, so nothing is still writing the host side)
+  int32_t seq = 0;
+  ((volatile int32_t*)S->h_count)[2] = 0;
+  HK(hipMemsetAsync(S->d_count + 2, 0, 4 * sizeof(int32_t), st), "hipMemsetAsync seq");  // (+ k_tail_small's arrivals)
+  while (it < max_iter) {
+    if (S->Bcur <= FUSE_ROWS && S->opt.use_graph) {  // one graph, one host round trip
+      CK(run_phase(S, resto_rows > 0 ? P_FUSED_R : P_FUSED));
+      *evals += ev_newton + 2 + (resto_rows > 0 ? (S->fd ? 1 : 0) + 3 : 0);
+    } else {
+      CK(run_phase(S, P_NEWTON));  // the Newton step and the whole regular line search
+      *evals += ev_newton;
+      CK(read_flags(S));
+      if (S->h_flag[1] || S->h_flag[0]) {  // an instance found no acceptable trial: the soft restoration step
+        CK(run_phase(S, P_SOFT));
+        ++*evals;
+      }
+      const bool may_fail = S->h_flag[1] || S->h_flag[0];
+      if (resto_rows > 0) {  // one restoration-phase iteration of the instances inside it
+        CK(run_phase(S, P_RNEWTON));
+        *evals += (S->fd ? 1 : 0) + 3;
+      }
+      CK(run_phase(S, may_fail ? P_ACCEPT : P_ACCEPT_NR));
+      ++*evals;
+    }
+    ++it;
+    if (S->Bcur <= COUNT1_MAX) {  // k_count1 delivered the counts to the mailbox
+      CK(wait_mail(S, ++seq));
+    } else {
+      HK(hipMemcpyAsync(S->h_count, S->d_count, 8, hipMemcpyDeviceToHost, st), "hipMemcpyAsync count");
+      HK(hipStreamSynchronize(st), "hipStreamSynchronize");
+    }
+    const int64_t cnt = ((volatile int32_t*)S->h_count)[0];
+    resto_rows = ((volatile int32_t*)S->h_count)[1];
+    if (cnt == 0) break;
+    // max_wall_time, at the iteration's host synchronisation: the active rows stop where they are
+    if (S->opt.max_wall_time > 0.0 &&
+        std::chrono::duration<double>(std::chrono::steady_clock::now() - S->t_start).count() > S->opt.max_wall_time) {
+      hipLaunchKernelGGL(k_time_limit, dim3(blocks_elems(S->Bcur)), dim3(256), 0, st, S->Bcur, S->active, S->status);
+      LAUNCHED("k_time_limit");
+      break;
+    }
+    if (compacting && S->Bcur > min_rows && 2 * cnt <= S->Bcur) {
+      // shrink to the smallest halving of the current size that holds the active instances
+      int64_t Bn = S->Bcur;
+      while (Bn / 2 >= cnt && Bn / 2 >= min_rows) Bn = (Bn + 1) / 2;
+      if (Bn < S->Bcur) CK(compact(S, cnt, Bn));
+    }
+  }
+  *it_out = it;
+  return CPL_OK;
+}
+
+// The finish: the final convergence test, the results of every row still in the batch to its instance's
+// place, IPOPT's honor_original_bounds projection with its re-evaluation, the caller's outputs.
+int32_t solve_finish(cpl_solver* S, const double* d_mass, const uint8_t* d_env_tag, const cpl_instance_data* inst,
+                     int32_t fixed_from_x0, double* d_x, double* d_y, int32_t* d_status, int32_t* d_iters, double* d_obj,
+                     double* d_primal_inf, double* d_dual_inf, int64_t* evals) {
+  const int64_t B = S->B;
+  const int n = S->n, m = S->m, nf = S->nf, nw = S->nw;
+  hipStream_t st = S->stream;
+  // final convergence test at the last iterate (the barrier update outputs go to scratch)
+  const int64_t Bc = S->Bcur;
+  CK(cpl_ipm_dense_a(Bc, m, nw, nf, S->nnz_rec, S->amap, S->row_slack, S->J, S->A, S->active, st));
+  hipLaunchKernelGGL(k_prep, dim3(blocks_for(Bc)), dim3(256), 0, st, Bc, n, m, nf, nw, S->free32, S->row_slack, S->gl,
+                     S->grad, S->g, S->w, S->gradw, S->c);
+  LAUNCHED("k_prep");
+  const cpl_term_args term_fin = S->term ? term_args(S, false) : cpl_term_args{};
+  CK(ipm_optimality(opt_args_of(S), nullptr, S->term ? &term_fin : nullptr, st));
+  if (S->term) {
+    hipLaunchKernelGGL(k_scatter_term, dim3(blocks_elems(Bc * nw)), dim3(256), 0, st, Bc * nw, nw, false, S->orig,
+                       S->active, S->u_dinf, S->u_cviol, S->u_compl, S->zL, S->zU, S->fu_dinf, S->fu_cviol, S->fu_compl,
+                       S->fzL, S->fzU);
+    LAUNCHED("k_scatter_term");
+  }
+  const LeaveArgs leave = leave_args(S, false);
+  if (S->opt.fallback_viol_tol > 0.0) {
+    hipLaunchKernelGGL(k_fallback, dim3(blocks_for(Bc)), dim3(256), 0, st, Bc, leave);
+    LAUNCHED("k_fallback");
+  }
+  // every row still in the batch to its instance's place in the full-batch results
+  hipLaunchKernelGGL(k_scatter_final, dim3(blocks_for(Bc)), dim3(256), 0, st, Bc, leave);
+  LAUNCHED("k_scatter_final");
+  CK(scatter_warm(S, false));
+  // IPOPT honor_original_bounds: the final point projected into the original bounds, re-evaluated
+  double* Xf = d_x ? d_x : S->Xn;
+  // (fixed_from_x0: the projection skips the fixed entries — the template's bound is not the instance's value)
+  hipLaunchKernelGGL(fixed_from_x0 ? k_unpack_free : k_unpack, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, n, nw,
+                     S->freepos, S->fX, S->fw, S->xl, S->xu, Xf);
+  LAUNCHED("k_unpack (final)");
+  // (the full batch in the instances' own order: the caller's masses, tags and instance data)
+  if (inst)
+    CK(cpl_eval_batch_inst(&S->desc, B, Xf, d_mass, d_env_tag, inst, S->fin_g, nullptr, d_obj ? d_obj : S->fin_f, nullptr,
+                           nullptr, 0, st));
+  else
+    CK(cpl_eval_batch(&S->desc, B, Xf, d_mass, d_env_tag, S->fin_g, nullptr, d_obj ? d_obj : S->fin_f, nullptr, st));
+  ++*evals;
+  hipLaunchKernelGGL(k_final, dim3(blocks_for(B)), dim3(256), 0, st, B, m, S->fin_g, S->gl, S->gu, S->fstatus,
+                     S->fiters, d_primal_inf, d_status, d_iters);
+  LAUNCHED("k_final");
+  if (d_y) HK(hipMemcpyAsync(d_y, S->fy, 8 * (size_t)B * m, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync y");
+  if (d_dual_inf) HK(hipMemcpyAsync(d_dual_inf, S->fdinf, 8 * (size_t)B, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
+  HK(hipStreamSynchronize(st), "hipStreamSynchronize");
   return CPL_OK;
 }
 
@@ -3739,226 +1537,15 @@ int32_t cpl_solver_solve_warm(cpl_solver* S, const double* d_x0, const double* d
                      warm->mult_bound_push})
       if (!(v >= 0.0)) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_solve_warm: a push or mu_init is negative or NaN");
   }
-  const int64_t B = S->B;
-  const int n = S->n, m = S->m, nf = S->nf, nw = S->nw;
-  hipStream_t st = S->stream;
   // order after the caller's stream (its inputs), then run on the solver's own stream
   HK(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize (caller stream)");
-  S->Bcur = B;
-  S->compactions = 0;
-  // the iteration reads the solver's own copies of the masses / tags (compaction reorders them), so
-  // a captured graph never holds a caller's pointer
-  S->mass = d_mass ? S->mass_c : nullptr;
-  S->tag = d_env_tag ? S->tag_c : nullptr;
-  if (d_mass) HK(hipMemcpyAsync(S->mass_c, d_mass, 8 * (size_t)B, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync mass");
-  if (d_env_tag) HK(hipMemcpyAsync(S->tag_c, d_env_tag, (size_t)B, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync tag");
-  // ... and of the instance data, array by array (an array not given stays the template's value)
-  S->has_inst = has_inst;
-  S->inst = cpl_instance_data{nullptr, nullptr, nullptr, nullptr};
-  if (has_inst) {
-    const size_t N3 = 3 * (size_t)S->desc.n_contacts;
-    const struct { const double* src; double* dst; const double** slot; size_t width; } arrays[] = {
-        {inst->d_wrench, S->inst_w, &S->inst.d_wrench, 6}, {inst->d_com_ref, S->inst_c, &S->inst.d_com_ref, 3},
-        {inst->d_p_ref, S->inst_p, &S->inst.d_p_ref, N3}, {inst->d_F_ref, S->inst_F, &S->inst.d_F_ref, N3}};
-    for (const auto& a : arrays) {
-      if (!a.src) continue;
-      HK(hipMemcpyAsync(a.dst, a.src, 8 * (size_t)B * a.width, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync instance data");
-      *a.slot = a.dst;
-    }
-  }
-  hipLaunchKernelGGL(k_iota, dim3(blocks_elems(B)), dim3(256), 0, st, B, S->orig);
-  LAUNCHED("k_iota");
-  // the buffers carved ZEROED (per-instance flags and counts of the line search and the restoration
-  // phase) start cleared; the best iterate's objective starts at +inf
-  for (const BufRec& r : S->bufs)
-    if (r.zeroed) HK(hipMemsetAsync(r.ptr, 0, r.elem * (size_t)(B * r.width), st), "hipMemsetAsync");
-  hipLaunchKernelGGL(k_fill, dim3(blocks_elems(B)), dim3(256), 0, st, B, INFINITY, S->best_f);
-  LAUNCHED("k_fill best_f");
-  S->term_done = S->term;
-  if (S->term) {  // IPOPT's last_obj_val starts at -1e50; the measures of an instance never tested read 0
-    hipLaunchKernelGGL(k_fill, dim3(blocks_elems(B)), dim3(256), 0, st, B, -1e50, S->f_prev);
-    LAUNCHED("k_fill f_prev");
-    for (double* p : {S->u_dinf, S->u_cviol, S->u_compl})
-      HK(hipMemsetAsync(p, 0, 8 * (size_t)B, st), "hipMemsetAsync unscaled errors");
-  }
-  const auto t_start = std::chrono::steady_clock::now();
-  int64_t evals = 0;
-  if (S->fd && (d_mass || d_env_tag)) {
-    hipLaunchKernelGGL(k_repeat, dim3(blocks_elems(B * 2 * nf)), dim3(256), 0, st, B, 2 * nf, S->mass, S->mass_fd,
-                       S->tag, S->tag_fd);
-    LAUNCHED("k_repeat");
-  }
-  // starting point: x pushed into its bounds, slacks = g_I(x) pushed into theirs, least-squares y
-  if (fixed_from_x0) {  // k_xbase with the fixed entries from x0 as well: the copy
-    HK(hipMemcpyAsync(S->Xbase, d_x0, 8 * (size_t)(B * n), hipMemcpyDeviceToDevice, st), "hipMemcpyAsync x0");
-  } else {
-    hipLaunchKernelGGL(k_xbase, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, n, d_x0, S->is_fixed, S->xl, S->Xbase);
-    LAUNCHED("k_xbase");
-  }
-  // IPOPT's gradient-based NLP scaling from the callbacks at the starting point (fixed variables at
-  // their value); the iteration runs on the scaled problem when any instance has a factor != 1
-  // (and the NaN Jacobian entries there: cpl_solver_nan_jacobian)
-  S->scaled = false;
-  CK(eval_full(S, S->Xbase, S->f, S->grad, S->g, S->J));
-  ++evals;
-  HK(hipMemsetAsync(S->sc_any, 0, 4, st), "hipMemsetAsync");
-  hipLaunchKernelGGL(k_nlp_scaling, dim3(blocks_for(B)), dim3(256), 0, st, B, n, m, S->nnz_rec, S->opt.nlp_scaling,
-                     S->is_fixed, S->row_slack, S->srp, S->srq, S->grad, S->J, S->df, S->dc, S->sc_any, S->nan_cnt);
-  LAUNCHED("k_nlp_scaling");
-  if (S->opt.nlp_scaling) {
-    HK(hipMemcpyAsync(S->h_flag, S->sc_any, 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-    HK(hipStreamSynchronize(st), "hipStreamSynchronize");
-    S->scaled = S->h_flag[0] != 0;
-  }
-  WarmArgs wa;
-  bool any_cold = true;  // the batch holds an instance that needs the least-squares multipliers
-  if (is_warm) {
-    wa.y_in = warm->d_y; wa.zL_in = warm->d_zL; wa.zU_in = warm->d_zU; wa.mask = warm->d_mask;
-    wa.flag = S->warm_flag; wa.any_cold = S->warm_any;
-    wa.df = S->opt.nlp_scaling ? S->df : nullptr; wa.dc = S->opt.nlp_scaling ? S->dc : nullptr;
-    wa.mu = warm->mu_init > 0.0 ? warm->mu_init : S->opt.mu_init;
-    wa.bound_push = warm->bound_push; wa.bound_frac = warm->bound_frac;
-    wa.slack_push = warm->slack_bound_push; wa.slack_frac = warm->slack_bound_frac; wa.mult_push = warm->mult_bound_push;
-    // which instances start warm, and whether any starts cold (read on the host: it decides the launches below)
-    HK(hipMemsetAsync(S->warm_any, 0, 4, st), "hipMemsetAsync");
-    hipLaunchKernelGGL(k_warm_flag, dim3(blocks_for(B)), dim3(256), 0, st, B, n, m, nf, S->free32, S->hasL, S->hasU, wa);
-    LAUNCHED("k_warm_flag");
-    HK(hipMemcpyAsync(S->h_flag, S->warm_any, 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-    HK(hipStreamSynchronize(st), "hipStreamSynchronize");
-    any_cold = S->h_flag[0] != 0;
-    hipLaunchKernelGGL(k_start_x_warm, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, n, S->freepos, S->Xbase,
-                       S->hasL, S->hasU, S->wl0, S->wu0, S->warm_flag, wa.bound_push, wa.bound_frac, S->X);
-    LAUNCHED("k_start_x_warm");
-  } else {
-    hipLaunchKernelGGL(k_start_x, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, n, S->freepos, S->Xbase, S->hasL,
-                       S->hasU, S->wl0, S->wu0, S->X);
-    LAUNCHED("k_start_x");
-  }
-  CK(eval_full(S, S->X, S->f, S->grad, S->g, S->J));
-  ++evals;
-  if (is_warm) {
-    hipLaunchKernelGGL(k_init_state_warm, dim3(blocks_for(B)), dim3(256), 0, st, B, init_state_args(S), wa);
-    LAUNCHED("k_init_state_warm");
-  } else {
-    hipLaunchKernelGGL(k_init_state, dim3(blocks_for(B)), dim3(256), 0, st, B, init_state_args(S));
-    LAUNCHED("k_init_state");
-  }
-  if (any_cold) {  // (a batch of warm instances only: no least-squares solve)
-    CK(cpl_ipm_dense_a(B, m, nw, nf, S->nnz_rec, S->amap, S->row_slack, S->J, S->A, nullptr, st));
-    CK(cpl_kkt_solve(0, B, nw, m, S->M, S->A, S->r1, S->r2, S->mu, S->zeros_B, nullptr, S->dw, S->dy, S->delta_w,
-                     S->delta_c, S->info, S->ws, st));
-    if (S->jreg)
-      CK(kkt_aug_solve(0, B, nw, m, S->M, S->A, S->r1, S->r2, S->mu, S->zeros_B, nullptr, S->dw, S->dy, S->delta_w,
-                       S->delta_c, S->info, S->ws_aug, st));
-    if (is_warm) {
-      hipLaunchKernelGGL(k_y0_warm, dim3(blocks_for(B)), dim3(256), 0, st, B, m, S->dy, S->info, S->warm_flag, S->y);
-      LAUNCHED("k_y0_warm");
-    } else {
-      hipLaunchKernelGGL(k_y0, dim3(blocks_for(B)), dim3(256), 0, st, B, m, S->dy, S->info, S->y);
-      LAUNCHED("k_y0");
-    }
-  }
-  if (S->bfgs) {  // model initialised to init_val I (IPOPT's limited_memory_init_val = 1)
-    hipLaunchKernelGGL(k_lm_init, dim3(blocks_elems(B)), dim3(256), 0, st, B, nf, S->Hq);
-    LAUNCHED("k_lm_init");
-  }
-  const int64_t ev_newton = (S->fd ? 1 : 0) + 1 + S->opt.max_soc;
+  if (!has_inst) inst = nullptr;
   int it = 0;
-  const int max_iter = S->opt.max_iter;
-  const bool compacting = S->opt.compact != 0 && S->opt.use_graph;
-  const int64_t min_rows = 256;  // (below it a compaction costs more than its smaller iterations save: profiles/r5/compact_floor)
-  int32_t resto_rows = 0;  // instances in the restoration phase after the previous iteration
-  // the mailbox's sequence: the device counter restarts with this solve (the previous solve ended
-  // with a stream synchronisation, so nothing is still writing the host side)
-  int32_t seq = 0;
-  ((volatile int32_t*)S->h_count)[2] = 0;
-  HK(hipMemsetAsync(S->d_count + 2, 0, 4 * sizeof(int32_t), st), "hipMemsetAsync seq");  // (+ k_tail_small's arrivals)
-  while (it < max_iter) {
-    if (S->Bcur <= FUSE_ROWS && S->opt.use_graph) {  // one graph, one host round trip
-      CK(run_phase(S, resto_rows > 0 ? P_FUSED_R : P_FUSED));
-      evals += ev_newton + 2 + (resto_rows > 0 ? (S->fd ? 1 : 0) + 3 : 0);
-    } else {
-      CK(run_phase(S, P_NEWTON));  // the Newton step and the whole regular line search
-      evals += ev_newton;
-      CK(read_flags(S));
-      if (S->h_flag[1] || S->h_flag[0]) {  // an instance found no acceptable trial: the soft restoration step
-        CK(run_phase(S, P_SOFT));
-        ++evals;
-      }
-      const bool may_fail = S->h_flag[1] || S->h_flag[0];
-      if (resto_rows > 0) {  // one restoration-phase iteration of the instances inside it
-        CK(run_phase(S, P_RNEWTON));
-        evals += (S->fd ? 1 : 0) + 3;
-      }
-      CK(run_phase(S, may_fail ? P_ACCEPT : P_ACCEPT_NR));
-      ++evals;
-    }
-    ++it;
-    if (S->Bcur <= COUNT1_MAX) {  // k_count1 delivered the counts to the mailbox
-      CK(wait_mail(S, ++seq));
-    } else {
-      HK(hipMemcpyAsync(S->h_count, S->d_count, 8, hipMemcpyDeviceToHost, st), "hipMemcpyAsync count");
-      HK(hipStreamSynchronize(st), "hipStreamSynchronize");
-    }
-    const int64_t cnt = ((volatile int32_t*)S->h_count)[0];
-    resto_rows = ((volatile int32_t*)S->h_count)[1];
-    if (cnt == 0) break;
-    // max_wall_time, at the iteration's host synchronisation: the active rows stop where they are
-    if (S->opt.max_wall_time > 0.0 &&
-        std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count() > S->opt.max_wall_time) {
-      hipLaunchKernelGGL(k_time_limit, dim3(blocks_elems(S->Bcur)), dim3(256), 0, st, S->Bcur, S->active, S->status);
-      LAUNCHED("k_time_limit");
-      break;
-    }
-    if (compacting && S->Bcur > min_rows && 2 * cnt <= S->Bcur) {
-      // shrink to the smallest halving of the current size that holds the active instances
-      int64_t Bn = S->Bcur;
-      while (Bn / 2 >= cnt && Bn / 2 >= min_rows) Bn = (Bn + 1) / 2;
-      if (Bn < S->Bcur) CK(compact(S, cnt, Bn));
-    }
-  }
-  // final convergence test at the last iterate (the barrier update outputs go to scratch)
-  const int64_t Bc = S->Bcur;
-  CK(cpl_ipm_dense_a(Bc, m, nw, nf, S->nnz_rec, S->amap, S->row_slack, S->J, S->A, S->active, st));
-  hipLaunchKernelGGL(k_prep, dim3(blocks_for(Bc)), dim3(256), 0, st, Bc, n, m, nf, nw, S->free32, S->row_slack, S->gl,
-                     S->grad, S->g, S->w, S->gradw, S->c);
-  LAUNCHED("k_prep");
-  const cpl_term_args term_fin = S->term ? term_args(S, false) : cpl_term_args{};
-  CK(ipm_optimality(opt_args_of(S), nullptr, S->term ? &term_fin : nullptr, st));
-  if (S->term) {
-    hipLaunchKernelGGL(k_scatter_term, dim3(blocks_elems(Bc * nw)), dim3(256), 0, st, Bc * nw, nw, false, S->orig,
-                       S->active, S->u_dinf, S->u_cviol, S->u_compl, S->zL, S->zU, S->fu_dinf, S->fu_cviol, S->fu_compl,
-                       S->fzL, S->fzU);
-    LAUNCHED("k_scatter_term");
-  }
-  const LeaveArgs leave = leave_args(S, false);
-  if (S->opt.fallback_viol_tol > 0.0) {
-    hipLaunchKernelGGL(k_fallback, dim3(blocks_for(Bc)), dim3(256), 0, st, Bc, leave);
-    LAUNCHED("k_fallback");
-  }
-  // every row still in the batch to its instance's place in the full-batch results
-  hipLaunchKernelGGL(k_scatter_final, dim3(blocks_for(Bc)), dim3(256), 0, st, Bc, leave);
-  LAUNCHED("k_scatter_final");
-  CK(scatter_warm(S, false));
-  // IPOPT honor_original_bounds: the final point projected into the original bounds, re-evaluated
-  double* Xf = d_x ? d_x : S->Xn;
-  // (fixed_from_x0: the projection skips the fixed entries — the template's bound is not the instance's value)
-  hipLaunchKernelGGL(fixed_from_x0 ? k_unpack_free : k_unpack, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, n, nw,
-                     S->freepos, S->fX, S->fw, S->xl, S->xu, Xf);
-  LAUNCHED("k_unpack (final)");
-  // (the full batch in the instances' own order: the caller's masses, tags and instance data)
-  if (has_inst)
-    CK(cpl_eval_batch_inst(&S->desc, B, Xf, d_mass, d_env_tag, inst, S->fin_g, nullptr, d_obj ? d_obj : S->fin_f, nullptr,
-                           nullptr, 0, st));
-  else
-    CK(cpl_eval_batch(&S->desc, B, Xf, d_mass, d_env_tag, S->fin_g, nullptr, d_obj ? d_obj : S->fin_f, nullptr, st));
-  ++evals;
-  hipLaunchKernelGGL(k_final, dim3(blocks_for(B)), dim3(256), 0, st, B, m, S->fin_g, S->gl, S->gu, S->fstatus,
-                     S->fiters, d_primal_inf, d_status, d_iters);
-  LAUNCHED("k_final");
-  if (d_y) HK(hipMemcpyAsync(d_y, S->fy, 8 * (size_t)B * m, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync y");
-  if (d_dual_inf) HK(hipMemcpyAsync(d_dual_inf, S->fdinf, 8 * (size_t)B, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
-  HK(hipStreamSynchronize(st), "hipStreamSynchronize");
+  int64_t evals = 0;
+  CK(solve_start(S, d_x0, d_mass, d_env_tag, inst, fixed_from_x0, is_warm ? warm : nullptr, &evals));
+  CK(solve_iterate(S, &it, &evals));
+  CK(solve_finish(S, d_mass, d_env_tag, inst, fixed_from_x0, d_x, d_y, d_status, d_iters, d_obj, d_primal_inf, d_dual_inf,
+                  &evals));
   if (iterations_run) *iterations_run = it;
   if (evaluations) *evaluations = evals;
   return CPL_OK;

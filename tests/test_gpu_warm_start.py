@@ -260,6 +260,24 @@ def test_without_warm_data_it_is_cpl_solver_solve_inst(workload, hessian):
     assert bool(half.success.all()) and bool((half.iterations[mask] < c.iterations[mask]).all())
 
 
+@pytest.mark.parametrize("hessian", ["exact", "limited-memory"])
+@pytest.mark.parametrize("nlp_scaling", ["gradient-based", "none"])
+def test_all_cold_warm_batch_is_the_cold_solve(nlp_scaling, hessian):
+    """A warm start whose mask is all False against the cold solve of the same inputs, byte for byte: the
+    start kernels' <true> instantiation on its cold branch (every flag 0) against the <false> one.  B = 6 is
+    one full workgroup of four waves and a partial one: a second block, and the b >= B guard."""
+    prob = solve_problem().GetCplProblem()
+    X0, mass = solve_inputs(prob, 6, seed=17)
+    kw = dict(max_iter=300, hessian=hessian, nlp_scaling=nlp_scaling)
+    cold = batch_ipm_solve(prob, dev(X0), dev(mass), **kw)
+    assert bool(cold.success.all()), cold.status
+    ws = cold.warm_start(mu_init=1e-4, mask=torch.zeros(6, dtype=torch.bool, device=DEV))
+    got = batch_ipm_solve(prob, dev(X0), dev(mass), warm_start=ws, **kw)
+    for k in ("x", "y", "mult_x_L", "mult_x_U", "mu", "status", "iterations"):
+        a, b = (getattr(r, k).contiguous().view(torch.uint8) for r in (got, cold))
+        assert torch.equal(a, b), k
+
+
 # ---- 8. the export survives compaction -----------------------------------------------------------------
 @pytest.mark.parametrize("kw", [dict(), dict(termination="ipopt", nlp_scaling="none"),
                                 dict(hessian="limited-memory")], ids=["default", "ipopt-unscaled", "limited-memory"])
