@@ -8,7 +8,8 @@ Importing it loads ``libcpl_mi355x.so`` and fails loudly if it has not been buil
 from ._abi import (ENV_GROUND, ENV_MIXED, ENV_NONE, ENV_SUPERQUADRIC, INF, MAX_CONTACTS, CplError, InvalidArgument,
                    OutOfRange, ProblemDesc)
 from .planner import CentroidalPlanner, CoMPlanner, ContactValues, Solution
-from .problem import CplProblem, EnvironmentClass, Ground, InstanceData, MixedEnvironment, Superquadric
+from .problem import (CplProblem, EnvironmentClass, Ground, InstanceBounds, InstanceData, MixedEnvironment,
+                      Superquadric)
 
 __all__ = [
     "CentroidalPlanner",
@@ -16,6 +17,7 @@ __all__ = [
     "Solution",
     "ContactValues",
     "CplProblem",
+    "InstanceBounds",
     "InstanceData",
     "EnvironmentClass",
     "Ground",

@@ -148,6 +148,15 @@ class InstanceDataC(ctypes.Structure):
     ]
 
 
+class InstanceBoundsC(ctypes.Structure):
+    """cpl_instance_bounds (include/cpl_mi355x.h): the two device arrays [batch, n], both or neither."""
+
+    _fields_ = [
+        ("d_x_lb", c_void_p),
+        ("d_x_ub", c_void_p),
+    ]
+
+
 class WarmStart(ctypes.Structure):
     """cpl_warm_start (include/cpl_mi355x.h): device pointers (d_mask may be NULL) and the warm_start_* constants."""
 
@@ -320,6 +329,10 @@ SIGNATURES = {
     "cpl_solver_solve_warm": (c_int32, [c_void_p] * 4 + [POINTER(InstanceDataC), c_int32, POINTER(WarmStart)]
                               + [c_void_p] * 7 + [POINTER(c_int32), POINTER(c_int64), c_void_p]),
     "cpl_solver_warm_state": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cpl_instance_bounds_sizeof": (c_size_t, []),
+    "cpl_solver_solve_box": (c_int32, [c_void_p] * 4 + [POINTER(InstanceDataC), c_int32, POINTER(WarmStart),
+                                       POINTER(InstanceBoundsC)]
+                             + [c_void_p] * 7 + [POINTER(c_int32), POINTER(c_int64), c_void_p]),
 }
 
 
@@ -401,3 +414,5 @@ if lib.cpl_solve_options_sizeof() != ctypes.sizeof(SolveOptions):  # pragma: no 
     raise ImportError("cpl_solve_options layout mismatch between header and ctypes mirror")
 if lib.cpl_warm_start_sizeof() != ctypes.sizeof(WarmStart):  # pragma: no cover - layout guard
     raise ImportError("cpl_warm_start layout mismatch between header and ctypes mirror")
+if lib.cpl_instance_bounds_sizeof() != ctypes.sizeof(InstanceBoundsC):  # pragma: no cover - layout guard
+    raise ImportError("cpl_instance_bounds layout mismatch between header and ctypes mirror")

@@ -66,7 +66,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import INF
-from .problem import InstanceData
+from .problem import InstanceBounds, InstanceData
 
 EPS = float(np.finfo(np.float64).eps)
 LM_HIST, LM_MAX_SKIP = 6, 2  # IPOPT limited_memory_max_history / limited_memory_max_skipping
@@ -339,8 +339,10 @@ class NativeSolver:
             self.handle = None
 
     def solve(self, X0, mass=None, env_tag=None, instance=None, fixed_from_x0=False,
-              warm_start=None) -> "BatchSolveResult":
-        """instance: per-instance wrench / cost references (InstanceData); fixed_from_x0: every variable
+              warm_start=None, bounds=None) -> "BatchSolveResult":
+        """bounds: per-instance variable bounds (InstanceBounds, cpl_solver_solve_box): instance b's free
+        variables are boxed by its own rows, the template still says which variables are fixed.
+        instance: per-instance wrench / cost references (InstanceData); fixed_from_x0: every variable
         the template fixes (lb == ub) takes instance b's value from X0[b] instead of the template's
         bound (cpl_solver_solve_inst).  warm_start: a WarmStart (cpl_solver_solve_warm); the start point
         is still X0."""
@@ -368,9 +370,23 @@ class NativeSolver:
         obj, pinf, dinf = (torch.empty(B, dtype=torch.float64, device=dev) for _ in range(3))
         it = ctypes.c_int32()
         ev = ctypes.c_int64()
-        if warm_start is not None:
-            if not isinstance(warm_start, WarmStart):
-                raise ValueError("warm_start must be a WarmStart")
+        if bounds is not None and not isinstance(bounds, InstanceBounds):
+            raise ValueError("bounds must be an InstanceBounds")
+        if warm_start is not None and not isinstance(warm_start, WarmStart):
+            raise ValueError("warm_start must be a WarmStart")
+        if bounds is not None and bounds:
+            x_lb, x_ub = bounds.packed(self.problem, B, dev)
+            box = _abi.InstanceBoundsC(x_lb.data_ptr(), x_ub.data_ptr())
+            inst = (instance if instance is not None else InstanceData()).validated(B, len(self.problem.contact_names), dev)
+            cs = inst.c_struct()
+            ws = None if warm_start is None else warm_start.validated(B, n, m, dev)
+            wcs = None if ws is None else ws.c_struct()
+            _abi.check(_abi.lib.cpl_solver_solve_box(
+                self.handle, _ptr(X0), None if mass is None else _ptr(mass), None if env_tag is None else _ptr(env_tag),
+                ctypes.byref(cs), 1 if fixed_from_x0 else 0, None if wcs is None else ctypes.byref(wcs),
+                ctypes.byref(box), _ptr(x), _ptr(y), _ptr(status), _ptr(iters), _ptr(obj), _ptr(pinf), _ptr(dinf),
+                ctypes.byref(it), ctypes.byref(ev), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        elif warm_start is not None:
             ws = warm_start.validated(B, n, m, dev)
             wcs = ws.c_struct()
             inst = (instance if instance is not None else InstanceData()).validated(B, len(self.problem.contact_names), dev)
@@ -462,7 +478,8 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
                     compl_inf_tol: float = 1e-4, acceptable_dual_inf_tol: float = 1e10,
                     acceptable_constr_viol_tol: float = 1e-2, acceptable_compl_inf_tol: float = 1e-2,
                     acceptable_obj_change_tol: float = 1e20, diverging_iterates_tol: float = 1e20,
-                    max_wall_time: float = 0.0, warm_start: Optional[WarmStart] = None) -> BatchSolveResult:
+                    max_wall_time: float = 0.0, warm_start: Optional[WarmStart] = None,
+                    bounds: Optional[InstanceBounds] = None) -> BatchSolveResult:
     """Solve B instances of `problem`'s template from the starting points X0 [B, n] (torch float64,
     device tensor), per-instance robot masses `mass` [B] (None: the template's).
 
@@ -528,6 +545,10 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
     and max(mult_bound_push, -/+ y_r) on row r's slack, mu = warm_start.mu_init; no least-squares
     multipliers.  The other instances (mask False, a non-finite warm value) start cold, bit for bit.
     The result's mult_x_L / mult_x_U / mu are what the next warm start takes.
+    bounds (device engine only): per-instance variable bounds (InstanceBounds, cpl_solver_solve_box) — instance
+    b's free variables are boxed by its own rows; row b is bitwise the solve of a batch of one whose template
+    carries those bounds.  The template still decides which variables are fixed.  The host restatement raises
+    ValueError, as for instance.
     IFOPT_OPTIONS is the set IFOPT's IpoptSolver runs with."""
     if termination not in ("scaled", "ipopt"):
         raise ValueError("termination must be 'scaled' or 'ipopt'")
@@ -551,6 +572,12 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
     use_bfgs = hessian == "limited-memory"
     import torch
 
+    if bounds is not None and not isinstance(bounds, InstanceBounds):
+        raise ValueError("bounds must be an InstanceBounds")
+    if bounds is not None and bounds and (not X0.is_cuda or (evaluator is not None
+                                                               and not isinstance(evaluator, KernelEvaluator))):
+        raise ValueError("bounds: the device engine only (the host restatement solves one template per call: write "
+                         "each instance's bounds into a template of its own)")
     if watchdog and X0.is_cuda:
         raise ValueError("watchdog: the host restatement only (the device engine has no watchdog)")
 
@@ -567,7 +594,7 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
         if instance is None and evaluator is not None:
             instance = evaluator.instance
         r = ns.solve(X0, mass, None if evaluator is None else evaluator.env_tag, instance=instance,
-                     fixed_from_x0=fixed_from_x0, warm_start=warm_start)
+                     fixed_from_x0=fixed_from_x0, warm_start=warm_start, bounds=bounds)
         if evaluator is not None:
             evaluator.calls += r.evaluations
         return r

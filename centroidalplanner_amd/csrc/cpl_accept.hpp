@@ -21,6 +21,36 @@ constexpr double LS_ETA_PHI = 1e-8, LS_OBJ_MAX_INC = 5.0;
 constexpr int LS_MAX_SOFT_RESTO = 10;  // max_soft_resto_iters
 constexpr double LS_KAPPA_SOC = 0.99;  // kappa_soc
 
+// The bounds of w = [x_free, s]: which are finite (the template decides: [nw] always) and their relaxed
+// values — the template's constants [nw] (stride 0) or one row per instance [batch, nw] (stride nw: a solve
+// with per-instance bounds, cpl_solver_solve_box).  Every kernel of the iteration takes this group and reads
+// instance b's values through row(b).  No member is __restrict__ (cpl_solver_common.hpp's groups).
+struct BoundsRow {
+  const uint8_t *hasL, *hasU;
+  const double *wl0, *wu0;
+};
+struct Bounds {
+  const uint8_t *hasL = nullptr, *hasU = nullptr;
+  const double *wl0 = nullptr, *wu0 = nullptr;
+  int64_t stride = 0;
+  __host__ __device__ __forceinline__ BoundsRow row(int64_t b) const {
+    return BoundsRow{hasL, hasU, wl0 + b * stride, wu0 + b * stride};
+  }
+  // row(b) where every lane of the wave holds the same b (the wave-per-instance kernels): the offset goes
+  // through the scalar unit, so the row pointers stay in scalar registers as the template's constants did
+  __device__ __forceinline__ BoundsRow row_wave(int64_t b) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int64_t off = b * stride;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)off);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)off >> 32));
+    const int64_t u = (int64_t)(((uint64_t)hi << 32) | lo);
+    return BoundsRow{hasL, hasU, wl0 + u, wu0 + u};
+#else
+    return row(b);
+#endif
+  }
+};
+
 // The accepted step's state commit for instance b on one wave (cpl_ipm_accept_kernel; the solve
 // engine's k_resto_enter runs it in its launch): the filter (augmented / reset), y, z with the
 // kappa_Sigma safeguard, w, mu and the iteration count.
@@ -30,8 +60,7 @@ struct IpmAcceptArgs {
   const double *alpha, *a_z, *theta, *phi, *filt_t_in, *filt_p_in;
   const int64_t* fcount_in;
   const double *w_new, *dy, *dzL, *dzU, *mu;
-  const uint8_t *hasL, *hasU;
-  const double *wl0, *wu0;
+  Bounds bd;
   double *w, *y, *zL, *zU, *mu_state;
   int64_t* iters;
   double *filt_t, *filt_p;
@@ -56,17 +85,18 @@ __device__ __forceinline__ void ipm_accept_one(const IpmAcceptArgs& a, int64_t b
     a.filt_p[b * nfilt + k] = fp;
   }
   const double al = a.alpha[b], az = (a.rest && a.rest[b]) ? 0.0 : a.a_z[b], mub = a.mu[b];
+  const BoundsRow bd = a.bd.row_wave(b);
   for (int r = lane; r < m; r += 64)
     if (act) a.y[b * m + r] += al * a.dy[b * m + r];
   for (int k = lane; k < nw; k += 64) {
     const double wn = a.w_new[b * nw + k];
     if (act) {
-      if (a.hasL[k]) {
-        const double dl = wn - a.wl0[k];
+      if (bd.hasL[k]) {
+        const double dl = wn - bd.wl0[k];
         a.zL[b * nw + k] = fmin(fmax(a.zL[b * nw + k] + az * a.dzL[b * nw + k], mub / (1e10 * dl)), 1e10 * mub / dl);
       }
-      if (a.hasU[k]) {
-        const double du = a.wu0[k] - wn;
+      if (bd.hasU[k]) {
+        const double du = bd.wu0[k] - wn;
         a.zU[b * nw + k] = fmin(fmax(a.zU[b * nw + k] + az * a.dzU[b * nw + k], mub / (1e10 * du)), 1e10 * mub / du);
       }
       a.w[b * nw + k] = wn;
@@ -136,8 +166,8 @@ struct PostStepArgs {
   int32_t nw = 0;
   const double *w = nullptr, *dw = nullptr, *zL = nullptr, *zU = nullptr, *gphi = nullptr, *mu = nullptr;
   const double* tau = nullptr;
-  const uint8_t *hasL = nullptr, *hasU = nullptr;
-  const double *wl0 = nullptr, *wu0 = nullptr, *theta = nullptr, *theta_min = nullptr;
+  Bounds bd;
+  const double *theta = nullptr, *theta_min = nullptr;
   const uint8_t* active = nullptr;
   const double* delta_w = nullptr;
   double *dwl = nullptr, *dzL = nullptr, *dzU = nullptr, *a_max = nullptr, *a_z = nullptr, *gd_out = nullptr;
@@ -164,10 +194,7 @@ struct LsBacktrackArgs {
   const int32_t* freepos = nullptr;     // [n] position in w of each variable, -1 fixed
   const int32_t* row_slack = nullptr;   // [m] slack of each inequality row, -1 equality
   const double* gl = nullptr;
-  const uint8_t* hasL = nullptr;
-  const uint8_t* hasU = nullptr;
-  const double* wl0 = nullptr;
-  const double* wu0 = nullptr;
+  Bounds bd;                            // of w: the template's constants or the instances' rows
   const double* mu = nullptr;
   const double* theta_k = nullptr;
   const double* phi_k = nullptr;
@@ -334,19 +361,20 @@ __device__ __forceinline__ void ipm_post_step_one(const PostStepArgs& P, int64_t
   const int nw = P.nw;
   const int lane = threadIdx.x & 63;
   const double mub = P.mu[b], t = P.tau[b];
+  const BoundsRow bd = P.bd.row_wave(b);
   double rp = INFINITY, rz = INFINITY, gd = 0.0;
   for (int k = lane; k < nw; k += 64) {
     const double wk = P.w[b * nw + k], dk = P.dw[b * nw + k];
     gd += P.gphi[b * nw + k] * dk;
     double dzl = 0.0, dzu = 0.0;
-    if (P.hasL[k]) {
-      const double dl = wk - P.wl0[k], zl = P.zL[b * nw + k];
+    if (bd.hasL[k]) {
+      const double dl = wk - bd.wl0[k], zl = P.zL[b * nw + k];
       dzl = mub / dl - zl - zl / dl * dk;
       if (dk < 0.0) rp = fmin(rp, -t * dl / dk);
       if (dzl < 0.0) rz = fmin(rz, -t * zl / dzl);
     }
-    if (P.hasU[k]) {
-      const double du = P.wu0[k] - wk, zu = P.zU[b * nw + k];
+    if (bd.hasU[k]) {
+      const double du = bd.wu0[k] - wk, zu = P.zU[b * nw + k];
       dzu = mub / du - zu + zu / du * dk;
       if (dk > 0.0) rp = fmin(rp, -t * du / -dk);
       if (dzu < 0.0) rz = fmin(rz, -t * zu / dzu);

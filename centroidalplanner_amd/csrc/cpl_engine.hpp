@@ -27,8 +27,8 @@ struct IpmOptArgs {
   int acc_iter = 0, mu_rounds = 0;
   double mu_min = 0.0;
   const double *A = nullptr, *gw = nullptr, *c = nullptr, *w = nullptr, *y = nullptr, *zL = nullptr, *zU = nullptr;
-  const uint8_t *hasL = nullptr, *hasU = nullptr;
-  const double *wl0 = nullptr, *wu0 = nullptr, *mu_in = nullptr, *filt_t = nullptr, *filt_p = nullptr;
+  Bounds bd;
+  const double *mu_in = nullptr, *filt_t = nullptr, *filt_p = nullptr;
   const int64_t* fcount = nullptr;
   uint8_t* active = nullptr;
   int64_t *status = nullptr, *acc = nullptr;
@@ -51,8 +51,7 @@ struct NewtonSetupArgs {
   int nw = 0, m = 0, nf = 0;
   const double *w = nullptr, *zL = nullptr, *zU = nullptr, *gw = nullptr, *A = nullptr, *y = nullptr, *c = nullptr;
   const double *f = nullptr, *mu = nullptr;
-  const uint8_t *hasL = nullptr, *hasU = nullptr;
-  const double *wl0 = nullptr, *wu0 = nullptr;
+  Bounds bd;
   const double* H = nullptr;
   int h_sym = 0;
   const double* Hc = nullptr;
@@ -68,8 +67,7 @@ struct JudgeTakeArgs {
   int nw = 0, m = 0, nf = 0, nfilt = 0;
   const int32_t* row_slack = nullptr;
   const double* gl = nullptr;
-  const uint8_t *hasL = nullptr, *hasU = nullptr;
-  const double *wl0 = nullptr, *wu0 = nullptr;
+  Bounds bd;
   const double *wt = nullptr, *f_t = nullptr, *g_t = nullptr, *alpha = nullptr;  // the trial
   const double *mu = nullptr, *theta_k = nullptr, *phi_k = nullptr, *gd = nullptr;
   const uint8_t* switch_ok = nullptr;
@@ -87,6 +85,9 @@ int32_t ipm_judge_take(const JudgeTakeArgs& a, void* stream);
 int32_t ipm_post_step_ex(int64_t batch, const PostStepArgs& P, const LsSetupArgs* ls, void* stream);
 // cpl_ipm_accept on the argument block the restoration entry also takes
 int32_t ipm_accept_ex(int64_t batch, const IpmAcceptArgs& a, void* stream);
+// cpl_ipm_max_step's primal form against the bounds group (the instances' rows where it has a stride)
+int32_t ipm_max_step(int64_t batch, int nw, const double* d_v, const double* d_dir, const Bounds& bd,
+                     const double* d_tau, double* d_out, void* stream);
 
 // ---- cpl_kernels.hip ----
 

@@ -62,9 +62,10 @@ __global__ __launch_bounds__(256) void cpl_ipm_judge_take_kernel(const JudgeTake
     th += fabs(s < 0 ? gb[r] - a.gl[r] : gb[r] - wb[nf + s]);
   }
   double lg = 0.0;
+  const BoundsRow bd = a.bd.row_wave(b);
   for (int k = lane; k < nw; k += 64) {
-    if (a.hasL[k]) lg += log(wb[k] - a.wl0[k]);
-    if (a.hasU[k]) lg += log(a.wu0[k] - wb[k]);
+    if (bd.hasL[k]) lg += log(wb[k] - bd.wl0[k]);
+    if (bd.hasU[k]) lg += log(bd.wu0[k] - wb[k]);
   }
   th = ipm_wave_sum(th);
   lg = ipm_wave_sum(lg);
@@ -125,7 +126,7 @@ __device__ __forceinline__ void ipm_optimality_body(const IpmOptArgs& a, const I
   const int lane = threadIdx.x & 63;
   const int nw = a.nw, m = a.m, nfilt = a.nfilt;
   const double *w = a.w, *zL = a.zL, *zU = a.zU, *filt_t = a.filt_t, *filt_p = a.filt_p;
-  const uint8_t *hasL = a.hasL, *hasU = a.hasU;
+  const auto [hasL, hasU, wl0, wu0] = a.bd.row_wave(b);
   // (the fused line search's flags cleared here, one launch before the search sets them)
   if (b == 0 && lane == 0 && up.any_reset) up.any_reset[0] = up.any_reset[1] = 0;
   // the solve loop's unpack (IpmUnpack) at the iteration's barrier parameter and active flag
@@ -175,8 +176,8 @@ __device__ __forceinline__ void ipm_optimality_body(const IpmOptArgs& a, const I
         du = fmax(du, ad / dfv);
       }
       zs += fabs(zl) + fabs(zu);
-      cl[h] = hasL[k] ? (wk - a.wl0[k]) * zl : 0.0;
-      cu[h] = hasU[k] ? (a.wu0[k] - wk) * zu : 0.0;
+      cl[h] = hasL[k] ? (wk - wl0[k]) * zl : 0.0;
+      cu[h] = hasU[k] ? (wu0[k] - wk) * zu : 0.0;
       clmax = fmax(clmax, cl[h]);
       cumax = fmax(cumax, cu[h]);
     }
@@ -309,13 +310,15 @@ __global__ __launch_bounds__(256) void cpl_ipm_max_step_kernel(int64_t batch, in
                                                                const double* __restrict__ d2,
                                                                const uint8_t* __restrict__ hasL,
                                                                const uint8_t* __restrict__ hasU,
-                                                               const double* __restrict__ lo,
-                                                               const double* __restrict__ up,
+                                                               const double* lo0, const double* up0, int64_t bstride,
                                                                const double* __restrict__ tau,
                                                                double* __restrict__ out) {
   const int64_t b = (int64_t)blockIdx.x * IPM_WAVES + (threadIdx.x >> 6);
   if (b >= batch) return;
   const int lane = threadIdx.x & 63;
+  const BoundsRow br = Bounds{hasL, hasU, lo0, up0, bstride}.row_wave(b);  // (the instance's row, or the template's)
+  const double* __restrict__ lo = br.wl0;
+  const double* __restrict__ up = br.wu0;
   const double t = tau[b];
   double r = INFINITY;
   for (int k = lane; k < nw; k += 64) {
@@ -353,8 +356,8 @@ __global__ __launch_bounds__(256) void cpl_ipm_newton_setup_kernel(
     const double* __restrict__ zU, const double* __restrict__ gw, const double* __restrict__ A,
     const double* __restrict__ y, const double* __restrict__ c, const double* __restrict__ f,
     const double* __restrict__ mu, const uint8_t* __restrict__ hasL, const uint8_t* __restrict__ hasU,
-    const double* __restrict__ wl0, const double* __restrict__ wu0, const double* __restrict__ H, int h_sym,
-    double* __restrict__ M, double* __restrict__ r1, double* __restrict__ r2, double* __restrict__ gphi,
+    const double* wl0_, const double* wu0_, int64_t bstride, const double* __restrict__ H,
+    int h_sym, double* __restrict__ M, double* __restrict__ r1, double* __restrict__ r2, double* __restrict__ gphi,
     double* __restrict__ mr_diag, double* __restrict__ theta, double* __restrict__ phi,
     const uint8_t* __restrict__ active, const double* __restrict__ Hc, int lm_pairs) {
   const int64_t b = WIDE ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * IPM_WAVES + (threadIdx.x >> 6);
@@ -363,6 +366,9 @@ __global__ __launch_bounds__(256) void cpl_ipm_newton_setup_kernel(
   const bool w0 = !WIDE || threadIdx.x < 64;  // the wave doing the per-variable / per-row work
   const int et = WIDE ? (int)threadIdx.x : lane, es = WIDE ? 256 : 64;  // the M entries' thread / stride
   const double mub = mu[b];
+  const BoundsRow br = Bounds{hasL, hasU, wl0_, wu0_, bstride}.row_wave(b);  // (the instance's row, or the template's)
+  const double* __restrict__ wl0 = br.wl0;
+  const double* __restrict__ wu0 = br.wu0;
   const double* Ab = A + b * (int64_t)m * nw;
   const double* yb = y + b * m;
   double* Mb = M + b * (int64_t)nw * nw;
@@ -648,6 +654,14 @@ int32_t ipm_accept_ex(int64_t batch, const IpmAcceptArgs& a, void* stream) {
   return launch_waves("cpl_ipm_accept", cpl_ipm_accept_kernel, batch, stream, a, batch);
 }
 
+// the primal fraction-to-the-boundary step against the bounds group (cpl_ipm_max_step with v2 == NULL)
+int32_t ipm_max_step(int64_t batch, int nw, const double* d_v, const double* d_dir, const Bounds& bd,
+                     const double* d_tau, double* d_out, void* stream) {
+  return launch_waves("cpl_ipm_max_step", cpl_ipm_max_step_kernel, batch, stream, batch, nw, d_v, d_dir,
+                      (const double*)nullptr, (const double*)nullptr, bd.hasL, bd.hasU, bd.wl0, bd.wu0, bd.stride, d_tau,
+                      d_out);
+}
+
 int32_t ipm_judge_take(const JudgeTakeArgs& a, void* stream) {
   return launch_waves("cpl_ipm_judge_take", cpl_ipm_judge_take_kernel, a.batch, stream, a);
 }
@@ -667,7 +681,7 @@ int32_t ipm_newton_setup(const NewtonSetupArgs& a, void* stream) {
          : (wide ? cpl_ipm_newton_setup_kernel<false, true> : cpl_ipm_newton_setup_kernel<false, false>);
   // (the kernel keeps its positional __restrict__ list: as a block its one-workgroup LM form lost a wave per SIMD)
   return ipm_launch("cpl_ipm_newton_setup", kernel, blocks, lds, stream, a.batch, a.nw, a.m, a.nf, a.w, a.zL, a.zU,
-                    a.gw, a.A, a.y, a.c, a.f, a.mu, a.hasL, a.hasU, a.wl0, a.wu0, a.H, a.h_sym, a.M, a.r1, a.r2, a.gphi,
+                    a.gw, a.A, a.y, a.c, a.f, a.mu, a.bd.hasL, a.bd.hasU, a.bd.wl0, a.bd.wu0, a.bd.stride, a.H, a.h_sym, a.M, a.r1, a.r2, a.gphi,
                     a.mr_diag, a.theta, a.phi, a.active, a.Hc, a.lm_pairs);
 }
 
@@ -697,8 +711,8 @@ static IpmOptArgs opt_args_abi(int64_t batch, int32_t nw, int32_t m, int32_t nfi
   IpmOptArgs a;
   a.batch = batch; a.nw = nw; a.m = m; a.nfilt = nfilt; a.nbounds = nbounds; a.tol = tol; a.acc_tol = acc_tol;
   a.acc_iter = acc_iter; a.mu_rounds = IPM_MU_ROUNDS; a.mu_min = ipm_mu_min(tol);
-  a.A = d_A; a.gw = d_gw; a.c = d_c; a.w = d_w; a.y = d_y; a.zL = d_zL; a.zU = d_zU; a.hasL = d_hasL; a.hasU = d_hasU;
-  a.wl0 = d_wl0; a.wu0 = d_wu0; a.mu_in = d_mu; a.filt_t = d_filt_t; a.filt_p = d_filt_p; a.fcount = d_fcount;
+  a.A = d_A; a.gw = d_gw; a.c = d_c; a.w = d_w; a.y = d_y; a.zL = d_zL; a.zU = d_zU;
+  a.bd = Bounds{d_hasL, d_hasU, d_wl0, d_wu0, 0}; a.mu_in = d_mu; a.filt_t = d_filt_t; a.filt_p = d_filt_p; a.fcount = d_fcount;
   a.active = d_active; a.status = d_status; a.acc = d_acc; a.d_inf_out = d_d_inf; a.err0_out = d_err0;
   a.base_out = d_base; a.mu_out = d_mu_out; a.filt_t_out = d_filt_t_out; a.filt_p_out = d_filt_p_out;
   a.fcount_out = d_fcount_out;
@@ -743,7 +757,7 @@ int32_t cpl_ipm_judge_take(int64_t batch, int32_t nw, int32_t m, int32_t nf, int
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_judge_take: missing buffer");
   JudgeTakeArgs a;
   a.batch = batch; a.nw = nw; a.m = m; a.nf = nf; a.nfilt = nfilt; a.row_slack = d_row_slack; a.gl = d_gl;
-  a.hasL = d_hasL; a.hasU = d_hasU; a.wl0 = d_wl0; a.wu0 = d_wu0; a.wt = d_wt; a.f_t = d_f_t; a.g_t = d_g_t;
+  a.bd = Bounds{d_hasL, d_hasU, d_wl0, d_wu0, 0}; a.wt = d_wt; a.f_t = d_f_t; a.g_t = d_g_t;
   a.alpha = d_alpha; a.mu = d_mu; a.theta_k = d_theta_k; a.phi_k = d_phi_k; a.gd = d_gd; a.switch_ok = d_switch_ok;
   a.theta_max = d_theta_max; a.filt_t = d_filt_t; a.filt_p = d_filt_p; a.extra_mask = d_extra_mask;
   a.searching = d_searching; a.st_f = d_st_f; a.st_g = d_st_g; a.st_w = d_st_w; a.st_alpha = d_st_alpha;
@@ -823,7 +837,7 @@ int32_t cpl_ipm_max_step(int64_t batch, int32_t nw, const double* d_v, const dou
   if (!d_v || !d_dir || !d_hasL || !d_hasU || (d_v2 ? !d_dir2 : (!d_lo || !d_up)) || !d_tau || !d_out)
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_max_step: missing buffer");
   return launch_waves("cpl_ipm_max_step", cpl_ipm_max_step_kernel, batch, stream, batch, nw, d_v, d_dir, d_v2, d_dir2,
-                      d_hasL, d_hasU, d_lo, d_up, d_tau, d_out);
+                      d_hasL, d_hasU, d_lo, d_up, (int64_t)0, d_tau, d_out);
 }
 
 
@@ -869,7 +883,7 @@ int32_t cpl_ipm_newton_setup_ex(int64_t batch, int32_t nw, int32_t m, int32_t nf
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_newton_setup: missing buffer");
   NewtonSetupArgs a;
   a.batch = batch; a.nw = nw; a.m = m; a.nf = nf; a.w = d_w; a.zL = d_zL; a.zU = d_zU; a.gw = d_gw; a.A = d_A;
-  a.y = d_y; a.c = d_c; a.f = d_f; a.mu = d_mu; a.hasL = d_hasL; a.hasU = d_hasU; a.wl0 = d_wl0; a.wu0 = d_wu0;
+  a.y = d_y; a.c = d_c; a.f = d_f; a.mu = d_mu; a.bd = Bounds{d_hasL, d_hasU, d_wl0, d_wu0, 0};
   a.H = d_H; a.h_sym = h_sym; a.M = d_M; a.r1 = d_r1; a.r2 = d_r2; a.gphi = d_gphi; a.mr_diag = d_mr_diag;
   a.theta = d_theta; a.phi = d_phi; a.active = d_active; a.Hc = d_Hc; a.lm_pairs = d_Hc ? lm_pairs : 0;
   return ipm_newton_setup(a, stream);
@@ -888,7 +902,7 @@ int32_t cpl_ipm_post_step(int64_t batch, int32_t nw, const double* d_w, const do
       !d_theta || !d_theta_min || !d_active || !d_delta_w || !d_dwl || !d_dzL || !d_dzU || !d_a_max || !d_a_z ||
       !d_gd || !d_switch_ok)
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_post_step: missing buffer");
-  const PostStepArgs P{(int32_t)nw, d_w, d_dw, d_zL, d_zU, d_gphi, d_mu, d_tau, d_hasL, d_hasU, d_wl0, d_wu0,
+  const PostStepArgs P{(int32_t)nw, d_w, d_dw, d_zL, d_zU, d_gphi, d_mu, d_tau, Bounds{d_hasL, d_hasU, d_wl0, d_wu0, 0},
                        d_theta, d_theta_min, d_active, d_delta_w, d_dwl, d_dzL, d_dzU, d_a_max, d_a_z, d_gd,
                        d_switch_ok};
   return ipm_post_step_ex(batch, P, nullptr, stream);
@@ -910,8 +924,8 @@ int32_t cpl_ipm_accept(int64_t batch, int32_t nw, int32_t m, int32_t nfilt, cons
       !d_filt_p || !d_fcount)
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_ipm_accept: missing buffer");
   const IpmAcceptArgs a{(int)nw, (int)m, (int)nfilt, d_active, d_aug, d_failed, d_rest, d_alpha, d_a_z, d_theta,
-                        d_phi, d_filt_t_in, d_filt_p_in, d_fcount_in, d_w_new, d_dy, d_dzL, d_dzU, d_mu, d_hasL,
-                        d_hasU, d_wl0, d_wu0, d_w, d_y, d_zL, d_zU, d_mu_state, d_iters, d_filt_t, d_filt_p,
+                        d_phi, d_filt_t_in, d_filt_p_in, d_fcount_in, d_w_new, d_dy, d_dzL, d_dzU, d_mu,
+                        Bounds{d_hasL, d_hasU, d_wl0, d_wu0, 0}, d_w, d_y, d_zL, d_zU, d_mu_state, d_iters, d_filt_t, d_filt_p,
                         d_fcount};
   return ipm_accept_ex(batch, a, stream);
 }

@@ -3504,6 +3504,7 @@ __global__ __launch_bounds__(64) void cpl_ls_backtrack_kernel(const KParams K, c
     const double* wb = A.w + b * nw;
     const double* db = A.dw + b * nw;
     const double* Xb = A.Xbase + b * n;
+    const BoundsRow bd = A.bd.row(b);  // (this instance's row, or the template's constants)
     const double m_i = A.mass ? A.mass[b] : K.mass_default;
     const bool sq = ENVK == CPL_ENV_SUPERQUADRIC ||
                     (ENVK == CPL_ENV_MIXED && A.env_tag[b] == CPL_ENV_SUPERQUADRIC);
@@ -3553,8 +3554,8 @@ __global__ __launch_bounds__(64) void cpl_ls_backtrack_kernel(const KParams K, c
       }
       double lg = 0.0;
       for (int k = lane; k < nw; k += 64) {
-        if (A.hasL[k]) lg += log(wt[k] - A.wl0[k]);
-        if (A.hasU[k]) lg += log(A.wu0[k] - wt[k]);
+        if (bd.hasL[k]) lg += log(wt[k] - bd.wl0[k]);
+        if (bd.hasU[k]) lg += log(bd.wu0[k] - wt[k]);
       }
       double pn = 0.0, lpn = 0.0, prox = 0.0;
       if (RESTO) {  // (k_resto_judge's terms; th above is replaced by the restoration problem's)
@@ -3639,8 +3640,8 @@ __global__ __launch_bounds__(64) void cpl_ls_backtrack_kernel(const KParams K, c
         const double t = A.tau[b];
         for (int k = lane; k < nw; k += 64) {
           const double vk = wb[k], dk = dwv;
-          if (A.hasL[k] && dk < 0.0) r = fmin(r, -t * (vk - A.wl0[k]) / dk);
-          if (A.hasU[k] && dk > 0.0) r = fmin(r, -t * (A.wu0[k] - vk) / -dk);
+          if (bd.hasL[k] && dk < 0.0) r = fmin(r, -t * (vk - bd.wl0[k]) / dk);
+          if (bd.hasU[k] && dk > 0.0) r = fmin(r, -t * (bd.wu0[k] - vk) / -dk);
         }
         a_soc = fmin(wave_min(r), 1.0);
         dir = Dv;

@@ -6,7 +6,9 @@
 // (CPU tensors, the oracle's callbacks) is the checker of this engine — with every per-instance quantity
 // a row of a device buffer, and no framework ops.
 //
-// A solve (cpl_solver_solve_warm; _solve and _solve_inst are the same call with less given) is three
+// A solve (cpl_solver_solve_box; _solve, _solve_inst and _solve_warm are the same call with less given) is,
+// after box_prepare where the caller gave per-instance bounds (validated and turned into the solver's own rows:
+// bounds_of() then hands every kernel those rows with a stride), three
 // functions on the solver's own stream: solve_start (inputs, scaling, the cold or warm starting iterate),
 // solve_iterate (the loop below), solve_finish (the final test, the rows' results, the outputs).
 //
@@ -205,9 +207,12 @@ int32_t hessian_into(cpl_solver* S, const cpl_problem_desc* d, const uint8_t* ma
 }
 
 // ---- the kernels' argument structs from the solver's buffers: each buffer is named here, once ----
+// (the one place the row stride is set: the template's constants, or this solve's per-instance rows)
 Bounds bounds_of(const cpl_solver* S) {
   Bounds b;
-  b.hasL = S->hasL; b.hasU = S->hasU; b.wl0 = S->wl0; b.wu0 = S->wu0;
+  b.hasL = S->hasL; b.hasU = S->hasU;
+  b.wl0 = S->has_box ? S->box_wl : S->wl0; b.wu0 = S->has_box ? S->box_wu : S->wu0;
+  b.stride = S->has_box ? S->nw : 0;
   return b;
 }
 Iterate iterate_of(const cpl_solver* S) {
@@ -328,7 +333,7 @@ IpmOptArgs opt_args_of(const cpl_solver* S) {
   a.tol = o.tol; a.acc_tol = o.acceptable_tol; a.acc_iter = o.acceptable_iter;
   a.mu_rounds = MU_ROUNDS; a.mu_min = S->mu_min;
   a.A = S->A; a.gw = S->gradw; a.c = S->c; a.w = S->w; a.y = S->y; a.zL = S->zL; a.zU = S->zU;
-  a.hasL = S->hasL; a.hasU = S->hasU; a.wl0 = S->wl0; a.wu0 = S->wu0;
+  a.bd = bounds_of(S);
   a.mu_in = S->mu; a.filt_t = S->filt_t; a.filt_p = S->filt_p; a.fcount = S->fcount;
   a.active = S->active; a.status = S->status; a.acc = S->acc; a.d_inf_out = S->d_inf; a.err0_out = S->err0;
   a.base_out = S->base; a.mu_out = S->mu_o; a.filt_t_out = S->ft; a.filt_p_out = S->fp; a.fcount_out = S->fc;
@@ -342,7 +347,7 @@ NewtonSetupArgs newton_args_of(const cpl_solver* S, bool resto) {
   NewtonSetupArgs a;
   a.batch = S->Bcur; a.nw = S->nw; a.m = S->m; a.nf = S->nf;
   a.w = S->w; a.A = S->A; a.y = S->y; a.c = S->c; a.f = S->f;
-  a.hasL = S->hasL; a.hasU = S->hasU; a.wl0 = S->wl0; a.wu0 = S->wu0;
+  a.bd = bounds_of(S);
   a.M = S->M; a.r1 = S->r1; a.gphi = S->gphi; a.mr_diag = S->mr_diag;
   a.zL = resto ? S->zLR : S->zL; a.zU = resto ? S->zUR : S->zU;
   a.gw = resto ? S->gfR : S->gradw;
@@ -356,8 +361,7 @@ NewtonSetupArgs newton_args_of(const cpl_solver* S, bool resto) {
 PostStepArgs post_step_args_of(const cpl_solver* S) {
   PostStepArgs p;
   p.nw = S->nw; p.w = S->w; p.dw = S->dw; p.zL = S->zL; p.zU = S->zU; p.gphi = S->gphi;
-  p.mu = S->mu_o; p.tau = S->tau; p.hasL = S->hasL; p.hasU = S->hasU; p.wl0 = S->wl0;
-  p.wu0 = S->wu0; p.theta = S->theta_k; p.theta_min = S->theta_min; p.active = S->act;
+  p.mu = S->mu_o; p.tau = S->tau; p.bd = bounds_of(S); p.theta = S->theta_k; p.theta_min = S->theta_min; p.active = S->act;
   p.delta_w = S->delta_w; p.dwl = S->dwl; p.dzL = S->dzL; p.dzU = S->dzU; p.a_max = S->a_max;
   p.a_z = S->a_z; p.gd_out = S->gd; p.switch_ok = S->switch_ok;
   return p;
@@ -409,7 +413,7 @@ LsBacktrackArgs ls_backtrack_args(const cpl_solver* S, const Search& q) {
   la.act = q.act; la.tiny = S->tiny_now; la.soft_now = S->soft_now; la.soft_cnt = S->soft_cnt;
   la.searching = q.searching; la.alpha = q.alpha; la.a_min = q.a_min;
   la.w = S->w; la.dw = S->dw; la.Xbase = S->Xbase; la.freepos = S->freepos; la.row_slack = S->row_slack;
-  la.gl = S->gl; la.hasL = S->hasL; la.hasU = S->hasU; la.wl0 = S->wl0; la.wu0 = S->wu0;
+  la.gl = S->gl; la.bd = bounds_of(S);
   la.mu = q.mu; la.theta_k = q.theta; la.phi_k = q.phi; la.gd = q.gd; la.switch_ok = q.switch_ok;
   la.theta_max = q.theta_max; la.filt_t = q.filt_t; la.filt_p = q.filt_p;
   la.mass = S->mass; la.env_tag = S->tag;
@@ -461,10 +465,9 @@ int32_t step_phase(cpl_solver* S, int phase, const StepMode mode = {}) {
                    double* th, uint8_t* ok) {
     const Search q = search_of(S);
     const Staged t = staged_of(S);
-    const Bounds bd = bounds_of(S);
     JudgeTakeArgs j;
     j.batch = B; j.nw = nw; j.m = m; j.nf = nf; j.nfilt = FMAX; j.row_slack = S->row_slack; j.gl = S->gl;
-    j.hasL = bd.hasL; j.hasU = bd.hasU; j.wl0 = bd.wl0; j.wu0 = bd.wu0;
+    j.bd = bounds_of(S);
     j.wt = wt; j.f_t = ft_; j.g_t = gt_; j.alpha = al; j.extra_mask = extra; j.th_out = th; j.ok_out = ok;
     j.mu = q.mu; j.theta_k = q.theta; j.phi_k = q.phi; j.gd = q.gd; j.switch_ok = q.switch_ok;
     j.theta_max = q.theta_max; j.filt_t = q.filt_t; j.filt_p = q.filt_p; j.searching = q.searching;
@@ -502,8 +505,7 @@ int32_t step_phase(cpl_solver* S, int phase, const StepMode mode = {}) {
         if (S->jreg)
           CK(kkt_aug_solve(1, B, nw, m, S->M, S->A, S->r1, S->r2s, nullptr, nullptr, S->soc, S->dws, S->dys, nullptr,
                            S->delta_c, nullptr, S->ws_aug, st));
-        CK(cpl_ipm_max_step(B, nw, S->w, S->dws, nullptr, nullptr, S->hasL, S->hasU, S->wl0, S->wu0, S->tau, S->a_soc,
-                            st));
+        CK(ipm_max_step(B, nw, S->w, S->dws, bounds_of(S), S->tau, S->a_soc, st));
         CK(cpl_ipm_trial_point(B, n, nf, nw, S->free64, S->fixed64, S->Xbase, S->w, S->dws, S->a_soc, S->soc, S->st_w,
                                S->ws_, S->Xs, st));
         CK(eval_fg(S, S->Xs, S->f_s, S->g_s));
@@ -610,8 +612,8 @@ int32_t step_phase(cpl_solver* S, int phase, const StepMode mode = {}) {
       CK(eval_full(S, S->Xn, S->f_n, S->grad_n, S->g_n, S->J_n));
       if (S->bfgs) CK(lbfgs_update(S, S->moved, S->gradw, S->grad_n));
       const IpmAcceptArgs acc{nw, m, FMAX, S->moved, S->st_aug, nullptr, nullptr, S->st_alpha, S->a_z, S->theta_k,
-                              S->phi_k, S->ft, S->fp, S->fc, S->st_w, S->dy, S->dzL, S->dzU, S->mu_o, S->hasL,
-                              S->hasU, S->wl0, S->wu0, S->w, S->y, S->zL, S->zU, S->mu, S->iters, S->filt_t,
+                              S->phi_k, S->ft, S->fp, S->fc, S->st_w, S->dy, S->dzL, S->dzU, S->mu_o,
+                              bounds_of(S), S->w, S->y, S->zL, S->zU, S->mu, S->iters, S->filt_t,
                               S->filt_p, S->fcount};
       if (phase == P_ACCEPT_NR) {  // no instance can have failed its search: no entry
         CK(ipm_accept_ex(B, acc, st));
@@ -619,7 +621,7 @@ int32_t step_phase(cpl_solver* S, int phase, const StepMode mode = {}) {
         return count_rows(phase);
       }
       // the restoration phase starts where the line search failed
-      RestoEnterArgs E{m, nw, S->failed, S->c, S->w, S->zL, S->zU, S->mu_o, S->theta_k, S->phi_k, S->hasL, S->hasU,
+      RestoEnterArgs E{m, nw, S->failed, S->c, S->w, S->zL, S->zU, S->mu_o, S->theta_k, S->phi_k, bounds_of(S),
                        S->filt_t, S->filt_p, S->fcount, S->iters, S->in_resto, S->n_resto, S->wR, S->pR, S->nR, S->zp,
                        S->zn, S->zLR, S->zUR, S->muR, S->ftR, S->fpR, S->fcR, S->thmaxR, S->thminR, S->th_o0, S->ph_o0,
                        S->dwlR, S->lm_cnt, S->lm_skip, S->bfgs ? S->Hq : nullptr, lmc, S->M, S->r1, S->r2, S->Dinv, ar,
@@ -653,14 +655,14 @@ int32_t step_phase(cpl_solver* S, int phase, const StepMode mode = {}) {
       CK(hessian_into(S, &S->desc_R, S->actR, &ns.H, &ns.h_sym));
       CK(ipm_newton_setup(ns, st));
       hipLaunchKernelGGL(k_resto_prep2, dim3(blocks_for(B)), dim3(256), 0, st, B, m, nf, nw, S->actR, S->c, S->w, S->y,
-                         S->wR, S->pR, S->nR, S->zp, S->zn, S->muR, S->hasL, S->hasU, S->wl0, S->wu0, S->M, S->rp,
+                         S->wR, S->pR, S->nR, S->zp, S->zn, S->muR, bounds_of(S), S->M, S->rp,
                          S->rn, S->Dinv, S->r2, S->thetaR, S->phiR);
       LAUNCHED("k_resto_prep2");
       CK(cpl_kkt_qd_solve(B, nw, m, S->M, S->A, S->Dinv, S->r1, S->r2, S->actR, S->dwlR, S->dw, S->dy, S->scr1,
                           S->Kqd, st));
       hipLaunchKernelGGL(k_resto_post, dim3(blocks_for(B)), dim3(256), 0, st, B, m, nw, S->actR, S->w, S->dw, S->dy,
-                         S->gphi, S->pR, S->nR, S->zp, S->zn, S->zLR, S->zUR, S->rp, S->rn, S->muR, S->tauR, S->hasL,
-                         S->hasU, S->wl0, S->wu0, S->thetaR, S->thminR, S->f, S->g, S->dp, S->dn, S->dzL, S->dzU,
+                         S->gphi, S->pR, S->nR, S->zp, S->zn, S->zLR, S->zUR, S->rp, S->rn, S->muR, S->tauR,
+                         bounds_of(S), S->thetaR, S->thminR, S->f, S->g, S->dp, S->dn, S->dzL, S->dzU,
                          S->dzp, S->dzn, S->a_maxR, S->a_zR, S->gdR, S->switchR, S->a_minR, S->searchingR, S->st_f,
                          S->st_g, S->st_w, S->st_p, S->st_n, S->st_alpha, S->st_aug, S->alphaR, S->d_any);
       LAUNCHED("k_resto_post");
@@ -678,7 +680,7 @@ int32_t step_phase(cpl_solver* S, int phase, const StepMode mode = {}) {
     }
     case P_RACCEPT: {
       hipLaunchKernelGGL(k_unpack, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, n, nw, S->freepos, S->Xbase,
-                         S->st_w, nullptr, nullptr, S->Xn);
+                         S->st_w, nullptr, nullptr, (int64_t)0, S->Xn);
       LAUNCHED("k_unpack (resto)");
       CK(eval_full(S, S->Xn, S->f_n, S->grad_n, S->g_n, S->J_n));
       if (S->bfgs) {  // the restoration phase's own model: pairs from J^T y (its constraint curvature)
@@ -712,11 +714,12 @@ int32_t step_phase(cpl_solver* S, int phase, const StepMode mode = {}) {
 int32_t run_phase(cpl_solver* S, int phase) {
   if (!S->opt.use_graph) return step_phase(S, phase);
   // (a graph holds the pointers its launches were given: one bit per input that may be absent — the
-  // masses, the tags and each of the four instance arrays, whose slot is null when the caller gave none)
+  // masses, the tags and each of the four instance arrays, whose slot is null when the caller gave none —
+  // and one for per-instance bounds, whose launches carry the solver's rows and their stride)
   const int inst_bits = (S->inst.d_wrench ? 1 : 0) | (S->inst.d_com_ref ? 2 : 0) | (S->inst.d_p_ref ? 4 : 0) |
                         (S->inst.d_F_ref ? 8 : 0);
-  const int64_t key =
-      ((S->Bcur * 128 + inst_bits * 8 + (S->scaled ? 4 : 0) + (S->mass ? 2 : 0) + (S->tag ? 1 : 0)) * 16) + phase;
+  const int64_t key = ((S->Bcur * 256 + (S->has_box ? 128 : 0) + inst_bits * 8 + (S->scaled ? 4 : 0) +
+                        (S->mass ? 2 : 0) + (S->tag ? 1 : 0)) * 16) + phase;
   auto it = S->graphs.find(key);
   if (it == S->graphs.end()) {
     HK(hipStreamBeginCapture(S->stream, hipStreamCaptureModeRelaxed), "hipStreamBeginCapture");
@@ -805,7 +808,7 @@ int32_t compact(cpl_solver* S, int64_t count, int64_t Bn) {
   for (const BufRec& r : S->bufs) {
     const bool moved = r.when == ALWAYS || (r.when == IF_SCALED && S->scaled) ||
                        (r.when == IF_MASS && S->mass) || (r.when == IF_TAG && S->tag) ||
-                       (r.when == IF_INST && S->has_inst);
+                       (r.when == IF_INST && S->has_inst) || (r.when == IF_BOX && S->has_box);
     if (!moved || r.width <= 0) continue;
     const dim3 grid(blocks_elems(count * r.width)), blk(256);
     if (r.elem == 8)
@@ -927,8 +930,8 @@ int32_t solve_start(cpl_solver* S, const double* d_x0, const double* d_mass, con
     HK(hipStreamSynchronize(st), "hipStreamSynchronize");
     any_cold = S->h_flag[0] != 0;
   }
-  hipLaunchKernelGGL(start_x, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, n, S->freepos, S->Xbase, S->hasL,
-                     S->hasU, S->wl0, S->wu0, S->X, wa);
+  hipLaunchKernelGGL(start_x, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, n, S->freepos, S->Xbase, bounds_of(S),
+                     S->X, wa);
   LAUNCHED("k_start_x");
   CK(eval_full(S, S->X, S->f, S->grad, S->g, S->J));
   ++*evals;
@@ -949,6 +952,34 @@ int32_t solve_start(cpl_solver* S, const double* d_x0, const double* d_mass, con
     LAUNCHED("k_lm_init");
   }
   return CPL_OK;
+}
+
+// Per-instance bounds (cpl_solver_solve_box): the caller's rows validated and turned into the solver's own
+// (k_box_prepare), once, before the start; the one host read is the fault word.  A refusal names the first
+// offending entry and launches nothing else.
+int32_t box_prepare(cpl_solver* S, const cpl_instance_bounds* box) {
+  hipStream_t st = S->stream;
+  const int64_t B = S->B;
+  const int n = S->n;
+  HK(hipMemsetAsync(S->box_fault, 0xff, sizeof(unsigned long long), st), "hipMemsetAsync box fault");
+  BoxPrepArgs a;
+  a.n = n; a.nf = S->nf; a.nw = S->nw; a.freepos = S->freepos; a.x_lb = box->d_x_lb; a.x_ub = box->d_x_ub;
+  a.xl_t = S->xl; a.xu_t = S->xu; a.wl_t = S->wl0; a.wu_t = S->wu0;
+  a.wl = S->box_wl; a.wu = S->box_wu; a.xl = S->box_xl; a.xu = S->box_xu; a.fault = S->box_fault;
+  const int64_t total = B * (n + S->nI);
+  hipLaunchKernelGGL(k_box_prepare, dim3(blocks_elems(total)), dim3(256), 0, st, total, a);
+  LAUNCHED("k_box_prepare");
+  unsigned long long code = 0;
+  HK(hipMemcpyAsync(&code, S->box_fault, sizeof(code), hipMemcpyDeviceToHost, st), "hipMemcpyAsync box fault");
+  HK(hipStreamSynchronize(st), "hipStreamSynchronize");
+  if (code == ~0ull) return CPL_OK;
+  const int kind = (int)(code & 3ull);
+  const long long e = (long long)(code >> 2), b = e / n, j = e % n;
+  const char* what = kind == BOX_LB_BAD   ? "lb is NaN, infinite or |lb| >= 1e19"
+                     : kind == BOX_UB_BAD ? "ub is NaN, infinite or |ub| >= 1e19"
+                                          : "ub does not exceed lb (ub - lb <= 1e-14 max(1, |lb|): an empty or a fixed box)";
+  return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_solve_box: instance " + std::to_string(b) + ", variable " +
+                                            std::to_string(j) + ": " + what);
 }
 
 // The iteration loop: the phases, the counts (mailbox or copy), max_wall_time, the compaction.  *it: the
@@ -1048,8 +1079,10 @@ int32_t solve_finish(cpl_solver* S, const double* d_mass, const uint8_t* d_env_t
   // IPOPT honor_original_bounds: the final point projected into the original bounds, re-evaluated
   double* Xf = d_x ? d_x : S->Xn;
   // (fixed_from_x0: the projection skips the fixed entries — the template's bound is not the instance's value)
+  // (per-instance bounds: each instance's own unrelaxed rows, by original instance as fX / fw are)
   hipLaunchKernelGGL(fixed_from_x0 ? k_unpack_free : k_unpack, dim3(blocks_elems(B * n)), dim3(256), 0, st, B * n, n, nw,
-                     S->freepos, S->fX, S->fw, S->xl, S->xu, Xf);
+                     S->freepos, S->fX, S->fw, S->has_box ? S->box_xl : S->xl, S->has_box ? S->box_xu : S->xu,
+                     (int64_t)(S->has_box ? n : 0), Xf);
   LAUNCHED("k_unpack (final)");
   // (the full batch in the instances' own order: the caller's masses, tags and instance data)
   if (inst)
@@ -1312,6 +1345,9 @@ int32_t cpl_solver_create(const cpl_problem_desc* d, int64_t batch, const cpl_so
   S->opt = opt;
   S->B = batch;
   S->n = n; S->m = m; S->nnz = nnz; S->nnz_rec = nnz_rec; S->nf = nf; S->nI = nI; S->nw = nw; S->nbounds = nbounds;
+  S->box_ok = true;  // per-instance bounds need both bounds of every free variable in the template, below BIG
+  for (int k = 0; k < nf; ++k)
+    S->box_ok = S->box_ok && hasL[k] && hasU[k] && std::fabs(xl[free_idx[k]]) < BIG && std::fabs(xu[free_idx[k]]) < BIG;
   S->jreg = opt.jacobian_regularization == 1;
   if (S->jreg && kkt_aug_workspace_doubles(nw, m) < 0) {
     delete S;
@@ -1441,6 +1477,10 @@ int32_t cpl_solver_create(const cpl_problem_desc* d, int64_t batch, const cpl_so
   S->fzL = c.full<double>(tw * nw); S->fzU = c.full<double>(tw * nw);
   S->warm_flag = c.temp<uint8_t>(1); S->warm_any = c.fixed<uint8_t>(4);
   S->wzL = c.full<double>(n); S->wzU = c.full<double>(n); S->wmu = c.full<double>(1);
+  // per-instance bounds (cpl_solver_solve_box), carved here whether or not a solve gives any (2 (nw + n)
+  // doubles per instance): the relaxed w-order rows by batch row, the unrelaxed x-order rows by instance
+  S->box_wl = c.state<double>(nw, IF_BOX); S->box_wu = c.state<double>(nw, IF_BOX);
+  S->box_xl = c.full<double>(n); S->box_xu = c.full<double>(n); S->box_fault = c.fixed<unsigned long long>(1);
   // last: the gather scratch holds the widest state row of every instance, in 8-byte words
   S->scratch_words = (int64_t)((c.row_bytes + 7) / 8);
   S->scratch = c.temp<uint64_t>((size_t)S->scratch_words);
@@ -1520,7 +1560,28 @@ int32_t cpl_solver_solve_warm(cpl_solver* S, const double* d_x0, const double* d
                               double* d_x, double* d_y, int32_t* d_status, int32_t* d_iters, double* d_obj,
                               double* d_primal_inf, double* d_dual_inf, int32_t* iterations_run, int64_t* evaluations,
                               void* stream) {
+  return cpl_solver_solve_box(S, d_x0, d_mass, d_env_tag, inst, fixed_from_x0, warm, nullptr, d_x, d_y, d_status, d_iters,
+                              d_obj, d_primal_inf, d_dual_inf, iterations_run, evaluations, stream);
+}
+
+size_t cpl_instance_bounds_sizeof(void) { return sizeof(cpl_instance_bounds); }
+
+int32_t cpl_solver_solve_box(cpl_solver* S, const double* d_x0, const double* d_mass, const uint8_t* d_env_tag,
+                             const cpl_instance_data* inst, int32_t fixed_from_x0, const cpl_warm_start* warm,
+                             const cpl_instance_bounds* box, double* d_x, double* d_y, int32_t* d_status,
+                             int32_t* d_iters, double* d_obj, double* d_primal_inf, double* d_dual_inf,
+                             int32_t* iterations_run, int64_t* evaluations, void* stream) {
+  // per-instance bounds: both arrays, or none (then this is cpl_solver_solve_warm)
+  const bool has_box = box && (box->d_x_lb || box->d_x_ub);
+  if (has_box && (!box->d_x_lb || !box->d_x_ub))
+    return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_solve_box: per-instance bounds need d_x_lb and d_x_ub together");
   if (!S || !d_x0) return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_solve: missing solver or x0");
+  if (has_box) {
+    if (!S->box_ok)
+      return fail(CPL_ERR_UNSUPPORTED,
+                  "cpl_solver_solve_box: the template leaves a free variable without a finite lower or upper bound "
+                  "(|bound| >= 1e19): per-instance bounds need both");
+  }
   if (S->desc.env_kind == CPL_ENV_MIXED && !d_env_tag)
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_solve: mixed batches need the env tags");
   const bool has_inst = inst && (inst->d_wrench || inst->d_com_ref || inst->d_p_ref || inst->d_F_ref);
@@ -1540,6 +1601,9 @@ int32_t cpl_solver_solve_warm(cpl_solver* S, const double* d_x0, const double* d
   // order after the caller's stream (its inputs), then run on the solver's own stream
   HK(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize (caller stream)");
   if (!has_inst) inst = nullptr;
+  S->has_box = false;
+  if (has_box) CK(box_prepare(S, box));  // (validated on the device: nothing else is launched when it refuses)
+  S->has_box = has_box;
   int it = 0;
   int64_t evals = 0;
   CK(solve_start(S, d_x0, d_mass, d_env_tag, inst, fixed_from_x0, is_warm ? warm : nullptr, &evals));

@@ -24,10 +24,8 @@ inline unsigned blocks_elems(int64_t total) { return (unsigned)((total + 255) / 
 // unpack a group with a structured binding — every buffer is named once per group, not once per
 // position of a 50-pointer list.  No member is __restrict__: several kernels store to the iterate or
 // the staged trial through one group and read it through another.
-struct Bounds {  // of w = [x_free, s]: which are finite, and their (relaxed) values
-  const uint8_t *hasL = nullptr, *hasU = nullptr;
-  const double *wl0 = nullptr, *wu0 = nullptr;
-};
+// (Bounds — of w = [x_free, s]: which are finite, their relaxed values and the row stride — is
+// cpl_accept.hpp's: cpl_ipm.hip's and cpl_kernels.hip's argument blocks carry it too)
 struct Iterate {  // the primal-dual iterate (the restoration phase's: its own bound multipliers)
   double *w = nullptr, *y = nullptr, *zL = nullptr, *zU = nullptr;
 };

@@ -45,7 +45,7 @@ struct RestoEnterArgs {
   int m, nw;
   const uint8_t* failed;
   const double *c, *w, *zL, *zU, *mu, *theta_k, *phi_k;
-  const uint8_t *hasL, *hasU;
+  Bounds bd;  // (the entry reads hasL / hasU alone)
   double *filt_t, *filt_p;
   int64_t *fcount, *iters;
   uint8_t* in_resto;
@@ -72,8 +72,8 @@ __device__ __forceinline__ void resto_enter_one(const RestoEnterArgs& E, int64_t
   const double* __restrict__ mu = E.mu;
   const double* __restrict__ theta_k = E.theta_k;
   const double* __restrict__ phi_k = E.phi_k;
-  const uint8_t* __restrict__ hasL = E.hasL;
-  const uint8_t* __restrict__ hasU = E.hasU;
+  const uint8_t* __restrict__ hasL = E.bd.hasL;
+  const uint8_t* __restrict__ hasU = E.bd.hasU;
   double* filt_t = E.filt_t;
   double* filt_p = E.filt_p;
   int64_t* fcount = E.fcount;
@@ -216,12 +216,12 @@ struct RestoArgs {
 };
 __global__ __launch_bounds__(256) void k_resto_prep1(int64_t B, const RestoArgs R) {
   const int m = R.m, nf = R.nf, nw = R.nw;
-  const auto [hasL, hasU, wl0, wu0] = R.bd;
   const auto [w, y, zLR, zUR] = R.it;
   const auto [wR, pR, nR, zp, zn] = R.rv;
   const auto [actR, searching, alpha, a_min, muR, thetaR, phiR, gdR, switchR, thmaxR, ftR, fpR] = R.ls;
   const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
   if (b >= B) return;
+  const auto [hasL, hasU, wl0, wu0] = R.bd.row_wave(b);
   const int lane = threadIdx.x & 63;
   const bool a = R.active[b] && R.in_resto[b];
   if (!a) {
@@ -360,13 +360,17 @@ __global__ __launch_bounds__(256) void k_resto_prep2(
     int64_t B, int m, int nf, int nw, const uint8_t* __restrict__ actR, const double* __restrict__ c,
     const double* __restrict__ w, const double* __restrict__ y, const double* __restrict__ wR,
     const double* __restrict__ pR, const double* __restrict__ nR, const double* __restrict__ zp,
-    const double* __restrict__ zn, const double* __restrict__ muR, const uint8_t* __restrict__ hasL,
-    const uint8_t* __restrict__ hasU, const double* __restrict__ wl0, const double* __restrict__ wu0,
+    const double* __restrict__ zn, const double* __restrict__ muR, const Bounds bd,
     double* __restrict__ M, double* __restrict__ rp, double* __restrict__ rn, double* __restrict__ Dinv,
     double* __restrict__ r2, double* __restrict__ thetaR, double* __restrict__ phiR) {
   const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
   if (b >= B || !actR[b]) return;
   const int lane = threadIdx.x & 63;
+  const uint8_t* __restrict__ hasL = bd.hasL;
+  const uint8_t* __restrict__ hasU = bd.hasU;
+  const BoundsRow br = bd.row_wave(b);  // (the instance's row, or the template's constants)
+  const double* __restrict__ wl0 = br.wl0;
+  const double* __restrict__ wu0 = br.wu0;
   const double mu = muR[b], eta = sqrt(mu);
   double prox = 0.0, lg = 0.0, th = 0.0, pn = 0.0, lpn = 0.0;
   for (int k = lane; k < nw; k += 64) {
@@ -414,8 +418,7 @@ __global__ __launch_bounds__(256) void k_resto_post(
     const double* __restrict__ pR, const double* __restrict__ nR, const double* __restrict__ zp,
     const double* __restrict__ zn, const double* __restrict__ zLR, const double* __restrict__ zUR,
     const double* __restrict__ rp, const double* __restrict__ rn, const double* __restrict__ muR,
-    const double* __restrict__ tauR, const uint8_t* __restrict__ hasL, const uint8_t* __restrict__ hasU,
-    const double* __restrict__ wl0, const double* __restrict__ wu0, const double* __restrict__ thetaR,
+    const double* __restrict__ tauR, const Bounds bd, const double* __restrict__ thetaR,
     const double* __restrict__ thminR, const double* __restrict__ f, const double* __restrict__ g,
     double* __restrict__ dp, double* __restrict__ dn, double* __restrict__ dzL, double* __restrict__ dzU,
     double* __restrict__ dzp, double* __restrict__ dzn, double* __restrict__ a_max, double* __restrict__ a_z,
@@ -428,6 +431,11 @@ __global__ __launch_bounds__(256) void k_resto_post(
   const int lane = threadIdx.x & 63;
   if (b == 0 && lane == 0 && any) any[2] = 0;
   if (!actR[b]) return;
+  const uint8_t* __restrict__ hasL = bd.hasL;
+  const uint8_t* __restrict__ hasU = bd.hasU;
+  const BoundsRow br = bd.row_wave(b);  // (the instance's row, or the template's constants)
+  const double* __restrict__ wl0 = br.wl0;
+  const double* __restrict__ wu0 = br.wu0;
   const double mu = muR[b], t = tauR[b];
   double rpmax = INFINITY, rz = INFINITY, gd = 0.0;
   for (int k = lane; k < nw; k += 64) {
@@ -491,12 +499,12 @@ __global__ __launch_bounds__(256) void k_resto_post(
 // the restoration line search's acceptance test at one trial point (p, n along with w) and the take
 __global__ __launch_bounds__(256) void k_resto_judge(int64_t B, const RestoArgs R) {
   const int m = R.m, nf = R.nf, nw = R.nw;
-  const auto [hasL, hasU, wl0, wu0] = R.bd;
   const auto [wR, pR, nR, zp, zn] = R.rv;
   const auto [actR, searching, alpha, a_min, muR, thetaR, phiR, gdR, switchR, thmaxR, ftR, fpR] = R.ls;
   const auto [st_f, st_g, st_w, st_alpha, st_aug, st_p, st_n] = R.st;
   const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
   if (b >= B || !searching[b]) return;
+  const auto [hasL, hasU, wl0, wu0] = R.bd.row_wave(b);
   const int lane = threadIdx.x & 63;
   const double al = alpha[b], mu = muR[b], eta = sqrt(mu);
   const double* wb = R.wt + b * nw;
@@ -548,7 +556,6 @@ __global__ __launch_bounds__(256) void k_resto_judge(int64_t B, const RestoArgs 
 // reset to 1 when any exceeds 1000, y = 0, a fresh quasi-Newton model)
 __global__ __launch_bounds__(256) void k_resto_accept(int64_t B, const RestoArgs R) {
   const int m = R.m, nf = R.nf, nw = R.nw;
-  const auto [hasL, hasU, wl0, wu0] = R.bd;
   const auto [w, y, zLR, zUR] = R.it;
   const auto [wR, pR, nR, zp, zn] = R.rv;
   const auto [dw, dy, dzL, dzU] = R.sp;
@@ -556,6 +563,7 @@ __global__ __launch_bounds__(256) void k_resto_accept(int64_t B, const RestoArgs
   const auto [st_f, st_g, st_w, st_alpha, st_aug, st_p, st_n] = R.st;
   const int64_t b = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
   if (b >= B) return;
+  const auto [hasL, hasU, wl0, wu0] = R.bd.row_wave(b);
   const int lane = threadIdx.x & 63;
   if (!actR[b]) {
     if (lane == 0) R.movedR[b] = 0;

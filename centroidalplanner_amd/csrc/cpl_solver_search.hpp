@@ -65,29 +65,31 @@ __global__ void k_unpack_tau(int64_t total, int n, int nw, const int32_t* __rest
 }
 
 // X = unpack(w), the free variables clamped into [xl, xu]; the fixed ones keep Xbase's value (the
-// instance's own under fixed_from_x0, where the template's bound is not theirs)
+// instance's own under fixed_from_x0, where the template's bound is not theirs).  xstride: 0 — xl, xu
+// are the template's [n]; n — one row per instance [B, n] (per-instance bounds).
 __global__ void k_unpack_free(int64_t total, int n, int nw, const int32_t* __restrict__ freepos,
                               const double* __restrict__ Xbase, const double* __restrict__ w,
-                              const double* __restrict__ xl, const double* __restrict__ xu, double* __restrict__ X) {
+                              const double* __restrict__ xl, const double* __restrict__ xu, int64_t xstride,
+                              double* __restrict__ X) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= total) return;
   const int64_t b = e / n;
   const int j = (int)(e - b * n);
   const int k = freepos[j];
-  X[e] = k >= 0 ? fmin(fmax(w[b * nw + k], xl[j]), xu[j]) : Xbase[e];
+  X[e] = k >= 0 ? fmin(fmax(w[b * nw + k], xl[b * xstride + j]), xu[b * xstride + j]) : Xbase[e];
 }
 
-// X = unpack(w) (optionally clamped into [xl, xu]: IPOPT honor_original_bounds)
+// X = unpack(w) (optionally clamped into [xl, xu]: IPOPT honor_original_bounds; xstride as above)
 __global__ void k_unpack(int64_t total, int n, int nw, const int32_t* __restrict__ freepos,
                          const double* __restrict__ Xbase, const double* __restrict__ w, const double* __restrict__ xl,
-                         const double* __restrict__ xu, double* __restrict__ X) {
+                         const double* __restrict__ xu, int64_t xstride, double* __restrict__ X) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= total) return;
   const int64_t b = e / n;
   const int j = (int)(e - b * n);
   const int k = freepos[j];
   double v = k >= 0 ? w[b * nw + k] : Xbase[e];
-  if (xl) v = fmin(fmax(v, xl[j]), xu[j]);
+  if (xl) v = fmin(fmax(v, xl[b * xstride + j]), xu[b * xstride + j]);
   X[e] = v;
 }
 
@@ -277,7 +279,7 @@ __device__ __forceinline__ double pd_error_wave(int m, int nf, int nw, const dou
 // soft phase starts or continues); the step's alpha then also moves the bound multipliers
 __device__ __forceinline__ void soft_judge_wave(int64_t b, const SoftStepArgs& a) {
   const int n = a.n, m = a.m, nf = a.nf, nw = a.nw, nnz_rec = a.nnz_rec;
-  const auto [hasL, hasU, wl0, wu0] = a.bd;
+  const auto [hasL, hasU, wl0, wu0] = a.bd.row_wave(b);
   const auto [w, y, zL, zU] = a.it;
   const auto [dw, dy, dzL, dzU] = a.sp;
   const auto [act, searching, alpha, a_min, mu, theta_k, phi_k, gd, switch_ok, theta_max, ft, fp] = a.ls;

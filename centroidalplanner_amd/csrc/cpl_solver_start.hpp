@@ -21,6 +21,59 @@ __global__ void k_xbase(int64_t total, int n, const double* __restrict__ x0, con
   Xbase[e] = is_fixed[j] ? xl[j] : x0[e];
 }
 
+// ---- per-instance bounds (cpl_solver_solve_box) ----
+// The caller's x-order rows x_lb, x_ub [B, n] into the solver's own: the relaxed w-order rows wl, wu
+// [B, nw] every kernel of the iteration reads (Bounds with stride nw) and the unrelaxed x-order rows xl, xu
+// [B, n] of the final projection.  One thread per entry of [B, n + nI]:
+//   a free variable j (w position k): its two values validated, copied to xl / xu, relaxed exactly as
+//     cpl_solver_create relaxes the template's (lo - 1e-8 max(|lo|, 1), up + 1e-8 max(|up|, 1): no
+//     contraction, the host's bits) into wl / wu;
+//   a template-fixed variable: the caller's entries are not read; xl / xu take the template's;
+//   a slack k >= nf: the template's relaxed g_l / g_u.
+// An entry is invalid when it is NaN or |v| >= 1e19 (BIG), or when ub - lb <= 1e-14 max(1, |lb|) (an empty
+// box, or one cpl_solver_create's test would call fixed).  fault: one 64-bit word, all ones before the
+// launch; an invalid entry leaves min over ((b n + j) 4 + kind), kind 0: lb not finite, 1: ub not finite,
+// 2: ub does not exceed lb — the first offending instance and variable in row-major order.
+constexpr int BOX_LB_BAD = 0, BOX_UB_BAD = 1, BOX_EMPTY = 2;
+struct BoxPrepArgs {
+  int n = 0, nf = 0, nw = 0;
+  const int32_t* freepos = nullptr;                          // [n]
+  const double *x_lb = nullptr, *x_ub = nullptr;             // the caller's [B, n]
+  const double *xl_t = nullptr, *xu_t = nullptr;             // the template's [n]
+  const double *wl_t = nullptr, *wu_t = nullptr;             // the template's relaxed [nw]
+  double *wl = nullptr, *wu = nullptr, *xl = nullptr, *xu = nullptr;
+  unsigned long long* fault = nullptr;
+};
+__global__ void k_box_prepare(int64_t total, const BoxPrepArgs a) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const int per = a.n + (a.nw - a.nf);
+  const int64_t b = e / per;
+  const int j = (int)(e - b * per);
+  if (j >= a.n) {  // a slack: the template's
+    const int k = a.nf + (j - a.n);
+    a.wl[b * a.nw + k] = a.wl_t[k];
+    a.wu[b * a.nw + k] = a.wu_t[k];
+    return;
+  }
+  const int k = a.freepos[j];
+  if (k < 0) {
+    a.xl[b * a.n + j] = a.xl_t[j];
+    a.xu[b * a.n + j] = a.xu_t[j];
+    return;
+  }
+  const double lo = a.x_lb[b * a.n + j], up = a.x_ub[b * a.n + j];
+  int kind = -1;
+  if (!(fabs(lo) < BIG)) kind = BOX_LB_BAD;
+  else if (!(fabs(up) < BIG)) kind = BOX_UB_BAD;
+  else if (up - lo <= 1e-14 * fmax(1.0, fabs(lo))) kind = BOX_EMPTY;
+  if (kind >= 0) atomicMin(a.fault, (unsigned long long)((b * a.n + j) * 4 + kind));
+  a.xl[b * a.n + j] = lo;
+  a.xu[b * a.n + j] = up;
+  a.wl[b * a.nw + k] = lo - 1e-8 * fmax(fabs(lo), 1.0);
+  a.wu[b * a.nw + k] = up + 1e-8 * fmax(fabs(up), 1.0);
+}
+
 // ---- warm start [IPOPT-ext: warm_start_init_point, WarmStartIterateInitializer restated in this
 // engine's sign convention; include/cpl_mi355x.h cpl_warm_start, batch_ipm.py WarmStart] ----
 struct WarmArgs {
@@ -35,13 +88,12 @@ struct WarmArgs {
 // instance's by its warm_start_bound_push / _frac
 template <bool WARM>
 __global__ void k_start_x(int64_t total, int n, const int32_t* __restrict__ freepos, const double* __restrict__ Xbase,
-                          const uint8_t* __restrict__ hasL, const uint8_t* __restrict__ hasU,
-                          const double* __restrict__ wl0, const double* __restrict__ wu0, double* __restrict__ X,
-                          const WarmArgs wa) {
+                          const Bounds bd, double* __restrict__ X, const WarmArgs wa) {
   const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= total) return;
   const int j = (int)(e % n);
   const int k = freepos[j];
+  const auto [hasL, hasU, wl0, wu0] = bd.row(e / n);
   double kp = 1e-2, kf = 1e-2;
   if constexpr (WARM) {
     if (wa.flag[e / n]) {
@@ -82,7 +134,7 @@ __global__ __launch_bounds__(256) void k_init_state(int64_t B, const InitStateAr
   if (b >= B) return;
   const int lane = threadIdx.x & 63;
   const int n = a.n, m = a.m, nf = a.nf, nw = a.nw;
-  const auto [hasL, hasU, wl0, wu0] = a.bd;
+  const auto [hasL, hasU, wl0, wu0] = a.bd.row_wave(b);
   const auto [w, y, zL, zU] = a.it;
   // the push of x and of the slacks, the barrier parameter: the cold start's, or a warm instance's own
   bool warm = false;

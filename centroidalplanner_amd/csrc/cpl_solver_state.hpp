@@ -28,8 +28,8 @@ struct Arena {
 //   temp   [B, width] by batch row, written before it is read within an iteration
 //   full   [B, width] by original instance (results, constant zeros)
 // ZEROED: cleared at the start of every solve.
-// (the solve is scaled / has masses / tags / instance data)
-enum MoveWhen : uint8_t { NEVER, ALWAYS, IF_SCALED, IF_MASS, IF_TAG, IF_INST };
+// (the solve is scaled / has masses / tags / instance data / per-instance bounds)
+enum MoveWhen : uint8_t { NEVER, ALWAYS, IF_SCALED, IF_MASS, IF_TAG, IF_INST, IF_BOX };
 constexpr bool ZEROED = true;
 struct BufRec { void* ptr; size_t elem; int64_t width; MoveWhen when; bool zeroed; };  // elem: bytes; width: per row
 struct Carver {
@@ -133,6 +133,13 @@ struct cpl_solver {
   double *inst_w, *inst_c, *inst_p, *inst_F;
   cpl_instance_data inst = {nullptr, nullptr, nullptr, nullptr};
   bool has_inst = false;
+  // this solve's per-instance bounds (cpl_solver_solve_box; k_box_prepare writes them): the relaxed w-order
+  // rows [B, nw] by batch row (moved by the compaction; bounds_of() hands them to every kernel with stride
+  // nw), the unrelaxed x-order rows [B, n] by original instance (the final projection), the validation's
+  // fault word; box_ok: the template bounds every free variable on both sides
+  double *box_wl, *box_wu, *box_xl, *box_xu;
+  unsigned long long* box_fault;
+  bool has_box = false, box_ok = false;
   int64_t *fstatus, *fiters, *fresto;
   uint64_t* scratch;
   int64_t scratch_words = 0;

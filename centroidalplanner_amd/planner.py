@@ -136,13 +136,15 @@ class CentroidalPlanner:
             out.contact_values_map[name] = ContactValues(cv["force"], cv["position"], cv["normal"])
         return out
 
-    def SolveBatch(self, X0, mass=None, instance=None, fixed_from_x0: bool = False, warm_start=None, **solve_options):
+    def SolveBatch(self, X0, mass=None, instance=None, fixed_from_x0: bool = False, warm_start=None, bounds=None,
+                   **solve_options):
         """Solve B instances of this planner's problem in one batched solve on the GPU (no reference
         counterpart: B Solve() calls).  X0 [B, n]: float64 CUDA start points; mass [B]: per-instance
         robot masses (None: the planner's); instance: per-instance manipulation wrench and cost
         references (InstanceData); fixed_from_x0: every variable this planner fixes (lb == ub) takes
         instance b's value from X0[b]; warm_start: a previous result's warm_start() (batch_ipm.WarmStart:
-        its multipliers start the solve; the start point is still X0).  solve_options go to
+        its multipliers start the solve; the start point is still X0); bounds: per-instance variable bounds
+        (InstanceBounds: the batched SetPosBounds / SetForceBounds).  solve_options go to
         batch_ipm_solve (default hessian: the planner's).  Returns the BatchSolveResult; the planner's own variables are left as they were."""
         from .batch_ipm import batch_ipm_solve
 
@@ -151,7 +153,7 @@ class CentroidalPlanner:
         if not getattr(X0, "is_cuda", False):
             raise ValueError("SolveBatch: X0 must be a float64 CUDA tensor [B, n]")
         return batch_ipm_solve(self._cpl_problem, X0, mass=mass, instance=instance, fixed_from_x0=fixed_from_x0,
-                               warm_start=warm_start, **opts)
+                               warm_start=warm_start, bounds=bounds, **opts)
 
     # ---- validation helpers ------------------------------------------------------------------
     def HasContact(self, contact_name: str) -> bool:  # :359-370
@@ -358,7 +360,7 @@ class CoMPlanner:
         return self._cp.GetSolverOptions()
 
     def SolveBatch(self, positions, normals=None, com_ref=None, wrench=None, mass=None, warm_start=None,
-                   **solve_options):
+                   force_lb=None, force_ub=None, **solve_options):
         """The stance query, batched: are these B candidate stances statically feasible, and with what
         forces and CoM?  The batched form of B x (SetContactPosition / SetContactNormal / SetCoMRef /
         Solve).  positions [B, N, 3] (contact_names order), normals [B, N, 3] (None: the planner's),
@@ -368,11 +370,13 @@ class CoMPlanner:
         clipped to the force bounds, and the given positions and normals.  warm_start: the previous
         stance's result.warm_start(mu_init=1e-4) — the solve starts from its multipliers and, when it carries
         x, from its CoM and forces instead of the built-in guess (positions and normals still come from the
-        arguments): r = planner.SolveBatch(p[t], warm_start=r.warm_start(mu_init=1e-4)).  Returns the
+        arguments): r = planner.SolveBatch(p[t], warm_start=r.warm_start(mu_init=1e-4)).  force_lb, force_ub
+        [B, N, 3] (both or neither): per-stance force bounds, the batched SetForceBounds; the built-in force guess
+        is clipped into them.  Returns the
         BatchSolveResult of the solve with fixed_from_x0."""
         import torch
 
-        from .problem import InstanceData
+        from .problem import InstanceBounds, InstanceData
 
         prob = self._cp.GetCplProblem()
         N = len(self._contact_names)
@@ -394,6 +398,10 @@ class CoMPlanner:
         normals = per_batch(normals, (B, N, 3), "normals")
         com_ref = per_batch(com_ref, (B, 3), "com_ref")
         mass = per_batch(mass, (B,), "mass")
+        if (force_lb is None) != (force_ub is None):
+            raise ValueError("force_lb and force_ub come together")
+        force_lb = per_batch(force_lb, (B, N, 3), "force_lb")
+        force_ub = per_batch(force_ub, (B, N, 3), "force_ub")
         d = prob.desc()
         X0 = torch.empty(B, 3 + 9 * N, dtype=torch.float64, device=dev)
         X0[:, 0:3] = com_ref if com_ref is not None else torch.tensor(list(d.com_ref), dtype=torch.float64, device=dev)
@@ -403,7 +411,10 @@ class CoMPlanner:
         F0 = torch.stack([torch.ones_like(fz), torch.ones_like(fz), fz], dim=1)  # [B, 3]
         F_lb = torch.tensor([list(d.F_lb[i]) for i in range(N)], dtype=torch.float64, device=dev)
         F_ub = torch.tensor([list(d.F_ub[i]) for i in range(N)], dtype=torch.float64, device=dev)
-        blocks[:, :, 0:3] = torch.minimum(torch.maximum(F0[:, None, :], F_lb[None]), F_ub[None])
+        if force_lb is not None:
+            blocks[:, :, 0:3] = torch.minimum(torch.maximum(F0[:, None, :], force_lb), force_ub)
+        else:
+            blocks[:, :, 0:3] = torch.minimum(torch.maximum(F0[:, None, :], F_lb[None]), F_ub[None])
         if warm_start is not None and warm_start.x is not None:  # the previous solution's CoM and forces
             xw = per_batch(warm_start.x, (B, 3 + 9 * N), "warm_start.x")
             X0[:, 0:3] = xw[:, 0:3]
@@ -412,8 +423,9 @@ class CoMPlanner:
         blocks[:, :, 6:9] = normals if normals is not None else torch.tensor(
             [list(d.n_lb[i]) for i in range(N)], dtype=torch.float64, device=dev)[None]
         inst = InstanceData(wrench=wrench, com_ref=com_ref)
+        box = None if force_lb is None else InstanceBounds(F_lb=force_lb, F_ub=force_ub)
         return self._cp.SolveBatch(X0, mass=mass, instance=inst if inst else None, fixed_from_x0=True,
-                                   warm_start=warm_start, **solve_options)
+                                   warm_start=warm_start, bounds=box, **solve_options)
 
     def SetCoMWeight(self, w):
         self._cp.SetCoMWeight(w)

@@ -145,6 +145,72 @@ class InstanceData:
                                     for k in self.FIELDS))
 
 
+class InstanceBounds:
+    """Per-instance variable bounds of a batch (cpl_instance_bounds): the batched form of SetPosBounds /
+    SetForceBounds / SetNormalBounds and the CoM box.  com_lb, com_ub [B, 3] and F_lb, F_ub, p_lb, p_ub,
+    n_lb, n_ub [B, N, 3] (contacts in contact_names order), float64 CUDA tensors; a pair left None takes
+    the template's bounds for every instance.  Or the two x-order arrays whole: x_lb, x_ub [B, n]
+    (CoM | F_i p_i n_i per contact).  A lower bound needs its upper bound and the reverse.  The template
+    still says which variables are fixed: entries there are never read."""
+
+    PAIRS = (("com_lb", "com_ub"), ("F_lb", "F_ub"), ("p_lb", "p_ub"), ("n_lb", "n_ub"))
+    FIELDS = tuple(k for pair in PAIRS for k in pair) + ("x_lb", "x_ub")
+
+    def __init__(self, com_lb=None, com_ub=None, F_lb=None, F_ub=None, p_lb=None, p_ub=None, n_lb=None, n_ub=None,
+                 x_lb=None, x_ub=None):
+        self.com_lb, self.com_ub, self.F_lb, self.F_ub = com_lb, com_ub, F_lb, F_ub
+        self.p_lb, self.p_ub, self.n_lb, self.n_ub, self.x_lb, self.x_ub = p_lb, p_ub, n_lb, n_ub, x_lb, x_ub
+        for lo, up in self.PAIRS + (("x_lb", "x_ub"),):
+            if (getattr(self, lo) is None) != (getattr(self, up) is None):
+                given, missing = (lo, up) if getattr(self, up) is None else (up, lo)
+                raise ValueError(f"InstanceBounds.{given} needs InstanceBounds.{missing}: a lower and an upper bound "
+                                 "come together")
+        if x_lb is not None and any(getattr(self, k) is not None for pair in self.PAIRS for k in pair):
+            raise ValueError("InstanceBounds.x_lb / x_ub are the whole arrays: give them or the per-set fields, not both")
+
+    def __bool__(self):
+        return any(getattr(self, k) is not None for k in self.FIELDS)
+
+    def packed(self, problem: "CplProblem", batch: int, device):
+        """The two x-order arrays (x_lb, x_ub) [batch, n] on `device`, contiguous: the given fields over the
+        template's bounds (problem.get_bounds_info()).  ValueError naming the field on a wrong type, dtype,
+        shape or device."""
+        import torch
+
+        N = len(problem.contact_names)
+        n = 3 + 9 * N
+        shapes = {"com_lb": (batch, 3), "com_ub": (batch, 3), "x_lb": (batch, n), "x_ub": (batch, n)}
+        for k in ("F_lb", "F_ub", "p_lb", "p_ub", "n_lb", "n_ub"):
+            shapes[k] = (batch, N, 3)
+        device = torch.device(device)
+        for k in self.FIELDS:
+            t = getattr(self, k)
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or t.dtype != torch.float64:
+                raise ValueError(f"InstanceBounds.{k} must be a float64 tensor")
+            if tuple(t.shape) != shapes[k]:
+                raise ValueError(f"InstanceBounds.{k} must have shape {shapes[k]}, not {tuple(t.shape)}")
+            if t.device != device:
+                raise ValueError(f"InstanceBounds.{k} must be on the batch's device {device}, not {t.device}")
+        if self.x_lb is not None:
+            return self.x_lb.contiguous(), self.x_ub.contiguous()
+        xl, xu = problem.get_bounds_info()[:2]
+        out = []
+        for side, tmpl in ((0, xl), (1, xu)):
+            x = torch.as_tensor(np.asarray(tmpl, dtype=np.float64), device=device).repeat(batch, 1)
+            blocks = x[:, 3:].view(batch, N, 9)
+            com = getattr(self, self.PAIRS[0][side])
+            if com is not None:
+                x[:, 0:3] = com
+            for q, pair in enumerate(self.PAIRS[1:]):  # F, p, n: columns 0:3, 3:6, 6:9 of a contact's block
+                t = getattr(self, pair[side])
+                if t is not None:
+                    blocks[:, :, 3 * q:3 * q + 3] = t
+            out.append(x)
+        return out[0], out[1]
+
+
 class CplProblem:
     """One CentroidalPlanner problem template; evaluates single instances (TNLP hooks) or batches.
 

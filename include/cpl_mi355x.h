@@ -854,6 +854,49 @@ int32_t cpl_solver_solve_warm(cpl_solver* s, const double* d_x0, const double* d
  * unbounded entries, and the final barrier parameter [batch] (any may be NULL) */
 int32_t cpl_solver_warm_state(const cpl_solver* s, double* d_zL, double* d_zU, double* d_mu, void* stream);
 
+/*
+ * Per-instance variable bounds: the batched form of CentroidalPlanner::SetPosBounds / SetForceBounds and
+ * the CoM box.  Instance b's free variable j is bounded by [d_x_lb[b][j], d_x_ub[b][j]] instead of the
+ * template's box; fixed_from_x0 stays the degenerate box lb == ub.
+ *   - The template still decides structure: WHICH variables are fixed (cpl_solver_create's lb == ub test),
+ *     which bounds exist and how many.  Entries at template-fixed variables are never read (NaN there is
+ *     fine; with fixed_from_x0 those values come from d_x0 as before).  A template that leaves a free
+ *     variable without a finite bound on either side (|b| >= 1e19) cannot take per-instance bounds: the
+ *     call returns CPL_ERR_UNSUPPORTED before any launch.  (Variable3D's default is +-1000.)
+ *   - The bounds of a free variable are relaxed exactly as cpl_solver_create relaxes the template's,
+ *     lo - 1e-8 max(|lo|, 1) and up + 1e-8 max(|up|, 1), on the device, which computes the host's bits (the
+ *     library is built without contraction).  The slack bounds stay the template's g_l / g_u.
+ *   - Everything that reads a bound during the solve reads the instance's: the push of the start point
+ *     (cold and warm), the barrier terms, Sigma and the complementarity measures, both
+ *     fraction-to-the-boundary steps, the kappa_Sigma safeguard of the accept, the fused line search and
+ *     its soft restoration step, the restoration phase, and the final projection onto the original,
+ *     unrelaxed bounds (honor_original_bounds).
+ *   - The contract, as for instance data: row b is bitwise the solve of a batch of one whose template
+ *     carries instance b's bounds — x, y, status, iterations, restorations, objective and the bound
+ *     multipliers cpl_solver_warm_state returns.
+ *   - Validation runs on the device, once, before the start: an entry of a free variable is invalid when
+ *     it is NaN or infinite or |v| >= 1e19, or when ub - lb <= 1e-14 max(1, |lb|) (lb > ub, or a box
+ *     cpl_solver_create's test would call fixed).  The call then returns CPL_ERR_INVALID_ARGUMENT,
+ *     cpl_last_error() names the first offending instance and variable and whether lb or ub is at fault,
+ *     nothing else has been launched and the solver stays usable.
+ *   - Independent of the Hessian mode, of instance data and of a warm start.
+ * The solver keeps its own copies (2 (nw + n) doubles per instance, carved by cpl_solver_create whether or
+ * not a solve ever gives bounds; the active-set compaction moves the rows the iteration reads).
+ */
+typedef struct cpl_instance_bounds {
+  const double* d_x_lb; /* [batch, n] device, x order (CoM | F_i p_i n_i in contact_names order) */
+  const double* d_x_ub; /* [batch, n] */
+} cpl_instance_bounds;
+size_t cpl_instance_bounds_sizeof(void); /* sizeof(cpl_instance_bounds), for FFI layout checks */
+/* cpl_solver_solve_warm with per-instance bounds.  box == NULL, or both pointers NULL: exactly
+ * cpl_solver_solve_warm (the same launches, the same bits).  Exactly one of the two given:
+ * CPL_ERR_INVALID_ARGUMENT before any launch. */
+int32_t cpl_solver_solve_box(cpl_solver* s, const double* d_x0, const double* d_mass, const uint8_t* d_env_tag,
+                             const cpl_instance_data* inst, int32_t fixed_from_x0, const cpl_warm_start* warm,
+                             const cpl_instance_bounds* box, double* d_x, double* d_y, int32_t* d_status,
+                             int32_t* d_iters, double* d_obj, double* d_primal_inf, double* d_dual_inf,
+                             int32_t* iterations_run, int64_t* evaluations, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
