@@ -8,7 +8,7 @@ Importing it loads ``libcpl_mi355x.so`` and fails loudly if it has not been buil
 from ._abi import (ENV_GROUND, ENV_MIXED, ENV_NONE, ENV_SUPERQUADRIC, INF, MAX_CONTACTS, CplError, InvalidArgument,
                    OutOfRange, ProblemDesc)
 from .planner import CentroidalPlanner, CoMPlanner, ContactValues, Solution
-from .problem import (CplProblem, EnvironmentClass, Ground, InstanceBounds, InstanceData, MixedEnvironment,
+from .problem import (CplProblem, EnvironmentClass, Ground, InstanceBounds, InstanceCones, InstanceData, MixedEnvironment,
                       Superquadric)
 
 __all__ = [
@@ -18,6 +18,7 @@ __all__ = [
     "ContactValues",
     "CplProblem",
     "InstanceBounds",
+    "InstanceCones",
     "InstanceData",
     "EnvironmentClass",
     "Ground",

@@ -157,6 +157,15 @@ class InstanceBoundsC(ctypes.Structure):
     ]
 
 
+class InstanceConesC(ctypes.Structure):
+    """cpl_instance_cones (include/cpl_mi355x.h): device pointers [batch] and [batch, N], either may be NULL."""
+
+    _fields_ = [
+        ("d_mu", c_void_p),
+        ("d_F_thr", c_void_p),
+    ]
+
+
 class WarmStart(ctypes.Structure):
     """cpl_warm_start (include/cpl_mi355x.h): device pointers (d_mask may be NULL) and the warm_start_* constants."""
 
@@ -252,6 +261,14 @@ SIGNATURES = {
         c_int32,
         [_DESC_P, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32],
     ),
+    "cpl_instance_cones_sizeof": (c_size_t, []),
+    "cpl_eval_batch_cones": (
+        c_int32,
+        [_DESC_P, c_int64, c_void_p, c_void_p, c_void_p, POINTER(InstanceDataC), POINTER(InstanceConesC), c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p],
+    ),
+    "cpl_lagrangian_hessian_cones": (c_int32, [_DESC_P, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_int32, POINTER(InstanceConesC), c_void_p, c_void_p]),
     "cpl_derivative_test": (
         c_int32,
         [_DESC_P, c_int64, c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p, POINTER(DerivativeReport),
@@ -333,6 +350,9 @@ SIGNATURES = {
     "cpl_solver_solve_box": (c_int32, [c_void_p] * 4 + [POINTER(InstanceDataC), c_int32, POINTER(WarmStart),
                                        POINTER(InstanceBoundsC)]
                              + [c_void_p] * 7 + [POINTER(c_int32), POINTER(c_int64), c_void_p]),
+    "cpl_solver_solve_cones": (c_int32, [c_void_p] * 4 + [POINTER(InstanceDataC), c_int32, POINTER(WarmStart),
+                                         POINTER(InstanceBoundsC), POINTER(InstanceConesC)]
+                               + [c_void_p] * 7 + [POINTER(c_int32), POINTER(c_int64), c_void_p]),
 }
 
 
@@ -416,3 +436,5 @@ if lib.cpl_warm_start_sizeof() != ctypes.sizeof(WarmStart):  # pragma: no cover 
     raise ImportError("cpl_warm_start layout mismatch between header and ctypes mirror")
 if lib.cpl_instance_bounds_sizeof() != ctypes.sizeof(InstanceBoundsC):  # pragma: no cover - layout guard
     raise ImportError("cpl_instance_bounds layout mismatch between header and ctypes mirror")
+if lib.cpl_instance_cones_sizeof() != ctypes.sizeof(InstanceConesC):  # pragma: no cover - layout guard
+    raise ImportError("cpl_instance_cones layout mismatch between header and ctypes mirror")

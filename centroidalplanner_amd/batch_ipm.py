@@ -66,7 +66,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import INF
-from .problem import InstanceBounds, InstanceData
+from .problem import InstanceBounds, InstanceCones, InstanceData
 
 EPS = float(np.finfo(np.float64).eps)
 LM_HIST, LM_MAX_SKIP = 6, 2  # IPOPT limited_memory_max_history / limited_memory_max_skipping
@@ -126,26 +126,29 @@ class KernelEvaluator:
     cpl_eval_batch launch on device-resident tensors (CplProblem.eval_batch raises unless the
     inputs are CUDA tensors and the HIP library is loaded — there is no CPU fallback)."""
 
-    def __init__(self, problem, env_tag=None, instance=None):
+    def __init__(self, problem, env_tag=None, instance=None, cones=None):
         self.problem = problem
         self.env_tag = env_tag
         self.instance = instance  # per-instance wrench / references (InstanceData, cpl_eval_batch_inst)
+        self.cones = cones        # per-instance mu / force thresholds (InstanceCones, cpl_eval_batch_cones)
         self.calls = 0
 
     def __call__(self, X, mass, outputs=("g", "jac", "f", "grad"), jac_folded=False):
         """jac_folded: values-only Jacobian records (CPL_EVAL_JAC_FOLDED; CplProblem.jac_fold_info)."""
         self.calls += 1
         return self.problem.eval_batch(X, mass, self.env_tag, outputs=outputs, jac_folded=jac_folded,
-                                       instance=self.instance)
+                                       instance=self.instance, cones=self.cones)
 
     def lagrangian_grad(self, X, mass, y, y_repeat, csc, active=None):
         """grad f + J^T y of every instance in one fused launch (cpl_eval_lagrangian_grad: the
         Jacobian stays in LDS); None where the fused path does not exist (Superquadric / mixed
         batches: the caller takes eval + cpl_lagrangian_grad, the same result) — nor with instance data:
-        cpl_eval_lagrangian_grad evaluates the template, and the unfused evaluation honours `instance`."""
+        cpl_eval_lagrangian_grad evaluates the template, and the unfused evaluation honours `instance` — nor
+        with per-instance cones, for the same reason."""
         import torch
 
-        if getattr(self, "_no_fused", False) or (self.instance is not None and self.instance):
+        if (getattr(self, "_no_fused", False) or (self.instance is not None and self.instance)
+                or (self.cones is not None and self.cones)):
             return None
         out = torch.empty(X.shape[0], X.shape[1], dtype=torch.float64, device=X.device)
         st = _abi.lib.cpl_eval_lagrangian_grad(
@@ -162,7 +165,8 @@ class KernelEvaluator:
 
     def hessian(self, X, y, free, zero_cost=False):
         """The analytic Hessian of f + y^T g over the variables `free` of every instance, [B, nf, nf]
-        (cpl_lagrangian_hessian_ex: every environment kind); zero_cost: of y^T g alone."""
+        (cpl_lagrangian_hessian_ex: every environment kind; with per-instance cones
+        cpl_lagrangian_hessian_cones, which reads each instance's mu); zero_cost: of y^T g alone."""
         import torch
 
         desc = self.problem.desc()
@@ -175,6 +179,14 @@ class KernelEvaluator:
         fi = free.to(torch.int32).contiguous()
         nf = int(fi.numel())
         H = torch.empty(X.shape[0], nf, nf, dtype=torch.float64, device=X.device)
+        if self.cones is not None and self.cones:
+            cn = self.cones.validated(X.shape[0], len(self.problem.contact_names), X.device)
+            ccs = cn.c_struct()
+            _abi.check(_abi.lib.cpl_lagrangian_hessian_cones(
+                ctypes.byref(desc), X.shape[0], _ptr(X), _ptr(y), None if self.env_tag is None else _ptr(self.env_tag),
+                None, _ptr(fi), nf, ctypes.byref(ccs), _ptr(H),
+                ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)))
+            return H
         _abi.check(_abi.lib.cpl_lagrangian_hessian_ex(
             ctypes.byref(desc), X.shape[0], _ptr(X), _ptr(y), None if self.env_tag is None else _ptr(self.env_tag), None,
             _ptr(fi), nf, _ptr(H), ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)))
@@ -339,8 +351,11 @@ class NativeSolver:
             self.handle = None
 
     def solve(self, X0, mass=None, env_tag=None, instance=None, fixed_from_x0=False,
-              warm_start=None, bounds=None) -> "BatchSolveResult":
-        """bounds: per-instance variable bounds (InstanceBounds, cpl_solver_solve_box): instance b's free
+              warm_start=None, bounds=None, cones=None) -> "BatchSolveResult":
+        """cones: per-instance friction coefficients and force thresholds (InstanceCones,
+        cpl_solver_solve_cones): instance b's cone rows read its own mu and F_thr; the values are validated
+        on the device before the start (InvalidArgument naming the instance and the field).
+        bounds: per-instance variable bounds (InstanceBounds, cpl_solver_solve_box): instance b's free
         variables are boxed by its own rows, the template still says which variables are fixed.
         instance: per-instance wrench / cost references (InstanceData); fixed_from_x0: every variable
         the template fixes (lb == ub) takes instance b's value from X0[b] instead of the template's
@@ -374,7 +389,26 @@ class NativeSolver:
             raise ValueError("bounds must be an InstanceBounds")
         if warm_start is not None and not isinstance(warm_start, WarmStart):
             raise ValueError("warm_start must be a WarmStart")
-        if bounds is not None and bounds:
+        if cones is not None and not isinstance(cones, InstanceCones):
+            raise ValueError("cones must be an InstanceCones")
+        if cones is not None and cones:
+            cn = cones.validated(B, len(self.problem.contact_names), dev)
+            ccs = cn.c_struct()
+            box = None
+            if bounds is not None and bounds:
+                x_lb, x_ub = bounds.packed(self.problem, B, dev)
+                box = _abi.InstanceBoundsC(x_lb.data_ptr(), x_ub.data_ptr())
+            inst = (instance if instance is not None else InstanceData()).validated(B, len(self.problem.contact_names), dev)
+            cs = inst.c_struct()
+            ws = None if warm_start is None else warm_start.validated(B, n, m, dev)
+            wcs = None if ws is None else ws.c_struct()
+            _abi.check(_abi.lib.cpl_solver_solve_cones(
+                self.handle, _ptr(X0), None if mass is None else _ptr(mass), None if env_tag is None else _ptr(env_tag),
+                ctypes.byref(cs), 1 if fixed_from_x0 else 0, None if wcs is None else ctypes.byref(wcs),
+                None if box is None else ctypes.byref(box), ctypes.byref(ccs), _ptr(x), _ptr(y), _ptr(status),
+                _ptr(iters), _ptr(obj), _ptr(pinf), _ptr(dinf), ctypes.byref(it), ctypes.byref(ev),
+                ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        elif bounds is not None and bounds:
             x_lb, x_ub = bounds.packed(self.problem, B, dev)
             box = _abi.InstanceBoundsC(x_lb.data_ptr(), x_ub.data_ptr())
             inst = (instance if instance is not None else InstanceData()).validated(B, len(self.problem.contact_names), dev)
@@ -479,7 +513,8 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
                     acceptable_constr_viol_tol: float = 1e-2, acceptable_compl_inf_tol: float = 1e-2,
                     acceptable_obj_change_tol: float = 1e20, diverging_iterates_tol: float = 1e20,
                     max_wall_time: float = 0.0, warm_start: Optional[WarmStart] = None,
-                    bounds: Optional[InstanceBounds] = None) -> BatchSolveResult:
+                    bounds: Optional[InstanceBounds] = None,
+                    cones: Optional[InstanceCones] = None) -> BatchSolveResult:
     """Solve B instances of `problem`'s template from the starting points X0 [B, n] (torch float64,
     device tensor), per-instance robot masses `mass` [B] (None: the template's).
 
@@ -549,6 +584,10 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
     b's free variables are boxed by its own rows; row b is bitwise the solve of a batch of one whose template
     carries those bounds.  The template still decides which variables are fixed.  The host restatement raises
     ValueError, as for instance.
+    cones (device engine only): per-instance friction coefficients and force thresholds (InstanceCones,
+    cpl_solver_solve_cones) — instance b solves the problem whose template carries mu[b] and F_thr[b], bit for
+    bit.  Needs a Hessian that is not central differences (not "fd", nor "exact" on a Superquadric / mixed
+    template).  The host restatement raises ValueError, as for bounds.
     IFOPT_OPTIONS is the set IFOPT's IpoptSolver runs with."""
     if termination not in ("scaled", "ipopt"):
         raise ValueError("termination must be 'scaled' or 'ipopt'")
@@ -578,6 +617,15 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
                                                                and not isinstance(evaluator, KernelEvaluator))):
         raise ValueError("bounds: the device engine only (the host restatement solves one template per call: write "
                          "each instance's bounds into a template of its own)")
+    if cones is not None and not isinstance(cones, InstanceCones):
+        raise ValueError("cones must be an InstanceCones")
+    if cones is not None and cones:
+        if hessian == "fd" or (hessian == "exact" and problem.desc().env_kind in (_abi.ENV_SUPERQUADRIC, _abi.ENV_MIXED)):
+            raise ValueError("cones: per-instance cones need a Hessian that is not central differences (hessian='fd', "
+                             "or 'exact' on a Superquadric / mixed template): use 'analytic' or 'limited-memory'")
+        if not X0.is_cuda or (evaluator is not None and not isinstance(evaluator, KernelEvaluator)):
+            raise ValueError("cones: the device engine only (the host restatement solves one template per call: write "
+                             "each instance's mu and force thresholds into a template of its own)")
     if watchdog and X0.is_cuda:
         raise ValueError("watchdog: the host restatement only (the device engine has no watchdog)")
 
@@ -593,8 +641,10 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
                      max_wall_time=max_wall_time, **term_tols)
         if instance is None and evaluator is not None:
             instance = evaluator.instance
+        if cones is None and evaluator is not None:
+            cones = evaluator.cones
         r = ns.solve(X0, mass, None if evaluator is None else evaluator.env_tag, instance=instance,
-                     fixed_from_x0=fixed_from_x0, warm_start=warm_start, bounds=bounds)
+                     fixed_from_x0=fixed_from_x0, warm_start=warm_start, bounds=bounds, cones=cones)
         if evaluator is not None:
             evaluator.calls += r.evaluations
         return r

@@ -21,7 +21,7 @@ SOURCES = ["cpl_host.cpp", "cpl_kernels.hip", "cpl_kkt.hip", "cpl_ipm.hip", "cpl
 HEADERS = ["cpl_layout.hpp", "cpl_status.hpp", "cpl_wave.hpp", "cpl_accept.hpp", "cpl_engine.hpp", "cpl_kkt_block.hpp",
            "cpl_kkt_qd.hpp", "cpl_kkt_wave.hpp", "cpl_solver_common.hpp", "cpl_solver_start.hpp",
            "cpl_solver_search.hpp", "cpl_solver_lbfgs.hpp", "cpl_solver_resto.hpp", "cpl_solver_batch.hpp",
-           "cpl_solver_state.hpp"]
+           "cpl_solver_state.hpp", "cpl_hessian_body.inc"]
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950",

@@ -270,6 +270,11 @@ struct LsBacktrackArgs {
   const double* inst_p_ref = nullptr;
   const double* inst_F_ref = nullptr;
   int32_t inst_off = 0;
+  // a solve with per-instance cones (set by ls_backtrack, read by the LS_CONE instantiations only): the
+  // solver's copies of cpl_instance_cones' arrays in the rows' order (null: the template's value); their
+  // 1 + N values follow the instance data's in the LDS image
+  const double* cone_mu = nullptr;
+  const double* cone_F_thr = nullptr;
 };
 
 // s + sum_{r < m} a[r * stride] * v[r], accumulated in r order exactly as the plain loop

@@ -2347,8 +2347,12 @@ using EntryKernT = void (*)(const KParams, int64_t, const double*, const double*
 // place (the cheap cost / torque terms).  Each entry is the same expression as a thread per entry
 // (bitwise the same values); this layout keeps the cone's transcendental path off every wave.
 // ------------------------------------------------------------------------------------------
+// MU: the friction coefficient is mu_b, this instance's cpl_instance_cones value, instead of the template's
+// K.mu (read where it is used, so the template's instantiation is the code it was)
+template <bool MU = false>
 __device__ __forceinline__ double hessian_entry(const KParams& K, const double* __restrict__ xb,
-                                                const double* __restrict__ yb, const int* s_pos, int uu, int vv) {
+                                                const double* __restrict__ yb, const int* s_pos, int uu, int vv,
+                                                const double mu_b = 0.0) {
   // decode: kind 0 CoM, 1 F, 2 p, 3 n; contact i; axis a
   auto decode = [](int u, int& kind, int& i, int& a) {
     if (u < 3) { kind = 0; i = -1; a = u; return; }
@@ -2387,7 +2391,7 @@ __device__ __forceinline__ double hessian_entry(const KParams& K, const double* 
     const double rr = sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
     const bool fn = (ku == 1 && kv == 3) || (ku == 3 && kv == 1);
     const int aF = ku == 1 ? au : av, an = ku == 3 ? au : av;  // (for the mixed block)
-    if (fn && aF == an) h -= y0 + K.mu * y1;  // -F.n and -mu s: d2/dF_a dn_a = -1
+    if (fn && aF == an) h -= y0 + (MU ? mu_b : K.mu) * y1;  // -F.n and -mu s: d2/dF_a dn_a = -1
     if (rr > 0.0 && rr < INFINITY && y1 != 0.0) {
       const double u[3] = {t[0] / rr, t[1] / rr, t[2] / rr};
       // columns of J for the two variables
@@ -2460,71 +2464,29 @@ __global__ __launch_bounds__(256) void cpl_lagrangian_hessian_kernel(const KPara
                                                                      const uint8_t* __restrict__ active,
                                                                      const int32_t* __restrict__ free_idx,
                                                                      double* __restrict__ H) {
-  __shared__ int s_pos[CPL_MAX_CONTACTS];          // block position (map order) of contact i
-  __shared__ double s_cone[CPL_MAX_CONTACTS * 36];  // (F, n) x (F, n) entries of contact i
-  __shared__ int s_col[3 + 9 * CPL_MAX_CONTACTS];   // free index -> column of x
-  __shared__ double s_ax[SQ ? CPL_MAX_CONTACTS * 9 : 1];  // (SQ) e, h, t of (contact i, axis a)
-  __shared__ double s_sq[SQ ? CPL_MAX_CONTACTS * 9 : 1];  // (SQ) the p x p block of contact i
-  __shared__ int s_sqok[SQ ? CPL_MAX_CONTACTS : 1];       // (SQ) every entry of the block is finite
-  const int64_t b = blockIdx.x;
-  if (b >= batch || (active && !active[b])) return;  // (uniform per workgroup)
-  const int tid = threadIdx.x;
-  if (tid < K.N) s_pos[K.map_order[tid]] = tid;
-  for (int k = tid; k < nf; k += blockDim.x) s_col[k] = free_idx[k];
-  const double* xb = x + b * (int64_t)K.n;
-  const double* yb = y + b * (int64_t)K.m;
-  // (uniform per workgroup) this instance's contacts are Superquadric ones
-  const bool sq = SQ && (K.env_kind == CPL_ENV_SUPERQUADRIC || env_tag[b] == CPL_ENV_SUPERQUADRIC);
-  if (SQ && sq) {
-    for (int t = tid; t < 3 * K.N; t += blockDim.x) {
-      const int i = t / 3, a = t - 3 * i;
-      sq_axis_terms(K, a, xb[6 + 9 * i + a], s_ax + 3 * t);
-    }
-  }
-  __syncthreads();
-  // (F, n) x (F, n) blocks: local index 0-2 F_a (column 3 + 9i + a), 3-5 n_a (column 9 + 9i + a)
-  for (int t = tid; t < 36 * K.N; t += blockDim.x) {
-    const int i = t / 36, r = t - 36 * i, u6 = r / 6, v6 = r - 6 * (r / 6);
-    const int uu = 3 + 9 * i + (u6 < 3 ? u6 : 3 + u6), vv = 3 + 9 * i + (v6 < 3 ? v6 : 3 + v6);
-    s_cone[t] = hessian_entry(K, xb, yb, s_pos, uu, vv);
-  }
-  if (SQ && sq) {
-    // the pairs a <= b of contact i: 0 (0,0), 1 (0,1), 2 (0,2), 3 (1,1), 4 (1,2), 5 (2,2)
-    for (int t = tid; t < 6 * K.N; t += blockDim.x) {
-      const int i = t / 6, q = t - 6 * i;
-      const int a = q < 3 ? 0 : (q < 5 ? 1 : 2), c = q < 3 ? q : (q < 5 ? q - 2 : 2);
-      const double v = sq_pair_entry(s_ax + 9 * i, yb + 6 + 6 * s_pos[i], a, c);
-      s_sq[9 * i + 3 * a + c] = v;
-      s_sq[9 * i + 3 * c + a] = v;
-    }
-    __syncthreads();
-    if (tid < K.N) {
-      bool ok = true;
-      for (int q = 0; q < 9; ++q) ok = ok && fabs(s_sq[9 * tid + q]) < INFINITY;
-      s_sqok[tid] = ok ? 1 : 0;
-    }
-  }
-  __syncthreads();
-  double* Hb = H + b * (int64_t)nf * nf;
-  // row-major walk of the output: (row, col) of entry tid + 256 s advanced incrementally
-  const int step_r = blockDim.x / nf, step_c = blockDim.x - step_r * nf;
-  int row = tid / nf, col = tid - row * nf;
-  for (int e = tid; e < nf * nf; e += blockDim.x) {
-    const int uu = s_col[row], vv = s_col[col];
-    const int ru = uu - 3, rv = vv - 3;
-    const int iu = ru / 9, iv = rv / 9, tu = ru - 9 * iu, tv = rv - 9 * iv;
-    double h;
-    if (uu >= 3 && vv >= 3 && iu == iv && (tu < 3 || tu >= 6) && (tv < 3 || tv >= 6))
-      h = s_cone[36 * iu + 6 * (tu < 3 ? tu : tu - 3) + (tv < 3 ? tv : tv - 3)];
-    else
-      h = hessian_entry(K, xb, yb, s_pos, uu, vv);
-    if (SQ && sq && uu >= 3 && vv >= 3 && iu == iv && tu >= 3 && tu < 6 && tv >= 3 && tv < 6 && s_sqok[iu])
-      h += s_sq[9 * iu + 3 * (tu - 3) + (tv - 3)];
-    Hb[e] = h;
-    row += step_r;
-    col += step_c;
-    if (col >= nf) { col -= nf; ++row; }
-  }
+#define CPL_HESSIAN_MU false
+#define CPL_HESSIAN_MU_OF_B 0.0
+#include "cpl_hessian_body.inc"
+#undef CPL_HESSIAN_MU
+#undef CPL_HESSIAN_MU_OF_B
+}
+
+// the same with a friction coefficient per instance (cpl_lagrangian_hessian_cones); its own kernel, launched
+// only when one is given, so that the template's keeps its symbol and its code
+template <bool SQ>
+__global__ __launch_bounds__(256) void cpl_lagrangian_hessian_mu_kernel(const KParams K, int64_t batch, int nf,
+                                                                        const double* __restrict__ x,
+                                                                        const double* __restrict__ y,
+                                                                        const uint8_t* __restrict__ env_tag,
+                                                                        const uint8_t* __restrict__ active,
+                                                                        const int32_t* __restrict__ free_idx,
+                                                                        double* __restrict__ H,
+                                                                        const double* __restrict__ mu_inst) {
+#define CPL_HESSIAN_MU true
+#define CPL_HESSIAN_MU_OF_B mu_inst[b]
+#include "cpl_hessian_body.inc"
+#undef CPL_HESSIAN_MU
+#undef CPL_HESSIAN_MU_OF_B
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3408,19 +3370,163 @@ static int32_t launch_overlay(const cpl_problem_desc* d, int64_t batch, const do
   return e != hipSuccess ? hip_fail(e, "cpl_inst_overlay_kernel launch") : CPL_OK;
 }
 
-// the evaluation with instance data: the template's evaluation (whichever path launch_eval picks) with
-// f and grad switched off, the overlay on the same stream, then (norms) a pass over the finished g —
-// the fused norms would see the template's statics rows
-static int32_t launch_eval_inst(const EvalCall& c, const InstPtrs& I) {
-  if (!I.any()) return launch_eval(c);
+// ------------------------------------------------------------------------------------------
+// The cone overlay (cpl_eval_batch_cones, the solve engine with per-instance cones): the outputs that
+// depend on cpl_instance_cones — per contact the two FrictionCone values (row 0: the force threshold,
+// row 1: mu) and the six Jacobian entries of row 1 (their - mu n_a / - mu F_a terms) — of every
+// instance, recomputed from x with the instance's mu and F_thr and written over the template's.
+// cone_rows_inst is cone_rows / contact_item's expressions with mu and the threshold as arguments (the
+// library is built without contraction: the same trees give the same bits, NaN at |F_t| = 0 included).
+// One 256-thread workgroup per tile of T consecutive instances (T even, at most 64; 8 (n + 9N + 2) bytes
+// of LDS per instance): x, mu and F_thr copied in with 16-byte accesses (a NULL array staged from the
+// template), one item per (instance, contact) into LDS images, then the g pairs as 16-byte stores (m and
+// the contact's row count are even) and the Jacobian entries with the lanes along the tile's runs of six.
+// Row 1's entries are variable in every layout: contact block k's cone entries start at jbase +
+// cstride k + (15 | 12 | 0: CSR with a surface | FOLD_COMMON with a surface | FOLD_GROUND, no surface).
+struct ConePtrs {
+  const double *mu, *F_thr;  // cpl_instance_cones' arrays (device; either may be null)
+  bool any() const { return mu || F_thr; }
+};
+
+__device__ __forceinline__ void cone_rows_inst(const double mu, const double F_thr, const double* __restrict__ q,
+                                               double* __restrict__ gk, double* __restrict__ j1) {
+  const double F0 = q[0], F1 = q[1], F2 = q[2];
+  const double n0 = q[6], n1 = q[7], n2 = q[8];
+  const double t1 = dot3(F0, F1, F2, n0, n1, n2);
+  if (gk) {
+    const double nF = dot3(n0, n1, n2, F0, F1, F2);
+    const double u0 = F0 - nF * n0, u1 = F1 - nF * n1, u2 = F2 - nF * n2;
+    gk[0] = -t1 + F_thr;
+    gk[1] = sqrt((u0 * u0 + u1 * u1) + u2 * u2) - mu * t1;
+  }
+  if (j1) {
+    const double t2 = F0 - n0 * t1;
+    const double t3 = F1 - n1 * t1;
+    const double t4 = F2 - n2 * t1;
+    const double t5 = F0 * n0;
+    const double t6 = F1 * n1;
+    const double t7 = F2 * n2;
+    const double s = sqrt(t2 * t2 + t3 * t3 + t4 * t4);
+    j1[0] = (t2 * (n0 * n0 - 1.0) * 2.0 + n0 * n1 * t3 * 2.0 + n0 * n2 * t4 * 2.0) * 1.0 / s * (-1.0 / 2.0) - mu * n0;
+    j1[1] = (t3 * (n1 * n1 - 1.0) * 2.0 + n0 * n1 * t2 * 2.0 + n1 * n2 * t4 * 2.0) * 1.0 / s * (-1.0 / 2.0) - mu * n1;
+    j1[2] = (t4 * (n2 * n2 - 1.0) * 2.0 + n0 * n2 * t2 * 2.0 + n1 * n2 * t3 * 2.0) * 1.0 / s * (-1.0 / 2.0) - mu * n2;
+    j1[3] = (t2 * (t6 + t7 + t5 * 2.0) * 2.0 + F0 * n1 * t3 * 2.0 + F0 * n2 * t4 * 2.0) * 1.0 / s * (-1.0 / 2.0) - mu * F0;
+    j1[4] = (t3 * (t5 + t7 + t6 * 2.0) * 2.0 + F1 * n0 * t2 * 2.0 + F1 * n2 * t4 * 2.0) * 1.0 / s * (-1.0 / 2.0) - mu * F1;
+    j1[5] = (t4 * (t5 + t6 + t7 * 2.0) * 2.0 + F2 * n0 * t2 * 2.0 + F2 * n1 * t3 * 2.0) * 1.0 / s * (-1.0 / 2.0) - mu * F2;
+  }
+}
+
+template <bool NT>
+__global__ __launch_bounds__(256) void cpl_cone_overlay_kernel(const KParams K, int64_t batch,
+                                                               const double* __restrict__ x, const ConePtrs C,
+                                                               double* __restrict__ g_out,
+                                                               double* __restrict__ jac_out) {
+  extern __shared__ __align__(16) double smem[];
+  if (K.gate && *K.gate == 0) return;  // (every thread of every workgroup: the same byte)
+  const int tid = threadIdx.x;
+  const int T = K.T, n = K.n, m = K.m, N = K.N;
+  const int64_t b0 = (int64_t)blockIdx.x * T;
+  if (b0 >= batch) return;
+  const int valid = (int)((batch - b0) < T ? (batch - b0) : T);
+  double* X = smem;               // [T][n]
+  double* Gc = X + T * n;         // [T][N][2]  cone values, map order
+  double* Jc = Gc + T * 2 * N;    // [T][N][6]  row 1's Jacobian entries, map order
+  double* Ft = Jc + T * 6 * N;    // [T][N]     F_thr, vector order
+  double* Mu = Ft + T * N;        // [T]
+  load_ctab(K);
+  auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  // (T even: every tile's first record of every array is 16-byte aligned when the array is)
+  copy_in<256>(X, x + b0 * n, valid * n, tid, aligned(x));
+  if (C.F_thr) copy_in<256>(Ft, C.F_thr + b0 * N, valid * N, tid, aligned(C.F_thr));
+  else for (int e = tid; e < valid * N; e += 256) Ft[e] = K.F_thr[e % N];
+  if (C.mu) copy_in<256>(Mu, C.mu + b0, valid, tid, aligned(C.mu));
+  else for (int e = tid; e < valid; e += 256) Mu[e] = K.mu;
+  __syncthreads();
+  for (int e = tid; e < valid * N; e += 256) {
+    const int r = e / N, k = e - r * N;
+    const int i = s_ct.map_order[k];
+    cone_rows_inst(Mu[r], Ft[r * N + i], X + r * n + 3 + 9 * i, K.want_g ? Gc + 2 * e : nullptr,
+                   K.want_j ? Jc + 6 * e : nullptr);
+  }
+  __syncthreads();
+  const int crows = K.has_env ? 6 : 2;
+  if (K.want_g) {
+    if (aligned(g_out)) {  // (m and crows even: every cone pair of every record is one aligned pair)
+      for (int e = tid; e < valid * N; e += 256) {
+        const int r = e / N, k = e - r * N;
+        const double2 v = reinterpret_cast<const double2*>(Gc)[e];
+        double2* dst = reinterpret_cast<double2*>(g_out + (b0 + r) * m + 6 + crows * k + (crows - 2));
+        if (NT) {
+          __builtin_nontemporal_store(v.x, &dst->x);
+          __builtin_nontemporal_store(v.y, &dst->y);
+        } else {
+          *dst = v;
+        }
+      }
+    } else {
+      for (int e = tid; e < valid * 2 * N; e += 256) {
+        const int r = e / (2 * N), q = e - r * 2 * N;
+        g_out[(b0 + r) * m + 6 + crows * (q >> 1) + (crows - 2) + (q & 1)] = Gc[e];
+      }
+    }
+  }
+  if (K.want_j) {
+    // (the record length may be odd — 6 + 27N without a surface — so no 16-byte stores: eight-byte ones,
+    // consecutive lanes on consecutive entries of a run)
+    const int coff = K.has_env ? (K.fold == FOLD_NONE ? 15 : (K.fold == FOLD_COMMON ? 12 : 0)) : 0;
+    const int j0 = K.jbase + coff + 6;
+    for (int e = tid; e < valid * 6 * N; e += 256) {
+      const int r = e / (6 * N), q = e - r * 6 * N, k = q / 6, c = q - 6 * k;
+      double* dst = jac_out + (b0 + r) * (int64_t)K.nnz + j0 + K.cstride * k + c;
+      if (NT) __builtin_nontemporal_store(Jc[e], dst);
+      else *dst = Jc[e];
+    }
+  }
+}
+
+// the cone overlay's launch: g (its cone rows) and jac (row 1's entries, CSR or folded records) — either may
+// be null
+static int32_t launch_cone_overlay(const cpl_problem_desc* d, int64_t batch, const double* x, const ConePtrs& C,
+                                   double* g, double* jac, int32_t flags, hipStream_t stream, const uint8_t* gate) {
+  if (batch <= 0 || (!g && !jac)) return CPL_OK;
+  KParams K;
+  fill_params(d, K, x);
+  K.gate = gate;
+  if (flags & CPL_EVAL_JAC_FOLDED) {  // (launch_eval's settings)
+    K.fold = fold_level(d->env_kind);
+    K.nnz = folded_nnz(K.N, d->env_kind);
+    K.jbase = 6 + 12 * K.N;
+    K.cstride = folded_contact_nnz(d->env_kind);
+  }
+  K.want_g = g != nullptr; K.want_j = jac != nullptr; K.want_f = 0; K.want_grad = 0;
+  const size_t per = sizeof(double) * (size_t)(K.n + 9 * K.N + 2);
+  int T = (int)(tile_budget() / per) & ~1;  // (the tile kernel's LDS budget: 48 KiB by default)
+  K.T = T > 64 ? 64 : (T < 2 ? 2 : T);
+  const size_t lds = per * (size_t)K.T;
+  const int64_t grid = (batch + K.T - 1) / K.T;
+  if (grid > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "batch too large");
+  hipLaunchKernelGGL(g_nt ? cpl_cone_overlay_kernel<true> : cpl_cone_overlay_kernel<false>, dim3((unsigned)grid),
+                     dim3(256), lds, stream, K, batch, x, C, g, jac);
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? hip_fail(e, "cpl_cone_overlay_kernel launch") : CPL_OK;
+}
+
+// the evaluation with instance data and / or cones: the template's evaluation (whichever path launch_eval
+// picks; with instance data f and grad switched off), the overlay(s) on the same stream, then (norms) a pass
+// over the finished g — the fused norms would see the template's statics and cone rows
+static int32_t launch_eval_inst(const EvalCall& c, const InstPtrs& I, const ConePtrs& Cn = ConePtrs{}) {
+  if (!I.any() && !Cn.any()) return launch_eval(c);
   if (c.flags & CPL_EVAL_SOA)
-    return fail(CPL_ERR_UNSUPPORTED, "instance data: entry-major (CPL_EVAL_SOA) outputs are not supported");
+    return fail(CPL_ERR_UNSUPPORTED, Cn.any() ? "cones: entry-major (CPL_EVAL_SOA) outputs are not supported"
+                                              : "instance data: entry-major (CPL_EVAL_SOA) outputs are not supported");
   EvalCall t = c;
-  t.f = nullptr;
-  t.grad = nullptr;
+  if (I.any()) {
+    t.f = nullptr;
+    t.grad = nullptr;
+  }
   t.norms = nullptr;
   if (c.norms && !c.g) return fail(CPL_ERR_INVALID_ARGUMENT, "residual norms need the g output");
-  if (!c.g && !c.jac) {  // (launch_eval launches nothing without an output: its argument checks only)
+  if (!t.g && !t.jac && !t.f && !t.grad) {  // (launch_eval launches nothing without an output: its argument checks only)
     int32_t st = validate_desc(c.d);
     if (st) return st;
     if (c.flags & ~(CPL_EVAL_JAC_FOLDED | CPL_EVAL_SOA)) return fail(CPL_ERR_INVALID_ARGUMENT, "unknown eval flags");
@@ -3430,7 +3536,10 @@ static int32_t launch_eval_inst(const EvalCall& c, const InstPtrs& I) {
     return st;
   }
   if (c.batch == 0) return c.norms ? launch_eval(c) : CPL_OK;  // (the empty batch's zero norms)
-  if (int32_t st = launch_overlay(c.d, c.batch, c.x, c.mass, I, c.g, c.f, c.grad, c.stream, c.gate)) return st;
+  if (I.any())
+    if (int32_t st = launch_overlay(c.d, c.batch, c.x, c.mass, I, c.g, c.f, c.grad, c.stream, c.gate)) return st;
+  if (Cn.any())
+    if (int32_t st = launch_cone_overlay(c.d, c.batch, c.x, Cn, c.g, c.jac, c.flags, c.stream, c.gate)) return st;
   return c.norms && c.finish ? cpl_residual_norms(c.d, c.batch, c.g, c.norms, c.stream) : CPL_OK;
 }
 
@@ -3455,11 +3564,17 @@ static int32_t launch_eval_inst(const EvalCall& c, const InstPtrs& I) {
 // records, and the trial points' statics / cost items read them there (InstSrc).  A bit of the first
 // argument instead of a new parameter: the instantiations without it keep their symbols and their
 // code (profiles/instance_data/resource_usage.txt).
+// LS_CONE (with LS_INST; a solve with per-instance cones, launched only then): the instance's mu and its N
+// force thresholds (a null array: the template's) are staged behind the instance data, and after a trial
+// point's items each contact's two cone values are computed again from them (cone_rows_inst: the cone
+// overlay's function, the items' expression trees) over the template's.
 constexpr int LS_INST = 8;
+constexpr int LS_CONE = 16;
 template <int ENVKI, bool RESTO, bool FIRST, bool GF = false, bool AUGR = false>
 __global__ __launch_bounds__(64) void cpl_ls_backtrack_kernel(const KParams K, const LsBacktrackArgs A) {
-  constexpr int ENVK = ENVKI & ~LS_INST;
+  constexpr int ENVK = ENVKI & ~(LS_INST | LS_CONE);
   constexpr bool INST = (ENVKI & LS_INST) != 0;
+  constexpr bool CONE = (ENVKI & LS_CONE) != 0;
   using SRC = typename std::conditional<INST, InstSrc, TemplateSrc>::type;
   extern __shared__ __align__(16) double smem[];
   __shared__ double s_f;
@@ -3499,6 +3614,12 @@ __global__ __launch_bounds__(64) void cpl_ls_backtrack_kernel(const KParams K, c
         Q[9 + 3 * N + e] = A.inst_F_ref ? A.inst_F_ref[b * 3 * N + e] : K.F_ref[e / 3][e % 3];
       }
       src = InstSrc{Q, Q + 6, Q + 9, Q + 9 + 3 * N};  // (published by the barrier below)
+    }
+    const double* Qc = smem + A.inst_off + 9 + 6 * N;  // (CONE) [mu | F_thr, vector order]
+    if constexpr (CONE) {
+      double* Q = smem + A.inst_off + 9 + 6 * N;
+      if (lane == 0) Q[0] = A.cone_mu ? A.cone_mu[b] : K.mu;
+      for (int e = lane; e < N; e += 64) Q[1 + e] = A.cone_F_thr ? A.cone_F_thr[b * N + e] : K.F_thr[e];
     }
     __syncthreads();
     const double* wb = A.w + b * nw;
@@ -3542,6 +3663,14 @@ __global__ __launch_bounds__(64) void cpl_ls_backtrack_kernel(const KParams K, c
         }
       }
       __syncthreads();
+      if constexpr (CONE) {  // the instance's cone values over the template's
+        constexpr int CR = ENVK == CPL_ENV_NONE ? 2 : 6;
+        for (int k = lane; k < N; k += 64) {
+          const int i = s_ct.map_order[k];
+          cone_rows_inst(Qc[0], Qc[1 + i], X + 3 + 9 * i, G + 6 + CR * k + (CR - 2), nullptr);
+        }
+        __syncthreads();
+      }
       if (A.dc) {  // the scaled problem's values (LsBacktrackArgs::df / dc)
         for (int r = lane; r < m; r += 64) G[r] = G[r] * A.dc[b * m + r];
         if (lane == 0) s_f = s_f * A.df[b];
@@ -3709,8 +3838,9 @@ bool ls_post_prologue(int64_t batch) { return batch < LS_GF_MIN; }
 
 // inst (optional): the solve's instance data, [batch] rows in the rows' current order — the search then
 // runs the per-instance instantiations
+// cones (optional): the solve's per-instance cones, likewise
 int32_t ls_backtrack(const cpl_problem_desc* d, const LsBacktrackArgs& a, hipStream_t stream,
-                     const cpl_instance_data* inst) {
+                     const cpl_instance_data* inst, const cpl_instance_cones* cones) {
   if (a.batch <= 0) return CPL_OK;
   if (a.batch > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "ls_backtrack: batch too large");
   KParams K;
@@ -3752,17 +3882,31 @@ int32_t ls_backtrack(const cpl_problem_desc* d, const LsBacktrackArgs& a, hipStr
       CPL_LS_KERNELS(false, true, false, false),  CPL_LS_KERNELS(false, true, true, false),
       CPL_LS_KERNELS(false, true, false, true),   CPL_LS_KERNELS(false, true, true, true)};
 #undef CPL_LS_KERNELS
+#define CPL_LS_KERNELS(R, F, G, AG)                                                \
+  {cpl_ls_backtrack_kernel<CPL_ENV_NONE | LS_INST | LS_CONE, R, F, G, AG>,         \
+   cpl_ls_backtrack_kernel<CPL_ENV_GROUND | LS_INST | LS_CONE, R, F, G, AG>,       \
+   cpl_ls_backtrack_kernel<CPL_ENV_SUPERQUADRIC | LS_INST | LS_CONE, R, F, G, AG>, \
+   cpl_ls_backtrack_kernel<CPL_ENV_MIXED | LS_INST | LS_CONE, R, F, G, AG>}
+  static const KernT table_cone[6][4] = {
+      CPL_LS_KERNELS(false, false, false, false), CPL_LS_KERNELS(true, false, false, false),
+      CPL_LS_KERNELS(false, true, false, false),  CPL_LS_KERNELS(false, true, true, false),
+      CPL_LS_KERNELS(false, true, false, true),   CPL_LS_KERNELS(false, true, true, true)};
+#undef CPL_LS_KERNELS
   const InstPtrs I = inst ? InstPtrs{inst->d_wrench, inst->d_com_ref, inst->d_p_ref, inst->d_F_ref} : InstPtrs{};
-  const bool with_inst = I.any();
+  const ConePtrs Cn = cones ? ConePtrs{cones->d_mu, cones->d_F_thr} : ConePtrs{};
+  // (cones: one set of instantiations, which stage the instance data as well — a null array's values are
+  // the template's)
+  const bool with_cone = Cn.any(), with_inst = I.any() || with_cone;
   const int inst_off = (int)((lds / sizeof(double) + 1) & ~(size_t)1);  // the instance's values past the image
-  if (with_inst) lds = sizeof(double) * ((size_t)inst_off + 9 + 6 * (size_t)K.N);
+  if (with_inst) lds = sizeof(double) * ((size_t)inst_off + 9 + 6 * (size_t)K.N + (with_cone ? 1 + (size_t)K.N : 0));
   auto launch = [&](int row, LsBacktrackArgs args) {
     if (with_inst) {
       args.inst_wrench = I.wrench; args.inst_com_ref = I.com_ref; args.inst_p_ref = I.p_ref; args.inst_F_ref = I.F_ref;
       args.inst_off = inst_off;
+      args.cone_mu = Cn.mu; args.cone_F_thr = Cn.F_thr;
     }
-    hipLaunchKernelGGL((with_inst ? table_inst : table)[row][K.env_kind], dim3((unsigned)a.batch), dim3(64), lds, stream,
-                       K, args);
+    hipLaunchKernelGGL((with_cone ? table_cone : (with_inst ? table_inst : table))[row][K.env_kind],
+                       dim3((unsigned)a.batch), dim3(64), lds, stream, K, args);
   };
   const bool augr = first && a.aug_ws && a.aug_dc;
   if (a.resto && (!a.pR || !a.nR || !a.dp || !a.dn || !a.wR || !a.st_p || !a.st_n))
@@ -3813,6 +3957,14 @@ int32_t eval_overlay(const cpl_problem_desc* d, int64_t batch, const double* d_x
                         d_g, d_f, d_grad, (hipStream_t)stream, gate);
 }
 
+// (internal, the solve engine) the cone overlay alone: the cone rows of g and row 1's entries of the
+// Jacobian records of every row from the solver's own copies of the cones; honours the gate byte
+int32_t eval_cone_overlay(const cpl_problem_desc* d, int64_t batch, const double* d_x, const cpl_instance_cones* cones,
+                          double* d_g, double* d_jac, int32_t flags, void* stream, const uint8_t* gate) {
+  return launch_cone_overlay(d, batch, d_x, ConePtrs{cones->d_mu, cones->d_F_thr}, d_g, d_jac, flags,
+                             (hipStream_t)stream, gate);
+}
+
 }  // namespace cpl
 
 using namespace cpl;
@@ -3827,6 +3979,18 @@ int32_t cpl_eval_batch_inst(const cpl_problem_desc* d, int64_t batch, const doub
   const InstPtrs I = inst ? InstPtrs{inst->d_wrench, inst->d_com_ref, inst->d_p_ref, inst->d_F_ref} : InstPtrs{};
   return launch_eval_inst(
       EvalCall{d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, d_norms, (hipStream_t)stream, flags}, I);
+}
+
+size_t cpl_instance_cones_sizeof(void) { return sizeof(cpl_instance_cones); }
+
+int32_t cpl_eval_batch_cones(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
+                             const uint8_t* d_env_tag, const cpl_instance_data* inst, const cpl_instance_cones* cones,
+                             double* d_g, double* d_jac, double* d_f, double* d_grad, double* d_norms, int32_t flags,
+                             void* stream) {
+  const InstPtrs I = inst ? InstPtrs{inst->d_wrench, inst->d_com_ref, inst->d_p_ref, inst->d_F_ref} : InstPtrs{};
+  const ConePtrs Cn = cones ? ConePtrs{cones->d_mu, cones->d_F_thr} : ConePtrs{};
+  return launch_eval_inst(
+      EvalCall{d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, d_norms, (hipStream_t)stream, flags}, I, Cn);
 }
 
 int32_t cpl_eval_batch(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
@@ -3851,7 +4015,8 @@ int32_t cpl_eval_lagrangian_grad(const cpl_problem_desc* d, int64_t batch, const
 
 static int32_t launch_hessian(const char* who, const cpl_problem_desc* d, int64_t batch, const double* d_x,
                               const double* d_y, const uint8_t* d_env_tag, const uint8_t* d_active,
-                              const int32_t* d_free_idx, int32_t nf, double* d_H, void* stream) {
+                              const int32_t* d_free_idx, int32_t nf, double* d_H, void* stream,
+                              const double* d_mu = nullptr) {
   const std::string w(who);
   KParams K;
   fill_params(d, K, d_x);
@@ -3861,9 +4026,14 @@ static int32_t launch_hessian(const char* who, const cpl_problem_desc* d, int64_
   if (d->env_kind == CPL_ENV_MIXED && !d_env_tag) return fail(CPL_ERR_INVALID_ARGUMENT, w + ": mixed needs tags");
   if (batch > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, w + ": batch too large");
   const bool sq = d->env_kind == CPL_ENV_SUPERQUADRIC || d->env_kind == CPL_ENV_MIXED;
-  hipLaunchKernelGGL(sq ? cpl_lagrangian_hessian_kernel<true> : cpl_lagrangian_hessian_kernel<false>,
-                     dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, K, batch, (int)nf, d_x, d_y, d_env_tag,
-                     d_active, d_free_idx, d_H);
+  if (d_mu)
+    hipLaunchKernelGGL(sq ? cpl_lagrangian_hessian_mu_kernel<true> : cpl_lagrangian_hessian_mu_kernel<false>,
+                       dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, K, batch, (int)nf, d_x, d_y, d_env_tag,
+                       d_active, d_free_idx, d_H, d_mu);
+  else
+    hipLaunchKernelGGL(sq ? cpl_lagrangian_hessian_kernel<true> : cpl_lagrangian_hessian_kernel<false>,
+                       dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, K, batch, (int)nf, d_x, d_y, d_env_tag,
+                       d_active, d_free_idx, d_H);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, (w + " launch").c_str());
   return CPL_OK;
@@ -3886,6 +4056,15 @@ int32_t cpl_lagrangian_hessian_ex(const cpl_problem_desc* d, int64_t batch, cons
   if (st) return st;
   return launch_hessian("cpl_lagrangian_hessian_ex", d, batch, d_x, d_y, d_env_tag, d_active, d_free_idx, nf, d_H,
                         stream);
+}
+
+int32_t cpl_lagrangian_hessian_cones(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_y,
+                                     const uint8_t* d_env_tag, const uint8_t* d_active, const int32_t* d_free_idx,
+                                     int32_t nf, const cpl_instance_cones* cones, double* d_H, void* stream) {
+  int32_t st = validate_desc(d);
+  if (st) return st;
+  return launch_hessian("cpl_lagrangian_hessian_cones", d, batch, d_x, d_y, d_env_tag, d_active, d_free_idx, nf, d_H,
+                        stream, cones ? cones->d_mu : nullptr);
 }
 
 int32_t cpl_eval_batch_ex(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,

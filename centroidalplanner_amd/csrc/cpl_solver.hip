@@ -90,10 +90,14 @@ int32_t apply_scaling(cpl_solver* S, double* fo, double* grado, double* go, doub
 // evaluation; other paths evaluate, then k_apply_scaling)
 // (instance data: the unfused route — the template's evaluation without f / grad, the overlay, then
 // k_apply_scaling; the overlay needs no scaling arguments)
+// (per-instance cones: the same route with the cone overlay — the template's evaluation keeps f / grad
+// when there is no instance data —, so the scaling sees the overlaid cone rows and Jacobian entries)
 int32_t eval_fg(cpl_solver* S, const double* X, double* fo, double* go) {
-  if (S->has_inst) {
-    CK(cpl_eval_batch(&S->desc, S->Bcur, X, S->mass, S->tag, go, nullptr, nullptr, nullptr, S->stream));
-    CK(eval_overlay(&S->desc, S->Bcur, X, S->mass, &S->inst, go, fo, nullptr, S->stream, nullptr));
+  if (S->has_inst || S->has_cones) {
+    CK(cpl_eval_batch(&S->desc, S->Bcur, X, S->mass, S->tag, go, nullptr, S->has_inst ? nullptr : fo, nullptr,
+                      S->stream));
+    if (S->has_inst) CK(eval_overlay(&S->desc, S->Bcur, X, S->mass, &S->inst, go, fo, nullptr, S->stream, nullptr));
+    if (S->has_cones) CK(eval_cone_overlay(&S->desc, S->Bcur, X, &S->cones, go, nullptr, 0, S->stream, nullptr));
     return apply_scaling(S, fo, nullptr, go, nullptr);
   }
   if (S->scaled && S->sc_fused) {
@@ -110,10 +114,12 @@ int32_t eval_fg(cpl_solver* S, const double* X, double* fo, double* go) {
 // an evaluation whose outputs nobody reads when the byte is 0)
 int32_t eval_full(cpl_solver* S, const double* X, double* fo, double* grado, double* go, double* jo,
                   const uint8_t* gate = nullptr) {
-  if (S->has_inst) {
-    CK(eval_batch_gated(&S->desc, S->Bcur, X, S->mass, S->tag, go, jo, nullptr, nullptr, CPL_EVAL_JAC_FOLDED, S->stream,
-                        gate));
-    CK(eval_overlay(&S->desc, S->Bcur, X, S->mass, &S->inst, go, fo, grado, S->stream, gate));
+  if (S->has_inst || S->has_cones) {
+    CK(eval_batch_gated(&S->desc, S->Bcur, X, S->mass, S->tag, go, jo, S->has_inst ? nullptr : fo,
+                        S->has_inst ? nullptr : grado, CPL_EVAL_JAC_FOLDED, S->stream, gate));
+    if (S->has_inst) CK(eval_overlay(&S->desc, S->Bcur, X, S->mass, &S->inst, go, fo, grado, S->stream, gate));
+    if (S->has_cones)
+      CK(eval_cone_overlay(&S->desc, S->Bcur, X, &S->cones, go, jo, CPL_EVAL_JAC_FOLDED, S->stream, gate));
     return apply_scaling(S, fo, grado, go, jo);
   }
   if (S->scaled && S->sc_fused) {
@@ -176,7 +182,9 @@ int32_t hessian_into(cpl_solver* S, const cpl_problem_desc* d, const uint8_t* ma
     return CPL_OK;
   };
   if (S->analytic_H) {
-    if (o.hessian == CPL_HESSIAN_ANALYTIC)  // every environment kind (Ground / none: the same kernel)
+    if (S->has_cones && S->cones.d_mu)  // (either mode: the kernel of every environment kind with mu per row)
+      CK(cpl_lagrangian_hessian_cones(d, B, S->X, yh, S->tag, mask, S->free32, nf, &S->cones, S->H, st));
+    else if (o.hessian == CPL_HESSIAN_ANALYTIC)  // every environment kind (Ground / none: the same kernel)
       CK(cpl_lagrangian_hessian_ex(d, B, S->X, yh, S->tag, mask, S->free32, nf, S->H, st));
     else
       CK(cpl_lagrangian_hessian(d, B, S->X, yh, mask, S->free32, nf, S->H, st));
@@ -583,7 +591,7 @@ int32_t step_phase(cpl_solver* S, int phase, const StepMode mode = {}) {
       } else {  // the remaining trials of every instance still searching, in one launch
         HK(hipMemsetAsync(S->d_any, 0, 2, st), "hipMemsetAsync flags");
       }
-      return ls_backtrack(&S->desc, la, st, S->has_inst ? &S->inst : nullptr);
+      return ls_backtrack(&S->desc, la, st, S->has_inst ? &S->inst : nullptr, S->has_cones ? &S->cones : nullptr);
     }
     case P_SOFT: {
       const SoftStepArgs soft = soft_step_args(S);
@@ -674,7 +682,7 @@ int32_t step_phase(cpl_solver* S, int phase, const StepMode mode = {}) {
         la.rho = RHO_R;
         la.pR = S->pR; la.nR = S->nR; la.dp = S->dp; la.dn = S->dn; la.wR = S->wR;
         la.st_p = S->st_p; la.st_n = S->st_n;
-        CK(ls_backtrack(&S->desc, la, st, S->has_inst ? &S->inst : nullptr));
+        CK(ls_backtrack(&S->desc, la, st, S->has_inst ? &S->inst : nullptr, S->has_cones ? &S->cones : nullptr));
       }
       return step_phase(S, P_RACCEPT);
     }
@@ -718,7 +726,9 @@ int32_t run_phase(cpl_solver* S, int phase) {
   // and one for per-instance bounds, whose launches carry the solver's rows and their stride)
   const int inst_bits = (S->inst.d_wrench ? 1 : 0) | (S->inst.d_com_ref ? 2 : 0) | (S->inst.d_p_ref ? 4 : 0) |
                         (S->inst.d_F_ref ? 8 : 0);
-  const int64_t key = ((S->Bcur * 256 + (S->has_box ? 128 : 0) + inst_bits * 8 + (S->scaled ? 4 : 0) +
+  // (and one per cone array)
+  const int cone_bits = (S->cones.d_mu ? 1 : 0) | (S->cones.d_F_thr ? 2 : 0);
+  const int64_t key = ((S->Bcur * 1024 + cone_bits * 256 + (S->has_box ? 128 : 0) + inst_bits * 8 + (S->scaled ? 4 : 0) +
                         (S->mass ? 2 : 0) + (S->tag ? 1 : 0)) * 16) + phase;
   auto it = S->graphs.find(key);
   if (it == S->graphs.end()) {
@@ -808,7 +818,8 @@ int32_t compact(cpl_solver* S, int64_t count, int64_t Bn) {
   for (const BufRec& r : S->bufs) {
     const bool moved = r.when == ALWAYS || (r.when == IF_SCALED && S->scaled) ||
                        (r.when == IF_MASS && S->mass) || (r.when == IF_TAG && S->tag) ||
-                       (r.when == IF_INST && S->has_inst) || (r.when == IF_BOX && S->has_box);
+                       (r.when == IF_INST && S->has_inst) || (r.when == IF_BOX && S->has_box) ||
+                       (r.when == IF_CONE && S->has_cones);
     if (!moved || r.width <= 0) continue;
     const dim3 grid(blocks_elems(count * r.width)), blk(256);
     if (r.elem == 8)
@@ -838,7 +849,8 @@ int32_t compact(cpl_solver* S, int64_t count, int64_t Bn) {
 // flags, the starting iterate (cold, or per instance warm), the least-squares y, the quasi-Newton model.
 // inst: null without instance data; warm: null for a cold solve.
 int32_t solve_start(cpl_solver* S, const double* d_x0, const double* d_mass, const uint8_t* d_env_tag,
-                    const cpl_instance_data* inst, int32_t fixed_from_x0, const cpl_warm_start* warm, int64_t* evals) {
+                    const cpl_instance_data* inst, const cpl_instance_cones* cones, int32_t fixed_from_x0,
+                    const cpl_warm_start* warm, int64_t* evals) {
   const int64_t B = S->B;
   const int n = S->n, m = S->m, nf = S->nf, nw = S->nw;
   hipStream_t st = S->stream;
@@ -863,6 +875,18 @@ int32_t solve_start(cpl_solver* S, const double* d_x0, const double* d_mass, con
       HK(hipMemcpyAsync(a.dst, a.src, 8 * (size_t)B * a.width, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync instance data");
       *a.slot = a.dst;
     }
+  }
+  // ... and of the cones (validated before: cones_check)
+  S->has_cones = cones != nullptr;
+  S->cones = cpl_instance_cones{nullptr, nullptr};
+  if (cones && cones->d_mu) {
+    HK(hipMemcpyAsync(S->cone_mu, cones->d_mu, 8 * (size_t)B, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync cones mu");
+    S->cones.d_mu = S->cone_mu;
+  }
+  if (cones && cones->d_F_thr) {
+    HK(hipMemcpyAsync(S->cone_F, cones->d_F_thr, 8 * (size_t)B * S->desc.n_contacts, hipMemcpyDeviceToDevice, st),
+       "hipMemcpyAsync cones F_thr");
+    S->cones.d_F_thr = S->cone_F;
   }
   hipLaunchKernelGGL(k_iota, dim3(blocks_elems(B)), dim3(256), 0, st, B, S->orig);
   LAUNCHED("k_iota");
@@ -982,6 +1006,31 @@ int32_t box_prepare(cpl_solver* S, const cpl_instance_bounds* box) {
                                             std::to_string(j) + ": " + what);
 }
 
+// Per-instance cones (cpl_solver_solve_cones): the caller's values validated on the device (k_cone_check), once,
+// before the start, by the bounds' mechanism — one launch, one host read of the fault word.  mu must be finite
+// and > 0 (EnvironmentClass::SetMu), F_thr finite and >= 0 (CentroidalPlanner::SetForceThreshold).  A refusal
+// names the first offending instance and field (and contact) and launches nothing else.
+int32_t cones_check(cpl_solver* S, const cpl_instance_cones* cones) {
+  hipStream_t st = S->stream;
+  const int64_t B = S->B;
+  const int N = S->desc.n_contacts;
+  HK(hipMemsetAsync(S->cone_fault, 0xff, sizeof(unsigned long long), st), "hipMemsetAsync cone fault");
+  const int64_t total = B * (1 + N);
+  hipLaunchKernelGGL(k_cone_check, dim3(blocks_elems(total)), dim3(256), 0, st, total, N, cones->d_mu, cones->d_F_thr,
+                     S->cone_fault);
+  LAUNCHED("k_cone_check");
+  unsigned long long code = 0;
+  HK(hipMemcpyAsync(&code, S->cone_fault, sizeof(code), hipMemcpyDeviceToHost, st), "hipMemcpyAsync cone fault");
+  HK(hipStreamSynchronize(st), "hipStreamSynchronize");
+  if (code == ~0ull) return CPL_OK;
+  const long long b = (long long)(code / (unsigned long long)(1 + N)), j = (long long)(code % (unsigned long long)(1 + N));
+  if (j == 0)
+    return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_solve_cones: instance " + std::to_string(b) +
+                                              ", mu: the friction coefficient must be finite and > 0");
+  return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_solve_cones: instance " + std::to_string(b) + ", F_thr of contact " +
+                                            std::to_string(j - 1) + ": a force threshold must be finite and >= 0");
+}
+
 // The iteration loop: the phases, the counts (mailbox or copy), max_wall_time, the compaction.  *it: the
 // lock-step iterations run.
 int32_t solve_iterate(cpl_solver* S, int* it_out, int64_t* evals) {
@@ -1048,7 +1097,7 @@ int32_t solve_iterate(cpl_solver* S, int* it_out, int64_t* evals) {
 // The finish: the final convergence test, the results of every row still in the batch to its instance's
 // place, IPOPT's honor_original_bounds projection with its re-evaluation, the caller's outputs.
 int32_t solve_finish(cpl_solver* S, const double* d_mass, const uint8_t* d_env_tag, const cpl_instance_data* inst,
-                     int32_t fixed_from_x0, double* d_x, double* d_y, int32_t* d_status, int32_t* d_iters, double* d_obj,
+                     const cpl_instance_cones* cones, int32_t fixed_from_x0, double* d_x, double* d_y, int32_t* d_status, int32_t* d_iters, double* d_obj,
                      double* d_primal_inf, double* d_dual_inf, int64_t* evals) {
   const int64_t B = S->B;
   const int n = S->n, m = S->m, nf = S->nf, nw = S->nw;
@@ -1084,8 +1133,11 @@ int32_t solve_finish(cpl_solver* S, const double* d_mass, const uint8_t* d_env_t
                      S->freepos, S->fX, S->fw, S->has_box ? S->box_xl : S->xl, S->has_box ? S->box_xu : S->xu,
                      (int64_t)(S->has_box ? n : 0), Xf);
   LAUNCHED("k_unpack (final)");
-  // (the full batch in the instances' own order: the caller's masses, tags and instance data)
-  if (inst)
+  // (the full batch in the instances' own order: the caller's masses, tags, instance data and cones)
+  if (cones)
+    CK(cpl_eval_batch_cones(&S->desc, B, Xf, d_mass, d_env_tag, inst, cones, S->fin_g, nullptr, d_obj ? d_obj : S->fin_f,
+                            nullptr, nullptr, 0, st));
+  else if (inst)
     CK(cpl_eval_batch_inst(&S->desc, B, Xf, d_mass, d_env_tag, inst, S->fin_g, nullptr, d_obj ? d_obj : S->fin_f, nullptr,
                            nullptr, 0, st));
   else
@@ -1463,6 +1515,8 @@ int32_t cpl_solver_create(const cpl_problem_desc* d, int64_t batch, const cpl_so
   S->inst_w = c.state<double>(6, IF_INST); S->inst_c = c.state<double>(3, IF_INST);
   S->inst_p = c.state<double>(3 * (size_t)d->n_contacts, IF_INST);
   S->inst_F = c.state<double>(3 * (size_t)d->n_contacts, IF_INST);
+  S->cone_mu = c.state<double>(1, IF_CONE); S->cone_F = c.state<double>((size_t)d->n_contacts, IF_CONE);
+  S->cone_fault = c.fixed<unsigned long long>(1);
   S->fw = c.full<double>(nw); S->fy = c.full<double>(m); S->fX = c.full<double>(n);
   S->fdinf = c.full<double>(1); S->fstatus = c.full<int64_t>(1); S->fiters = c.full<int64_t>(1);
   S->fresto = c.full<int64_t>(1);
@@ -1571,6 +1625,15 @@ int32_t cpl_solver_solve_box(cpl_solver* S, const double* d_x0, const double* d_
                              const cpl_instance_bounds* box, double* d_x, double* d_y, int32_t* d_status,
                              int32_t* d_iters, double* d_obj, double* d_primal_inf, double* d_dual_inf,
                              int32_t* iterations_run, int64_t* evaluations, void* stream) {
+  return cpl_solver_solve_cones(S, d_x0, d_mass, d_env_tag, inst, fixed_from_x0, warm, box, nullptr, d_x, d_y, d_status,
+                                d_iters, d_obj, d_primal_inf, d_dual_inf, iterations_run, evaluations, stream);
+}
+
+int32_t cpl_solver_solve_cones(cpl_solver* S, const double* d_x0, const double* d_mass, const uint8_t* d_env_tag,
+                               const cpl_instance_data* inst, int32_t fixed_from_x0, const cpl_warm_start* warm,
+                               const cpl_instance_bounds* box, const cpl_instance_cones* cones, double* d_x,
+                               double* d_y, int32_t* d_status, int32_t* d_iters, double* d_obj, double* d_primal_inf,
+                               double* d_dual_inf, int32_t* iterations_run, int64_t* evaluations, void* stream) {
   // per-instance bounds: both arrays, or none (then this is cpl_solver_solve_warm)
   const bool has_box = box && (box->d_x_lb || box->d_x_ub);
   if (has_box && (!box->d_x_lb || !box->d_x_ub))
@@ -1589,6 +1652,12 @@ int32_t cpl_solver_solve_box(cpl_solver* S, const double* d_x0, const double* d_
     return fail(CPL_ERR_UNSUPPORTED,
                 "cpl_solver_solve_inst: instance data needs a Hessian that is not central differences: create the "
                 "solver with CPL_HESSIAN_ANALYTIC or CPL_HESSIAN_LIMITED_MEMORY");
+  // per-instance cones: either array, or none (then this is cpl_solver_solve_box)
+  const bool has_cones = cones && (cones->d_mu || cones->d_F_thr);
+  if (has_cones && S->fd)  // (the same rule: the perturbed points would need the arrays replicated)
+    return fail(CPL_ERR_UNSUPPORTED,
+                "cpl_solver_solve_cones: per-instance cones need a Hessian that is not central differences: create the "
+                "solver with CPL_HESSIAN_ANALYTIC or CPL_HESSIAN_LIMITED_MEMORY");
   // a warm start: all three multiplier arrays, or none (then this is cpl_solver_solve_inst)
   const bool is_warm = warm && (warm->d_y || warm->d_zL || warm->d_zU);
   if (is_warm) {
@@ -1601,14 +1670,16 @@ int32_t cpl_solver_solve_box(cpl_solver* S, const double* d_x0, const double* d_
   // order after the caller's stream (its inputs), then run on the solver's own stream
   HK(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize (caller stream)");
   if (!has_inst) inst = nullptr;
+  if (!has_cones) cones = nullptr;
   S->has_box = false;
-  if (has_box) CK(box_prepare(S, box));  // (validated on the device: nothing else is launched when it refuses)
+  if (cones) CK(cones_check(S, cones));  // (validated on the device: nothing else is launched when it refuses)
+  if (has_box) CK(box_prepare(S, box));  // (likewise)
   S->has_box = has_box;
   int it = 0;
   int64_t evals = 0;
-  CK(solve_start(S, d_x0, d_mass, d_env_tag, inst, fixed_from_x0, is_warm ? warm : nullptr, &evals));
+  CK(solve_start(S, d_x0, d_mass, d_env_tag, inst, cones, fixed_from_x0, is_warm ? warm : nullptr, &evals));
   CK(solve_iterate(S, &it, &evals));
-  CK(solve_finish(S, d_mass, d_env_tag, inst, fixed_from_x0, d_x, d_y, d_status, d_iters, d_obj, d_primal_inf, d_dual_inf,
+  CK(solve_finish(S, d_mass, d_env_tag, inst, cones, fixed_from_x0, d_x, d_y, d_status, d_iters, d_obj, d_primal_inf, d_dual_inf,
                   &evals));
   if (iterations_run) *iterations_run = it;
   if (evaluations) *evaluations = evals;

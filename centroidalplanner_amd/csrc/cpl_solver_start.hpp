@@ -74,6 +74,27 @@ __global__ void k_box_prepare(int64_t total, const BoxPrepArgs a) {
   a.wu[b * a.nw + k] = up + 1e-8 * fmax(fabs(up), 1.0);
 }
 
+// Per-instance cones (cpl_solver_solve_cones): the caller's mu [B] and F_thr [B, N] validated, one thread per
+// value of [B, 1 + N] (column 0: mu, column 1 + i: contact i's threshold; a null array is not read).  mu is
+// invalid unless it is finite and > 0, a threshold unless it is finite and >= 0 (NaN fails both tests).
+// fault: one 64-bit word, all ones before the launch; an invalid value leaves min over b (1 + N) + column —
+// the first offending instance, mu before its thresholds.
+__global__ void k_cone_check(int64_t total, int N, const double* __restrict__ mu, const double* __restrict__ F_thr,
+                             unsigned long long* fault) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const int64_t b = e / (1 + N);
+  const int j = (int)(e - b * (1 + N));
+  bool bad = false;
+  if (j == 0) {
+    if (mu) { const double v = mu[b]; bad = !(v > 0.0 && v < INFINITY); }
+  } else if (F_thr) {
+    const double v = F_thr[b * N + (j - 1)];
+    bad = !(v >= 0.0 && v < INFINITY);
+  }
+  if (bad) atomicMin(fault, (unsigned long long)e);
+}
+
 // ---- warm start [IPOPT-ext: warm_start_init_point, WarmStartIterateInitializer restated in this
 // engine's sign convention; include/cpl_mi355x.h cpl_warm_start, batch_ipm.py WarmStart] ----
 struct WarmArgs {

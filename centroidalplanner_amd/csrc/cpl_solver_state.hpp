@@ -28,8 +28,8 @@ struct Arena {
 //   temp   [B, width] by batch row, written before it is read within an iteration
 //   full   [B, width] by original instance (results, constant zeros)
 // ZEROED: cleared at the start of every solve.
-// (the solve is scaled / has masses / tags / instance data / per-instance bounds)
-enum MoveWhen : uint8_t { NEVER, ALWAYS, IF_SCALED, IF_MASS, IF_TAG, IF_INST, IF_BOX };
+// (the solve is scaled / has masses / tags / instance data / per-instance bounds / per-instance cones)
+enum MoveWhen : uint8_t { NEVER, ALWAYS, IF_SCALED, IF_MASS, IF_TAG, IF_INST, IF_BOX, IF_CONE };
 constexpr bool ZEROED = true;
 struct BufRec { void* ptr; size_t elem; int64_t width; MoveWhen when; bool zeroed; };  // elem: bytes; width: per row
 struct Carver {
@@ -133,6 +133,13 @@ struct cpl_solver {
   double *inst_w, *inst_c, *inst_p, *inst_F;
   cpl_instance_data inst = {nullptr, nullptr, nullptr, nullptr};
   bool has_inst = false;
+  // this solve's per-instance cones (cpl_solver_solve_cones): the solver's own copies, mu [B] and F_thr
+  // [B, N] by batch row (moved by the compaction with their rows); cones' pointers name them, null where the
+  // caller gave no array; cone_fault: the validation's word
+  double *cone_mu, *cone_F;
+  cpl_instance_cones cones = {nullptr, nullptr};
+  bool has_cones = false;
+  unsigned long long* cone_fault;
   // this solve's per-instance bounds (cpl_solver_solve_box; k_box_prepare writes them): the relaxed w-order
   // rows [B, nw] by batch row (moved by the compaction; bounds_of() hands them to every kernel with stride
   // nw), the unrelaxed x-order rows [B, n] by original instance (the final projection), the validation's

@@ -137,14 +137,16 @@ class CentroidalPlanner:
         return out
 
     def SolveBatch(self, X0, mass=None, instance=None, fixed_from_x0: bool = False, warm_start=None, bounds=None,
-                   **solve_options):
+                   cones=None, **solve_options):
         """Solve B instances of this planner's problem in one batched solve on the GPU (no reference
         counterpart: B Solve() calls).  X0 [B, n]: float64 CUDA start points; mass [B]: per-instance
         robot masses (None: the planner's); instance: per-instance manipulation wrench and cost
         references (InstanceData); fixed_from_x0: every variable this planner fixes (lb == ub) takes
         instance b's value from X0[b]; warm_start: a previous result's warm_start() (batch_ipm.WarmStart:
         its multipliers start the solve; the start point is still X0); bounds: per-instance variable bounds
-        (InstanceBounds: the batched SetPosBounds / SetForceBounds).  solve_options go to
+        (InstanceBounds: the batched SetPosBounds / SetForceBounds); cones: per-instance friction coefficients
+        and force thresholds (InstanceCones: the batched SetMu / SetForceThreshold; a lifted contact's force
+        stays fixed at 0 for every row — pass 0 in its threshold column).  solve_options go to
         batch_ipm_solve (default hessian: the planner's).  Returns the BatchSolveResult; the planner's own variables are left as they were."""
         from .batch_ipm import batch_ipm_solve
 
@@ -153,7 +155,7 @@ class CentroidalPlanner:
         if not getattr(X0, "is_cuda", False):
             raise ValueError("SolveBatch: X0 must be a float64 CUDA tensor [B, n]")
         return batch_ipm_solve(self._cpl_problem, X0, mass=mass, instance=instance, fixed_from_x0=fixed_from_x0,
-                               warm_start=warm_start, bounds=bounds, **opts)
+                               warm_start=warm_start, bounds=bounds, cones=cones, **opts)
 
     # ---- validation helpers ------------------------------------------------------------------
     def HasContact(self, contact_name: str) -> bool:  # :359-370
@@ -360,7 +362,7 @@ class CoMPlanner:
         return self._cp.GetSolverOptions()
 
     def SolveBatch(self, positions, normals=None, com_ref=None, wrench=None, mass=None, warm_start=None,
-                   force_lb=None, force_ub=None, **solve_options):
+                   force_lb=None, force_ub=None, mu=None, force_threshold=None, **solve_options):
         """The stance query, batched: are these B candidate stances statically feasible, and with what
         forces and CoM?  The batched form of B x (SetContactPosition / SetContactNormal / SetCoMRef /
         Solve).  positions [B, N, 3] (contact_names order), normals [B, N, 3] (None: the planner's),
@@ -372,14 +374,23 @@ class CoMPlanner:
         x, from its CoM and forces instead of the built-in guess (positions and normals still come from the
         arguments): r = planner.SolveBatch(p[t], warm_start=r.warm_start(mu_init=1e-4)).  force_lb, force_ub
         [B, N, 3] (both or neither): per-stance force bounds, the batched SetForceBounds; the built-in force guess
-        is clipped into them.  Returns the
+        is clipped into them.  mu [B], force_threshold [B, N] (either or both): per-stance friction
+        coefficient (for all contacts of the stance) and force thresholds, the batched SetMu /
+        SetForceThreshold (InstanceCones; mu must be > 0 and a threshold >= 0: the solve refuses other
+        values).  A contact the planner lifts (SetLiftingContact) keeps its force fixed at 0 for every
+        stance: pass 0 in its force_threshold column.  Returns the
         BatchSolveResult of the solve with fixed_from_x0."""
         import torch
 
-        from .problem import InstanceBounds, InstanceData
+        from .problem import InstanceBounds, InstanceCones, InstanceData
 
         prob = self._cp.GetCplProblem()
         N = len(self._contact_names)
+        if torch.is_tensor(positions) and positions.dim() == 3:  # (dtype and shape before anything needs a device)
+            for t, shape, name in ((mu, (positions.shape[0],), "mu"),
+                                   (force_threshold, (positions.shape[0], N), "force_threshold")):
+                if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float64 or tuple(t.shape) != shape):
+                    raise ValueError(f"{name} must be a float64 tensor {list(shape)}")
         if (not torch.is_tensor(positions) or positions.dtype != torch.float64 or not positions.is_cuda
                 or positions.dim() != 3 or tuple(positions.shape[1:]) != (N, 3)):
             raise ValueError(f"positions must be a float64 CUDA tensor [B, {N}, 3]")
@@ -402,6 +413,8 @@ class CoMPlanner:
             raise ValueError("force_lb and force_ub come together")
         force_lb = per_batch(force_lb, (B, N, 3), "force_lb")
         force_ub = per_batch(force_ub, (B, N, 3), "force_ub")
+        mu = per_batch(mu, (B,), "mu")
+        force_threshold = per_batch(force_threshold, (B, N), "force_threshold")
         d = prob.desc()
         X0 = torch.empty(B, 3 + 9 * N, dtype=torch.float64, device=dev)
         X0[:, 0:3] = com_ref if com_ref is not None else torch.tensor(list(d.com_ref), dtype=torch.float64, device=dev)
@@ -424,8 +437,9 @@ class CoMPlanner:
             [list(d.n_lb[i]) for i in range(N)], dtype=torch.float64, device=dev)[None]
         inst = InstanceData(wrench=wrench, com_ref=com_ref)
         box = None if force_lb is None else InstanceBounds(F_lb=force_lb, F_ub=force_ub)
+        cones = InstanceCones(mu=mu, F_thr=force_threshold)
         return self._cp.SolveBatch(X0, mass=mass, instance=inst if inst else None, fixed_from_x0=True,
-                                   warm_start=warm_start, bounds=box, **solve_options)
+                                   warm_start=warm_start, bounds=box, cones=cones if cones else None, **solve_options)
 
     def SetCoMWeight(self, w):
         self._cp.SetCoMWeight(w)

@@ -145,6 +145,47 @@ class InstanceData:
                                     for k in self.FIELDS))
 
 
+class InstanceCones:
+    """Per-instance friction cones of a batch (cpl_instance_cones): the batched form of SetMu (one friction
+    coefficient per instance, for all its contacts) and SetForceThreshold, as float64 CUDA tensors mu [B] and
+    F_thr [B, N] (contacts in contact_names order).  A field left None takes the template's value for every
+    instance.  The solvers validate the values (mu finite and > 0, F_thr finite and >= 0); eval_batch does
+    not.  A contact the template lifts (SetLiftingContact) keeps its force fixed at 0 for every row: pass 0
+    in its F_thr column."""
+
+    FIELDS = ("mu", "F_thr")
+
+    def __init__(self, mu=None, F_thr=None):
+        self.mu, self.F_thr = mu, F_thr
+
+    def __bool__(self):
+        return any(getattr(self, k) is not None for k in self.FIELDS)
+
+    def validated(self, batch: int, n_contacts: int, device) -> "InstanceCones":
+        """The fields checked against the batch (ValueError naming the field) and made contiguous."""
+        import torch
+
+        shapes = {"mu": (batch,), "F_thr": (batch, n_contacts)}
+        out = InstanceCones()
+        for k in self.FIELDS:
+            t = getattr(self, k)
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or t.dtype != torch.float64:
+                raise ValueError(f"InstanceCones.{k} must be a float64 tensor")
+            if tuple(t.shape) != shapes[k]:
+                raise ValueError(f"InstanceCones.{k} must have shape {shapes[k]}, not {tuple(t.shape)}")
+            if not t.is_cuda or t.device != device:
+                raise ValueError(f"InstanceCones.{k} must be a CUDA tensor on the batch's device {device}, not {t.device}")
+            setattr(out, k, t.contiguous())
+        return out
+
+    def c_struct(self) -> "_abi.InstanceConesC":
+        """The C record over these tensors (which must stay alive while it is in use)."""
+        return _abi.InstanceConesC(*(None if getattr(self, k) is None else getattr(self, k).data_ptr()
+                                     for k in self.FIELDS))
+
+
 class InstanceBounds:
     """Per-instance variable bounds of a batch (cpl_instance_bounds): the batched form of SetPosBounds /
     SetForceBounds / SetNormalBounds and the CoM box.  com_lb, com_ub [B, 3] and F_lb, F_ub, p_lb, p_ub,
@@ -525,7 +566,8 @@ class CplProblem:
 
     # ---- the batched hot path ---------------------------------------------------------------
     def eval_batch(self, x, mass=None, env_tag=None, outputs: Iterable[str] = ("g", "jac"), out=None,
-                   stream=None, jac_folded: bool = False, soa: bool = False, instance: Optional[InstanceData] = None):
+                   stream=None, jac_folded: bool = False, soa: bool = False, instance: Optional[InstanceData] = None,
+                   cones: Optional["InstanceCones"] = None):
         """Evaluate B instances on the GPU in one launch.
 
         x: torch.float64 CUDA tensor [B, n] (contiguous).  mass: [B] or None.  env_tag: uint8 [B]
@@ -539,6 +581,10 @@ class CplProblem:
         instance: per-instance wrench / cost references (InstanceData, cpl_eval_batch_inst: the
         template's evaluation, then the instance overlay's launch for g[0:6], f and grad; "norms" is
         then a separate pass over g); not with soa.
+        cones: per-instance friction coefficients and force thresholds (InstanceCones,
+        cpl_eval_batch_cones: after the template's evaluation a cone overlay launch recomputes every
+        contact's two cone values and row 1's six Jacobian entries, CSR or folded; the values are not
+        validated here); not with soa.
         """
         import torch
 
@@ -589,6 +635,17 @@ class CplProblem:
             elif tuple(t.shape) != (2,) or t.dtype != torch.float64 or t.device != x.device or not t.is_contiguous():
                 raise InvalidArgument(_abi.ERR_INVALID_ARGUMENT, f"output 'norms' must be a contiguous float64 (2,) tensor on {x.device}")
             res["norms"] = t
+        if cones is not None and not isinstance(cones, InstanceCones):
+            raise ValueError("cones must be an InstanceCones")
+        if cones is not None and cones:
+            cn = cones.validated(B, len(self._contact_names), x.device)
+            inst = (instance if instance is not None else InstanceData()).validated(B, len(self._contact_names), x.device)
+            cs, ccs = inst.c_struct(), cn.c_struct()
+            check(lib.cpl_eval_batch_cones(ctypes.byref(self.desc()), B, p(x), p(mass), p(env_tag), ctypes.byref(cs),
+                                           ctypes.byref(ccs), p(res.get("g")), p(res.get("jac")), p(res.get("f")),
+                                           p(res.get("grad")), p(res.get("norms")), flags,
+                                           ctypes.c_void_p(s.cuda_stream)))
+            return res
         if instance is not None and instance:
             inst = instance.validated(B, len(self._contact_names), x.device)
             cs = inst.c_struct()

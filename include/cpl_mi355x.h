@@ -231,6 +231,38 @@ int32_t cpl_eval_batch_inst(const cpl_problem_desc* d, int64_t batch, const doub
                             double* d_f, double* d_grad, double* d_norms, int32_t flags, void* stream);
 
 /*
+ * Per-instance friction cones: the batched form of EnvironmentClass::SetMu / CoMPlanner::SetMu (one
+ * friction coefficient per instance, for all its contacts — the reference has one mu per environment) and
+ * of CentroidalPlanner::SetForceThreshold.  Device pointers, instance-major; either may be NULL = the
+ * template's value (cpl_problem_desc.mu / F_thr) for every instance.  A struct of its own:
+ * cpl_instance_data stays four pointers.
+ */
+typedef struct cpl_instance_cones {
+  const double* d_mu;     /* [batch]     friction coefficient of instance b (all its contacts), or NULL = d->mu */
+  const double* d_F_thr;  /* [batch][N]  force thresholds, contact_names (vector) order, or NULL = d->F_thr */
+} cpl_instance_cones;
+size_t cpl_instance_cones_sizeof(void); /* sizeof(cpl_instance_cones), for FFI layout checks */
+
+/*
+ * cpl_eval_batch_inst with per-instance cones.  cones == NULL or both pointers NULL: exactly
+ * cpl_eval_batch_inst (the same launches, the same bits).  Otherwise the template's evaluation runs (and,
+ * with instance data, its overlay), then a cone overlay launch on the same stream recomputes, for every
+ * contact of every instance, the two FrictionCone values (row 0 reads F_thr, row 1 mu) and the six
+ * Jacobian entries of row 1 (their - mu n_a and - mu F_a terms), in the CSR record or the
+ * CPL_EVAL_JAC_FOLDED one (row 1's entries are variable in both), from the same expressions as the
+ * evaluation kernels: row b is bitwise cpl_eval_batch_inst on a batch of one whose template carries
+ * mu = d_mu[b], F_thr = d_F_thr[b], NaN entries (0/0 where the tangential force is 0) included.  f and
+ * grad do not depend on the cones.  d_norms come from a cpl_residual_norms pass over the finished g.
+ * CPL_EVAL_SOA with cones returns CPL_ERR_UNSUPPORTED before any launch.
+ * The values are NOT validated here (SetMu's mu > 0 and SetForceThreshold's F_thr >= 0 are the solve
+ * engine's checks, cpl_solver_solve_cones): the evaluation computes with whatever it is given.
+ */
+int32_t cpl_eval_batch_cones(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
+                             const uint8_t* d_env_tag, const cpl_instance_data* inst, const cpl_instance_cones* cones,
+                             double* d_g, double* d_jac, double* d_f, double* d_grad, double* d_norms, int32_t flags,
+                             void* stream);
+
+/*
  * The folded Jacobian layout of `d` (host only): *nnz_folded values per record; var_k[j] = the
  * CSR position (0..nnz-1, cpl_structure order) of folded value j; const_k[c] / const_val[c] = the
  * CSR position and value of skipped constant c, *n_const of them (nnz = nnz_folded + n_const).
@@ -405,6 +437,15 @@ int32_t cpl_lagrangian_hessian(const cpl_problem_desc* d, int64_t batch, const d
 int32_t cpl_lagrangian_hessian_ex(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_y,
                                   const uint8_t* d_env_tag, const uint8_t* d_active, const int32_t* d_free_idx,
                                   int32_t nf, double* d_H, void* stream);
+/*
+ * cpl_lagrangian_hessian_ex with per-instance cones.  Only cones->d_mu enters the Hessian (the term
+ * -(y0 + mu y1) of the cone's d2/dF_a dn_a entries; the force thresholds are constants of row 0):
+ * instance b is bitwise cpl_lagrangian_hessian_ex on a template with mu = d_mu[b].  cones == NULL or
+ * d_mu == NULL: exactly cpl_lagrangian_hessian_ex (the same kernel).
+ */
+int32_t cpl_lagrangian_hessian_cones(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_y,
+                                     const uint8_t* d_env_tag, const uint8_t* d_active, const int32_t* d_free_idx,
+                                     int32_t nf, const cpl_instance_cones* cones, double* d_H, void* stream);
 int32_t cpl_kkt_solve(int32_t mode, int64_t batch, int32_t nw, int32_t m, const double* d_M, const double* d_A,
                       const double* d_r1, const double* d_r2, const double* d_mu, const double* d_delta_w_last,
                       const uint8_t* d_active, double* d_dw, double* d_dy, double* d_delta_w, double* d_delta_c,
@@ -896,6 +937,34 @@ int32_t cpl_solver_solve_box(cpl_solver* s, const double* d_x0, const double* d_
                              const cpl_instance_bounds* box, double* d_x, double* d_y, int32_t* d_status,
                              int32_t* d_iters, double* d_obj, double* d_primal_inf, double* d_dual_inf,
                              int32_t* iterations_run, int64_t* evaluations, void* stream);
+
+/*
+ * cpl_solver_solve_box with per-instance friction cones (cpl_instance_cones: mu [batch], F_thr [batch][N]).
+ * cones == NULL, or both pointers NULL: exactly cpl_solver_solve_box (the same launches, the same bits).
+ *   - The solver keeps its own copies (1 + N doubles per instance, carved by cpl_solver_create; the
+ *     active-set compaction moves them with their rows).
+ *   - Everything that evaluates a cone row reads the instance's values: the evaluations of the iteration
+ *     (the template's evaluation, then the overlay launches, then the NLP scaling — so the scaling factors
+ *     and the NaN-Jacobian count come from the overlaid Jacobian), the fused line search with its
+ *     restoration search and soft step, the analytic Hessian (mu), and the final re-evaluation.
+ *   - The contract: row b is bitwise the solve of a batch of one whose template carries mu = d_mu[b] and
+ *     F_thr = d_F_thr[b] — x, y, status, iterations, restorations, objective, the bound multipliers and mu
+ *     of cpl_solver_warm_state.
+ *   - Validation runs on the device, once, before the start: mu must be finite and > 0 (SetMu's rule), a
+ *     force threshold finite and >= 0 (SetForceThreshold's).  A bad value returns CPL_ERR_INVALID_ARGUMENT,
+ *     cpl_last_error() names the first offending instance and the field (and the contact for F_thr), nothing
+ *     else has been launched and the solver stays usable.
+ *   - Cones need a Hessian that is not central differences, as instance data does: with CPL_HESSIAN_FD, or
+ *     CPL_HESSIAN_EXACT on a Superquadric / mixed template, CPL_ERR_UNSUPPORTED before any launch.
+ *   - A contact whose force the template fixes at 0 (a lifted contact) keeps it for every row: pass 0 in its
+ *     threshold column (a positive threshold there is infeasible).
+ *   - Independent of instance data, per-instance bounds, fixed_from_x0 and a warm start.
+ */
+int32_t cpl_solver_solve_cones(cpl_solver* s, const double* d_x0, const double* d_mass, const uint8_t* d_env_tag,
+                               const cpl_instance_data* inst, int32_t fixed_from_x0, const cpl_warm_start* warm,
+                               const cpl_instance_bounds* box, const cpl_instance_cones* cones, double* d_x,
+                               double* d_y, int32_t* d_status, int32_t* d_iters, double* d_obj, double* d_primal_inf,
+                               double* d_dual_inf, int32_t* iterations_run, int64_t* evaluations, void* stream);
 
 #ifdef __cplusplus
 }
