@@ -8,8 +8,8 @@ Importing it loads ``libcpl_mi355x.so`` and fails loudly if it has not been buil
 from ._abi import (ENV_GROUND, ENV_MIXED, ENV_NONE, ENV_SUPERQUADRIC, INF, MAX_CONTACTS, CplError, InvalidArgument,
                    OutOfRange, ProblemDesc)
 from .planner import CentroidalPlanner, CoMPlanner, ContactValues, Solution
-from .problem import (CplProblem, EnvironmentClass, Ground, InstanceBounds, InstanceCones, InstanceData, MixedEnvironment,
-                      Superquadric)
+from .problem import (CplProblem, EnvironmentClass, Ground, InstanceBounds, InstanceCones, InstanceData, InstanceWeights,
+                      MixedEnvironment, Superquadric)
 
 __all__ = [
     "CentroidalPlanner",
@@ -20,6 +20,7 @@ __all__ = [
     "InstanceBounds",
     "InstanceCones",
     "InstanceData",
+    "InstanceWeights",
     "EnvironmentClass",
     "Ground",
     "Superquadric",

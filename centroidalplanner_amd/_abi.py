@@ -166,6 +166,16 @@ class InstanceConesC(ctypes.Structure):
     ]
 
 
+class InstanceWeightsC(ctypes.Structure):
+    """cpl_instance_weights (include/cpl_mi355x.h): device pointers [batch], [batch, N], [batch, N]; any may be NULL."""
+
+    _fields_ = [
+        ("d_W_com", c_void_p),
+        ("d_W_F", c_void_p),
+        ("d_W_p", c_void_p),
+    ]
+
+
 class WarmStart(ctypes.Structure):
     """cpl_warm_start (include/cpl_mi355x.h): device pointers (d_mask may be NULL) and the warm_start_* constants."""
 
@@ -269,6 +279,15 @@ SIGNATURES = {
     ),
     "cpl_lagrangian_hessian_cones": (c_int32, [_DESC_P, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                c_int32, POINTER(InstanceConesC), c_void_p, c_void_p]),
+    "cpl_instance_weights_sizeof": (c_size_t, []),
+    "cpl_eval_batch_weights": (
+        c_int32,
+        [_DESC_P, c_int64, c_void_p, c_void_p, c_void_p, POINTER(InstanceDataC), POINTER(InstanceConesC), c_void_p,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, POINTER(InstanceWeightsC)],
+    ),
+    "cpl_lagrangian_hessian_weights": (c_int32, [_DESC_P, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                 c_int32, POINTER(InstanceConesC), c_void_p, c_void_p,
+                                                 POINTER(InstanceWeightsC)]),
     "cpl_derivative_test": (
         c_int32,
         [_DESC_P, c_int64, c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p, POINTER(DerivativeReport),
@@ -353,6 +372,10 @@ SIGNATURES = {
     "cpl_solver_solve_cones": (c_int32, [c_void_p] * 4 + [POINTER(InstanceDataC), c_int32, POINTER(WarmStart),
                                          POINTER(InstanceBoundsC), POINTER(InstanceConesC)]
                                + [c_void_p] * 7 + [POINTER(c_int32), POINTER(c_int64), c_void_p]),
+    "cpl_solver_solve_weights": (c_int32, [c_void_p] * 4 + [POINTER(InstanceDataC), c_int32, POINTER(WarmStart),
+                                           POINTER(InstanceBoundsC), POINTER(InstanceConesC)]
+                                 + [c_void_p] * 7 + [POINTER(c_int32), POINTER(c_int64), c_void_p,
+                                                     POINTER(InstanceWeightsC)]),
 }
 
 
@@ -438,3 +461,5 @@ if lib.cpl_instance_bounds_sizeof() != ctypes.sizeof(InstanceBoundsC):  # pragma
     raise ImportError("cpl_instance_bounds layout mismatch between header and ctypes mirror")
 if lib.cpl_instance_cones_sizeof() != ctypes.sizeof(InstanceConesC):  # pragma: no cover - layout guard
     raise ImportError("cpl_instance_cones layout mismatch between header and ctypes mirror")
+if lib.cpl_instance_weights_sizeof() != ctypes.sizeof(InstanceWeightsC):  # pragma: no cover - layout guard
+    raise ImportError("cpl_instance_weights layout mismatch between header and ctypes mirror")

@@ -66,7 +66,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import INF
-from .problem import InstanceBounds, InstanceCones, InstanceData
+from .problem import InstanceBounds, InstanceCones, InstanceData, InstanceWeights
 
 EPS = float(np.finfo(np.float64).eps)
 LM_HIST, LM_MAX_SKIP = 6, 2  # IPOPT limited_memory_max_history / limited_memory_max_skipping
@@ -126,29 +126,30 @@ class KernelEvaluator:
     cpl_eval_batch launch on device-resident tensors (CplProblem.eval_batch raises unless the
     inputs are CUDA tensors and the HIP library is loaded — there is no CPU fallback)."""
 
-    def __init__(self, problem, env_tag=None, instance=None, cones=None):
+    def __init__(self, problem, env_tag=None, instance=None, cones=None, weights=None):
         self.problem = problem
         self.env_tag = env_tag
         self.instance = instance  # per-instance wrench / references (InstanceData, cpl_eval_batch_inst)
         self.cones = cones        # per-instance mu / force thresholds (InstanceCones, cpl_eval_batch_cones)
+        self.weights = weights    # per-instance cost weights (InstanceWeights, cpl_eval_batch_weights)
         self.calls = 0
 
     def __call__(self, X, mass, outputs=("g", "jac", "f", "grad"), jac_folded=False):
         """jac_folded: values-only Jacobian records (CPL_EVAL_JAC_FOLDED; CplProblem.jac_fold_info)."""
         self.calls += 1
         return self.problem.eval_batch(X, mass, self.env_tag, outputs=outputs, jac_folded=jac_folded,
-                                       instance=self.instance, cones=self.cones)
+                                       instance=self.instance, cones=self.cones, weights=self.weights)
 
     def lagrangian_grad(self, X, mass, y, y_repeat, csc, active=None):
         """grad f + J^T y of every instance in one fused launch (cpl_eval_lagrangian_grad: the
         Jacobian stays in LDS); None where the fused path does not exist (Superquadric / mixed
         batches: the caller takes eval + cpl_lagrangian_grad, the same result) — nor with instance data:
         cpl_eval_lagrangian_grad evaluates the template, and the unfused evaluation honours `instance` — nor
-        with per-instance cones, for the same reason."""
+        with per-instance cones or weights, for the same reason."""
         import torch
 
         if (getattr(self, "_no_fused", False) or (self.instance is not None and self.instance)
-                or (self.cones is not None and self.cones)):
+                or (self.cones is not None and self.cones) or (self.weights is not None and self.weights)):
             return None
         out = torch.empty(X.shape[0], X.shape[1], dtype=torch.float64, device=X.device)
         st = _abi.lib.cpl_eval_lagrangian_grad(
@@ -166,7 +167,9 @@ class KernelEvaluator:
     def hessian(self, X, y, free, zero_cost=False):
         """The analytic Hessian of f + y^T g over the variables `free` of every instance, [B, nf, nf]
         (cpl_lagrangian_hessian_ex: every environment kind; with per-instance cones
-        cpl_lagrangian_hessian_cones, which reads each instance's mu); zero_cost: of y^T g alone."""
+        cpl_lagrangian_hessian_cones, which reads each instance's mu; with per-instance weights
+        cpl_lagrangian_hessian_weights, which reads each instance's weights and mu); zero_cost: of y^T g
+        alone (no weight is read then)."""
         import torch
 
         desc = self.problem.desc()
@@ -179,6 +182,16 @@ class KernelEvaluator:
         fi = free.to(torch.int32).contiguous()
         nf = int(fi.numel())
         H = torch.empty(X.shape[0], nf, nf, dtype=torch.float64, device=X.device)
+        if self.weights is not None and self.weights and not zero_cost:
+            N = len(self.problem.contact_names)
+            wt = self.weights.validated(X.shape[0], N, X.device)
+            cn = (self.cones if self.cones is not None else InstanceCones()).validated(X.shape[0], N, X.device)
+            ccs, wcs = cn.c_struct(), wt.c_struct()
+            _abi.check(_abi.lib.cpl_lagrangian_hessian_weights(
+                ctypes.byref(desc), X.shape[0], _ptr(X), _ptr(y), None if self.env_tag is None else _ptr(self.env_tag),
+                None, _ptr(fi), nf, ctypes.byref(ccs), _ptr(H),
+                ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream), ctypes.byref(wcs)))
+            return H
         if self.cones is not None and self.cones:
             cn = self.cones.validated(X.shape[0], len(self.problem.contact_names), X.device)
             ccs = cn.c_struct()
@@ -351,8 +364,11 @@ class NativeSolver:
             self.handle = None
 
     def solve(self, X0, mass=None, env_tag=None, instance=None, fixed_from_x0=False,
-              warm_start=None, bounds=None, cones=None) -> "BatchSolveResult":
-        """cones: per-instance friction coefficients and force thresholds (InstanceCones,
+              warm_start=None, bounds=None, cones=None, weights=None) -> "BatchSolveResult":
+        """weights: per-instance cost weights (InstanceWeights, cpl_solver_solve_weights): instance b's f, grad f
+        and Hessian diagonal read its own W_com, W_F, W_p; the values are validated on the device before the
+        start (InvalidArgument naming the instance, the field and the contact).
+        cones: per-instance friction coefficients and force thresholds (InstanceCones,
         cpl_solver_solve_cones): instance b's cone rows read its own mu and F_thr; the values are validated
         on the device before the start (InvalidArgument naming the instance and the field).
         bounds: per-instance variable bounds (InstanceBounds, cpl_solver_solve_box): instance b's free
@@ -391,7 +407,29 @@ class NativeSolver:
             raise ValueError("warm_start must be a WarmStart")
         if cones is not None and not isinstance(cones, InstanceCones):
             raise ValueError("cones must be an InstanceCones")
-        if cones is not None and cones:
+        if weights is not None and not isinstance(weights, InstanceWeights):
+            raise ValueError("weights must be an InstanceWeights")
+        if weights is not None and weights:
+            N = len(self.problem.contact_names)
+            wt = weights.validated(B, N, dev)
+            wts = wt.c_struct()
+            cn = (cones if cones is not None else InstanceCones()).validated(B, N, dev)
+            ccs = cn.c_struct()
+            box = None
+            if bounds is not None and bounds:
+                x_lb, x_ub = bounds.packed(self.problem, B, dev)
+                box = _abi.InstanceBoundsC(x_lb.data_ptr(), x_ub.data_ptr())
+            inst = (instance if instance is not None else InstanceData()).validated(B, N, dev)
+            cs = inst.c_struct()
+            ws = None if warm_start is None else warm_start.validated(B, n, m, dev)
+            wcs = None if ws is None else ws.c_struct()
+            _abi.check(_abi.lib.cpl_solver_solve_weights(
+                self.handle, _ptr(X0), None if mass is None else _ptr(mass), None if env_tag is None else _ptr(env_tag),
+                ctypes.byref(cs), 1 if fixed_from_x0 else 0, None if wcs is None else ctypes.byref(wcs),
+                None if box is None else ctypes.byref(box), ctypes.byref(ccs), _ptr(x), _ptr(y), _ptr(status),
+                _ptr(iters), _ptr(obj), _ptr(pinf), _ptr(dinf), ctypes.byref(it), ctypes.byref(ev),
+                ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), ctypes.byref(wts)))
+        elif cones is not None and cones:
             cn = cones.validated(B, len(self.problem.contact_names), dev)
             ccs = cn.c_struct()
             box = None
@@ -514,7 +552,8 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
                     acceptable_obj_change_tol: float = 1e20, diverging_iterates_tol: float = 1e20,
                     max_wall_time: float = 0.0, warm_start: Optional[WarmStart] = None,
                     bounds: Optional[InstanceBounds] = None,
-                    cones: Optional[InstanceCones] = None) -> BatchSolveResult:
+                    cones: Optional[InstanceCones] = None,
+                    weights: Optional[InstanceWeights] = None) -> BatchSolveResult:
     """Solve B instances of `problem`'s template from the starting points X0 [B, n] (torch float64,
     device tensor), per-instance robot masses `mass` [B] (None: the template's).
 
@@ -588,6 +627,9 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
     cpl_solver_solve_cones) — instance b solves the problem whose template carries mu[b] and F_thr[b], bit for
     bit.  Needs a Hessian that is not central differences (not "fd", nor "exact" on a Superquadric / mixed
     template).  The host restatement raises ValueError, as for bounds.
+    weights (device engine only): per-instance cost weights (InstanceWeights, cpl_solver_solve_weights) —
+    instance b solves the problem whose template carries com[b], force[b] and pos[b] as W_com, W_F and W_p,
+    bit for bit.  The same Hessian rule as cones.  The host restatement raises ValueError, as for cones.
     IFOPT_OPTIONS is the set IFOPT's IpoptSolver runs with."""
     if termination not in ("scaled", "ipopt"):
         raise ValueError("termination must be 'scaled' or 'ipopt'")
@@ -626,6 +668,16 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
         if not X0.is_cuda or (evaluator is not None and not isinstance(evaluator, KernelEvaluator)):
             raise ValueError("cones: the device engine only (the host restatement solves one template per call: write "
                              "each instance's mu and force thresholds into a template of its own)")
+    if weights is not None and not isinstance(weights, InstanceWeights):
+        raise ValueError("weights must be an InstanceWeights")
+    if weights is not None and weights:
+        if hessian == "fd" or (hessian == "exact" and problem.desc().env_kind in (_abi.ENV_SUPERQUADRIC, _abi.ENV_MIXED)):
+            raise ValueError("weights: per-instance weights need a Hessian that is not central differences "
+                             "(hessian='fd', or 'exact' on a Superquadric / mixed template): use 'analytic' or "
+                             "'limited-memory'")
+        if not X0.is_cuda or (evaluator is not None and not isinstance(evaluator, KernelEvaluator)):
+            raise ValueError("weights: the device engine only (the host restatement solves one template per call: "
+                             "write each instance's weights into a template of its own)")
     if watchdog and X0.is_cuda:
         raise ValueError("watchdog: the host restatement only (the device engine has no watchdog)")
 
@@ -643,8 +695,11 @@ def batch_ipm_solve(problem, X0, mass=None, evaluator: Optional[Callable] = None
             instance = evaluator.instance
         if cones is None and evaluator is not None:
             cones = evaluator.cones
+        if weights is None and evaluator is not None:
+            weights = evaluator.weights
         r = ns.solve(X0, mass, None if evaluator is None else evaluator.env_tag, instance=instance,
-                     fixed_from_x0=fixed_from_x0, warm_start=warm_start, bounds=bounds, cones=cones)
+                     fixed_from_x0=fixed_from_x0, warm_start=warm_start, bounds=bounds, cones=cones,
+                     weights=weights)
         if evaluator is not None:
             evaluator.calls += r.evaluations
         return r

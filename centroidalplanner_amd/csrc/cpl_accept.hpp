@@ -275,6 +275,12 @@ struct LsBacktrackArgs {
   // 1 + N values follow the instance data's in the LDS image
   const double* cone_mu = nullptr;
   const double* cone_F_thr = nullptr;
+  // a solve with per-instance cost weights (set by ls_backtrack, read by the LS_WGT instantiations only): the
+  // solver's copies of cpl_instance_weights' arrays in the rows' order (null: the template's value); their
+  // 1 + 2N values follow the cone values in the LDS image
+  const double* wgt_com = nullptr;
+  const double* wgt_F = nullptr;
+  const double* wgt_p = nullptr;
 };
 
 // s + sum_{r < m} a[r * stride] * v[r], accumulated in r order exactly as the plain loop

@@ -94,7 +94,8 @@ int32_t ipm_max_step(int64_t batch, int nw, const double* d_v, const double* d_d
 // the backtracking line search, one wave per instance (inst: the solve's instance data in the rows'
 // current order, or null — then the template's search)
 int32_t ls_backtrack(const cpl_problem_desc* d, const LsBacktrackArgs& a, hipStream_t stream,
-                     const cpl_instance_data* inst = nullptr, const cpl_instance_cones* cones = nullptr);
+                     const cpl_instance_data* inst = nullptr, const cpl_instance_cones* cones = nullptr,
+                     const cpl_instance_weights* weights = nullptr);
 // the fused search kernel takes the post-step prologue (LsBacktrackArgs::with_post) at this batch size
 bool ls_post_prologue(int64_t batch);
 // the instance overlay — g[0:6], f, grad of every row from its instance data
@@ -104,6 +105,11 @@ int32_t eval_overlay(const cpl_problem_desc* d, int64_t batch, const double* d_x
 // the cone overlay — the cone rows of g and row 1's Jacobian entries of every row from its cones
 int32_t eval_cone_overlay(const cpl_problem_desc* d, int64_t batch, const double* d_x, const cpl_instance_cones* cones,
                           double* d_g, double* d_jac, int32_t flags, void* stream, const uint8_t* gate);
+// the weight overlay — f, grad of every row from its cost weights (with inst: from its references too, and
+// g[0:6]; the instance overlay is then not launched)
+int32_t eval_weight_overlay(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
+                            const cpl_instance_data* inst, const cpl_instance_weights* weights, double* d_g,
+                            double* d_f, double* d_grad, void* stream, const uint8_t* gate);
 // the NLP-scaled evaluation (pipelined kernel; CPL_ERR_UNSUPPORTED: not that path)
 int32_t eval_batch_scaled(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
                           const uint8_t* d_env_tag, double* d_g, double* d_jac, double* d_f, double* d_grad,

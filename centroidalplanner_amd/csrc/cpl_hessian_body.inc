@@ -1,6 +1,8 @@
 // cpl_hessian_body.inc — the body of the Lagrangian Hessian kernels (cpl_kernels.hip), included once per
 // kernel: cpl_lagrangian_hessian_kernel<SQ> (CPL_HESSIAN_MU false: the template's K.mu) and
-// cpl_lagrangian_hessian_mu_kernel<SQ> (CPL_HESSIAN_MU true, CPL_HESSIAN_MU_OF_B = mu_inst[b]).  Text, not a
+// cpl_lagrangian_hessian_mu_kernel<SQ> (CPL_HESSIAN_MU true, CPL_HESSIAN_MU_OF_B = mu_inst[b]) and
+// cpl_lagrangian_hessian_wgt_kernel<SQ> (CPL_HESSIAN_WGT true as well, CPL_HESSIAN_WGT_OF_B = the instance's
+// weight pointers; mu_inst may be null there).  Text, not a
 // function: behind an inlined call the template's kernel compiled to two more SGPRs than it had, and the
 // per-instance kernels must leave the existing ones' code as it was (profiles/cones/resource_usage.txt).
   __shared__ int s_pos[CPL_MAX_CONTACTS];          // block position (map order) of contact i
@@ -29,7 +31,8 @@
   for (int t = tid; t < 36 * K.N; t += blockDim.x) {
     const int i = t / 36, r = t - 36 * i, u6 = r / 6, v6 = r - 6 * (r / 6);
     const int uu = 3 + 9 * i + (u6 < 3 ? u6 : 3 + u6), vv = 3 + 9 * i + (v6 < 3 ? v6 : 3 + v6);
-    s_cone[t] = hessian_entry<CPL_HESSIAN_MU>(K, xb, yb, s_pos, uu, vv, CPL_HESSIAN_MU_OF_B);
+    s_cone[t] = hessian_entry<CPL_HESSIAN_MU, CPL_HESSIAN_WGT>(K, xb, yb, s_pos, uu, vv, CPL_HESSIAN_MU_OF_B,
+                                                               CPL_HESSIAN_WGT_OF_B);
   }
   if (SQ && sq) {
     // the pairs a <= b of contact i: 0 (0,0), 1 (0,1), 2 (0,2), 3 (1,1), 4 (1,2), 5 (2,2)
@@ -60,7 +63,8 @@
     if (uu >= 3 && vv >= 3 && iu == iv && (tu < 3 || tu >= 6) && (tv < 3 || tv >= 6))
       h = s_cone[36 * iu + 6 * (tu < 3 ? tu : tu - 3) + (tv < 3 ? tv : tv - 3)];
     else
-      h = hessian_entry<CPL_HESSIAN_MU>(K, xb, yb, s_pos, uu, vv, CPL_HESSIAN_MU_OF_B);
+      h = hessian_entry<CPL_HESSIAN_MU, CPL_HESSIAN_WGT>(K, xb, yb, s_pos, uu, vv, CPL_HESSIAN_MU_OF_B,
+                                                         CPL_HESSIAN_WGT_OF_B);
     if (SQ && sq && uu >= 3 && vv >= 3 && iu == iv && tu >= 3 && tu < 6 && tv >= 3 && tv < 6 && s_sqok[iu])
       h += s_sq[9 * iu + 3 * (tu - 3) + (tv - 3)];
     Hb[e] = h;

@@ -998,12 +998,16 @@ __device__ __forceinline__ void contact_item(const KParams& K, const double* __r
 // Where the statics / cost items read the manipulation wrench and the cost references from.
 // TemplateSrc (the default of every item): the kernarg template, one value for the whole batch.
 // InstSrc: one instance's own values, staged by the caller (LDS): wrench [6], com_ref [3], p_ref and
-// F_ref [N][3] in contact_names (vector) order — cpl_instance_data's records.
+// F_ref [N][3] in contact_names (vector) order — cpl_instance_data's records.  The cost weights (W_com, W_F,
+// W_p) are read through the source too: the template's in both of these.
 struct TemplateSrc {
   __device__ __forceinline__ double wrench(const KParams& K, int t) const { return K.wrench[t]; }
   __device__ __forceinline__ double com_ref(const KParams& K, int a) const { return K.com_ref[a]; }
   __device__ __forceinline__ double p_ref(const KParams& K, int i, int a) const { return K.p_ref[i][a]; }
   __device__ __forceinline__ double F_ref(const KParams& K, int i, int a) const { return K.F_ref[i][a]; }
+  __device__ __forceinline__ double W_com(const KParams& K) const { return K.W_com; }
+  __device__ __forceinline__ double W_F(const KParams& K, int i) const { return K.W_F[i]; }
+  __device__ __forceinline__ double W_p(const KParams& K, int i) const { return K.W_p[i]; }
 };
 struct InstSrc {
   const double* w;
@@ -1014,6 +1018,27 @@ struct InstSrc {
   __device__ __forceinline__ double com_ref(const KParams&, int a) const { return c[a]; }
   __device__ __forceinline__ double p_ref(const KParams&, int i, int a) const { return p[3 * i + a]; }
   __device__ __forceinline__ double F_ref(const KParams&, int i, int a) const { return F[3 * i + a]; }
+  __device__ __forceinline__ double W_com(const KParams& K) const { return K.W_com; }
+  __device__ __forceinline__ double W_F(const KParams& K, int i) const { return K.W_F[i]; }
+  __device__ __forceinline__ double W_p(const KParams& K, int i) const { return K.W_p[i]; }
+};
+// InstWSrc: InstSrc with the instance's own cost weights as well (cpl_instance_weights' records, staged by
+// the caller): W_com [1], W_F and W_p [N] in contact_names (vector) order.
+struct InstWSrc {
+  const double* w;
+  const double* c;
+  const double* p;
+  const double* F;
+  const double* wc;
+  const double* wF;
+  const double* wp;
+  __device__ __forceinline__ double wrench(const KParams&, int t) const { return w[t]; }
+  __device__ __forceinline__ double com_ref(const KParams&, int a) const { return c[a]; }
+  __device__ __forceinline__ double p_ref(const KParams&, int i, int a) const { return p[3 * i + a]; }
+  __device__ __forceinline__ double F_ref(const KParams&, int i, int a) const { return F[3 * i + a]; }
+  __device__ __forceinline__ double W_com(const KParams&) const { return wc[0]; }
+  __device__ __forceinline__ double W_F(const KParams&, int i) const { return wF[i]; }
+  __device__ __forceinline__ double W_p(const KParams&, int i) const { return wp[i]; }
 };
 
 // CentroidalStatics::GetValues (src/Constraints/CentroidalStatics.cpp:37-61) and Jacobian rows 0-2
@@ -1162,10 +1187,10 @@ __device__ __forceinline__ double cost_value(const KParams& K, const double* __r
     const double* q = xr + 3 + 9 * i;
     const double e0 = q[3] - src.p_ref(K, i, 0), e1 = q[4] - src.p_ref(K, i, 1), e2 = q[5] - src.p_ref(K, i, 2);
     const double h0 = q[0] - src.F_ref(K, i, 0), h1 = q[1] - src.F_ref(K, i, 1), h2 = q[2] - src.F_ref(K, i, 2);
-    value += 0.5 * K.W_p[i] * ((e0 * e0 + e1 * e1) + e2 * e2) + 0.5 * K.W_F[i] * ((h0 * h0 + h1 * h1) + h2 * h2);
+    value += 0.5 * src.W_p(K, i) * ((e0 * e0 + e1 * e1) + e2 * e2) + 0.5 * src.W_F(K, i) * ((h0 * h0 + h1 * h1) + h2 * h2);
   }
   const double r0 = xr[0] - src.com_ref(K, 0), r1 = xr[1] - src.com_ref(K, 1), r2 = xr[2] - src.com_ref(K, 2);
-  value += 0.5 * K.W_com * ((r0 * r0 + r1 * r1) + r2 * r2);
+  value += 0.5 * src.W_com(K) * ((r0 * r0 + r1 * r1) + r2 * r2);
   return value;
 }
 
@@ -1177,18 +1202,18 @@ __device__ __forceinline__ void cost_item(const KParams& K, const double* __rest
   const double c0 = xr[0], c1 = xr[1], c2 = xr[2];
   if (K.want_f) *f = fscale ? cost_value(K, xr, src) * *fscale : cost_value(K, xr, src);
   if (K.want_grad) {
-    Dr[0] = K.W_com * (c0 - src.com_ref(K, 0));
-    Dr[1] = K.W_com * (c1 - src.com_ref(K, 1));
-    Dr[2] = K.W_com * (c2 - src.com_ref(K, 2));
+    Dr[0] = src.W_com(K) * (c0 - src.com_ref(K, 0));
+    Dr[1] = src.W_com(K) * (c1 - src.com_ref(K, 1));
+    Dr[2] = src.W_com(K) * (c2 - src.com_ref(K, 2));
     for (int i = 0; i < N; ++i) {
       const double* q = xr + 3 + 9 * i;
       double* d = Dr + 3 + 9 * i;
-      d[0] = K.W_F[i] * (q[0] - src.F_ref(K, i, 0));
-      d[1] = K.W_F[i] * (q[1] - src.F_ref(K, i, 1));
-      d[2] = K.W_F[i] * (q[2] - src.F_ref(K, i, 2));
-      d[3] = K.W_p[i] * (q[3] - src.p_ref(K, i, 0));
-      d[4] = K.W_p[i] * (q[4] - src.p_ref(K, i, 1));
-      d[5] = K.W_p[i] * (q[5] - src.p_ref(K, i, 2));
+      d[0] = src.W_F(K, i) * (q[0] - src.F_ref(K, i, 0));
+      d[1] = src.W_F(K, i) * (q[1] - src.F_ref(K, i, 1));
+      d[2] = src.W_F(K, i) * (q[2] - src.F_ref(K, i, 2));
+      d[3] = src.W_p(K, i) * (q[3] - src.p_ref(K, i, 0));
+      d[4] = src.W_p(K, i) * (q[4] - src.p_ref(K, i, 1));
+      d[5] = src.W_p(K, i) * (q[5] - src.p_ref(K, i, 2));
       d[6] = 0.0; d[7] = 0.0; d[8] = 0.0;
     }
   }
@@ -2349,10 +2374,16 @@ using EntryKernT = void (*)(const KParams, int64_t, const double*, const double*
 // ------------------------------------------------------------------------------------------
 // MU: the friction coefficient is mu_b, this instance's cpl_instance_cones value, instead of the template's
 // K.mu (read where it is used, so the template's instantiation is the code it was)
-template <bool MU = false>
+// WGT: the cost weights on the diagonal are instance w.b's cpl_instance_weights values (a null array: the
+// template's), likewise read where they are used
+struct HessWgt {
+  const double *W_com = nullptr, *W_F = nullptr, *W_p = nullptr;  // [batch], [batch][N], [batch][N]; any may be null
+  int64_t b = 0;
+};
+template <bool MU = false, bool WGT = false>
 __device__ __forceinline__ double hessian_entry(const KParams& K, const double* __restrict__ xb,
                                                 const double* __restrict__ yb, const int* s_pos, int uu, int vv,
-                                                const double mu_b = 0.0) {
+                                                const double mu_b = 0.0, const HessWgt& w = HessWgt{}) {
   // decode: kind 0 CoM, 1 F, 2 p, 3 n; contact i; axis a
   auto decode = [](int u, int& kind, int& i, int& a) {
     if (u < 3) { kind = 0; i = -1; a = u; return; }
@@ -2367,7 +2398,14 @@ __device__ __forceinline__ double hessian_entry(const KParams& K, const double* 
   decode(vv, kv, iv, av);
   double h = 0.0;
   // cost (diagonal)
-  if (uu == vv) h += ku == 0 ? K.W_com : (ku == 1 ? K.W_F[iu] : (ku == 2 ? K.W_p[iu] : 0.0));
+  if constexpr (WGT) {
+    if (uu == vv)
+      h += ku == 0 ? (w.W_com ? w.W_com[w.b] : K.W_com)
+                   : (ku == 1 ? (w.W_F ? w.W_F[w.b * K.N + iu] : K.W_F[iu])
+                              : (ku == 2 ? (w.W_p ? w.W_p[w.b * K.N + iu] : K.W_p[iu]) : 0.0));
+  } else {
+    if (uu == vv) h += ku == 0 ? K.W_com : (ku == 1 ? K.W_F[iu] : (ku == 2 ? K.W_p[iu] : 0.0));
+  }
   // torque rows: E_ab = sum_k y_{3+k} eps_kab
   auto E = [&](int a, int c) {
     if (a == c) return 0.0;
@@ -2466,9 +2504,13 @@ __global__ __launch_bounds__(256) void cpl_lagrangian_hessian_kernel(const KPara
                                                                      double* __restrict__ H) {
 #define CPL_HESSIAN_MU false
 #define CPL_HESSIAN_MU_OF_B 0.0
+#define CPL_HESSIAN_WGT false
+#define CPL_HESSIAN_WGT_OF_B HessWgt{}
 #include "cpl_hessian_body.inc"
 #undef CPL_HESSIAN_MU
 #undef CPL_HESSIAN_MU_OF_B
+#undef CPL_HESSIAN_WGT
+#undef CPL_HESSIAN_WGT_OF_B
 }
 
 // the same with a friction coefficient per instance (cpl_lagrangian_hessian_cones); its own kernel, launched
@@ -2484,9 +2526,39 @@ __global__ __launch_bounds__(256) void cpl_lagrangian_hessian_mu_kernel(const KP
                                                                         const double* __restrict__ mu_inst) {
 #define CPL_HESSIAN_MU true
 #define CPL_HESSIAN_MU_OF_B mu_inst[b]
+#define CPL_HESSIAN_WGT false
+#define CPL_HESSIAN_WGT_OF_B HessWgt{}
 #include "cpl_hessian_body.inc"
 #undef CPL_HESSIAN_MU
 #undef CPL_HESSIAN_MU_OF_B
+#undef CPL_HESSIAN_WGT
+#undef CPL_HESSIAN_WGT_OF_B
+}
+
+// the same with cost weights per instance (cpl_lagrangian_hessian_weights) and, when the call has cones as
+// well, a friction coefficient per instance: each pointer null for the template's value, so one kernel serves
+// weights with cones and without; launched only when weights are given
+template <bool SQ>
+__global__ __launch_bounds__(256) void cpl_lagrangian_hessian_wgt_kernel(const KParams K, int64_t batch, int nf,
+                                                                         const double* __restrict__ x,
+                                                                         const double* __restrict__ y,
+                                                                         const uint8_t* __restrict__ env_tag,
+                                                                         const uint8_t* __restrict__ active,
+                                                                         const int32_t* __restrict__ free_idx,
+                                                                         double* __restrict__ H,
+                                                                         const double* __restrict__ mu_inst,
+                                                                         const double* __restrict__ W_com,
+                                                                         const double* __restrict__ W_F,
+                                                                         const double* __restrict__ W_p) {
+#define CPL_HESSIAN_MU true
+#define CPL_HESSIAN_MU_OF_B (mu_inst ? mu_inst[b] : K.mu)
+#define CPL_HESSIAN_WGT true
+#define CPL_HESSIAN_WGT_OF_B HessWgt{W_com, W_F, W_p, b}
+#include "cpl_hessian_body.inc"
+#undef CPL_HESSIAN_MU
+#undef CPL_HESSIAN_MU_OF_B
+#undef CPL_HESSIAN_WGT
+#undef CPL_HESSIAN_WGT_OF_B
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3371,6 +3443,124 @@ static int32_t launch_overlay(const cpl_problem_desc* d, int64_t batch, const do
 }
 
 // ------------------------------------------------------------------------------------------
+// The weight overlay (cpl_eval_batch_weights, the solve engine with per-instance cost weights): f and grad f
+// of every instance from its own W_com, W_F, W_p (cpl_instance_weights) — and, when the call carries
+// instance data as well, from its own references, with g[0:6] from its wrench: then this launch stands in for
+// the instance overlay's.  It is that overlay's body with InstWSrc, a kernel of its own so that the instance
+// overlay keeps its symbols and its code.  cost_value / cost_item read the weights through the source: the
+// expression trees are the evaluation kernels' (the library is built without contraction), so row b has the
+// bits of the template path with b's weights written into the descriptor.
+// 8 (2n + 17 + 8N) bytes of LDS per instance — the instance overlay's image plus 1 + 2N weights —, so 46
+// instances of 4 contacts in the default 48 KiB.  A NULL array (instance data or weights) is staged from
+// the template.  Without instance data want_g is off and g is never touched.
+struct WgtPtrs {
+  const double *W_com, *W_F, *W_p;  // cpl_instance_weights' arrays (device; any may be null)
+  bool any() const { return W_com || W_F || W_p; }
+};
+
+template <bool NT>
+__global__ __launch_bounds__(256) void cpl_weight_overlay_kernel(const KParams K, int64_t batch,
+                                                                 const double* __restrict__ x,
+                                                                 const double* __restrict__ mass, const InstPtrs I,
+                                                                 const WgtPtrs W, double* __restrict__ g_out,
+                                                                 double* __restrict__ f_out,
+                                                                 double* __restrict__ grad_out) {
+  extern __shared__ __align__(16) double smem[];
+  if (K.gate && *K.gate == 0) return;  // (every thread of every workgroup: the same byte)
+  const int tid = threadIdx.x;
+  const int T = K.T, n = K.n, m = K.m, N = K.N;
+  const int64_t b0 = (int64_t)blockIdx.x * T;
+  if (b0 >= batch) return;
+  const int valid = (int)((batch - b0) < T ? (batch - b0) : T);
+  double* X = smem;              // [T][n]
+  double* Dt = X + T * n;        // [T][n]   grad f
+  double* G6 = Dt + T * n;       // [T][6]   statics values
+  double* Fv = G6 + T * 6;       // [T]      f
+  double* Wl = Fv + T;           // [T][6]   wrench
+  double* Cl = Wl + T * 6;       // [T][3]   com_ref
+  double* Pl = Cl + T * 3;       // [T][3N]  p_ref
+  double* Fl = Pl + T * 3 * N;   // [T][3N]  F_ref
+  double* Wc = Fl + T * 3 * N;   // [T]      W_com
+  double* WF = Wc + T;           // [T][N]   W_F
+  double* Wp = WF + T * N;       // [T][N]   W_p
+  load_ctab(K);
+  auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  // (T even: every tile's first record of every array is 16-byte aligned when the array is)
+  copy_in<256>(X, x + b0 * n, valid * n, tid, aligned(x));
+  if (I.wrench) copy_in<256>(Wl, I.wrench + b0 * 6, valid * 6, tid, aligned(I.wrench));
+  else for (int e = tid; e < valid * 6; e += 256) Wl[e] = K.wrench[e % 6];
+  if (I.com_ref) copy_in<256>(Cl, I.com_ref + b0 * 3, valid * 3, tid, aligned(I.com_ref));
+  else for (int e = tid; e < valid * 3; e += 256) Cl[e] = K.com_ref[e % 3];
+  if (I.p_ref) copy_in<256>(Pl, I.p_ref + b0 * 3 * N, valid * 3 * N, tid, aligned(I.p_ref));
+  else for (int e = tid; e < valid * 3 * N; e += 256) Pl[e] = K.p_ref[(e % (3 * N)) / 3][e % 3];
+  if (I.F_ref) copy_in<256>(Fl, I.F_ref + b0 * 3 * N, valid * 3 * N, tid, aligned(I.F_ref));
+  else for (int e = tid; e < valid * 3 * N; e += 256) Fl[e] = K.F_ref[(e % (3 * N)) / 3][e % 3];
+  if (W.W_com) copy_in<256>(Wc, W.W_com + b0, valid, tid, aligned(W.W_com));
+  else for (int e = tid; e < valid; e += 256) Wc[e] = K.W_com;
+  if (W.W_F) copy_in<256>(WF, W.W_F + b0 * N, valid * N, tid, aligned(W.W_F));
+  else for (int e = tid; e < valid * N; e += 256) WF[e] = K.W_F[e % N];
+  if (W.W_p) copy_in<256>(Wp, W.W_p + b0 * N, valid * N, tid, aligned(W.W_p));
+  else for (int e = tid; e < valid * N; e += 256) Wp[e] = K.W_p[e % N];
+  __syncthreads();
+  // one item per thread: (instance r, statics values | cost)
+  for (int e = tid; e < 2 * valid; e += 256) {
+    const int r = e >> 1;
+    const InstWSrc src{Wl + r * 6, Cl + r * 3, Pl + r * 3 * N, Fl + r * 3 * N, Wc + r, WF + r * N, Wp + r * N};
+    const double* xr = X + r * n;
+    if ((e & 1) == 0) {
+      if (K.want_g)
+        statics_values_item<InstWSrc>(K, xr, mass ? mass[b0 + r] : K.mass_default, G6 + r * 6, nullptr, false, nullptr,
+                                      false, src);
+    } else {
+      cost_item<InstWSrc>(K, xr, Fv + r, Dt + r * n, nullptr, src);
+    }
+  }
+  __syncthreads();
+  if (K.want_grad) copy_out<256, NT>(grad_out + b0 * n, Dt, valid * n, tid);
+  if (K.want_f) copy_out<256, NT>(f_out + b0, Fv, valid, tid);
+  if (K.want_g) {
+    if (aligned(g_out)) {  // (m even: g[0:6] of every record is three aligned pairs)
+      for (int e = tid; e < valid * 3; e += 256) {
+        const int r = e / 3, q = e - r * 3;
+        const double2 v = reinterpret_cast<const double2*>(G6)[e];
+        double2* dst = reinterpret_cast<double2*>(g_out + (b0 + r) * m) + q;
+        if (NT) {
+          __builtin_nontemporal_store(v.x, &dst->x);
+          __builtin_nontemporal_store(v.y, &dst->y);
+        } else {
+          *dst = v;
+        }
+      }
+    } else {
+      for (int e = tid; e < valid * 6; e += 256) g_out[(b0 + e / 6) * m + e % 6] = G6[e];
+    }
+  }
+}
+
+// the weight overlay's launch: f, grad — and g (its first six values per record) when the call has
+// instance data; any may be null
+static int32_t launch_weight_overlay(const cpl_problem_desc* d, int64_t batch, const double* x, const double* mass,
+                                     const InstPtrs& I, const WgtPtrs& W, double* g, double* f, double* grad,
+                                     hipStream_t stream, const uint8_t* gate) {
+  if (!I.any()) g = nullptr;  // (the statics values do not depend on the weights)
+  if (batch <= 0 || (!g && !f && !grad)) return CPL_OK;
+  KParams K;
+  fill_params(d, K, x);
+  K.gate = gate;
+  K.want_g = g != nullptr; K.want_j = 0; K.want_f = f != nullptr; K.want_grad = grad != nullptr;
+  const size_t per = sizeof(double) * (size_t)(2 * K.n + 17 + 8 * K.N);
+  int T = (int)(tile_budget() / per) & ~1;  // (the tile kernel's LDS budget: 48 KiB by default)
+  K.T = T > 64 ? 64 : (T < 2 ? 2 : T);
+  const size_t lds = per * (size_t)K.T;
+  const int64_t grid = (batch + K.T - 1) / K.T;
+  if (grid > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "batch too large");
+  hipLaunchKernelGGL(g_nt ? cpl_weight_overlay_kernel<true> : cpl_weight_overlay_kernel<false>, dim3((unsigned)grid),
+                     dim3(256), lds, stream, K, batch, x, mass, I, W, g, f, grad);
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? hip_fail(e, "cpl_weight_overlay_kernel launch") : CPL_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // The cone overlay (cpl_eval_batch_cones, the solve engine with per-instance cones): the outputs that
 // depend on cpl_instance_cones — per contact the two FrictionCone values (row 0: the force threshold,
 // row 1: mu) and the six Jacobian entries of row 1 (their - mu n_a / - mu F_a terms) — of every
@@ -3511,16 +3701,20 @@ static int32_t launch_cone_overlay(const cpl_problem_desc* d, int64_t batch, con
   return e != hipSuccess ? hip_fail(e, "cpl_cone_overlay_kernel launch") : CPL_OK;
 }
 
-// the evaluation with instance data and / or cones: the template's evaluation (whichever path launch_eval
-// picks; with instance data f and grad switched off), the overlay(s) on the same stream, then (norms) a pass
-// over the finished g — the fused norms would see the template's statics and cone rows
-static int32_t launch_eval_inst(const EvalCall& c, const InstPtrs& I, const ConePtrs& Cn = ConePtrs{}) {
-  if (!I.any() && !Cn.any()) return launch_eval(c);
+// the evaluation with instance data, cones and / or weights: the template's evaluation (whichever path
+// launch_eval picks; with instance data or weights f and grad switched off), the overlay(s) on the same
+// stream, then (norms) a pass over the finished g — the fused norms would see the template's statics and cone
+// rows.  Weights and instance data together are one overlay launch (the weight overlay writes g[0:6] too).
+static int32_t launch_eval_inst(const EvalCall& c, const InstPtrs& I, const ConePtrs& Cn = ConePtrs{},
+                                const WgtPtrs& Wg = WgtPtrs{}) {
+  if (!I.any() && !Cn.any() && !Wg.any()) return launch_eval(c);
   if (c.flags & CPL_EVAL_SOA)
-    return fail(CPL_ERR_UNSUPPORTED, Cn.any() ? "cones: entry-major (CPL_EVAL_SOA) outputs are not supported"
-                                              : "instance data: entry-major (CPL_EVAL_SOA) outputs are not supported");
+    return fail(CPL_ERR_UNSUPPORTED,
+                Wg.any()   ? "weights: entry-major (CPL_EVAL_SOA) outputs are not supported"
+                : Cn.any() ? "cones: entry-major (CPL_EVAL_SOA) outputs are not supported"
+                           : "instance data: entry-major (CPL_EVAL_SOA) outputs are not supported");
   EvalCall t = c;
-  if (I.any()) {
+  if (I.any() || Wg.any()) {
     t.f = nullptr;
     t.grad = nullptr;
   }
@@ -3536,8 +3730,12 @@ static int32_t launch_eval_inst(const EvalCall& c, const InstPtrs& I, const Cone
     return st;
   }
   if (c.batch == 0) return c.norms ? launch_eval(c) : CPL_OK;  // (the empty batch's zero norms)
-  if (I.any())
+  if (Wg.any()) {
+    if (int32_t st = launch_weight_overlay(c.d, c.batch, c.x, c.mass, I, Wg, c.g, c.f, c.grad, c.stream, c.gate))
+      return st;
+  } else if (I.any()) {
     if (int32_t st = launch_overlay(c.d, c.batch, c.x, c.mass, I, c.g, c.f, c.grad, c.stream, c.gate)) return st;
+  }
   if (Cn.any())
     if (int32_t st = launch_cone_overlay(c.d, c.batch, c.x, Cn, c.g, c.jac, c.flags, c.stream, c.gate)) return st;
   return c.norms && c.finish ? cpl_residual_norms(c.d, c.batch, c.g, c.norms, c.stream) : CPL_OK;
@@ -3568,14 +3766,21 @@ static int32_t launch_eval_inst(const EvalCall& c, const InstPtrs& I, const Cone
 // force thresholds (a null array: the template's) are staged behind the instance data, and after a trial
 // point's items each contact's two cone values are computed again from them (cone_rows_inst: the cone
 // overlay's function, the items' expression trees) over the template's.
+// LS_WGT (with LS_INST | LS_CONE; a solve with per-instance cost weights, launched only then): the instance's
+// 1 + 2N weights (W_com, W_F, W_p; a null array: the template's) are staged once behind the cone values, and
+// the trial points' cost items read them there (InstWSrc) — the regular search, the restoration search and the
+// soft step alike.
 constexpr int LS_INST = 8;
 constexpr int LS_CONE = 16;
+constexpr int LS_WGT = 32;
 template <int ENVKI, bool RESTO, bool FIRST, bool GF = false, bool AUGR = false>
 __global__ __launch_bounds__(64) void cpl_ls_backtrack_kernel(const KParams K, const LsBacktrackArgs A) {
-  constexpr int ENVK = ENVKI & ~(LS_INST | LS_CONE);
+  constexpr int ENVK = ENVKI & ~(LS_INST | LS_CONE | LS_WGT);
   constexpr bool INST = (ENVKI & LS_INST) != 0;
   constexpr bool CONE = (ENVKI & LS_CONE) != 0;
-  using SRC = typename std::conditional<INST, InstSrc, TemplateSrc>::type;
+  constexpr bool WGT = (ENVKI & LS_WGT) != 0;
+  using SRC = typename std::conditional<WGT, InstWSrc,
+                                        typename std::conditional<INST, InstSrc, TemplateSrc>::type>::type;
   extern __shared__ __align__(16) double smem[];
   __shared__ double s_f;
   const int64_t b = blockIdx.x;
@@ -3613,7 +3818,17 @@ __global__ __launch_bounds__(64) void cpl_ls_backtrack_kernel(const KParams K, c
         Q[9 + e] = A.inst_p_ref ? A.inst_p_ref[b * 3 * N + e] : K.p_ref[e / 3][e % 3];
         Q[9 + 3 * N + e] = A.inst_F_ref ? A.inst_F_ref[b * 3 * N + e] : K.F_ref[e / 3][e % 3];
       }
-      src = InstSrc{Q, Q + 6, Q + 9, Q + 9 + 3 * N};  // (published by the barrier below)
+      if constexpr (WGT) {
+        double* Qw = Q + 9 + 6 * N + 1 + N;  // [W_com | W_F | W_p, vector order], behind the cone values
+        if (lane == 0) Qw[0] = A.wgt_com ? A.wgt_com[b] : K.W_com;
+        for (int e = lane; e < N; e += 64) {
+          Qw[1 + e] = A.wgt_F ? A.wgt_F[b * N + e] : K.W_F[e];
+          Qw[1 + N + e] = A.wgt_p ? A.wgt_p[b * N + e] : K.W_p[e];
+        }
+        src = InstWSrc{Q, Q + 6, Q + 9, Q + 9 + 3 * N, Qw, Qw + 1, Qw + 1 + N};  // (published by the barrier below)
+      } else {
+        src = InstSrc{Q, Q + 6, Q + 9, Q + 9 + 3 * N};  // (published by the barrier below)
+      }
     }
     const double* Qc = smem + A.inst_off + 9 + 6 * N;  // (CONE) [mu | F_thr, vector order]
     if constexpr (CONE) {
@@ -3839,8 +4054,10 @@ bool ls_post_prologue(int64_t batch) { return batch < LS_GF_MIN; }
 // inst (optional): the solve's instance data, [batch] rows in the rows' current order — the search then
 // runs the per-instance instantiations
 // cones (optional): the solve's per-instance cones, likewise
+// weights (optional): the solve's per-instance cost weights, likewise
 int32_t ls_backtrack(const cpl_problem_desc* d, const LsBacktrackArgs& a, hipStream_t stream,
-                     const cpl_instance_data* inst, const cpl_instance_cones* cones) {
+                     const cpl_instance_data* inst, const cpl_instance_cones* cones,
+                     const cpl_instance_weights* weights) {
   if (a.batch <= 0) return CPL_OK;
   if (a.batch > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "ls_backtrack: batch too large");
   KParams K;
@@ -3892,20 +4109,36 @@ int32_t ls_backtrack(const cpl_problem_desc* d, const LsBacktrackArgs& a, hipStr
       CPL_LS_KERNELS(false, true, false, false),  CPL_LS_KERNELS(false, true, true, false),
       CPL_LS_KERNELS(false, true, false, true),   CPL_LS_KERNELS(false, true, true, true)};
 #undef CPL_LS_KERNELS
+#define CPL_LS_KERNELS(R, F, G, AG)                                                         \
+  {cpl_ls_backtrack_kernel<CPL_ENV_NONE | LS_INST | LS_CONE | LS_WGT, R, F, G, AG>,         \
+   cpl_ls_backtrack_kernel<CPL_ENV_GROUND | LS_INST | LS_CONE | LS_WGT, R, F, G, AG>,       \
+   cpl_ls_backtrack_kernel<CPL_ENV_SUPERQUADRIC | LS_INST | LS_CONE | LS_WGT, R, F, G, AG>, \
+   cpl_ls_backtrack_kernel<CPL_ENV_MIXED | LS_INST | LS_CONE | LS_WGT, R, F, G, AG>}
+  static const KernT table_wgt[6][4] = {
+      CPL_LS_KERNELS(false, false, false, false), CPL_LS_KERNELS(true, false, false, false),
+      CPL_LS_KERNELS(false, true, false, false),  CPL_LS_KERNELS(false, true, true, false),
+      CPL_LS_KERNELS(false, true, false, true),   CPL_LS_KERNELS(false, true, true, true)};
+#undef CPL_LS_KERNELS
   const InstPtrs I = inst ? InstPtrs{inst->d_wrench, inst->d_com_ref, inst->d_p_ref, inst->d_F_ref} : InstPtrs{};
   const ConePtrs Cn = cones ? ConePtrs{cones->d_mu, cones->d_F_thr} : ConePtrs{};
   // (cones: one set of instantiations, which stage the instance data as well — a null array's values are
   // the template's)
-  const bool with_cone = Cn.any(), with_inst = I.any() || with_cone;
+  // (weights: one set again, which stages the instance data and the cones as well)
+  const WgtPtrs Wg = weights ? WgtPtrs{weights->d_W_com, weights->d_W_F, weights->d_W_p} : WgtPtrs{};
+  const bool with_wgt = Wg.any();
+  const bool with_cone = Cn.any() || with_wgt, with_inst = I.any() || with_cone;
   const int inst_off = (int)((lds / sizeof(double) + 1) & ~(size_t)1);  // the instance's values past the image
-  if (with_inst) lds = sizeof(double) * ((size_t)inst_off + 9 + 6 * (size_t)K.N + (with_cone ? 1 + (size_t)K.N : 0));
+  if (with_inst)
+    lds = sizeof(double) * ((size_t)inst_off + 9 + 6 * (size_t)K.N + (with_cone ? 1 + (size_t)K.N : 0) +
+                            (with_wgt ? 1 + 2 * (size_t)K.N : 0));
   auto launch = [&](int row, LsBacktrackArgs args) {
     if (with_inst) {
       args.inst_wrench = I.wrench; args.inst_com_ref = I.com_ref; args.inst_p_ref = I.p_ref; args.inst_F_ref = I.F_ref;
       args.inst_off = inst_off;
       args.cone_mu = Cn.mu; args.cone_F_thr = Cn.F_thr;
+      args.wgt_com = Wg.W_com; args.wgt_F = Wg.W_F; args.wgt_p = Wg.W_p;
     }
-    hipLaunchKernelGGL((with_cone ? table_cone : (with_inst ? table_inst : table))[row][K.env_kind],
+    hipLaunchKernelGGL((with_wgt ? table_wgt : (with_cone ? table_cone : (with_inst ? table_inst : table)))[row][K.env_kind],
                        dim3((unsigned)a.batch), dim3(64), lds, stream, K, args);
   };
   const bool augr = first && a.aug_ws && a.aug_dc;
@@ -3965,6 +4198,17 @@ int32_t eval_cone_overlay(const cpl_problem_desc* d, int64_t batch, const double
                              (hipStream_t)stream, gate);
 }
 
+// (internal, the solve engine) the weight overlay alone: f and grad of every row from the solver's own copies
+// of the weights (and, with inst, its references and g[0:6] from its wrench: then instead of eval_overlay);
+// honours the gate byte
+int32_t eval_weight_overlay(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
+                            const cpl_instance_data* inst, const cpl_instance_weights* weights, double* d_g,
+                            double* d_f, double* d_grad, void* stream, const uint8_t* gate) {
+  const InstPtrs I = inst ? InstPtrs{inst->d_wrench, inst->d_com_ref, inst->d_p_ref, inst->d_F_ref} : InstPtrs{};
+  return launch_weight_overlay(d, batch, d_x, d_mass, I, WgtPtrs{weights->d_W_com, weights->d_W_F, weights->d_W_p},
+                               d_g, d_f, d_grad, (hipStream_t)stream, gate);
+}
+
 }  // namespace cpl
 
 using namespace cpl;
@@ -3993,6 +4237,20 @@ int32_t cpl_eval_batch_cones(const cpl_problem_desc* d, int64_t batch, const dou
       EvalCall{d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, d_norms, (hipStream_t)stream, flags}, I, Cn);
 }
 
+size_t cpl_instance_weights_sizeof(void) { return sizeof(cpl_instance_weights); }
+
+int32_t cpl_eval_batch_weights(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
+                               const uint8_t* d_env_tag, const cpl_instance_data* inst, const cpl_instance_cones* cones,
+                               double* d_g, double* d_jac, double* d_f, double* d_grad, double* d_norms, int32_t flags,
+                               void* stream, const cpl_instance_weights* weights) {
+  const InstPtrs I = inst ? InstPtrs{inst->d_wrench, inst->d_com_ref, inst->d_p_ref, inst->d_F_ref} : InstPtrs{};
+  const ConePtrs Cn = cones ? ConePtrs{cones->d_mu, cones->d_F_thr} : ConePtrs{};
+  const WgtPtrs Wg = weights ? WgtPtrs{weights->d_W_com, weights->d_W_F, weights->d_W_p} : WgtPtrs{};
+  return launch_eval_inst(
+      EvalCall{d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, d_norms, (hipStream_t)stream, flags}, I, Cn,
+      Wg);
+}
+
 int32_t cpl_eval_batch(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
                        const uint8_t* d_env_tag, double* d_g, double* d_jac, double* d_f, double* d_grad,
                        void* stream) {
@@ -4016,7 +4274,7 @@ int32_t cpl_eval_lagrangian_grad(const cpl_problem_desc* d, int64_t batch, const
 static int32_t launch_hessian(const char* who, const cpl_problem_desc* d, int64_t batch, const double* d_x,
                               const double* d_y, const uint8_t* d_env_tag, const uint8_t* d_active,
                               const int32_t* d_free_idx, int32_t nf, double* d_H, void* stream,
-                              const double* d_mu = nullptr) {
+                              const double* d_mu = nullptr, const WgtPtrs& Wg = WgtPtrs{}) {
   const std::string w(who);
   KParams K;
   fill_params(d, K, d_x);
@@ -4026,7 +4284,11 @@ static int32_t launch_hessian(const char* who, const cpl_problem_desc* d, int64_
   if (d->env_kind == CPL_ENV_MIXED && !d_env_tag) return fail(CPL_ERR_INVALID_ARGUMENT, w + ": mixed needs tags");
   if (batch > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, w + ": batch too large");
   const bool sq = d->env_kind == CPL_ENV_SUPERQUADRIC || d->env_kind == CPL_ENV_MIXED;
-  if (d_mu)
+  if (Wg.any())
+    hipLaunchKernelGGL(sq ? cpl_lagrangian_hessian_wgt_kernel<true> : cpl_lagrangian_hessian_wgt_kernel<false>,
+                       dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, K, batch, (int)nf, d_x, d_y, d_env_tag,
+                       d_active, d_free_idx, d_H, d_mu, Wg.W_com, Wg.W_F, Wg.W_p);
+  else if (d_mu)
     hipLaunchKernelGGL(sq ? cpl_lagrangian_hessian_mu_kernel<true> : cpl_lagrangian_hessian_mu_kernel<false>,
                        dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, K, batch, (int)nf, d_x, d_y, d_env_tag,
                        d_active, d_free_idx, d_H, d_mu);
@@ -4065,6 +4327,17 @@ int32_t cpl_lagrangian_hessian_cones(const cpl_problem_desc* d, int64_t batch, c
   if (st) return st;
   return launch_hessian("cpl_lagrangian_hessian_cones", d, batch, d_x, d_y, d_env_tag, d_active, d_free_idx, nf, d_H,
                         stream, cones ? cones->d_mu : nullptr);
+}
+
+int32_t cpl_lagrangian_hessian_weights(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_y,
+                                       const uint8_t* d_env_tag, const uint8_t* d_active, const int32_t* d_free_idx,
+                                       int32_t nf, const cpl_instance_cones* cones, double* d_H, void* stream,
+                                       const cpl_instance_weights* weights) {
+  int32_t st = validate_desc(d);
+  if (st) return st;
+  const WgtPtrs Wg = weights ? WgtPtrs{weights->d_W_com, weights->d_W_F, weights->d_W_p} : WgtPtrs{};
+  return launch_hessian(Wg.any() ? "cpl_lagrangian_hessian_weights" : "cpl_lagrangian_hessian_cones", d, batch, d_x, d_y,
+                        d_env_tag, d_active, d_free_idx, nf, d_H, stream, cones ? cones->d_mu : nullptr, Wg);
 }
 
 int32_t cpl_eval_batch_ex(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,

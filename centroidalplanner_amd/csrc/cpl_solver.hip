@@ -92,11 +92,17 @@ int32_t apply_scaling(cpl_solver* S, double* fo, double* grado, double* go, doub
 // k_apply_scaling; the overlay needs no scaling arguments)
 // (per-instance cones: the same route with the cone overlay — the template's evaluation keeps f / grad
 // when there is no instance data —, so the scaling sees the overlaid cone rows and Jacobian entries)
+// (per-instance weights: the same route with the weight overlay, which computes f / grad — and, with
+// instance data, g[0:6] in the instance overlay's stead)
 int32_t eval_fg(cpl_solver* S, const double* X, double* fo, double* go) {
-  if (S->has_inst || S->has_cones) {
-    CK(cpl_eval_batch(&S->desc, S->Bcur, X, S->mass, S->tag, go, nullptr, S->has_inst ? nullptr : fo, nullptr,
-                      S->stream));
-    if (S->has_inst) CK(eval_overlay(&S->desc, S->Bcur, X, S->mass, &S->inst, go, fo, nullptr, S->stream, nullptr));
+  if (S->has_inst || S->has_cones || S->has_wgt) {
+    CK(cpl_eval_batch(&S->desc, S->Bcur, X, S->mass, S->tag, go, nullptr, S->has_inst || S->has_wgt ? nullptr : fo,
+                      nullptr, S->stream));
+    if (S->has_wgt)
+      CK(eval_weight_overlay(&S->desc, S->Bcur, X, S->mass, S->has_inst ? &S->inst : nullptr, &S->wgt, go, fo, nullptr,
+                             S->stream, nullptr));
+    else if (S->has_inst)
+      CK(eval_overlay(&S->desc, S->Bcur, X, S->mass, &S->inst, go, fo, nullptr, S->stream, nullptr));
     if (S->has_cones) CK(eval_cone_overlay(&S->desc, S->Bcur, X, &S->cones, go, nullptr, 0, S->stream, nullptr));
     return apply_scaling(S, fo, nullptr, go, nullptr);
   }
@@ -114,10 +120,15 @@ int32_t eval_fg(cpl_solver* S, const double* X, double* fo, double* go) {
 // an evaluation whose outputs nobody reads when the byte is 0)
 int32_t eval_full(cpl_solver* S, const double* X, double* fo, double* grado, double* go, double* jo,
                   const uint8_t* gate = nullptr) {
-  if (S->has_inst || S->has_cones) {
-    CK(eval_batch_gated(&S->desc, S->Bcur, X, S->mass, S->tag, go, jo, S->has_inst ? nullptr : fo,
-                        S->has_inst ? nullptr : grado, CPL_EVAL_JAC_FOLDED, S->stream, gate));
-    if (S->has_inst) CK(eval_overlay(&S->desc, S->Bcur, X, S->mass, &S->inst, go, fo, grado, S->stream, gate));
+  if (S->has_inst || S->has_cones || S->has_wgt) {
+    const bool over = S->has_inst || S->has_wgt;  // (an overlay computes f / grad)
+    CK(eval_batch_gated(&S->desc, S->Bcur, X, S->mass, S->tag, go, jo, over ? nullptr : fo, over ? nullptr : grado,
+                        CPL_EVAL_JAC_FOLDED, S->stream, gate));
+    if (S->has_wgt)
+      CK(eval_weight_overlay(&S->desc, S->Bcur, X, S->mass, S->has_inst ? &S->inst : nullptr, &S->wgt, go, fo, grado,
+                             S->stream, gate));
+    else if (S->has_inst)
+      CK(eval_overlay(&S->desc, S->Bcur, X, S->mass, &S->inst, go, fo, grado, S->stream, gate));
     if (S->has_cones)
       CK(eval_cone_overlay(&S->desc, S->Bcur, X, &S->cones, go, jo, CPL_EVAL_JAC_FOLDED, S->stream, gate));
     return apply_scaling(S, fo, grado, go, jo);
@@ -182,7 +193,13 @@ int32_t hessian_into(cpl_solver* S, const cpl_problem_desc* d, const uint8_t* ma
     return CPL_OK;
   };
   if (S->analytic_H) {
-    if (S->has_cones && S->cones.d_mu)  // (either mode: the kernel of every environment kind with mu per row)
+    if (S->has_wgt) {
+      // (either mode: the kernel of every environment kind with the weights — and mu, if any — per row; the
+      // restoration phase's Hessian of y^T g alone (desc_R: zero weights) reads no instance's weight)
+      const cpl_instance_weights none = {nullptr, nullptr, nullptr};
+      CK(cpl_lagrangian_hessian_weights(d, B, S->X, yh, S->tag, mask, S->free32, nf, S->has_cones ? &S->cones : nullptr,
+                                        S->H, st, d == &S->desc_R ? &none : &S->wgt));
+    } else if (S->has_cones && S->cones.d_mu)  // (either mode: the kernel of every environment kind with mu per row)
       CK(cpl_lagrangian_hessian_cones(d, B, S->X, yh, S->tag, mask, S->free32, nf, &S->cones, S->H, st));
     else if (o.hessian == CPL_HESSIAN_ANALYTIC)  // every environment kind (Ground / none: the same kernel)
       CK(cpl_lagrangian_hessian_ex(d, B, S->X, yh, S->tag, mask, S->free32, nf, S->H, st));
@@ -591,7 +608,8 @@ int32_t step_phase(cpl_solver* S, int phase, const StepMode mode = {}) {
       } else {  // the remaining trials of every instance still searching, in one launch
         HK(hipMemsetAsync(S->d_any, 0, 2, st), "hipMemsetAsync flags");
       }
-      return ls_backtrack(&S->desc, la, st, S->has_inst ? &S->inst : nullptr, S->has_cones ? &S->cones : nullptr);
+      return ls_backtrack(&S->desc, la, st, S->has_inst ? &S->inst : nullptr, S->has_cones ? &S->cones : nullptr,
+                          S->has_wgt ? &S->wgt : nullptr);
     }
     case P_SOFT: {
       const SoftStepArgs soft = soft_step_args(S);
@@ -682,7 +700,8 @@ int32_t step_phase(cpl_solver* S, int phase, const StepMode mode = {}) {
         la.rho = RHO_R;
         la.pR = S->pR; la.nR = S->nR; la.dp = S->dp; la.dn = S->dn; la.wR = S->wR;
         la.st_p = S->st_p; la.st_n = S->st_n;
-        CK(ls_backtrack(&S->desc, la, st, S->has_inst ? &S->inst : nullptr, S->has_cones ? &S->cones : nullptr));
+        CK(ls_backtrack(&S->desc, la, st, S->has_inst ? &S->inst : nullptr, S->has_cones ? &S->cones : nullptr,
+                        S->has_wgt ? &S->wgt : nullptr));
       }
       return step_phase(S, P_RACCEPT);
     }
@@ -728,7 +747,9 @@ int32_t run_phase(cpl_solver* S, int phase) {
                         (S->inst.d_F_ref ? 8 : 0);
   // (and one per cone array)
   const int cone_bits = (S->cones.d_mu ? 1 : 0) | (S->cones.d_F_thr ? 2 : 0);
-  const int64_t key = ((S->Bcur * 1024 + cone_bits * 256 + (S->has_box ? 128 : 0) + inst_bits * 8 + (S->scaled ? 4 : 0) +
+  // (and one per weight array)
+  const int wgt_bits = (S->wgt.d_W_com ? 1 : 0) | (S->wgt.d_W_F ? 2 : 0) | (S->wgt.d_W_p ? 4 : 0);
+  const int64_t key = ((S->Bcur * 8192 + wgt_bits * 1024 + cone_bits * 256 + (S->has_box ? 128 : 0) + inst_bits * 8 + (S->scaled ? 4 : 0) +
                         (S->mass ? 2 : 0) + (S->tag ? 1 : 0)) * 16) + phase;
   auto it = S->graphs.find(key);
   if (it == S->graphs.end()) {
@@ -819,7 +840,7 @@ int32_t compact(cpl_solver* S, int64_t count, int64_t Bn) {
     const bool moved = r.when == ALWAYS || (r.when == IF_SCALED && S->scaled) ||
                        (r.when == IF_MASS && S->mass) || (r.when == IF_TAG && S->tag) ||
                        (r.when == IF_INST && S->has_inst) || (r.when == IF_BOX && S->has_box) ||
-                       (r.when == IF_CONE && S->has_cones);
+                       (r.when == IF_CONE && S->has_cones) || (r.when == IF_WGT && S->has_wgt);
     if (!moved || r.width <= 0) continue;
     const dim3 grid(blocks_elems(count * r.width)), blk(256);
     if (r.elem == 8)
@@ -849,8 +870,8 @@ int32_t compact(cpl_solver* S, int64_t count, int64_t Bn) {
 // flags, the starting iterate (cold, or per instance warm), the least-squares y, the quasi-Newton model.
 // inst: null without instance data; warm: null for a cold solve.
 int32_t solve_start(cpl_solver* S, const double* d_x0, const double* d_mass, const uint8_t* d_env_tag,
-                    const cpl_instance_data* inst, const cpl_instance_cones* cones, int32_t fixed_from_x0,
-                    const cpl_warm_start* warm, int64_t* evals) {
+                    const cpl_instance_data* inst, const cpl_instance_cones* cones, const cpl_instance_weights* weights,
+                    int32_t fixed_from_x0, const cpl_warm_start* warm, int64_t* evals) {
   const int64_t B = S->B;
   const int n = S->n, m = S->m, nf = S->nf, nw = S->nw;
   hipStream_t st = S->stream;
@@ -887,6 +908,24 @@ int32_t solve_start(cpl_solver* S, const double* d_x0, const double* d_mass, con
     HK(hipMemcpyAsync(S->cone_F, cones->d_F_thr, 8 * (size_t)B * S->desc.n_contacts, hipMemcpyDeviceToDevice, st),
        "hipMemcpyAsync cones F_thr");
     S->cones.d_F_thr = S->cone_F;
+  }
+  // ... and of the weights (validated before: weights_check)
+  S->has_wgt = weights != nullptr;
+  S->wgt = cpl_instance_weights{nullptr, nullptr, nullptr};
+  if (weights && weights->d_W_com) {
+    HK(hipMemcpyAsync(S->wgt_com, weights->d_W_com, 8 * (size_t)B, hipMemcpyDeviceToDevice, st),
+       "hipMemcpyAsync weights W_com");
+    S->wgt.d_W_com = S->wgt_com;
+  }
+  if (weights && weights->d_W_F) {
+    HK(hipMemcpyAsync(S->wgt_F, weights->d_W_F, 8 * (size_t)B * S->desc.n_contacts, hipMemcpyDeviceToDevice, st),
+       "hipMemcpyAsync weights W_F");
+    S->wgt.d_W_F = S->wgt_F;
+  }
+  if (weights && weights->d_W_p) {
+    HK(hipMemcpyAsync(S->wgt_p, weights->d_W_p, 8 * (size_t)B * S->desc.n_contacts, hipMemcpyDeviceToDevice, st),
+       "hipMemcpyAsync weights W_p");
+    S->wgt.d_W_p = S->wgt_p;
   }
   hipLaunchKernelGGL(k_iota, dim3(blocks_elems(B)), dim3(256), 0, st, B, S->orig);
   LAUNCHED("k_iota");
@@ -1031,6 +1070,34 @@ int32_t cones_check(cpl_solver* S, const cpl_instance_cones* cones) {
                                             std::to_string(j - 1) + ": a force threshold must be finite and >= 0");
 }
 
+// Per-instance cost weights (cpl_solver_solve_weights): the caller's values validated on the device
+// (k_weight_check) by the cones' mechanism — one launch, one host read of the fault word.  Every weight must be
+// finite and >= 0 (MinimizeCentroidalVariables throws "Invalid weight" below 0).  A refusal names the first
+// offending instance and field (and contact) and launches nothing else.
+int32_t weights_check(cpl_solver* S, const cpl_instance_weights* weights) {
+  hipStream_t st = S->stream;
+  const int64_t B = S->B;
+  const int N = S->desc.n_contacts;
+  HK(hipMemsetAsync(S->cone_fault, 0xff, sizeof(unsigned long long), st), "hipMemsetAsync weight fault");
+  const int64_t total = B * (1 + 2 * N);
+  hipLaunchKernelGGL(k_weight_check, dim3(blocks_elems(total)), dim3(256), 0, st, total, N, weights->d_W_com,
+                     weights->d_W_F, weights->d_W_p, S->cone_fault);
+  LAUNCHED("k_weight_check");
+  unsigned long long code = 0;
+  HK(hipMemcpyAsync(&code, S->cone_fault, sizeof(code), hipMemcpyDeviceToHost, st), "hipMemcpyAsync weight fault");
+  HK(hipStreamSynchronize(st), "hipStreamSynchronize");
+  if (code == ~0ull) return CPL_OK;
+  const unsigned long long w = (unsigned long long)(1 + 2 * N);
+  const long long b = (long long)(code / w), j = (long long)(code % w);
+  const std::string who = "cpl_solver_solve_weights: instance " + std::to_string(b) + ", ";
+  if (j == 0) return fail(CPL_ERR_INVALID_ARGUMENT, who + "W_com: a weight must be finite and >= 0");
+  if (j <= N)
+    return fail(CPL_ERR_INVALID_ARGUMENT,
+                who + "W_F of contact " + std::to_string(j - 1) + ": a weight must be finite and >= 0");
+  return fail(CPL_ERR_INVALID_ARGUMENT,
+              who + "W_p of contact " + std::to_string(j - 1 - N) + ": a weight must be finite and >= 0");
+}
+
 // The iteration loop: the phases, the counts (mailbox or copy), max_wall_time, the compaction.  *it: the
 // lock-step iterations run.
 int32_t solve_iterate(cpl_solver* S, int* it_out, int64_t* evals) {
@@ -1097,7 +1164,8 @@ int32_t solve_iterate(cpl_solver* S, int* it_out, int64_t* evals) {
 // The finish: the final convergence test, the results of every row still in the batch to its instance's
 // place, IPOPT's honor_original_bounds projection with its re-evaluation, the caller's outputs.
 int32_t solve_finish(cpl_solver* S, const double* d_mass, const uint8_t* d_env_tag, const cpl_instance_data* inst,
-                     const cpl_instance_cones* cones, int32_t fixed_from_x0, double* d_x, double* d_y, int32_t* d_status, int32_t* d_iters, double* d_obj,
+                     const cpl_instance_cones* cones, const cpl_instance_weights* weights, int32_t fixed_from_x0,
+                     double* d_x, double* d_y, int32_t* d_status, int32_t* d_iters, double* d_obj,
                      double* d_primal_inf, double* d_dual_inf, int64_t* evals) {
   const int64_t B = S->B;
   const int n = S->n, m = S->m, nf = S->nf, nw = S->nw;
@@ -1134,7 +1202,10 @@ int32_t solve_finish(cpl_solver* S, const double* d_mass, const uint8_t* d_env_t
                      (int64_t)(S->has_box ? n : 0), Xf);
   LAUNCHED("k_unpack (final)");
   // (the full batch in the instances' own order: the caller's masses, tags, instance data and cones)
-  if (cones)
+  if (weights)
+    CK(cpl_eval_batch_weights(&S->desc, B, Xf, d_mass, d_env_tag, inst, cones, S->fin_g, nullptr,
+                              d_obj ? d_obj : S->fin_f, nullptr, nullptr, 0, st, weights));
+  else if (cones)
     CK(cpl_eval_batch_cones(&S->desc, B, Xf, d_mass, d_env_tag, inst, cones, S->fin_g, nullptr, d_obj ? d_obj : S->fin_f,
                             nullptr, nullptr, 0, st));
   else if (inst)
@@ -1517,6 +1588,8 @@ int32_t cpl_solver_create(const cpl_problem_desc* d, int64_t batch, const cpl_so
   S->inst_F = c.state<double>(3 * (size_t)d->n_contacts, IF_INST);
   S->cone_mu = c.state<double>(1, IF_CONE); S->cone_F = c.state<double>((size_t)d->n_contacts, IF_CONE);
   S->cone_fault = c.fixed<unsigned long long>(1);
+  S->wgt_com = c.state<double>(1, IF_WGT); S->wgt_F = c.state<double>((size_t)d->n_contacts, IF_WGT);
+  S->wgt_p = c.state<double>((size_t)d->n_contacts, IF_WGT);
   S->fw = c.full<double>(nw); S->fy = c.full<double>(m); S->fX = c.full<double>(n);
   S->fdinf = c.full<double>(1); S->fstatus = c.full<int64_t>(1); S->fiters = c.full<int64_t>(1);
   S->fresto = c.full<int64_t>(1);
@@ -1634,6 +1707,16 @@ int32_t cpl_solver_solve_cones(cpl_solver* S, const double* d_x0, const double* 
                                const cpl_instance_bounds* box, const cpl_instance_cones* cones, double* d_x,
                                double* d_y, int32_t* d_status, int32_t* d_iters, double* d_obj, double* d_primal_inf,
                                double* d_dual_inf, int32_t* iterations_run, int64_t* evaluations, void* stream) {
+  return cpl_solver_solve_weights(S, d_x0, d_mass, d_env_tag, inst, fixed_from_x0, warm, box, cones, d_x, d_y, d_status,
+                                  d_iters, d_obj, d_primal_inf, d_dual_inf, iterations_run, evaluations, stream, nullptr);
+}
+
+int32_t cpl_solver_solve_weights(cpl_solver* S, const double* d_x0, const double* d_mass, const uint8_t* d_env_tag,
+                                 const cpl_instance_data* inst, int32_t fixed_from_x0, const cpl_warm_start* warm,
+                                 const cpl_instance_bounds* box, const cpl_instance_cones* cones, double* d_x,
+                                 double* d_y, int32_t* d_status, int32_t* d_iters, double* d_obj, double* d_primal_inf,
+                                 double* d_dual_inf, int32_t* iterations_run, int64_t* evaluations, void* stream,
+                                 const cpl_instance_weights* weights) {
   // per-instance bounds: both arrays, or none (then this is cpl_solver_solve_warm)
   const bool has_box = box && (box->d_x_lb || box->d_x_ub);
   if (has_box && (!box->d_x_lb || !box->d_x_ub))
@@ -1658,6 +1741,12 @@ int32_t cpl_solver_solve_cones(cpl_solver* S, const double* d_x0, const double* 
     return fail(CPL_ERR_UNSUPPORTED,
                 "cpl_solver_solve_cones: per-instance cones need a Hessian that is not central differences: create the "
                 "solver with CPL_HESSIAN_ANALYTIC or CPL_HESSIAN_LIMITED_MEMORY");
+  // per-instance weights: any array, or none (then this is cpl_solver_solve_cones)
+  const bool has_wgt = weights && (weights->d_W_com || weights->d_W_F || weights->d_W_p);
+  if (has_wgt && S->fd)  // (the same rule)
+    return fail(CPL_ERR_UNSUPPORTED,
+                "cpl_solver_solve_weights: per-instance weights need a Hessian that is not central differences: create "
+                "the solver with CPL_HESSIAN_ANALYTIC or CPL_HESSIAN_LIMITED_MEMORY");
   // a warm start: all three multiplier arrays, or none (then this is cpl_solver_solve_inst)
   const bool is_warm = warm && (warm->d_y || warm->d_zL || warm->d_zU);
   if (is_warm) {
@@ -1671,16 +1760,18 @@ int32_t cpl_solver_solve_cones(cpl_solver* S, const double* d_x0, const double* 
   HK(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize (caller stream)");
   if (!has_inst) inst = nullptr;
   if (!has_cones) cones = nullptr;
+  if (!has_wgt) weights = nullptr;
   S->has_box = false;
   if (cones) CK(cones_check(S, cones));  // (validated on the device: nothing else is launched when it refuses)
+  if (weights) CK(weights_check(S, weights));  // (likewise)
   if (has_box) CK(box_prepare(S, box));  // (likewise)
   S->has_box = has_box;
   int it = 0;
   int64_t evals = 0;
-  CK(solve_start(S, d_x0, d_mass, d_env_tag, inst, cones, fixed_from_x0, is_warm ? warm : nullptr, &evals));
+  CK(solve_start(S, d_x0, d_mass, d_env_tag, inst, cones, weights, fixed_from_x0, is_warm ? warm : nullptr, &evals));
   CK(solve_iterate(S, &it, &evals));
-  CK(solve_finish(S, d_mass, d_env_tag, inst, cones, fixed_from_x0, d_x, d_y, d_status, d_iters, d_obj, d_primal_inf, d_dual_inf,
-                  &evals));
+  CK(solve_finish(S, d_mass, d_env_tag, inst, cones, weights, fixed_from_x0, d_x, d_y, d_status, d_iters, d_obj,
+                  d_primal_inf, d_dual_inf, &evals));
   if (iterations_run) *iterations_run = it;
   if (evaluations) *evaluations = evals;
   return CPL_OK;

@@ -95,6 +95,24 @@ __global__ void k_cone_check(int64_t total, int N, const double* __restrict__ mu
   if (bad) atomicMin(fault, (unsigned long long)e);
 }
 
+// Per-instance cost weights (cpl_solver_solve_weights): the caller's W_com [B], W_F and W_p [B, N] validated,
+// one thread per value of [B, 1 + 2N] (column 0: W_com, 1 + i: contact i's W_F, 1 + N + i: its W_p; a null
+// array is not read).  A weight is invalid unless it is finite and >= 0 (NaN fails the test).  fault: as
+// k_cone_check's — min over b (1 + 2N) + column, the first offending instance, W_com before W_F before W_p.
+__global__ void k_weight_check(int64_t total, int N, const double* __restrict__ W_com, const double* __restrict__ W_F,
+                               const double* __restrict__ W_p, unsigned long long* fault) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const int64_t b = e / (1 + 2 * N);
+  const int j = (int)(e - b * (1 + 2 * N));
+  const double* src = j == 0 ? (W_com ? W_com + b : nullptr)
+                             : (j <= N ? (W_F ? W_F + b * N + (j - 1) : nullptr)
+                                       : (W_p ? W_p + b * N + (j - 1 - N) : nullptr));
+  if (!src) return;
+  const double v = *src;
+  if (!(v >= 0.0 && v < INFINITY)) atomicMin(fault, (unsigned long long)e);
+}
+
 // ---- warm start [IPOPT-ext: warm_start_init_point, WarmStartIterateInitializer restated in this
 // engine's sign convention; include/cpl_mi355x.h cpl_warm_start, batch_ipm.py WarmStart] ----
 struct WarmArgs {

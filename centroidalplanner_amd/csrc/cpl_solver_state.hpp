@@ -28,8 +28,9 @@ struct Arena {
 //   temp   [B, width] by batch row, written before it is read within an iteration
 //   full   [B, width] by original instance (results, constant zeros)
 // ZEROED: cleared at the start of every solve.
-// (the solve is scaled / has masses / tags / instance data / per-instance bounds / per-instance cones)
-enum MoveWhen : uint8_t { NEVER, ALWAYS, IF_SCALED, IF_MASS, IF_TAG, IF_INST, IF_BOX, IF_CONE };
+// (the solve is scaled / has masses / tags / instance data / per-instance bounds / per-instance cones /
+// per-instance weights)
+enum MoveWhen : uint8_t { NEVER, ALWAYS, IF_SCALED, IF_MASS, IF_TAG, IF_INST, IF_BOX, IF_CONE, IF_WGT };
 constexpr bool ZEROED = true;
 struct BufRec { void* ptr; size_t elem; int64_t width; MoveWhen when; bool zeroed; };  // elem: bytes; width: per row
 struct Carver {
@@ -140,6 +141,12 @@ struct cpl_solver {
   cpl_instance_cones cones = {nullptr, nullptr};
   bool has_cones = false;
   unsigned long long* cone_fault;
+  // this solve's per-instance cost weights (cpl_solver_solve_weights): the solver's own copies, W_com [B], W_F
+  // and W_p [B, N] by batch row (moved by the compaction with their rows); wgt's pointers name them, null
+  // where the caller gave no array (the validation shares cone_fault: the checks run one after the other)
+  double *wgt_com, *wgt_F, *wgt_p;
+  cpl_instance_weights wgt = {nullptr, nullptr, nullptr};
+  bool has_wgt = false;
   // this solve's per-instance bounds (cpl_solver_solve_box; k_box_prepare writes them): the relaxed w-order
   // rows [B, nw] by batch row (moved by the compaction; bounds_of() hands them to every kernel with stride
   // nw), the unrelaxed x-order rows [B, n] by original instance (the final projection), the validation's

@@ -137,7 +137,7 @@ class CentroidalPlanner:
         return out
 
     def SolveBatch(self, X0, mass=None, instance=None, fixed_from_x0: bool = False, warm_start=None, bounds=None,
-                   cones=None, **solve_options):
+                   cones=None, weights=None, **solve_options):
         """Solve B instances of this planner's problem in one batched solve on the GPU (no reference
         counterpart: B Solve() calls).  X0 [B, n]: float64 CUDA start points; mass [B]: per-instance
         robot masses (None: the planner's); instance: per-instance manipulation wrench and cost
@@ -146,7 +146,8 @@ class CentroidalPlanner:
         its multipliers start the solve; the start point is still X0); bounds: per-instance variable bounds
         (InstanceBounds: the batched SetPosBounds / SetForceBounds); cones: per-instance friction coefficients
         and force thresholds (InstanceCones: the batched SetMu / SetForceThreshold; a lifted contact's force
-        stays fixed at 0 for every row — pass 0 in its threshold column).  solve_options go to
+        stays fixed at 0 for every row — pass 0 in its threshold column); weights: per-instance cost weights
+        (InstanceWeights: the batched SetCoMWeight / SetForceWeight / SetPosWeight).  solve_options go to
         batch_ipm_solve (default hessian: the planner's).  Returns the BatchSolveResult; the planner's own variables are left as they were."""
         from .batch_ipm import batch_ipm_solve
 
@@ -155,7 +156,7 @@ class CentroidalPlanner:
         if not getattr(X0, "is_cuda", False):
             raise ValueError("SolveBatch: X0 must be a float64 CUDA tensor [B, n]")
         return batch_ipm_solve(self._cpl_problem, X0, mass=mass, instance=instance, fixed_from_x0=fixed_from_x0,
-                               warm_start=warm_start, bounds=bounds, cones=cones, **opts)
+                               warm_start=warm_start, bounds=bounds, cones=cones, weights=weights, **opts)
 
     # ---- validation helpers ------------------------------------------------------------------
     def HasContact(self, contact_name: str) -> bool:  # :359-370
@@ -362,7 +363,8 @@ class CoMPlanner:
         return self._cp.GetSolverOptions()
 
     def SolveBatch(self, positions, normals=None, com_ref=None, wrench=None, mass=None, warm_start=None,
-                   force_lb=None, force_ub=None, mu=None, force_threshold=None, **solve_options):
+                   force_lb=None, force_ub=None, mu=None, force_threshold=None, com_weight=None, force_weight=None,
+                   **solve_options):
         """The stance query, batched: are these B candidate stances statically feasible, and with what
         forces and CoM?  The batched form of B x (SetContactPosition / SetContactNormal / SetCoMRef /
         Solve).  positions [B, N, 3] (contact_names order), normals [B, N, 3] (None: the planner's),
@@ -378,17 +380,23 @@ class CoMPlanner:
         coefficient (for all contacts of the stance) and force thresholds, the batched SetMu /
         SetForceThreshold (InstanceCones; mu must be > 0 and a threshold >= 0: the solve refuses other
         values).  A contact the planner lifts (SetLiftingContact) keeps its force fixed at 0 for every
-        stance: pass 0 in its force_threshold column.  Returns the
+        stance: pass 0 in its force_threshold column.  com_weight [B], force_weight [B, N] (either or both):
+        per-stance cost weights, the batched SetCoMWeight / SetContactForceWeight (InstanceWeights; a weight
+        must be finite and >= 0: the solve refuses other values) — a large force weight on one contact of some
+        stances unloads that contact there without fixing it.  Positions are fixed here, so there is no
+        position weight at this level.  Returns the
         BatchSolveResult of the solve with fixed_from_x0."""
         import torch
 
-        from .problem import InstanceBounds, InstanceCones, InstanceData
+        from .problem import InstanceBounds, InstanceCones, InstanceData, InstanceWeights
 
         prob = self._cp.GetCplProblem()
         N = len(self._contact_names)
         if torch.is_tensor(positions) and positions.dim() == 3:  # (dtype and shape before anything needs a device)
             for t, shape, name in ((mu, (positions.shape[0],), "mu"),
-                                   (force_threshold, (positions.shape[0], N), "force_threshold")):
+                                   (force_threshold, (positions.shape[0], N), "force_threshold"),
+                                   (com_weight, (positions.shape[0],), "com_weight"),
+                                   (force_weight, (positions.shape[0], N), "force_weight")):
                 if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float64 or tuple(t.shape) != shape):
                     raise ValueError(f"{name} must be a float64 tensor {list(shape)}")
         if (not torch.is_tensor(positions) or positions.dtype != torch.float64 or not positions.is_cuda
@@ -415,6 +423,8 @@ class CoMPlanner:
         force_ub = per_batch(force_ub, (B, N, 3), "force_ub")
         mu = per_batch(mu, (B,), "mu")
         force_threshold = per_batch(force_threshold, (B, N), "force_threshold")
+        com_weight = per_batch(com_weight, (B,), "com_weight")
+        force_weight = per_batch(force_weight, (B, N), "force_weight")
         d = prob.desc()
         X0 = torch.empty(B, 3 + 9 * N, dtype=torch.float64, device=dev)
         X0[:, 0:3] = com_ref if com_ref is not None else torch.tensor(list(d.com_ref), dtype=torch.float64, device=dev)
@@ -438,8 +448,10 @@ class CoMPlanner:
         inst = InstanceData(wrench=wrench, com_ref=com_ref)
         box = None if force_lb is None else InstanceBounds(F_lb=force_lb, F_ub=force_ub)
         cones = InstanceCones(mu=mu, F_thr=force_threshold)
+        wts = InstanceWeights(com=com_weight, force=force_weight)
         return self._cp.SolveBatch(X0, mass=mass, instance=inst if inst else None, fixed_from_x0=True,
-                                   warm_start=warm_start, bounds=box, cones=cones if cones else None, **solve_options)
+                                   warm_start=warm_start, bounds=box, cones=cones if cones else None,
+                                   weights=wts if wts else None, **solve_options)
 
     def SetCoMWeight(self, w):
         self._cp.SetCoMWeight(w)

@@ -186,6 +186,46 @@ class InstanceCones:
                                      for k in self.FIELDS))
 
 
+class InstanceWeights:
+    """Per-instance cost weights of a batch (cpl_instance_weights): the batched form of SetCoMWeight,
+    SetForceWeight / SetContactForceWeight and SetPosWeight / SetContactPosWeight, as float64 CUDA tensors
+    com [B], force [B, N] and pos [B, N] (contacts in contact_names order).  A field left None takes the
+    template's value for every instance.  The solvers validate the values (finite and >= 0); eval_batch does
+    not."""
+
+    FIELDS = ("com", "force", "pos")
+
+    def __init__(self, com=None, force=None, pos=None):
+        self.com, self.force, self.pos = com, force, pos
+
+    def __bool__(self):
+        return any(getattr(self, k) is not None for k in self.FIELDS)
+
+    def validated(self, batch: int, n_contacts: int, device) -> "InstanceWeights":
+        """The fields checked against the batch (ValueError naming the field) and made contiguous."""
+        import torch
+
+        shapes = {"com": (batch,), "force": (batch, n_contacts), "pos": (batch, n_contacts)}
+        out = InstanceWeights()
+        for k in self.FIELDS:
+            t = getattr(self, k)
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or t.dtype != torch.float64:
+                raise ValueError(f"InstanceWeights.{k} must be a float64 tensor")
+            if tuple(t.shape) != shapes[k]:
+                raise ValueError(f"InstanceWeights.{k} must have shape {shapes[k]}, not {tuple(t.shape)}")
+            if not t.is_cuda or t.device != device:
+                raise ValueError(f"InstanceWeights.{k} must be a CUDA tensor on the batch's device {device}, not {t.device}")
+            setattr(out, k, t.contiguous())
+        return out
+
+    def c_struct(self) -> "_abi.InstanceWeightsC":
+        """The C record over these tensors (which must stay alive while it is in use)."""
+        return _abi.InstanceWeightsC(*(None if getattr(self, k) is None else getattr(self, k).data_ptr()
+                                       for k in self.FIELDS))
+
+
 class InstanceBounds:
     """Per-instance variable bounds of a batch (cpl_instance_bounds): the batched form of SetPosBounds /
     SetForceBounds / SetNormalBounds and the CoM box.  com_lb, com_ub [B, 3] and F_lb, F_ub, p_lb, p_ub,
@@ -567,7 +607,7 @@ class CplProblem:
     # ---- the batched hot path ---------------------------------------------------------------
     def eval_batch(self, x, mass=None, env_tag=None, outputs: Iterable[str] = ("g", "jac"), out=None,
                    stream=None, jac_folded: bool = False, soa: bool = False, instance: Optional[InstanceData] = None,
-                   cones: Optional["InstanceCones"] = None):
+                   cones: Optional["InstanceCones"] = None, weights: Optional["InstanceWeights"] = None):
         """Evaluate B instances on the GPU in one launch.
 
         x: torch.float64 CUDA tensor [B, n] (contiguous).  mass: [B] or None.  env_tag: uint8 [B]
@@ -585,6 +625,9 @@ class CplProblem:
         cpl_eval_batch_cones: after the template's evaluation a cone overlay launch recomputes every
         contact's two cone values and row 1's six Jacobian entries, CSR or folded; the values are not
         validated here); not with soa.
+        weights: per-instance cost weights (InstanceWeights, cpl_eval_batch_weights: the template's
+        evaluation without f / grad, then one weight overlay launch for f and grad — with instance data for
+        g[0:6] too, in the instance overlay's stead; the values are not validated here); not with soa.
         """
         import torch
 
@@ -637,6 +680,18 @@ class CplProblem:
             res["norms"] = t
         if cones is not None and not isinstance(cones, InstanceCones):
             raise ValueError("cones must be an InstanceCones")
+        if weights is not None and not isinstance(weights, InstanceWeights):
+            raise ValueError("weights must be an InstanceWeights")
+        if weights is not None and weights:
+            wt = weights.validated(B, len(self._contact_names), x.device)
+            cn = (cones if cones is not None else InstanceCones()).validated(B, len(self._contact_names), x.device)
+            inst = (instance if instance is not None else InstanceData()).validated(B, len(self._contact_names), x.device)
+            cs, ccs, wcs = inst.c_struct(), cn.c_struct(), wt.c_struct()
+            check(lib.cpl_eval_batch_weights(ctypes.byref(self.desc()), B, p(x), p(mass), p(env_tag), ctypes.byref(cs),
+                                             ctypes.byref(ccs), p(res.get("g")), p(res.get("jac")), p(res.get("f")),
+                                             p(res.get("grad")), p(res.get("norms")), flags,
+                                             ctypes.c_void_p(s.cuda_stream), ctypes.byref(wcs)))
+            return res
         if cones is not None and cones:
             cn = cones.validated(B, len(self._contact_names), x.device)
             inst = (instance if instance is not None else InstanceData()).validated(B, len(self._contact_names), x.device)

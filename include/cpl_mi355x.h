@@ -263,6 +263,37 @@ int32_t cpl_eval_batch_cones(const cpl_problem_desc* d, int64_t batch, const dou
                              void* stream);
 
 /*
+ * Per-instance cost weights: the batched form of MinimizeCentroidalVariables' SetCoMWeight, SetForceWeight /
+ * SetContactForceWeight and SetPosWeight / SetContactPosWeight.  Device pointers, instance-major; any may be
+ * NULL = the template's value (cpl_problem_desc.W_com / W_F / W_p) for every instance.  A struct of its own:
+ * cpl_instance_data and cpl_instance_cones keep their layouts.
+ */
+typedef struct cpl_instance_weights {
+  const double* d_W_com;  /* [batch]     CoM weight of instance b, or NULL = d->W_com */
+  const double* d_W_F;    /* [batch][N]  force weights, contact_names (vector) order, or NULL = d->W_F */
+  const double* d_W_p;    /* [batch][N]  position weights, contact_names (vector) order, or NULL = d->W_p */
+} cpl_instance_weights;
+size_t cpl_instance_weights_sizeof(void); /* sizeof(cpl_instance_weights), for FFI layout checks */
+
+/*
+ * cpl_eval_batch_cones with per-instance cost weights.  weights == NULL or all three pointers NULL: exactly
+ * cpl_eval_batch_cones (the same launches, the same bits).  Otherwise the template's evaluation runs with f
+ * and grad switched off, then one weight overlay launch on the same stream computes f and grad f of every
+ * instance from its own weights, from the same expressions as the evaluation kernels: row b is bitwise
+ * cpl_eval_batch_cones on a batch of one whose template carries W_com = d_W_com[b], W_F = d_W_F[b],
+ * W_p = d_W_p[b].  g and the Jacobian do not depend on the weights.  With instance data in the same call the
+ * weight overlay reads the instance's references and writes g[0:6] from its wrench as well: one overlay
+ * launch, the instance overlay is not launched.  Cones keep their own overlay launch.
+ * CPL_EVAL_JAC_FOLDED is supported; CPL_EVAL_SOA with weights returns CPL_ERR_UNSUPPORTED before any launch.
+ * d_norms come from a cpl_residual_norms pass over the finished g.
+ * The values are NOT validated here (a weight >= 0 is the solve engine's check, cpl_solver_solve_weights).
+ */
+int32_t cpl_eval_batch_weights(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
+                               const uint8_t* d_env_tag, const cpl_instance_data* inst, const cpl_instance_cones* cones,
+                               double* d_g, double* d_jac, double* d_f, double* d_grad, double* d_norms, int32_t flags,
+                               void* stream, const cpl_instance_weights* weights);
+
+/*
  * The folded Jacobian layout of `d` (host only): *nnz_folded values per record; var_k[j] = the
  * CSR position (0..nnz-1, cpl_structure order) of folded value j; const_k[c] / const_val[c] = the
  * CSR position and value of skipped constant c, *n_const of them (nnz = nnz_folded + n_const).
@@ -446,6 +477,17 @@ int32_t cpl_lagrangian_hessian_ex(const cpl_problem_desc* d, int64_t batch, cons
 int32_t cpl_lagrangian_hessian_cones(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_y,
                                      const uint8_t* d_env_tag, const uint8_t* d_active, const int32_t* d_free_idx,
                                      int32_t nf, const cpl_instance_cones* cones, double* d_H, void* stream);
+/*
+ * cpl_lagrangian_hessian_cones with per-instance cost weights, which sit on the diagonal (W_com on the CoM
+ * entries, W_F[i] / W_p[i] on contact i's force / position entries; the Superquadric p x p blocks are added on
+ * top): instance b is bitwise cpl_lagrangian_hessian_ex on a template with b's weights (and mu = d_mu[b] when
+ * cones carry one).  One kernel for weights with and without cones: every pointer NULL = the template's value.
+ * weights == NULL or all three pointers NULL: exactly cpl_lagrangian_hessian_cones (the same kernel).
+ */
+int32_t cpl_lagrangian_hessian_weights(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_y,
+                                       const uint8_t* d_env_tag, const uint8_t* d_active, const int32_t* d_free_idx,
+                                       int32_t nf, const cpl_instance_cones* cones, double* d_H, void* stream,
+                                       const cpl_instance_weights* weights);
 int32_t cpl_kkt_solve(int32_t mode, int64_t batch, int32_t nw, int32_t m, const double* d_M, const double* d_A,
                       const double* d_r1, const double* d_r2, const double* d_mu, const double* d_delta_w_last,
                       const uint8_t* d_active, double* d_dw, double* d_dy, double* d_delta_w, double* d_delta_c,
@@ -965,6 +1007,36 @@ int32_t cpl_solver_solve_cones(cpl_solver* s, const double* d_x0, const double* 
                                const cpl_instance_bounds* box, const cpl_instance_cones* cones, double* d_x,
                                double* d_y, int32_t* d_status, int32_t* d_iters, double* d_obj, double* d_primal_inf,
                                double* d_dual_inf, int32_t* iterations_run, int64_t* evaluations, void* stream);
+
+/*
+ * cpl_solver_solve_cones with per-instance cost weights (cpl_instance_weights: W_com [batch], W_F and W_p
+ * [batch][N]).  weights == NULL, or all three pointers NULL: exactly cpl_solver_solve_cones (the same
+ * launches, the same bits).
+ *   - The solver keeps its own copies (1 + 2N doubles per instance, carved by cpl_solver_create; the
+ *     active-set compaction moves them with their rows).
+ *   - The weights enter f, grad f and the diagonal of the Lagrangian Hessian, nothing else: the evaluations
+ *     of the iteration (the template's evaluation without f / grad, the weight overlay — which serves the
+ *     instance data too —, the cone overlay if any, then the NLP scaling, so the objective's scaling factor
+ *     comes from the overlaid grad f), the fused line search with its restoration search and soft step, the
+ *     analytic Hessian, and the final re-evaluation.  The restoration phase's Hessian of y^T g has no cost
+ *     term and reads no weight.
+ *   - The contract: row b is bitwise the solve of a batch of one whose template carries W_com = d_W_com[b],
+ *     W_F = d_W_F[b], W_p = d_W_p[b] — x, y, status, iterations, objective and the bound multipliers.
+ *   - Validation runs on the device, once, before the start: every weight must be finite and >= 0 (the
+ *     reference throws "Invalid weight" below 0).  A bad value returns CPL_ERR_INVALID_ARGUMENT,
+ *     cpl_last_error() names the first offending instance, the field and (W_F, W_p) the contact, nothing else
+ *     has been launched and the solver stays usable.
+ *   - Weights need a Hessian that is not central differences, as instance data and cones do: with
+ *     CPL_HESSIAN_FD, or CPL_HESSIAN_EXACT on a Superquadric / mixed template, CPL_ERR_UNSUPPORTED before any
+ *     launch.
+ *   - Independent of instance data, per-instance bounds, cones, fixed_from_x0 and a warm start.
+ */
+int32_t cpl_solver_solve_weights(cpl_solver* s, const double* d_x0, const double* d_mass, const uint8_t* d_env_tag,
+                                 const cpl_instance_data* inst, int32_t fixed_from_x0, const cpl_warm_start* warm,
+                                 const cpl_instance_bounds* box, const cpl_instance_cones* cones, double* d_x,
+                                 double* d_y, int32_t* d_status, int32_t* d_iters, double* d_obj, double* d_primal_inf,
+                                 double* d_dual_inf, int32_t* iterations_run, int64_t* evaluations, void* stream,
+                                 const cpl_instance_weights* weights);
 
 #ifdef __cplusplus
 }
