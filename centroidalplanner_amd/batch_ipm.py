@@ -409,78 +409,31 @@ class NativeSolver:
             raise ValueError("cones must be an InstanceCones")
         if weights is not None and not isinstance(weights, InstanceWeights):
             raise ValueError("weights must be an InstanceWeights")
-        if weights is not None and weights:
-            N = len(self.problem.contact_names)
-            wt = weights.validated(B, N, dev)
-            wts = wt.c_struct()
-            cn = (cones if cones is not None else InstanceCones()).validated(B, N, dev)
-            ccs = cn.c_struct()
-            box = None
-            if bounds is not None and bounds:
-                x_lb, x_ub = bounds.packed(self.problem, B, dev)
-                box = _abi.InstanceBoundsC(x_lb.data_ptr(), x_ub.data_ptr())
-            inst = (instance if instance is not None else InstanceData()).validated(B, N, dev)
-            cs = inst.c_struct()
-            ws = None if warm_start is None else warm_start.validated(B, n, m, dev)
-            wcs = None if ws is None else ws.c_struct()
-            _abi.check(_abi.lib.cpl_solver_solve_weights(
-                self.handle, _ptr(X0), None if mass is None else _ptr(mass), None if env_tag is None else _ptr(env_tag),
-                ctypes.byref(cs), 1 if fixed_from_x0 else 0, None if wcs is None else ctypes.byref(wcs),
-                None if box is None else ctypes.byref(box), ctypes.byref(ccs), _ptr(x), _ptr(y), _ptr(status),
-                _ptr(iters), _ptr(obj), _ptr(pinf), _ptr(dinf), ctypes.byref(it), ctypes.byref(ev),
-                ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), ctypes.byref(wts)))
-        elif cones is not None and cones:
-            cn = cones.validated(B, len(self.problem.contact_names), dev)
-            ccs = cn.c_struct()
-            box = None
-            if bounds is not None and bounds:
-                x_lb, x_ub = bounds.packed(self.problem, B, dev)
-                box = _abi.InstanceBoundsC(x_lb.data_ptr(), x_ub.data_ptr())
-            inst = (instance if instance is not None else InstanceData()).validated(B, len(self.problem.contact_names), dev)
-            cs = inst.c_struct()
-            ws = None if warm_start is None else warm_start.validated(B, n, m, dev)
-            wcs = None if ws is None else ws.c_struct()
-            _abi.check(_abi.lib.cpl_solver_solve_cones(
-                self.handle, _ptr(X0), None if mass is None else _ptr(mass), None if env_tag is None else _ptr(env_tag),
-                ctypes.byref(cs), 1 if fixed_from_x0 else 0, None if wcs is None else ctypes.byref(wcs),
-                None if box is None else ctypes.byref(box), ctypes.byref(ccs), _ptr(x), _ptr(y), _ptr(status),
-                _ptr(iters), _ptr(obj), _ptr(pinf), _ptr(dinf), ctypes.byref(it), ctypes.byref(ev),
-                ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        elif bounds is not None and bounds:
+        # each argument given is checked once, in the order the narrower entry points checked them — a warm start
+        # on its own before the instance data, with weights, cones or bounds after it —, then one call: a
+        # record not given is NULL (cpl_solver_solve_weights with NULLs is the narrower entry)
+        N = len(self.problem.contact_names)
+        wt = weights.validated(B, N, dev) if weights else None
+        cn = cones.validated(B, N, dev) if cones else None
+        box = None
+        if bounds:
             x_lb, x_ub = bounds.packed(self.problem, B, dev)
             box = _abi.InstanceBoundsC(x_lb.data_ptr(), x_ub.data_ptr())
-            inst = (instance if instance is not None else InstanceData()).validated(B, len(self.problem.contact_names), dev)
-            cs = inst.c_struct()
-            ws = None if warm_start is None else warm_start.validated(B, n, m, dev)
-            wcs = None if ws is None else ws.c_struct()
-            _abi.check(_abi.lib.cpl_solver_solve_box(
-                self.handle, _ptr(X0), None if mass is None else _ptr(mass), None if env_tag is None else _ptr(env_tag),
-                ctypes.byref(cs), 1 if fixed_from_x0 else 0, None if wcs is None else ctypes.byref(wcs),
-                ctypes.byref(box), _ptr(x), _ptr(y), _ptr(status), _ptr(iters), _ptr(obj), _ptr(pinf), _ptr(dinf),
-                ctypes.byref(it), ctypes.byref(ev), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        elif warm_start is not None:
+        warm_first = wt is None and cn is None and box is None
+        ws = warm_start.validated(B, n, m, dev) if warm_start is not None and warm_first else None
+        inst = instance.validated(B, N, dev) if instance else None
+        if warm_start is not None and not warm_first:
             ws = warm_start.validated(B, n, m, dev)
-            wcs = ws.c_struct()
-            inst = (instance if instance is not None else InstanceData()).validated(B, len(self.problem.contact_names), dev)
-            cs = inst.c_struct()
-            _abi.check(_abi.lib.cpl_solver_solve_warm(
-                self.handle, _ptr(X0), None if mass is None else _ptr(mass), None if env_tag is None else _ptr(env_tag),
-                ctypes.byref(cs), 1 if fixed_from_x0 else 0, ctypes.byref(wcs), _ptr(x), _ptr(y), _ptr(status),
-                _ptr(iters), _ptr(obj), _ptr(pinf), _ptr(dinf), ctypes.byref(it), ctypes.byref(ev),
-                ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        elif (instance is not None and instance) or fixed_from_x0:
-            inst = (instance if instance is not None else InstanceData()).validated(B, len(self.problem.contact_names), dev)
-            cs = inst.c_struct()
-            _abi.check(_abi.lib.cpl_solver_solve_inst(
-                self.handle, _ptr(X0), None if mass is None else _ptr(mass), None if env_tag is None else _ptr(env_tag),
-                ctypes.byref(cs), 1 if fixed_from_x0 else 0, _ptr(x), _ptr(y), _ptr(status), _ptr(iters), _ptr(obj),
-                _ptr(pinf), _ptr(dinf), ctypes.byref(it), ctypes.byref(ev),
-                ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        else:
-            _abi.check(_abi.lib.cpl_solver_solve(
-                self.handle, _ptr(X0), None if mass is None else _ptr(mass), None if env_tag is None else _ptr(env_tag),
-                _ptr(x), _ptr(y), _ptr(status), _ptr(iters), _ptr(obj), _ptr(pinf), _ptr(dinf), ctypes.byref(it),
-                ctypes.byref(ev), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        cs, wcs, ccs, wts = (None if a is None else a.c_struct() for a in (inst, ws, cn, wt))
+
+        def ref(rec):
+            return None if rec is None else ctypes.byref(rec)
+
+        _abi.check(_abi.lib.cpl_solver_solve_weights(
+            self.handle, _ptr(X0), None if mass is None else _ptr(mass), None if env_tag is None else _ptr(env_tag),
+            ref(cs), 1 if fixed_from_x0 else 0, ref(wcs), ref(box), ref(ccs), _ptr(x), _ptr(y), _ptr(status),
+            _ptr(iters), _ptr(obj), _ptr(pinf), _ptr(dinf), ctypes.byref(it), ctypes.byref(ev),
+            ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), ref(wts)))
         g = ctypes.c_int32()
         _abi.check(_abi.lib.cpl_solver_dims(self.handle, None, None, ctypes.byref(g)))
         nc, rows = ctypes.c_int32(), ctypes.c_int64()

@@ -91,25 +91,43 @@ int32_t ipm_max_step(int64_t batch, int nw, const double* d_v, const double* d_d
 
 // ---- cpl_kernels.hip ----
 
-// the backtracking line search, one wave per instance (inst: the solve's instance data in the rows'
-// current order, or null — then the template's search)
-int32_t ls_backtrack(const cpl_problem_desc* d, const LsBacktrackArgs& a, hipStream_t stream,
-                     const cpl_instance_data* inst = nullptr, const cpl_instance_cones* cones = nullptr,
-                     const cpl_instance_weights* weights = nullptr);
+// One call's per-instance arrays, whichever of the three public records they came in (device pointers, [batch]
+// rows; a null array: the template's value for every row).  The solve engine keeps one over its own copies.
+struct InstView {
+  const double *wrench = nullptr, *com_ref = nullptr, *p_ref = nullptr, *F_ref = nullptr;  // cpl_instance_data
+  const double *mu = nullptr, *F_thr = nullptr;                                            // cpl_instance_cones
+  const double *W_com = nullptr, *W_F = nullptr, *W_p = nullptr;                           // cpl_instance_weights
+  bool has_inst() const { return wrench || com_ref || p_ref || F_ref; }
+  bool has_cones() const { return mu || F_thr; }
+  bool has_wgt() const { return W_com || W_F || W_p; }
+  bool any() const { return has_inst() || has_cones() || has_wgt(); }
+  // an overlay computes f / grad (the template's evaluation then leaves them out)
+  bool overlays_cost() const { return has_inst() || has_wgt(); }
+  static InstView of(const cpl_instance_data* i, const cpl_instance_cones* c, const cpl_instance_weights* w) {
+    InstView v;
+    if (i) v.wrench = i->d_wrench, v.com_ref = i->d_com_ref, v.p_ref = i->d_p_ref, v.F_ref = i->d_F_ref;
+    if (c) v.mu = c->d_mu, v.F_thr = c->d_F_thr;
+    if (w) v.W_com = w->d_W_com, v.W_F = w->d_W_F, v.W_p = w->d_W_p;
+    return v;
+  }
+  // the public records again (for the C entries that take them)
+  cpl_instance_data data() const { return {wrench, com_ref, p_ref, F_ref}; }
+  cpl_instance_cones cones() const { return {mu, F_thr}; }
+  cpl_instance_weights weights() const { return {W_com, W_F, W_p}; }
+};
+
+// the backtracking line search, one wave per instance (V: the solve's per-instance arrays in the rows' current
+// order; an empty view: the template's search)
+int32_t ls_backtrack(const cpl_problem_desc* d, const LsBacktrackArgs& a, hipStream_t stream, const InstView& V);
 // the fused search kernel takes the post-step prologue (LsBacktrackArgs::with_post) at this batch size
 bool ls_post_prologue(int64_t batch);
-// the instance overlay — g[0:6], f, grad of every row from its instance data
-int32_t eval_overlay(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
-                     const cpl_instance_data* inst, double* d_g, double* d_f, double* d_grad, void* stream,
-                     const uint8_t* gate);
-// the cone overlay — the cone rows of g and row 1's Jacobian entries of every row from its cones
-int32_t eval_cone_overlay(const cpl_problem_desc* d, int64_t batch, const double* d_x, const cpl_instance_cones* cones,
-                          double* d_g, double* d_jac, int32_t flags, void* stream, const uint8_t* gate);
-// the weight overlay — f, grad of every row from its cost weights (with inst: from its references too, and
-// g[0:6]; the instance overlay is then not launched)
-int32_t eval_weight_overlay(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
-                            const cpl_instance_data* inst, const cpl_instance_weights* weights, double* d_g,
-                            double* d_f, double* d_grad, void* stream, const uint8_t* gate);
+// what follows the template's evaluation of a call with per-instance arrays, on the same stream: the instance
+// overlay (g[0:6], f, grad from the instance data and / or the weights; f, grad alone without instance data),
+// then the cone overlay (the cone rows of g, row 1's Jacobian entries; flags: the Jacobian's layout).  Any
+// output may be null; honours the gate byte.
+int32_t eval_overlays(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
+                      const InstView& V, double* d_g, double* d_jac, double* d_f, double* d_grad, int32_t flags,
+                      hipStream_t stream, const uint8_t* gate);
 // the NLP-scaled evaluation (pipelined kernel; CPL_ERR_UNSUPPORTED: not that path)
 int32_t eval_batch_scaled(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
                           const uint8_t* d_env_tag, double* d_g, double* d_jac, double* d_f, double* d_grad,

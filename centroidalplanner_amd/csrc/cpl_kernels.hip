@@ -3334,29 +3334,31 @@ static int32_t launch_eval(const EvalCall& c) {
 }
 
 // ------------------------------------------------------------------------------------------
-// The instance overlay (cpl_eval_batch_inst, the solve engine with instance data): the outputs that
-// depend on cpl_instance_data — the six statics values g[0:6], f and grad f — of every instance, from
-// x, the mass and the instance's own wrench / references, through the same items as the evaluation
-// kernels with the per-instance source (InstSrc).  It runs after the template's evaluation on the
-// same stream and overwrites that kernel's six template statics values per instance; the Jacobian
-// and the other rows of g do not depend on the instance data.
+// The instance overlay (cpl_eval_batch_inst / _weights, the solve engine with instance data or weights): the
+// outputs that depend on cpl_instance_data — the six statics values g[0:6], f and grad f — and on
+// cpl_instance_weights — f and grad f — of every instance, from x, the mass and the instance's own wrench /
+// references / weights, through the same items as the evaluation kernels with the per-instance source.  It
+// runs after the template's evaluation on the same stream and overwrites that kernel's six template statics
+// values per instance; the Jacobian and the other rows of g do not depend on these arrays.
+// One template over the source: InstSrc (instance data alone: the descriptor's weights from the kernel
+// arguments) and InstWSrc (a call with weights: W_com, W_F, W_p staged too, and cost_value / cost_item read
+// them through the source — the expression trees are the evaluation kernels', the library is built without
+// contraction, so row b has the bits of the template path with b's values written into the descriptor).
+// Without instance data the host switches want_g off and g is never touched.
 // One 256-thread workgroup per tile of T consecutive instances (T even, at most 64, sized by the host to
 // the tile kernel's LDS budget: 8 (2n + 16 + 6N) bytes per instance, so 52 instances of 4 contacts and
-// 14 of 16 in the default 48 KiB): the tile's x records and instance data copied into LDS with 16-byte accesses,
+// 14 of 16 in the default 48 KiB; with weights 8 (2n + 17 + 8N), 1 + 2N more, so 46 of 4 contacts): the tile's
+// x records and per-instance arrays copied into LDS with 16-byte accesses,
 // one item per thread (instance r's statics values, instance r's cost), the tile's grad / f images
 // copied out linearly and the six g values of each record as three 16-byte stores (m is even).
-// A NULL instance array is staged from the template, so every item reads LDS.
-struct InstPtrs {
-  const double *wrench, *com_ref, *p_ref, *F_ref;  // cpl_instance_data's arrays (device; any may be null)
-  bool any() const { return wrench || com_ref || p_ref || F_ref; }
-};
-
-template <bool NT>
+// A NULL array is staged from the template, so every item reads LDS.
+template <typename SRC, bool NT>
 __global__ __launch_bounds__(256) void cpl_inst_overlay_kernel(const KParams K, int64_t batch,
                                                                const double* __restrict__ x,
-                                                               const double* __restrict__ mass, const InstPtrs I,
+                                                               const double* __restrict__ mass, const InstView V,
                                                                double* __restrict__ g_out, double* __restrict__ f_out,
                                                                double* __restrict__ grad_out) {
+  constexpr bool WGT = std::is_same<SRC, InstWSrc>::value;
   extern __shared__ __align__(16) double smem[];
   if (K.gate && *K.gate == 0) return;  // (every thread of every workgroup: the same byte)
   const int tid = threadIdx.x;
@@ -3372,147 +3374,44 @@ __global__ __launch_bounds__(256) void cpl_inst_overlay_kernel(const KParams K, 
   double* Cl = Wl + T * 6;       // [T][3]   com_ref
   double* Pl = Cl + T * 3;       // [T][3N]  p_ref
   double* Fl = Pl + T * 3 * N;   // [T][3N]  F_ref
-  load_ctab(K);
-  auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  // (T even: every tile's first record of every array is 16-byte aligned when the array is)
-  copy_in<256>(X, x + b0 * n, valid * n, tid, aligned(x));
-  if (I.wrench) copy_in<256>(Wl, I.wrench + b0 * 6, valid * 6, tid, aligned(I.wrench));
-  else for (int e = tid; e < valid * 6; e += 256) Wl[e] = K.wrench[e % 6];
-  if (I.com_ref) copy_in<256>(Cl, I.com_ref + b0 * 3, valid * 3, tid, aligned(I.com_ref));
-  else for (int e = tid; e < valid * 3; e += 256) Cl[e] = K.com_ref[e % 3];
-  if (I.p_ref) copy_in<256>(Pl, I.p_ref + b0 * 3 * N, valid * 3 * N, tid, aligned(I.p_ref));
-  else for (int e = tid; e < valid * 3 * N; e += 256) Pl[e] = K.p_ref[(e % (3 * N)) / 3][e % 3];
-  if (I.F_ref) copy_in<256>(Fl, I.F_ref + b0 * 3 * N, valid * 3 * N, tid, aligned(I.F_ref));
-  else for (int e = tid; e < valid * 3 * N; e += 256) Fl[e] = K.F_ref[(e % (3 * N)) / 3][e % 3];
-  __syncthreads();
-  // one item per thread: (instance r, statics values | cost) — 2 T <= 128 items: half the workgroup
-  // computes, all of it copies (the kernel is its copies: 2 n + 16 + 6 N doubles moved per instance)
-  for (int e = tid; e < 2 * valid; e += 256) {
-    const int r = e >> 1;
-    const InstSrc src{Wl + r * 6, Cl + r * 3, Pl + r * 3 * N, Fl + r * 3 * N};
-    const double* xr = X + r * n;
-    if ((e & 1) == 0) {
-      if (K.want_g)
-        statics_values_item<InstSrc>(K, xr, mass ? mass[b0 + r] : K.mass_default, G6 + r * 6, nullptr, false, nullptr,
-                                     false, src);
-    } else {
-      cost_item<InstSrc>(K, xr, Fv + r, Dt + r * n, nullptr, src);
-    }
-  }
-  __syncthreads();
-  if (K.want_grad) copy_out<256, NT>(grad_out + b0 * n, Dt, valid * n, tid);
-  if (K.want_f) copy_out<256, NT>(f_out + b0, Fv, valid, tid);
-  if (K.want_g) {
-    if (aligned(g_out)) {  // (m even: g[0:6] of every record is three aligned pairs)
-      for (int e = tid; e < valid * 3; e += 256) {
-        const int r = e / 3, q = e - r * 3;
-        const double2 v = reinterpret_cast<const double2*>(G6)[e];
-        double2* dst = reinterpret_cast<double2*>(g_out + (b0 + r) * m) + q;
-        if (NT) {
-          __builtin_nontemporal_store(v.x, &dst->x);
-          __builtin_nontemporal_store(v.y, &dst->y);
-        } else {
-          *dst = v;
-        }
-      }
-    } else {
-      for (int e = tid; e < valid * 6; e += 256) g_out[(b0 + e / 6) * m + e % 6] = G6[e];
-    }
-  }
-}
-
-// the overlay's launch: g (its first six values per record), f, grad — any may be null
-static int32_t launch_overlay(const cpl_problem_desc* d, int64_t batch, const double* x, const double* mass,
-                              const InstPtrs& I, double* g, double* f, double* grad, hipStream_t stream,
-                              const uint8_t* gate) {
-  if (batch <= 0 || (!g && !f && !grad)) return CPL_OK;
-  KParams K;
-  fill_params(d, K, x);
-  K.gate = gate;
-  K.want_g = g != nullptr; K.want_j = 0; K.want_f = f != nullptr; K.want_grad = grad != nullptr;
-  const size_t per = sizeof(double) * (size_t)(2 * K.n + 6 + 1 + 9 + 6 * K.N);
-  int T = (int)(tile_budget() / per) & ~1;  // (the tile kernel's LDS budget: 48 KiB by default)
-  K.T = T > 64 ? 64 : (T < 2 ? 2 : T);
-  const size_t lds = per * (size_t)K.T;
-  const int64_t grid = (batch + K.T - 1) / K.T;
-  if (grid > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "batch too large");
-  hipLaunchKernelGGL(g_nt ? cpl_inst_overlay_kernel<true> : cpl_inst_overlay_kernel<false>, dim3((unsigned)grid),
-                     dim3(256), lds, stream, K, batch, x, mass, I, g, f, grad);
-  const hipError_t e = hipGetLastError();
-  return e != hipSuccess ? hip_fail(e, "cpl_inst_overlay_kernel launch") : CPL_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// The weight overlay (cpl_eval_batch_weights, the solve engine with per-instance cost weights): f and grad f
-// of every instance from its own W_com, W_F, W_p (cpl_instance_weights) — and, when the call carries
-// instance data as well, from its own references, with g[0:6] from its wrench: then this launch stands in for
-// the instance overlay's.  It is that overlay's body with InstWSrc, a kernel of its own so that the instance
-// overlay keeps its symbols and its code.  cost_value / cost_item read the weights through the source: the
-// expression trees are the evaluation kernels' (the library is built without contraction), so row b has the
-// bits of the template path with b's weights written into the descriptor.
-// 8 (2n + 17 + 8N) bytes of LDS per instance — the instance overlay's image plus 1 + 2N weights —, so 46
-// instances of 4 contacts in the default 48 KiB.  A NULL array (instance data or weights) is staged from
-// the template.  Without instance data want_g is off and g is never touched.
-struct WgtPtrs {
-  const double *W_com, *W_F, *W_p;  // cpl_instance_weights' arrays (device; any may be null)
-  bool any() const { return W_com || W_F || W_p; }
-};
-
-template <bool NT>
-__global__ __launch_bounds__(256) void cpl_weight_overlay_kernel(const KParams K, int64_t batch,
-                                                                 const double* __restrict__ x,
-                                                                 const double* __restrict__ mass, const InstPtrs I,
-                                                                 const WgtPtrs W, double* __restrict__ g_out,
-                                                                 double* __restrict__ f_out,
-                                                                 double* __restrict__ grad_out) {
-  extern __shared__ __align__(16) double smem[];
-  if (K.gate && *K.gate == 0) return;  // (every thread of every workgroup: the same byte)
-  const int tid = threadIdx.x;
-  const int T = K.T, n = K.n, m = K.m, N = K.N;
-  const int64_t b0 = (int64_t)blockIdx.x * T;
-  if (b0 >= batch) return;
-  const int valid = (int)((batch - b0) < T ? (batch - b0) : T);
-  double* X = smem;              // [T][n]
-  double* Dt = X + T * n;        // [T][n]   grad f
-  double* G6 = Dt + T * n;       // [T][6]   statics values
-  double* Fv = G6 + T * 6;       // [T]      f
-  double* Wl = Fv + T;           // [T][6]   wrench
-  double* Cl = Wl + T * 6;       // [T][3]   com_ref
-  double* Pl = Cl + T * 3;       // [T][3N]  p_ref
-  double* Fl = Pl + T * 3 * N;   // [T][3N]  F_ref
-  double* Wc = Fl + T * 3 * N;   // [T]      W_com
+  double* Wc = Fl + T * 3 * N;   // [T]      W_com   (WGT: these three)
   double* WF = Wc + T;           // [T][N]   W_F
   double* Wp = WF + T * N;       // [T][N]   W_p
   load_ctab(K);
   auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   // (T even: every tile's first record of every array is 16-byte aligned when the array is)
   copy_in<256>(X, x + b0 * n, valid * n, tid, aligned(x));
-  if (I.wrench) copy_in<256>(Wl, I.wrench + b0 * 6, valid * 6, tid, aligned(I.wrench));
+  if (V.wrench) copy_in<256>(Wl, V.wrench + b0 * 6, valid * 6, tid, aligned(V.wrench));
   else for (int e = tid; e < valid * 6; e += 256) Wl[e] = K.wrench[e % 6];
-  if (I.com_ref) copy_in<256>(Cl, I.com_ref + b0 * 3, valid * 3, tid, aligned(I.com_ref));
+  if (V.com_ref) copy_in<256>(Cl, V.com_ref + b0 * 3, valid * 3, tid, aligned(V.com_ref));
   else for (int e = tid; e < valid * 3; e += 256) Cl[e] = K.com_ref[e % 3];
-  if (I.p_ref) copy_in<256>(Pl, I.p_ref + b0 * 3 * N, valid * 3 * N, tid, aligned(I.p_ref));
+  if (V.p_ref) copy_in<256>(Pl, V.p_ref + b0 * 3 * N, valid * 3 * N, tid, aligned(V.p_ref));
   else for (int e = tid; e < valid * 3 * N; e += 256) Pl[e] = K.p_ref[(e % (3 * N)) / 3][e % 3];
-  if (I.F_ref) copy_in<256>(Fl, I.F_ref + b0 * 3 * N, valid * 3 * N, tid, aligned(I.F_ref));
+  if (V.F_ref) copy_in<256>(Fl, V.F_ref + b0 * 3 * N, valid * 3 * N, tid, aligned(V.F_ref));
   else for (int e = tid; e < valid * 3 * N; e += 256) Fl[e] = K.F_ref[(e % (3 * N)) / 3][e % 3];
-  if (W.W_com) copy_in<256>(Wc, W.W_com + b0, valid, tid, aligned(W.W_com));
-  else for (int e = tid; e < valid; e += 256) Wc[e] = K.W_com;
-  if (W.W_F) copy_in<256>(WF, W.W_F + b0 * N, valid * N, tid, aligned(W.W_F));
-  else for (int e = tid; e < valid * N; e += 256) WF[e] = K.W_F[e % N];
-  if (W.W_p) copy_in<256>(Wp, W.W_p + b0 * N, valid * N, tid, aligned(W.W_p));
-  else for (int e = tid; e < valid * N; e += 256) Wp[e] = K.W_p[e % N];
+  if constexpr (WGT) {
+    if (V.W_com) copy_in<256>(Wc, V.W_com + b0, valid, tid, aligned(V.W_com));
+    else for (int e = tid; e < valid; e += 256) Wc[e] = K.W_com;
+    if (V.W_F) copy_in<256>(WF, V.W_F + b0 * N, valid * N, tid, aligned(V.W_F));
+    else for (int e = tid; e < valid * N; e += 256) WF[e] = K.W_F[e % N];
+    if (V.W_p) copy_in<256>(Wp, V.W_p + b0 * N, valid * N, tid, aligned(V.W_p));
+    else for (int e = tid; e < valid * N; e += 256) Wp[e] = K.W_p[e % N];
+  }
   __syncthreads();
-  // one item per thread: (instance r, statics values | cost)
+  // one item per thread: (instance r, statics values | cost) — 2 T <= 128 items: half the workgroup
+  // computes, all of it copies (the kernel is its copies: 2 n + 16 + 6 N doubles moved per instance)
   for (int e = tid; e < 2 * valid; e += 256) {
     const int r = e >> 1;
-    const InstWSrc src{Wl + r * 6, Cl + r * 3, Pl + r * 3 * N, Fl + r * 3 * N, Wc + r, WF + r * N, Wp + r * N};
+    SRC src;
+    if constexpr (WGT) src = InstWSrc{Wl + r * 6, Cl + r * 3, Pl + r * 3 * N, Fl + r * 3 * N, Wc + r, WF + r * N, Wp + r * N};
+    else src = InstSrc{Wl + r * 6, Cl + r * 3, Pl + r * 3 * N, Fl + r * 3 * N};
     const double* xr = X + r * n;
     if ((e & 1) == 0) {
       if (K.want_g)
-        statics_values_item<InstWSrc>(K, xr, mass ? mass[b0 + r] : K.mass_default, G6 + r * 6, nullptr, false, nullptr,
-                                      false, src);
+        statics_values_item<SRC>(K, xr, mass ? mass[b0 + r] : K.mass_default, G6 + r * 6, nullptr, false, nullptr,
+                                 false, src);
     } else {
-      cost_item<InstWSrc>(K, xr, Fv + r, Dt + r * n, nullptr, src);
+      cost_item<SRC>(K, xr, Fv + r, Dt + r * n, nullptr, src);
     }
   }
   __syncthreads();
@@ -3537,27 +3436,31 @@ __global__ __launch_bounds__(256) void cpl_weight_overlay_kernel(const KParams K
   }
 }
 
-// the weight overlay's launch: f, grad — and g (its first six values per record) when the call has
-// instance data; any may be null
-static int32_t launch_weight_overlay(const cpl_problem_desc* d, int64_t batch, const double* x, const double* mass,
-                                     const InstPtrs& I, const WgtPtrs& W, double* g, double* f, double* grad,
-                                     hipStream_t stream, const uint8_t* gate) {
-  if (!I.any()) g = nullptr;  // (the statics values do not depend on the weights)
+// the overlay's launch: g (its first six values per record; dropped without instance data: the statics values
+// do not depend on the weights), f, grad — any may be null
+static int32_t launch_overlay(const cpl_problem_desc* d, int64_t batch, const double* x, const double* mass,
+                              const InstView& V, double* g, double* f, double* grad, hipStream_t stream,
+                              const uint8_t* gate) {
+  const bool wgt = V.has_wgt();
+  if (!V.has_inst()) g = nullptr;
   if (batch <= 0 || (!g && !f && !grad)) return CPL_OK;
   KParams K;
   fill_params(d, K, x);
   K.gate = gate;
   K.want_g = g != nullptr; K.want_j = 0; K.want_f = f != nullptr; K.want_grad = grad != nullptr;
-  const size_t per = sizeof(double) * (size_t)(2 * K.n + 17 + 8 * K.N);
+  const size_t per = sizeof(double) * (size_t)(wgt ? 2 * K.n + 17 + 8 * K.N : 2 * K.n + 16 + 6 * K.N);
   int T = (int)(tile_budget() / per) & ~1;  // (the tile kernel's LDS budget: 48 KiB by default)
   K.T = T > 64 ? 64 : (T < 2 ? 2 : T);
   const size_t lds = per * (size_t)K.T;
   const int64_t grid = (batch + K.T - 1) / K.T;
   if (grid > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "batch too large");
-  hipLaunchKernelGGL(g_nt ? cpl_weight_overlay_kernel<true> : cpl_weight_overlay_kernel<false>, dim3((unsigned)grid),
-                     dim3(256), lds, stream, K, batch, x, mass, I, W, g, f, grad);
+  using KernT = void (*)(const KParams, int64_t, const double*, const double*, const InstView, double*, double*, double*);
+  static const KernT table[2][2] = {{cpl_inst_overlay_kernel<InstSrc, false>, cpl_inst_overlay_kernel<InstSrc, true>},
+                                    {cpl_inst_overlay_kernel<InstWSrc, false>, cpl_inst_overlay_kernel<InstWSrc, true>}};
+  hipLaunchKernelGGL(table[wgt][g_nt ? 1 : 0], dim3((unsigned)grid), dim3(256), lds, stream, K, batch, x, mass, V, g, f,
+                     grad);
   const hipError_t e = hipGetLastError();
-  return e != hipSuccess ? hip_fail(e, "cpl_weight_overlay_kernel launch") : CPL_OK;
+  return e != hipSuccess ? hip_fail(e, "cpl_inst_overlay_kernel launch") : CPL_OK;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3573,9 +3476,8 @@ static int32_t launch_weight_overlay(const cpl_problem_desc* d, int64_t batch, c
 // the contact's row count are even) and the Jacobian entries with the lanes along the tile's runs of six.
 // Row 1's entries are variable in every layout: contact block k's cone entries start at jbase +
 // cstride k + (15 | 12 | 0: CSR with a surface | FOLD_COMMON with a surface | FOLD_GROUND, no surface).
-struct ConePtrs {
+struct ConePtrs {  // (the kernel's argument: the view's two cone arrays)
   const double *mu, *F_thr;  // cpl_instance_cones' arrays (device; either may be null)
-  bool any() const { return mu || F_thr; }
 };
 
 __device__ __forceinline__ void cone_rows_inst(const double mu, const double F_thr, const double* __restrict__ q,
@@ -3701,20 +3603,30 @@ static int32_t launch_cone_overlay(const cpl_problem_desc* d, int64_t batch, con
   return e != hipSuccess ? hip_fail(e, "cpl_cone_overlay_kernel launch") : CPL_OK;
 }
 
+// what follows the template's evaluation (cpl_engine.hpp): the instance overlay — one launch for instance data
+// and weights together —, then the cone overlay
+int32_t eval_overlays(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
+                      const InstView& V, double* d_g, double* d_jac, double* d_f, double* d_grad, int32_t flags,
+                      hipStream_t stream, const uint8_t* gate) {
+  if (V.overlays_cost())
+    if (int32_t st = launch_overlay(d, batch, d_x, d_mass, V, d_g, d_f, d_grad, stream, gate)) return st;
+  if (V.has_cones()) return launch_cone_overlay(d, batch, d_x, ConePtrs{V.mu, V.F_thr}, d_g, d_jac, flags, stream, gate);
+  return CPL_OK;
+}
+
 // the evaluation with instance data, cones and / or weights: the template's evaluation (whichever path
 // launch_eval picks; with instance data or weights f and grad switched off), the overlay(s) on the same
 // stream, then (norms) a pass over the finished g — the fused norms would see the template's statics and cone
-// rows.  Weights and instance data together are one overlay launch (the weight overlay writes g[0:6] too).
-static int32_t launch_eval_inst(const EvalCall& c, const InstPtrs& I, const ConePtrs& Cn = ConePtrs{},
-                                const WgtPtrs& Wg = WgtPtrs{}) {
-  if (!I.any() && !Cn.any() && !Wg.any()) return launch_eval(c);
+// rows.
+static int32_t launch_eval_inst(const EvalCall& c, const InstView& V) {
+  if (!V.any()) return launch_eval(c);
   if (c.flags & CPL_EVAL_SOA)
     return fail(CPL_ERR_UNSUPPORTED,
-                Wg.any()   ? "weights: entry-major (CPL_EVAL_SOA) outputs are not supported"
-                : Cn.any() ? "cones: entry-major (CPL_EVAL_SOA) outputs are not supported"
-                           : "instance data: entry-major (CPL_EVAL_SOA) outputs are not supported");
+                V.has_wgt()     ? "weights: entry-major (CPL_EVAL_SOA) outputs are not supported"
+                : V.has_cones() ? "cones: entry-major (CPL_EVAL_SOA) outputs are not supported"
+                                : "instance data: entry-major (CPL_EVAL_SOA) outputs are not supported");
   EvalCall t = c;
-  if (I.any() || Wg.any()) {
+  if (V.overlays_cost()) {
     t.f = nullptr;
     t.grad = nullptr;
   }
@@ -3730,14 +3642,8 @@ static int32_t launch_eval_inst(const EvalCall& c, const InstPtrs& I, const Cone
     return st;
   }
   if (c.batch == 0) return c.norms ? launch_eval(c) : CPL_OK;  // (the empty batch's zero norms)
-  if (Wg.any()) {
-    if (int32_t st = launch_weight_overlay(c.d, c.batch, c.x, c.mass, I, Wg, c.g, c.f, c.grad, c.stream, c.gate))
-      return st;
-  } else if (I.any()) {
-    if (int32_t st = launch_overlay(c.d, c.batch, c.x, c.mass, I, c.g, c.f, c.grad, c.stream, c.gate)) return st;
-  }
-  if (Cn.any())
-    if (int32_t st = launch_cone_overlay(c.d, c.batch, c.x, Cn, c.g, c.jac, c.flags, c.stream, c.gate)) return st;
+  if (int32_t st = eval_overlays(c.d, c.batch, c.x, c.mass, V, c.g, c.jac, c.f, c.grad, c.flags, c.stream, c.gate))
+    return st;
   return c.norms && c.finish ? cpl_residual_norms(c.d, c.batch, c.g, c.norms, c.stream) : CPL_OK;
 }
 
@@ -4051,13 +3957,9 @@ constexpr int64_t LS_GF_MIN = 2048;  // batches from this size re-solve from the
 // global-factor form it would cost that kernel its second wave per SIMD (238 VGPRs + 24 AGPRs)
 bool ls_post_prologue(int64_t batch) { return batch < LS_GF_MIN; }
 
-// inst (optional): the solve's instance data, [batch] rows in the rows' current order — the search then
-// runs the per-instance instantiations
-// cones (optional): the solve's per-instance cones, likewise
-// weights (optional): the solve's per-instance cost weights, likewise
-int32_t ls_backtrack(const cpl_problem_desc* d, const LsBacktrackArgs& a, hipStream_t stream,
-                     const cpl_instance_data* inst, const cpl_instance_cones* cones,
-                     const cpl_instance_weights* weights) {
+// V: the solve's per-instance arrays, [batch] rows in the rows' current order — the search then runs the
+// per-instance instantiations
+int32_t ls_backtrack(const cpl_problem_desc* d, const LsBacktrackArgs& a, hipStream_t stream, const InstView& V) {
   if (a.batch <= 0) return CPL_OK;
   if (a.batch > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, "ls_backtrack: batch too large");
   KParams K;
@@ -4082,63 +3984,35 @@ int32_t ls_backtrack(const cpl_problem_desc* d, const LsBacktrackArgs& a, hipStr
     lds = sizeof(double) * ((((size_t)a.n + a.m + 2 * (size_t)a.nw + nL + 1) & ~(size_t)1) +
                             (gf ? 2 * 47 : KktWave<47, 30>::LDS));
   using KernT = void (*)(const KParams, const LsBacktrackArgs);
-#define CPL_LS_KERNELS(R, F, G, AG)                                                                            \
-  {cpl_ls_backtrack_kernel<CPL_ENV_NONE, R, F, G, AG>, cpl_ls_backtrack_kernel<CPL_ENV_GROUND, R, F, G, AG>,   \
-   cpl_ls_backtrack_kernel<CPL_ENV_SUPERQUADRIC, R, F, G, AG>, cpl_ls_backtrack_kernel<CPL_ENV_MIXED, R, F, G, AG>}
-  static const KernT table[6][4] = {CPL_LS_KERNELS(false, false, false, false), CPL_LS_KERNELS(true, false, false, false),
-                                    CPL_LS_KERNELS(false, true, false, false), CPL_LS_KERNELS(false, true, true, false),
-                                    CPL_LS_KERNELS(false, true, false, true), CPL_LS_KERNELS(false, true, true, true)};
+#define CPL_LS_ROW(X, R, F, G, AG)                                                                               \
+  {cpl_ls_backtrack_kernel<CPL_ENV_NONE | (X), R, F, G, AG>, cpl_ls_backtrack_kernel<CPL_ENV_GROUND | (X), R, F, G, AG>, \
+   cpl_ls_backtrack_kernel<CPL_ENV_SUPERQUADRIC | (X), R, F, G, AG>, cpl_ls_backtrack_kernel<CPL_ENV_MIXED | (X), R, F, G, AG>}
+#define CPL_LS_KERNELS(X)                                                                        \
+  {CPL_LS_ROW(X, false, false, false, false), CPL_LS_ROW(X, true, false, false, false),          \
+   CPL_LS_ROW(X, false, true, false, false),  CPL_LS_ROW(X, false, true, true, false),           \
+   CPL_LS_ROW(X, false, true, false, true),   CPL_LS_ROW(X, false, true, true, true)}
+  // [the per-instance bits added to ENVKI][the search's form][the environment kind]
+  static const KernT table[4][6][4] = {CPL_LS_KERNELS(0), CPL_LS_KERNELS(LS_INST), CPL_LS_KERNELS(LS_INST | LS_CONE),
+                                       CPL_LS_KERNELS(LS_INST | LS_CONE | LS_WGT)};
 #undef CPL_LS_KERNELS
-#define CPL_LS_KERNELS(R, F, G, AG)                                                \
-  {cpl_ls_backtrack_kernel<CPL_ENV_NONE | LS_INST, R, F, G, AG>,                   \
-   cpl_ls_backtrack_kernel<CPL_ENV_GROUND | LS_INST, R, F, G, AG>,                 \
-   cpl_ls_backtrack_kernel<CPL_ENV_SUPERQUADRIC | LS_INST, R, F, G, AG>,           \
-   cpl_ls_backtrack_kernel<CPL_ENV_MIXED | LS_INST, R, F, G, AG>}
-  static const KernT table_inst[6][4] = {
-      CPL_LS_KERNELS(false, false, false, false), CPL_LS_KERNELS(true, false, false, false),
-      CPL_LS_KERNELS(false, true, false, false),  CPL_LS_KERNELS(false, true, true, false),
-      CPL_LS_KERNELS(false, true, false, true),   CPL_LS_KERNELS(false, true, true, true)};
-#undef CPL_LS_KERNELS
-#define CPL_LS_KERNELS(R, F, G, AG)                                                \
-  {cpl_ls_backtrack_kernel<CPL_ENV_NONE | LS_INST | LS_CONE, R, F, G, AG>,         \
-   cpl_ls_backtrack_kernel<CPL_ENV_GROUND | LS_INST | LS_CONE, R, F, G, AG>,       \
-   cpl_ls_backtrack_kernel<CPL_ENV_SUPERQUADRIC | LS_INST | LS_CONE, R, F, G, AG>, \
-   cpl_ls_backtrack_kernel<CPL_ENV_MIXED | LS_INST | LS_CONE, R, F, G, AG>}
-  static const KernT table_cone[6][4] = {
-      CPL_LS_KERNELS(false, false, false, false), CPL_LS_KERNELS(true, false, false, false),
-      CPL_LS_KERNELS(false, true, false, false),  CPL_LS_KERNELS(false, true, true, false),
-      CPL_LS_KERNELS(false, true, false, true),   CPL_LS_KERNELS(false, true, true, true)};
-#undef CPL_LS_KERNELS
-#define CPL_LS_KERNELS(R, F, G, AG)                                                         \
-  {cpl_ls_backtrack_kernel<CPL_ENV_NONE | LS_INST | LS_CONE | LS_WGT, R, F, G, AG>,         \
-   cpl_ls_backtrack_kernel<CPL_ENV_GROUND | LS_INST | LS_CONE | LS_WGT, R, F, G, AG>,       \
-   cpl_ls_backtrack_kernel<CPL_ENV_SUPERQUADRIC | LS_INST | LS_CONE | LS_WGT, R, F, G, AG>, \
-   cpl_ls_backtrack_kernel<CPL_ENV_MIXED | LS_INST | LS_CONE | LS_WGT, R, F, G, AG>}
-  static const KernT table_wgt[6][4] = {
-      CPL_LS_KERNELS(false, false, false, false), CPL_LS_KERNELS(true, false, false, false),
-      CPL_LS_KERNELS(false, true, false, false),  CPL_LS_KERNELS(false, true, true, false),
-      CPL_LS_KERNELS(false, true, false, true),   CPL_LS_KERNELS(false, true, true, true)};
-#undef CPL_LS_KERNELS
-  const InstPtrs I = inst ? InstPtrs{inst->d_wrench, inst->d_com_ref, inst->d_p_ref, inst->d_F_ref} : InstPtrs{};
-  const ConePtrs Cn = cones ? ConePtrs{cones->d_mu, cones->d_F_thr} : ConePtrs{};
+#undef CPL_LS_ROW
   // (cones: one set of instantiations, which stage the instance data as well — a null array's values are
-  // the template's)
-  // (weights: one set again, which stages the instance data and the cones as well)
-  const WgtPtrs Wg = weights ? WgtPtrs{weights->d_W_com, weights->d_W_F, weights->d_W_p} : WgtPtrs{};
-  const bool with_wgt = Wg.any();
-  const bool with_cone = Cn.any() || with_wgt, with_inst = I.any() || with_cone;
+  // the template's; weights: one set again, which stages the instance data and the cones as well)
+  const bool with_wgt = V.has_wgt();
+  const bool with_cone = V.has_cones() || with_wgt, with_inst = V.has_inst() || with_cone;
   const int inst_off = (int)((lds / sizeof(double) + 1) & ~(size_t)1);  // the instance's values past the image
   if (with_inst)
     lds = sizeof(double) * ((size_t)inst_off + 9 + 6 * (size_t)K.N + (with_cone ? 1 + (size_t)K.N : 0) +
                             (with_wgt ? 1 + 2 * (size_t)K.N : 0));
   auto launch = [&](int row, LsBacktrackArgs args) {
     if (with_inst) {
-      args.inst_wrench = I.wrench; args.inst_com_ref = I.com_ref; args.inst_p_ref = I.p_ref; args.inst_F_ref = I.F_ref;
+      args.inst_wrench = V.wrench; args.inst_com_ref = V.com_ref; args.inst_p_ref = V.p_ref; args.inst_F_ref = V.F_ref;
       args.inst_off = inst_off;
-      args.cone_mu = Cn.mu; args.cone_F_thr = Cn.F_thr;
-      args.wgt_com = Wg.W_com; args.wgt_F = Wg.W_F; args.wgt_p = Wg.W_p;
+      args.cone_mu = V.mu; args.cone_F_thr = V.F_thr;
+      args.wgt_com = V.W_com; args.wgt_F = V.W_F; args.wgt_p = V.W_p;
     }
-    hipLaunchKernelGGL((with_wgt ? table_wgt : (with_cone ? table_cone : (with_inst ? table_inst : table)))[row][K.env_kind],
+    // (weights imply the cones' staging, cones the instance data's: the three flags count the set)
+    hipLaunchKernelGGL(table[(int)with_inst + (int)with_cone + (int)with_wgt][row][K.env_kind],
                        dim3((unsigned)a.batch), dim3(64), lds, stream, K, args);
   };
   const bool augr = first && a.aug_ws && a.aug_dc;
@@ -4181,34 +4055,6 @@ int32_t eval_batch_gated(const cpl_problem_desc* d, int64_t batch, const double*
   return launch_eval(c);
 }
 
-// (internal, the solve engine) the instance overlay alone: g[0:6], f, grad of every row from the
-// solver's own copies of the instance data; honours the gate byte
-int32_t eval_overlay(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
-                     const cpl_instance_data* inst, double* d_g, double* d_f, double* d_grad, void* stream,
-                     const uint8_t* gate) {
-  return launch_overlay(d, batch, d_x, d_mass, InstPtrs{inst->d_wrench, inst->d_com_ref, inst->d_p_ref, inst->d_F_ref},
-                        d_g, d_f, d_grad, (hipStream_t)stream, gate);
-}
-
-// (internal, the solve engine) the cone overlay alone: the cone rows of g and row 1's entries of the
-// Jacobian records of every row from the solver's own copies of the cones; honours the gate byte
-int32_t eval_cone_overlay(const cpl_problem_desc* d, int64_t batch, const double* d_x, const cpl_instance_cones* cones,
-                          double* d_g, double* d_jac, int32_t flags, void* stream, const uint8_t* gate) {
-  return launch_cone_overlay(d, batch, d_x, ConePtrs{cones->d_mu, cones->d_F_thr}, d_g, d_jac, flags,
-                             (hipStream_t)stream, gate);
-}
-
-// (internal, the solve engine) the weight overlay alone: f and grad of every row from the solver's own copies
-// of the weights (and, with inst, its references and g[0:6] from its wrench: then instead of eval_overlay);
-// honours the gate byte
-int32_t eval_weight_overlay(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
-                            const cpl_instance_data* inst, const cpl_instance_weights* weights, double* d_g,
-                            double* d_f, double* d_grad, void* stream, const uint8_t* gate) {
-  const InstPtrs I = inst ? InstPtrs{inst->d_wrench, inst->d_com_ref, inst->d_p_ref, inst->d_F_ref} : InstPtrs{};
-  return launch_weight_overlay(d, batch, d_x, d_mass, I, WgtPtrs{weights->d_W_com, weights->d_W_F, weights->d_W_p},
-                               d_g, d_f, d_grad, (hipStream_t)stream, gate);
-}
-
 }  // namespace cpl
 
 using namespace cpl;
@@ -4220,9 +4066,9 @@ size_t cpl_instance_data_sizeof(void) { return sizeof(cpl_instance_data); }
 int32_t cpl_eval_batch_inst(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
                             const uint8_t* d_env_tag, const cpl_instance_data* inst, double* d_g, double* d_jac,
                             double* d_f, double* d_grad, double* d_norms, int32_t flags, void* stream) {
-  const InstPtrs I = inst ? InstPtrs{inst->d_wrench, inst->d_com_ref, inst->d_p_ref, inst->d_F_ref} : InstPtrs{};
   return launch_eval_inst(
-      EvalCall{d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, d_norms, (hipStream_t)stream, flags}, I);
+      EvalCall{d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, d_norms, (hipStream_t)stream, flags},
+      InstView::of(inst, nullptr, nullptr));
 }
 
 size_t cpl_instance_cones_sizeof(void) { return sizeof(cpl_instance_cones); }
@@ -4231,10 +4077,9 @@ int32_t cpl_eval_batch_cones(const cpl_problem_desc* d, int64_t batch, const dou
                              const uint8_t* d_env_tag, const cpl_instance_data* inst, const cpl_instance_cones* cones,
                              double* d_g, double* d_jac, double* d_f, double* d_grad, double* d_norms, int32_t flags,
                              void* stream) {
-  const InstPtrs I = inst ? InstPtrs{inst->d_wrench, inst->d_com_ref, inst->d_p_ref, inst->d_F_ref} : InstPtrs{};
-  const ConePtrs Cn = cones ? ConePtrs{cones->d_mu, cones->d_F_thr} : ConePtrs{};
   return launch_eval_inst(
-      EvalCall{d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, d_norms, (hipStream_t)stream, flags}, I, Cn);
+      EvalCall{d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, d_norms, (hipStream_t)stream, flags},
+      InstView::of(inst, cones, nullptr));
 }
 
 size_t cpl_instance_weights_sizeof(void) { return sizeof(cpl_instance_weights); }
@@ -4243,12 +4088,9 @@ int32_t cpl_eval_batch_weights(const cpl_problem_desc* d, int64_t batch, const d
                                const uint8_t* d_env_tag, const cpl_instance_data* inst, const cpl_instance_cones* cones,
                                double* d_g, double* d_jac, double* d_f, double* d_grad, double* d_norms, int32_t flags,
                                void* stream, const cpl_instance_weights* weights) {
-  const InstPtrs I = inst ? InstPtrs{inst->d_wrench, inst->d_com_ref, inst->d_p_ref, inst->d_F_ref} : InstPtrs{};
-  const ConePtrs Cn = cones ? ConePtrs{cones->d_mu, cones->d_F_thr} : ConePtrs{};
-  const WgtPtrs Wg = weights ? WgtPtrs{weights->d_W_com, weights->d_W_F, weights->d_W_p} : WgtPtrs{};
   return launch_eval_inst(
-      EvalCall{d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, d_norms, (hipStream_t)stream, flags}, I, Cn,
-      Wg);
+      EvalCall{d, batch, d_x, d_mass, d_env_tag, d_g, d_jac, d_f, d_grad, d_norms, (hipStream_t)stream, flags},
+      InstView::of(inst, cones, weights));
 }
 
 int32_t cpl_eval_batch(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,
@@ -4274,7 +4116,7 @@ int32_t cpl_eval_lagrangian_grad(const cpl_problem_desc* d, int64_t batch, const
 static int32_t launch_hessian(const char* who, const cpl_problem_desc* d, int64_t batch, const double* d_x,
                               const double* d_y, const uint8_t* d_env_tag, const uint8_t* d_active,
                               const int32_t* d_free_idx, int32_t nf, double* d_H, void* stream,
-                              const double* d_mu = nullptr, const WgtPtrs& Wg = WgtPtrs{}) {
+                              const InstView& V = InstView{}) {  // (reads mu and the weights)
   const std::string w(who);
   KParams K;
   fill_params(d, K, d_x);
@@ -4284,10 +4126,11 @@ static int32_t launch_hessian(const char* who, const cpl_problem_desc* d, int64_
   if (d->env_kind == CPL_ENV_MIXED && !d_env_tag) return fail(CPL_ERR_INVALID_ARGUMENT, w + ": mixed needs tags");
   if (batch > 0x7fffffffLL) return fail(CPL_ERR_INVALID_ARGUMENT, w + ": batch too large");
   const bool sq = d->env_kind == CPL_ENV_SUPERQUADRIC || d->env_kind == CPL_ENV_MIXED;
-  if (Wg.any())
+  const double* d_mu = V.mu;
+  if (V.has_wgt())
     hipLaunchKernelGGL(sq ? cpl_lagrangian_hessian_wgt_kernel<true> : cpl_lagrangian_hessian_wgt_kernel<false>,
                        dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, K, batch, (int)nf, d_x, d_y, d_env_tag,
-                       d_active, d_free_idx, d_H, d_mu, Wg.W_com, Wg.W_F, Wg.W_p);
+                       d_active, d_free_idx, d_H, d_mu, V.W_com, V.W_F, V.W_p);
   else if (d_mu)
     hipLaunchKernelGGL(sq ? cpl_lagrangian_hessian_mu_kernel<true> : cpl_lagrangian_hessian_mu_kernel<false>,
                        dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, K, batch, (int)nf, d_x, d_y, d_env_tag,
@@ -4326,7 +4169,7 @@ int32_t cpl_lagrangian_hessian_cones(const cpl_problem_desc* d, int64_t batch, c
   int32_t st = validate_desc(d);
   if (st) return st;
   return launch_hessian("cpl_lagrangian_hessian_cones", d, batch, d_x, d_y, d_env_tag, d_active, d_free_idx, nf, d_H,
-                        stream, cones ? cones->d_mu : nullptr);
+                        stream, InstView::of(nullptr, cones, nullptr));
 }
 
 int32_t cpl_lagrangian_hessian_weights(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_y,
@@ -4335,9 +4178,9 @@ int32_t cpl_lagrangian_hessian_weights(const cpl_problem_desc* d, int64_t batch,
                                        const cpl_instance_weights* weights) {
   int32_t st = validate_desc(d);
   if (st) return st;
-  const WgtPtrs Wg = weights ? WgtPtrs{weights->d_W_com, weights->d_W_F, weights->d_W_p} : WgtPtrs{};
-  return launch_hessian(Wg.any() ? "cpl_lagrangian_hessian_weights" : "cpl_lagrangian_hessian_cones", d, batch, d_x, d_y,
-                        d_env_tag, d_active, d_free_idx, nf, d_H, stream, cones ? cones->d_mu : nullptr, Wg);
+  const InstView V = InstView::of(nullptr, cones, weights);
+  return launch_hessian(V.has_wgt() ? "cpl_lagrangian_hessian_weights" : "cpl_lagrangian_hessian_cones", d, batch, d_x,
+                        d_y, d_env_tag, d_active, d_free_idx, nf, d_H, stream, V);
 }
 
 int32_t cpl_eval_batch_ex(const cpl_problem_desc* d, int64_t batch, const double* d_x, const double* d_mass,

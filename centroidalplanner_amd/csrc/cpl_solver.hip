@@ -88,22 +88,14 @@ int32_t apply_scaling(cpl_solver* S, double* fo, double* grado, double* go, doub
 }
 // (scaled: the pipelined evaluation applies the factors in its tile image — one launch fewer per
 // evaluation; other paths evaluate, then k_apply_scaling)
-// (instance data: the unfused route — the template's evaluation without f / grad, the overlay, then
-// k_apply_scaling; the overlay needs no scaling arguments)
-// (per-instance cones: the same route with the cone overlay — the template's evaluation keeps f / grad
-// when there is no instance data —, so the scaling sees the overlaid cone rows and Jacobian entries)
-// (per-instance weights: the same route with the weight overlay, which computes f / grad — and, with
-// instance data, g[0:6] in the instance overlay's stead)
+// (per-instance arrays: the unfused route — the template's evaluation, without f / grad where an overlay
+// computes them; eval_overlays: the instance overlay, with the weights if any, then the cone overlay; then
+// k_apply_scaling, which so sees the overlaid values; the overlays need no scaling arguments)
 int32_t eval_fg(cpl_solver* S, const double* X, double* fo, double* go) {
-  if (S->has_inst || S->has_cones || S->has_wgt) {
-    CK(cpl_eval_batch(&S->desc, S->Bcur, X, S->mass, S->tag, go, nullptr, S->has_inst || S->has_wgt ? nullptr : fo,
-                      nullptr, S->stream));
-    if (S->has_wgt)
-      CK(eval_weight_overlay(&S->desc, S->Bcur, X, S->mass, S->has_inst ? &S->inst : nullptr, &S->wgt, go, fo, nullptr,
-                             S->stream, nullptr));
-    else if (S->has_inst)
-      CK(eval_overlay(&S->desc, S->Bcur, X, S->mass, &S->inst, go, fo, nullptr, S->stream, nullptr));
-    if (S->has_cones) CK(eval_cone_overlay(&S->desc, S->Bcur, X, &S->cones, go, nullptr, 0, S->stream, nullptr));
+  if (S->iv.any()) {
+    CK(cpl_eval_batch(&S->desc, S->Bcur, X, S->mass, S->tag, go, nullptr, S->iv.overlays_cost() ? nullptr : fo, nullptr,
+                      S->stream));
+    CK(eval_overlays(&S->desc, S->Bcur, X, S->mass, S->iv, go, nullptr, fo, nullptr, 0, S->stream, nullptr));
     return apply_scaling(S, fo, nullptr, go, nullptr);
   }
   if (S->scaled && S->sc_fused) {
@@ -120,17 +112,11 @@ int32_t eval_fg(cpl_solver* S, const double* X, double* fo, double* go) {
 // an evaluation whose outputs nobody reads when the byte is 0)
 int32_t eval_full(cpl_solver* S, const double* X, double* fo, double* grado, double* go, double* jo,
                   const uint8_t* gate = nullptr) {
-  if (S->has_inst || S->has_cones || S->has_wgt) {
-    const bool over = S->has_inst || S->has_wgt;  // (an overlay computes f / grad)
+  if (S->iv.any()) {
+    const bool over = S->iv.overlays_cost();
     CK(eval_batch_gated(&S->desc, S->Bcur, X, S->mass, S->tag, go, jo, over ? nullptr : fo, over ? nullptr : grado,
                         CPL_EVAL_JAC_FOLDED, S->stream, gate));
-    if (S->has_wgt)
-      CK(eval_weight_overlay(&S->desc, S->Bcur, X, S->mass, S->has_inst ? &S->inst : nullptr, &S->wgt, go, fo, grado,
-                             S->stream, gate));
-    else if (S->has_inst)
-      CK(eval_overlay(&S->desc, S->Bcur, X, S->mass, &S->inst, go, fo, grado, S->stream, gate));
-    if (S->has_cones)
-      CK(eval_cone_overlay(&S->desc, S->Bcur, X, &S->cones, go, jo, CPL_EVAL_JAC_FOLDED, S->stream, gate));
+    CK(eval_overlays(&S->desc, S->Bcur, X, S->mass, S->iv, go, jo, fo, grado, CPL_EVAL_JAC_FOLDED, S->stream, gate));
     return apply_scaling(S, fo, grado, go, jo);
   }
   if (S->scaled && S->sc_fused) {
@@ -193,14 +179,15 @@ int32_t hessian_into(cpl_solver* S, const cpl_problem_desc* d, const uint8_t* ma
     return CPL_OK;
   };
   if (S->analytic_H) {
-    if (S->has_wgt) {
+    const cpl_instance_cones cones = S->iv.cones();
+    if (S->has_wgt()) {
       // (either mode: the kernel of every environment kind with the weights — and mu, if any — per row; the
       // restoration phase's Hessian of y^T g alone (desc_R: zero weights) reads no instance's weight)
-      const cpl_instance_weights none = {nullptr, nullptr, nullptr};
-      CK(cpl_lagrangian_hessian_weights(d, B, S->X, yh, S->tag, mask, S->free32, nf, S->has_cones ? &S->cones : nullptr,
-                                        S->H, st, d == &S->desc_R ? &none : &S->wgt));
-    } else if (S->has_cones && S->cones.d_mu)  // (either mode: the kernel of every environment kind with mu per row)
-      CK(cpl_lagrangian_hessian_cones(d, B, S->X, yh, S->tag, mask, S->free32, nf, &S->cones, S->H, st));
+      const cpl_instance_weights none = {nullptr, nullptr, nullptr}, wgt = S->iv.weights();
+      CK(cpl_lagrangian_hessian_weights(d, B, S->X, yh, S->tag, mask, S->free32, nf, &cones, S->H, st,
+                                        d == &S->desc_R ? &none : &wgt));
+    } else if (cones.d_mu)  // (either mode: the kernel of every environment kind with mu per row)
+      CK(cpl_lagrangian_hessian_cones(d, B, S->X, yh, S->tag, mask, S->free32, nf, &cones, S->H, st));
     else if (o.hessian == CPL_HESSIAN_ANALYTIC)  // every environment kind (Ground / none: the same kernel)
       CK(cpl_lagrangian_hessian_ex(d, B, S->X, yh, S->tag, mask, S->free32, nf, S->H, st));
     else
@@ -608,8 +595,7 @@ int32_t step_phase(cpl_solver* S, int phase, const StepMode mode = {}) {
       } else {  // the remaining trials of every instance still searching, in one launch
         HK(hipMemsetAsync(S->d_any, 0, 2, st), "hipMemsetAsync flags");
       }
-      return ls_backtrack(&S->desc, la, st, S->has_inst ? &S->inst : nullptr, S->has_cones ? &S->cones : nullptr,
-                          S->has_wgt ? &S->wgt : nullptr);
+      return ls_backtrack(&S->desc, la, st, S->iv);
     }
     case P_SOFT: {
       const SoftStepArgs soft = soft_step_args(S);
@@ -700,8 +686,7 @@ int32_t step_phase(cpl_solver* S, int phase, const StepMode mode = {}) {
         la.rho = RHO_R;
         la.pR = S->pR; la.nR = S->nR; la.dp = S->dp; la.dn = S->dn; la.wR = S->wR;
         la.st_p = S->st_p; la.st_n = S->st_n;
-        CK(ls_backtrack(&S->desc, la, st, S->has_inst ? &S->inst : nullptr, S->has_cones ? &S->cones : nullptr,
-                        S->has_wgt ? &S->wgt : nullptr));
+        CK(ls_backtrack(&S->desc, la, st, S->iv));
       }
       return step_phase(S, P_RACCEPT);
     }
@@ -736,20 +721,21 @@ int32_t step_phase(cpl_solver* S, int phase, const StepMode mode = {}) {
   }
 }
 
+// the graph key's bits of the per-instance arrays given: the four instance arrays at 8..64, the two cone arrays
+// at 256 and 512, the three weight arrays at 1024..4096 (128 is the per-instance bounds' bit)
+int view_bits(const InstView& v) {
+  return (v.wrench ? 8 : 0) | (v.com_ref ? 16 : 0) | (v.p_ref ? 32 : 0) | (v.F_ref ? 64 : 0) | (v.mu ? 256 : 0) |
+         (v.F_thr ? 512 : 0) | (v.W_com ? 1024 : 0) | (v.W_F ? 2048 : 0) | (v.W_p ? 4096 : 0);
+}
+
 // the graph of one phase at the current batch size (captured once per (size, inputs, phase), then
 // replayed); without graphs the phase is launched directly
 int32_t run_phase(cpl_solver* S, int phase) {
   if (!S->opt.use_graph) return step_phase(S, phase);
   // (a graph holds the pointers its launches were given: one bit per input that may be absent — the
-  // masses, the tags and each of the four instance arrays, whose slot is null when the caller gave none —
-  // and one for per-instance bounds, whose launches carry the solver's rows and their stride)
-  const int inst_bits = (S->inst.d_wrench ? 1 : 0) | (S->inst.d_com_ref ? 2 : 0) | (S->inst.d_p_ref ? 4 : 0) |
-                        (S->inst.d_F_ref ? 8 : 0);
-  // (and one per cone array)
-  const int cone_bits = (S->cones.d_mu ? 1 : 0) | (S->cones.d_F_thr ? 2 : 0);
-  // (and one per weight array)
-  const int wgt_bits = (S->wgt.d_W_com ? 1 : 0) | (S->wgt.d_W_F ? 2 : 0) | (S->wgt.d_W_p ? 4 : 0);
-  const int64_t key = ((S->Bcur * 8192 + wgt_bits * 1024 + cone_bits * 256 + (S->has_box ? 128 : 0) + inst_bits * 8 + (S->scaled ? 4 : 0) +
+  // masses, the tags and each of the view's nine arrays, whose slot is null when the caller gave none
+  // (view_bits) — and one for per-instance bounds, whose launches carry the solver's rows and their stride)
+  const int64_t key = ((S->Bcur * 8192 + view_bits(S->iv) + (S->has_box ? 128 : 0) + (S->scaled ? 4 : 0) +
                         (S->mass ? 2 : 0) + (S->tag ? 1 : 0)) * 16) + phase;
   auto it = S->graphs.find(key);
   if (it == S->graphs.end()) {
@@ -839,8 +825,8 @@ int32_t compact(cpl_solver* S, int64_t count, int64_t Bn) {
   for (const BufRec& r : S->bufs) {
     const bool moved = r.when == ALWAYS || (r.when == IF_SCALED && S->scaled) ||
                        (r.when == IF_MASS && S->mass) || (r.when == IF_TAG && S->tag) ||
-                       (r.when == IF_INST && S->has_inst) || (r.when == IF_BOX && S->has_box) ||
-                       (r.when == IF_CONE && S->has_cones) || (r.when == IF_WGT && S->has_wgt);
+                       (r.when == IF_INST && S->has_inst()) || (r.when == IF_BOX && S->has_box) ||
+                       (r.when == IF_CONE && S->has_cones()) || (r.when == IF_WGT && S->has_wgt());
     if (!moved || r.width <= 0) continue;
     const dim3 grid(blocks_elems(count * r.width)), blk(256);
     if (r.elem == 8)
@@ -868,9 +854,8 @@ int32_t compact(cpl_solver* S, int64_t count, int64_t Bn) {
 // ---- a solve in three parts (cpl_solver_solve_warm), all on the solver's stream --------------------
 // The start: the solver's own copies of the inputs, the resets, Xbase, IPOPT's NLP scaling, the warm
 // flags, the starting iterate (cold, or per instance warm), the least-squares y, the quasi-Newton model.
-// inst: null without instance data; warm: null for a cold solve.
-int32_t solve_start(cpl_solver* S, const double* d_x0, const double* d_mass, const uint8_t* d_env_tag,
-                    const cpl_instance_data* inst, const cpl_instance_cones* cones, const cpl_instance_weights* weights,
+// V: the caller's per-instance arrays; warm: null for a cold solve.
+int32_t solve_start(cpl_solver* S, const double* d_x0, const double* d_mass, const uint8_t* d_env_tag, const InstView& V,
                     int32_t fixed_from_x0, const cpl_warm_start* warm, int64_t* evals) {
   const int64_t B = S->B;
   const int n = S->n, m = S->m, nf = S->nf, nw = S->nw;
@@ -883,49 +868,24 @@ int32_t solve_start(cpl_solver* S, const double* d_x0, const double* d_mass, con
   S->tag = d_env_tag ? S->tag_c : nullptr;
   if (d_mass) HK(hipMemcpyAsync(S->mass_c, d_mass, 8 * (size_t)B, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync mass");
   if (d_env_tag) HK(hipMemcpyAsync(S->tag_c, d_env_tag, (size_t)B, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync tag");
-  // ... and of the instance data, array by array (an array not given stays the template's value)
-  S->has_inst = inst != nullptr;
-  S->inst = cpl_instance_data{nullptr, nullptr, nullptr, nullptr};
-  if (inst) {
-    const size_t N3 = 3 * (size_t)S->desc.n_contacts;
-    const struct { const double* src; double* dst; const double** slot; size_t width; } arrays[] = {
-        {inst->d_wrench, S->inst_w, &S->inst.d_wrench, 6}, {inst->d_com_ref, S->inst_c, &S->inst.d_com_ref, 3},
-        {inst->d_p_ref, S->inst_p, &S->inst.d_p_ref, N3}, {inst->d_F_ref, S->inst_F, &S->inst.d_F_ref, N3}};
-    for (const auto& a : arrays) {
-      if (!a.src) continue;
-      HK(hipMemcpyAsync(a.dst, a.src, 8 * (size_t)B * a.width, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync instance data");
-      *a.slot = a.dst;
-    }
-  }
-  // ... and of the cones (validated before: cones_check)
-  S->has_cones = cones != nullptr;
-  S->cones = cpl_instance_cones{nullptr, nullptr};
-  if (cones && cones->d_mu) {
-    HK(hipMemcpyAsync(S->cone_mu, cones->d_mu, 8 * (size_t)B, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync cones mu");
-    S->cones.d_mu = S->cone_mu;
-  }
-  if (cones && cones->d_F_thr) {
-    HK(hipMemcpyAsync(S->cone_F, cones->d_F_thr, 8 * (size_t)B * S->desc.n_contacts, hipMemcpyDeviceToDevice, st),
-       "hipMemcpyAsync cones F_thr");
-    S->cones.d_F_thr = S->cone_F;
-  }
-  // ... and of the weights (validated before: weights_check)
-  S->has_wgt = weights != nullptr;
-  S->wgt = cpl_instance_weights{nullptr, nullptr, nullptr};
-  if (weights && weights->d_W_com) {
-    HK(hipMemcpyAsync(S->wgt_com, weights->d_W_com, 8 * (size_t)B, hipMemcpyDeviceToDevice, st),
-       "hipMemcpyAsync weights W_com");
-    S->wgt.d_W_com = S->wgt_com;
-  }
-  if (weights && weights->d_W_F) {
-    HK(hipMemcpyAsync(S->wgt_F, weights->d_W_F, 8 * (size_t)B * S->desc.n_contacts, hipMemcpyDeviceToDevice, st),
-       "hipMemcpyAsync weights W_F");
-    S->wgt.d_W_F = S->wgt_F;
-  }
-  if (weights && weights->d_W_p) {
-    HK(hipMemcpyAsync(S->wgt_p, weights->d_W_p, 8 * (size_t)B * S->desc.n_contacts, hipMemcpyDeviceToDevice, st),
-       "hipMemcpyAsync weights W_p");
-    S->wgt.d_W_p = S->wgt_p;
+  // ... and of the per-instance arrays, array by array (an array not given stays the template's value; the
+  // cones and the weights were validated before: cones_check, weights_check)
+  const size_t N = (size_t)S->desc.n_contacts;
+  S->iv = InstView{};
+  const struct { const double* src; double* dst; const double** slot; size_t width; const char* what; } arrays[] = {
+      {V.wrench, S->inst_w, &S->iv.wrench, 6, "hipMemcpyAsync instance data"},
+      {V.com_ref, S->inst_c, &S->iv.com_ref, 3, "hipMemcpyAsync instance data"},
+      {V.p_ref, S->inst_p, &S->iv.p_ref, 3 * N, "hipMemcpyAsync instance data"},
+      {V.F_ref, S->inst_F, &S->iv.F_ref, 3 * N, "hipMemcpyAsync instance data"},
+      {V.mu, S->cone_mu, &S->iv.mu, 1, "hipMemcpyAsync cones mu"},
+      {V.F_thr, S->cone_F, &S->iv.F_thr, N, "hipMemcpyAsync cones F_thr"},
+      {V.W_com, S->wgt_com, &S->iv.W_com, 1, "hipMemcpyAsync weights W_com"},
+      {V.W_F, S->wgt_F, &S->iv.W_F, N, "hipMemcpyAsync weights W_F"},
+      {V.W_p, S->wgt_p, &S->iv.W_p, N, "hipMemcpyAsync weights W_p"}};
+  for (const auto& a : arrays) {
+    if (!a.src) continue;
+    HK(hipMemcpyAsync(a.dst, a.src, 8 * (size_t)B * a.width, hipMemcpyDeviceToDevice, st), a.what);
+    *a.slot = a.dst;
   }
   hipLaunchKernelGGL(k_iota, dim3(blocks_elems(B)), dim3(256), 0, st, B, S->orig);
   LAUNCHED("k_iota");
@@ -1163,10 +1123,9 @@ int32_t solve_iterate(cpl_solver* S, int* it_out, int64_t* evals) {
 
 // The finish: the final convergence test, the results of every row still in the batch to its instance's
 // place, IPOPT's honor_original_bounds projection with its re-evaluation, the caller's outputs.
-int32_t solve_finish(cpl_solver* S, const double* d_mass, const uint8_t* d_env_tag, const cpl_instance_data* inst,
-                     const cpl_instance_cones* cones, const cpl_instance_weights* weights, int32_t fixed_from_x0,
-                     double* d_x, double* d_y, int32_t* d_status, int32_t* d_iters, double* d_obj,
-                     double* d_primal_inf, double* d_dual_inf, int64_t* evals) {
+int32_t solve_finish(cpl_solver* S, const double* d_mass, const uint8_t* d_env_tag, const InstView& V,
+                     int32_t fixed_from_x0, double* d_x, double* d_y, int32_t* d_status, int32_t* d_iters,
+                     double* d_obj, double* d_primal_inf, double* d_dual_inf, int64_t* evals) {
   const int64_t B = S->B;
   const int n = S->n, m = S->m, nf = S->nf, nw = S->nw;
   hipStream_t st = S->stream;
@@ -1201,18 +1160,13 @@ int32_t solve_finish(cpl_solver* S, const double* d_mass, const uint8_t* d_env_t
                      S->freepos, S->fX, S->fw, S->has_box ? S->box_xl : S->xl, S->has_box ? S->box_xu : S->xu,
                      (int64_t)(S->has_box ? n : 0), Xf);
   LAUNCHED("k_unpack (final)");
-  // (the full batch in the instances' own order: the caller's masses, tags, instance data and cones)
-  if (weights)
-    CK(cpl_eval_batch_weights(&S->desc, B, Xf, d_mass, d_env_tag, inst, cones, S->fin_g, nullptr,
-                              d_obj ? d_obj : S->fin_f, nullptr, nullptr, 0, st, weights));
-  else if (cones)
-    CK(cpl_eval_batch_cones(&S->desc, B, Xf, d_mass, d_env_tag, inst, cones, S->fin_g, nullptr, d_obj ? d_obj : S->fin_f,
-                            nullptr, nullptr, 0, st));
-  else if (inst)
-    CK(cpl_eval_batch_inst(&S->desc, B, Xf, d_mass, d_env_tag, inst, S->fin_g, nullptr, d_obj ? d_obj : S->fin_f, nullptr,
-                           nullptr, 0, st));
-  else
-    CK(cpl_eval_batch(&S->desc, B, Xf, d_mass, d_env_tag, S->fin_g, nullptr, d_obj ? d_obj : S->fin_f, nullptr, st));
+  // (the full batch in the instances' own order: the caller's masses, tags and per-instance arrays; an empty
+  // record is the template's evaluation)
+  const cpl_instance_data inst = V.data();
+  const cpl_instance_cones cones = V.cones();
+  const cpl_instance_weights weights = V.weights();
+  CK(cpl_eval_batch_weights(&S->desc, B, Xf, d_mass, d_env_tag, &inst, &cones, S->fin_g, nullptr, d_obj ? d_obj : S->fin_f,
+                            nullptr, nullptr, 0, st, &weights));
   ++*evals;
   hipLaunchKernelGGL(k_final, dim3(blocks_for(B)), dim3(256), 0, st, B, m, S->fin_g, S->gl, S->gu, S->fstatus,
                      S->fiters, d_primal_inf, d_status, d_iters);
@@ -1730,20 +1684,18 @@ int32_t cpl_solver_solve_weights(cpl_solver* S, const double* d_x0, const double
   }
   if (S->desc.env_kind == CPL_ENV_MIXED && !d_env_tag)
     return fail(CPL_ERR_INVALID_ARGUMENT, "cpl_solver_solve: mixed batches need the env tags");
-  const bool has_inst = inst && (inst->d_wrench || inst->d_com_ref || inst->d_p_ref || inst->d_F_ref);
-  if (has_inst && S->fd)  // (the 2 nf perturbed points of every instance would need the arrays replicated)
+  const InstView V = InstView::of(inst, cones, weights);
+  if (V.has_inst() && S->fd)  // (the 2 nf perturbed points of every instance would need the arrays replicated)
     return fail(CPL_ERR_UNSUPPORTED,
                 "cpl_solver_solve_inst: instance data needs a Hessian that is not central differences: create the "
                 "solver with CPL_HESSIAN_ANALYTIC or CPL_HESSIAN_LIMITED_MEMORY");
   // per-instance cones: either array, or none (then this is cpl_solver_solve_box)
-  const bool has_cones = cones && (cones->d_mu || cones->d_F_thr);
-  if (has_cones && S->fd)  // (the same rule: the perturbed points would need the arrays replicated)
+  if (V.has_cones() && S->fd)  // (the same rule: the perturbed points would need the arrays replicated)
     return fail(CPL_ERR_UNSUPPORTED,
                 "cpl_solver_solve_cones: per-instance cones need a Hessian that is not central differences: create the "
                 "solver with CPL_HESSIAN_ANALYTIC or CPL_HESSIAN_LIMITED_MEMORY");
   // per-instance weights: any array, or none (then this is cpl_solver_solve_cones)
-  const bool has_wgt = weights && (weights->d_W_com || weights->d_W_F || weights->d_W_p);
-  if (has_wgt && S->fd)  // (the same rule)
+  if (V.has_wgt() && S->fd)  // (the same rule)
     return fail(CPL_ERR_UNSUPPORTED,
                 "cpl_solver_solve_weights: per-instance weights need a Hessian that is not central differences: create "
                 "the solver with CPL_HESSIAN_ANALYTIC or CPL_HESSIAN_LIMITED_MEMORY");
@@ -1758,20 +1710,17 @@ int32_t cpl_solver_solve_weights(cpl_solver* S, const double* d_x0, const double
   }
   // order after the caller's stream (its inputs), then run on the solver's own stream
   HK(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize (caller stream)");
-  if (!has_inst) inst = nullptr;
-  if (!has_cones) cones = nullptr;
-  if (!has_wgt) weights = nullptr;
   S->has_box = false;
-  if (cones) CK(cones_check(S, cones));  // (validated on the device: nothing else is launched when it refuses)
-  if (weights) CK(weights_check(S, weights));  // (likewise)
+  if (V.has_cones()) CK(cones_check(S, cones));  // (validated on the device: nothing else is launched when it refuses)
+  if (V.has_wgt()) CK(weights_check(S, weights));  // (likewise)
   if (has_box) CK(box_prepare(S, box));  // (likewise)
   S->has_box = has_box;
   int it = 0;
   int64_t evals = 0;
-  CK(solve_start(S, d_x0, d_mass, d_env_tag, inst, cones, weights, fixed_from_x0, is_warm ? warm : nullptr, &evals));
+  CK(solve_start(S, d_x0, d_mass, d_env_tag, V, fixed_from_x0, is_warm ? warm : nullptr, &evals));
   CK(solve_iterate(S, &it, &evals));
-  CK(solve_finish(S, d_mass, d_env_tag, inst, cones, weights, fixed_from_x0, d_x, d_y, d_status, d_iters, d_obj,
-                  d_primal_inf, d_dual_inf, &evals));
+  CK(solve_finish(S, d_mass, d_env_tag, V, fixed_from_x0, d_x, d_y, d_status, d_iters, d_obj, d_primal_inf, d_dual_inf,
+                  &evals));
   if (iterations_run) *iterations_run = it;
   if (evaluations) *evaluations = evals;
   return CPL_OK;

@@ -128,25 +128,17 @@ struct cpl_solver {
   int32_t *orig, *pos, *d_count, *h_count = nullptr;
   double *mass_c, *fw, *fy, *fX, *fdinf;
   uint8_t* tag_c;
-  // this solve's instance data (cpl_solver_solve_inst): the solver's own copies, by batch row (moved by
-  // the compaction with their rows); inst's pointers name them, null where the caller gave no array
-  // (the kernels then read the template's value)
-  double *inst_w, *inst_c, *inst_p, *inst_F;
-  cpl_instance_data inst = {nullptr, nullptr, nullptr, nullptr};
-  bool has_inst = false;
-  // this solve's per-instance cones (cpl_solver_solve_cones): the solver's own copies, mu [B] and F_thr
-  // [B, N] by batch row (moved by the compaction with their rows); cones' pointers name them, null where the
-  // caller gave no array; cone_fault: the validation's word
-  double *cone_mu, *cone_F;
-  cpl_instance_cones cones = {nullptr, nullptr};
-  bool has_cones = false;
+  // this solve's per-instance arrays (cpl_solver_solve_inst / _cones / _weights): the solver's own copies by
+  // batch row (moved by the compaction with their rows) — wrench [B, 6], com_ref [B, 3], p_ref and F_ref
+  // [B, 3N]; mu [B], F_thr [B, N]; W_com [B], W_F and W_p [B, N] — and the one view over them: iv's pointers
+  // name the copies, null where the caller gave no array (the kernels then read the template's value).
+  // cone_fault: the validation's word (cones_check and weights_check share it: they run one after the other)
+  double *inst_w, *inst_c, *inst_p, *inst_F, *cone_mu, *cone_F, *wgt_com, *wgt_F, *wgt_p;
+  cpl::InstView iv;
+  bool has_inst() const { return iv.has_inst(); }
+  bool has_cones() const { return iv.has_cones(); }
+  bool has_wgt() const { return iv.has_wgt(); }
   unsigned long long* cone_fault;
-  // this solve's per-instance cost weights (cpl_solver_solve_weights): the solver's own copies, W_com [B], W_F
-  // and W_p [B, N] by batch row (moved by the compaction with their rows); wgt's pointers name them, null
-  // where the caller gave no array (the validation shares cone_fault: the checks run one after the other)
-  double *wgt_com, *wgt_F, *wgt_p;
-  cpl_instance_weights wgt = {nullptr, nullptr, nullptr};
-  bool has_wgt = false;
   // this solve's per-instance bounds (cpl_solver_solve_box; k_box_prepare writes them): the relaxed w-order
   // rows [B, nw] by batch row (moved by the compaction; bounds_of() hands them to every kernel with stride
   // nw), the unrelaxed x-order rows [B, n] by original instance (the final projection), the validation's

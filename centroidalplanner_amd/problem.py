@@ -105,47 +105,64 @@ class MixedEnvironment(EnvironmentClass):
 # --------------------------------------------------------------------------------------------
 # CplProblem  (src/CplProblem.cpp)
 # --------------------------------------------------------------------------------------------
-class InstanceData:
+class _InstanceArrays:
+    """What InstanceData, InstanceCones and InstanceWeights share: named float64 CUDA tensors with one row per
+    instance, any of them None (the template's value then), behind one C record of device pointers.  A subclass
+    names its FIELDS (in the record's order), their shapes and the record's ctypes type."""
+
+    FIELDS = ()
+    C_STRUCT = None
+
+    @staticmethod
+    def _shapes(batch: int, n_contacts: int) -> Dict[str, tuple]:
+        raise NotImplementedError
+
+    def __bool__(self):
+        return any(getattr(self, k) is not None for k in self.FIELDS)
+
+    def validated(self, batch: int, n_contacts: int, device):
+        """The fields checked against the batch (ValueError naming the field) and made contiguous."""
+        import torch
+
+        name, shapes = type(self).__name__, self._shapes(batch, n_contacts)
+        out = type(self)()
+        for k in self.FIELDS:
+            t = getattr(self, k)
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or t.dtype != torch.float64:
+                raise ValueError(f"{name}.{k} must be a float64 tensor")
+            if tuple(t.shape) != shapes[k]:
+                raise ValueError(f"{name}.{k} must have shape {shapes[k]}, not {tuple(t.shape)}")
+            if not t.is_cuda or t.device != device:
+                raise ValueError(f"{name}.{k} must be a CUDA tensor on the batch's device {device}, not {t.device}")
+            setattr(out, k, t.contiguous())
+        return out
+
+    def c_struct(self):
+        """The C record over these tensors (which must stay alive while it is in use)."""
+        return self.C_STRUCT(*(None if getattr(self, k) is None else getattr(self, k).data_ptr() for k in self.FIELDS))
+
+
+class InstanceData(_InstanceArrays):
     """Per-instance problem data of a batch (cpl_instance_data): what a user of the reference changes
     from one problem to the next — SetManipulationWrench, SetCoMRef, SetPosRef, SetForceRef — as
     float64 CUDA tensors wrench [B, 6], com_ref [B, 3], p_ref [B, N, 3], F_ref [B, N, 3] (contacts in
     contact_names order).  A field left None takes the template's value for every instance."""
 
     FIELDS = ("wrench", "com_ref", "p_ref", "F_ref")
+    C_STRUCT = _abi.InstanceDataC
 
     def __init__(self, wrench=None, com_ref=None, p_ref=None, F_ref=None):
         self.wrench, self.com_ref, self.p_ref, self.F_ref = wrench, com_ref, p_ref, F_ref
 
-    def __bool__(self):
-        return any(getattr(self, k) is not None for k in self.FIELDS)
-
-    def validated(self, batch: int, n_contacts: int, device) -> "InstanceData":
-        """The fields checked against the batch (ValueError naming the field) and made contiguous."""
-        import torch
-
-        shapes = {"wrench": (batch, 6), "com_ref": (batch, 3), "p_ref": (batch, n_contacts, 3),
-                  "F_ref": (batch, n_contacts, 3)}
-        out = InstanceData()
-        for k in self.FIELDS:
-            t = getattr(self, k)
-            if t is None:
-                continue
-            if not torch.is_tensor(t) or t.dtype != torch.float64:
-                raise ValueError(f"InstanceData.{k} must be a float64 tensor")
-            if tuple(t.shape) != shapes[k]:
-                raise ValueError(f"InstanceData.{k} must have shape {shapes[k]}, not {tuple(t.shape)}")
-            if not t.is_cuda or t.device != device:
-                raise ValueError(f"InstanceData.{k} must be a CUDA tensor on the batch's device {device}, not {t.device}")
-            setattr(out, k, t.contiguous())
-        return out
-
-    def c_struct(self) -> "_abi.InstanceDataC":
-        """The C record over these tensors (which must stay alive while it is in use)."""
-        return _abi.InstanceDataC(*(None if getattr(self, k) is None else getattr(self, k).data_ptr()
-                                    for k in self.FIELDS))
+    @staticmethod
+    def _shapes(batch, n_contacts):
+        return {"wrench": (batch, 6), "com_ref": (batch, 3), "p_ref": (batch, n_contacts, 3),
+                "F_ref": (batch, n_contacts, 3)}
 
 
-class InstanceCones:
+class InstanceCones(_InstanceArrays):
     """Per-instance friction cones of a batch (cpl_instance_cones): the batched form of SetMu (one friction
     coefficient per instance, for all its contacts) and SetForceThreshold, as float64 CUDA tensors mu [B] and
     F_thr [B, N] (contacts in contact_names order).  A field left None takes the template's value for every
@@ -154,39 +171,17 @@ class InstanceCones:
     in its F_thr column."""
 
     FIELDS = ("mu", "F_thr")
+    C_STRUCT = _abi.InstanceConesC
 
     def __init__(self, mu=None, F_thr=None):
         self.mu, self.F_thr = mu, F_thr
 
-    def __bool__(self):
-        return any(getattr(self, k) is not None for k in self.FIELDS)
-
-    def validated(self, batch: int, n_contacts: int, device) -> "InstanceCones":
-        """The fields checked against the batch (ValueError naming the field) and made contiguous."""
-        import torch
-
-        shapes = {"mu": (batch,), "F_thr": (batch, n_contacts)}
-        out = InstanceCones()
-        for k in self.FIELDS:
-            t = getattr(self, k)
-            if t is None:
-                continue
-            if not torch.is_tensor(t) or t.dtype != torch.float64:
-                raise ValueError(f"InstanceCones.{k} must be a float64 tensor")
-            if tuple(t.shape) != shapes[k]:
-                raise ValueError(f"InstanceCones.{k} must have shape {shapes[k]}, not {tuple(t.shape)}")
-            if not t.is_cuda or t.device != device:
-                raise ValueError(f"InstanceCones.{k} must be a CUDA tensor on the batch's device {device}, not {t.device}")
-            setattr(out, k, t.contiguous())
-        return out
-
-    def c_struct(self) -> "_abi.InstanceConesC":
-        """The C record over these tensors (which must stay alive while it is in use)."""
-        return _abi.InstanceConesC(*(None if getattr(self, k) is None else getattr(self, k).data_ptr()
-                                     for k in self.FIELDS))
+    @staticmethod
+    def _shapes(batch, n_contacts):
+        return {"mu": (batch,), "F_thr": (batch, n_contacts)}
 
 
-class InstanceWeights:
+class InstanceWeights(_InstanceArrays):
     """Per-instance cost weights of a batch (cpl_instance_weights): the batched form of SetCoMWeight,
     SetForceWeight / SetContactForceWeight and SetPosWeight / SetContactPosWeight, as float64 CUDA tensors
     com [B], force [B, N] and pos [B, N] (contacts in contact_names order).  A field left None takes the
@@ -194,36 +189,14 @@ class InstanceWeights:
     not."""
 
     FIELDS = ("com", "force", "pos")
+    C_STRUCT = _abi.InstanceWeightsC
 
     def __init__(self, com=None, force=None, pos=None):
         self.com, self.force, self.pos = com, force, pos
 
-    def __bool__(self):
-        return any(getattr(self, k) is not None for k in self.FIELDS)
-
-    def validated(self, batch: int, n_contacts: int, device) -> "InstanceWeights":
-        """The fields checked against the batch (ValueError naming the field) and made contiguous."""
-        import torch
-
-        shapes = {"com": (batch,), "force": (batch, n_contacts), "pos": (batch, n_contacts)}
-        out = InstanceWeights()
-        for k in self.FIELDS:
-            t = getattr(self, k)
-            if t is None:
-                continue
-            if not torch.is_tensor(t) or t.dtype != torch.float64:
-                raise ValueError(f"InstanceWeights.{k} must be a float64 tensor")
-            if tuple(t.shape) != shapes[k]:
-                raise ValueError(f"InstanceWeights.{k} must have shape {shapes[k]}, not {tuple(t.shape)}")
-            if not t.is_cuda or t.device != device:
-                raise ValueError(f"InstanceWeights.{k} must be a CUDA tensor on the batch's device {device}, not {t.device}")
-            setattr(out, k, t.contiguous())
-        return out
-
-    def c_struct(self) -> "_abi.InstanceWeightsC":
-        """The C record over these tensors (which must stay alive while it is in use)."""
-        return _abi.InstanceWeightsC(*(None if getattr(self, k) is None else getattr(self, k).data_ptr()
-                                       for k in self.FIELDS))
+    @staticmethod
+    def _shapes(batch, n_contacts):
+        return {"com": (batch,), "force": (batch, n_contacts), "pos": (batch, n_contacts)}
 
 
 class InstanceBounds:
@@ -618,16 +591,17 @@ class CplProblem:
         ``stream`` (default: torch's current stream).
         jac_folded: values-only Jacobian records (structural constants skipped, see jac_fold_info);
         soa: entry-major outputs g [m, B], jac [nnz, B], grad [n, B] (cpl_eval_batch_ex).
-        instance: per-instance wrench / cost references (InstanceData, cpl_eval_batch_inst: the
-        template's evaluation, then the instance overlay's launch for g[0:6], f and grad; "norms" is
-        then a separate pass over g); not with soa.
-        cones: per-instance friction coefficients and force thresholds (InstanceCones,
-        cpl_eval_batch_cones: after the template's evaluation a cone overlay launch recomputes every
+        instance: per-instance wrench / cost references (InstanceData: the template's evaluation, then
+        the instance overlay's launch for g[0:6], f and grad; "norms" is then a separate pass over g);
+        not with soa.
+        cones: per-instance friction coefficients and force thresholds (InstanceCones:
+        after the template's evaluation a cone overlay launch recomputes every
         contact's two cone values and row 1's six Jacobian entries, CSR or folded; the values are not
         validated here); not with soa.
-        weights: per-instance cost weights (InstanceWeights, cpl_eval_batch_weights: the template's
-        evaluation without f / grad, then one weight overlay launch for f and grad — with instance data for
-        g[0:6] too, in the instance overlay's stead; the values are not validated here); not with soa.
+        weights: per-instance cost weights (InstanceWeights: the template's evaluation without f / grad,
+        then the instance overlay's launch with the weights staged too, for f and grad — and, with instance
+        data, g[0:6]; the values are not validated here); not with soa.
+        Every combination is one call of cpl_eval_batch_weights, with NULL for a record not given.
         """
         import torch
 
@@ -682,40 +656,18 @@ class CplProblem:
             raise ValueError("cones must be an InstanceCones")
         if weights is not None and not isinstance(weights, InstanceWeights):
             raise ValueError("weights must be an InstanceWeights")
-        if weights is not None and weights:
-            wt = weights.validated(B, len(self._contact_names), x.device)
-            cn = (cones if cones is not None else InstanceCones()).validated(B, len(self._contact_names), x.device)
-            inst = (instance if instance is not None else InstanceData()).validated(B, len(self._contact_names), x.device)
-            cs, ccs, wcs = inst.c_struct(), cn.c_struct(), wt.c_struct()
-            check(lib.cpl_eval_batch_weights(ctypes.byref(self.desc()), B, p(x), p(mass), p(env_tag), ctypes.byref(cs),
-                                             ctypes.byref(ccs), p(res.get("g")), p(res.get("jac")), p(res.get("f")),
-                                             p(res.get("grad")), p(res.get("norms")), flags,
-                                             ctypes.c_void_p(s.cuda_stream), ctypes.byref(wcs)))
-            return res
-        if cones is not None and cones:
-            cn = cones.validated(B, len(self._contact_names), x.device)
-            inst = (instance if instance is not None else InstanceData()).validated(B, len(self._contact_names), x.device)
-            cs, ccs = inst.c_struct(), cn.c_struct()
-            check(lib.cpl_eval_batch_cones(ctypes.byref(self.desc()), B, p(x), p(mass), p(env_tag), ctypes.byref(cs),
-                                           ctypes.byref(ccs), p(res.get("g")), p(res.get("jac")), p(res.get("f")),
-                                           p(res.get("grad")), p(res.get("norms")), flags,
-                                           ctypes.c_void_p(s.cuda_stream)))
-            return res
-        if instance is not None and instance:
-            inst = instance.validated(B, len(self._contact_names), x.device)
-            cs = inst.c_struct()
-            check(lib.cpl_eval_batch_inst(ctypes.byref(self.desc()), B, p(x), p(mass), p(env_tag), ctypes.byref(cs),
-                                          p(res.get("g")), p(res.get("jac")), p(res.get("f")), p(res.get("grad")),
-                                          p(res.get("norms")), flags, ctypes.c_void_p(s.cuda_stream)))
-            return res
-        if flags or want_norms:
-            check(lib.cpl_eval_batch_ex(ctypes.byref(self.desc()), B, p(x), p(mass), p(env_tag), p(res.get("g")),
-                                        p(res.get("jac")), p(res.get("f")), p(res.get("grad")), p(res.get("norms")),
-                                        flags, ctypes.c_void_p(s.cuda_stream)))
-            return res
-        check(lib.cpl_eval_batch(ctypes.byref(self.desc()), B, p(x), p(mass), p(env_tag), p(res.get("g")),
-                                 p(res.get("jac")), p(res.get("f")), p(res.get("grad")),
-                                 ctypes.c_void_p(s.cuda_stream)))
+        # one entry for every combination: a record not given is NULL, and cpl_eval_batch_weights with three
+        # NULLs is cpl_eval_batch_ex (with no flags and no norms: cpl_eval_batch)
+        N = len(self._contact_names)
+        given = [None if a is None or not a else a.validated(B, N, x.device) for a in (weights, cones, instance)]
+        wcs, ccs, cs = (None if a is None else a.c_struct() for a in given)
+
+        def ref(rec):
+            return None if rec is None else ctypes.byref(rec)
+
+        check(lib.cpl_eval_batch_weights(ctypes.byref(self.desc()), B, p(x), p(mass), p(env_tag), ref(cs), ref(ccs),
+                                         p(res.get("g")), p(res.get("jac")), p(res.get("f")), p(res.get("grad")),
+                                         p(res.get("norms")), flags, ctypes.c_void_p(s.cuda_stream), ref(wcs)))
         return res
 
     def residual_norms(self, g, stream=None):

@@ -318,3 +318,43 @@ def test_hessian_reads_the_weights_per_instance(cases, env, N, with_mu):
     diag = torch.arange(n, device=DEV)
     assert same(H1[:, diag[3:], diag[3:]].reshape(B, N, 9)[:, :, 0:3], want[:, diag[3:], diag[3:]].reshape(B, N, 9)[:, :, 0:3])
     assert same(H1[:, diag[:3], diag[:3]], base[:, diag[:3], diag[:3]])
+
+
+def off8(t):
+    """A contiguous copy of t that starts one double into a larger buffer: 8-byte aligned and no more."""
+    v = torch.empty(t.numel() + 1, dtype=torch.float64, device=DEV)[1:].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and v.data_ptr() % 16 == 8
+    return v
+
+
+@pytest.mark.parametrize("B", [3, 67])
+@pytest.mark.parametrize("env,N", [("ground", 4), ("mixed", 3)])
+def test_eight_byte_aligned_arrays_give_the_same_bits(cases, env, N, B):
+    """The overlays take 16-byte accesses only where the array's base allows them (x, every staged array, the g
+    output).  x, the instance data, the weights and g as views one double into a larger buffer: every output is
+    bitwise the call's on freshly allocated (16-byte aligned) copies — with instance data alone (the overlay
+    without weights) and with instance data, weights and cones (the one with).  B = 3 is one partial tile, B = 67
+    two tiles with the second partial."""
+    c = cases[(env, N, 67)]
+    prob = c["prob"]
+    head = lambda t: None if t is None else t[:B].clone()  # noqa: E731
+    x, mass, tag = head(c["xt"]), head(c["mt"]), head(c["tt"])
+    inst = {k: head(getattr(c["inst"], k)) for k in InstanceData.FIELDS}
+    wts = {k: head(c["Wt"][k]) for k in InstanceWeights.FIELDS}
+    cones = InstanceCones(mu=head(c["cones"].mu), F_thr=head(c["cones"].F_thr))
+    m = prob.get_nlp_info()[1]
+    for everything in (False, True):
+        def given(place):
+            kw = {"instance": InstanceData(**{k: place(v) for k, v in inst.items()})}
+            if everything:
+                kw.update(cones=cones, weights=InstanceWeights(**{k: place(v) for k, v in wts.items()}))
+            return kw
+        want = prob.eval_batch(x, mass, tag, outputs=OUTPUTS, **given(lambda v: v))
+        for t in [x, *inst.values(), *wts.values()]:
+            assert t.data_ptr() % 16 == 0
+        g = off8(torch.full((B, m), -3.0, dtype=torch.float64, device=DEV))
+        got = prob.eval_batch(off8(x), mass, tag, outputs=OUTPUTS, out={"g": g}, **given(off8))
+        assert got["g"] is g
+        for k in OUTPUTS:
+            assert same(got[k], want[k]), (k, everything)
